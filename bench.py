@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- HR-pixel throughput of the x4 SRGAN train step on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload gan_x4|gen_l1_x4|infer_x8|dip_x2]
+    python bench.py --gpus N --steps K --warmup W [--workload gan_x4|gen_l1_x4|infer_x8|dip_x2] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one synthetic batch already resident in HBM:
   gan_x4    : BASELINE config 3 (the configuration the metric is quoted on) -- full GAN step (train_GAN.py:38-71 recipe:
@@ -14,7 +14,13 @@ N > 1: one process per GPU, batch sharded data-parallel (weak scaling: fixed per
 The driver launches the ranks with torch.distributed.run; `python bench.py --gpus N` on its own starts them itself (as a
 child process, before this process touches the GPU) and relays rank 0's JSON line.  Rank 0 prints ONE JSON line.
 
-Extra legs (rank 0, N = 1 only; each can be switched off):
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`: wall time of one timed step).
+--dump-outputs DIR : after the timed steps rank 0 writes what its last step returned (losses, output images) as
+                  DIR/<name>.npy in float32 (float64 stays float64).  An array of more than 2^22 elements is written as
+                  a fixed sample of its flattened elements (the sorted indices drawn by numpy default_rng(0)), so that
+                  DIR stays below 64 MB.  Inputs and weights are seeded: the same arguments give the same inputs.
+
+Extra legs (--full only; rank 0, N = 1 only; each can be switched off):
   roofline      : three more steps, not timed for throughput, with EVERY kernel launch bracketed by HIP events on its launch
                   stream.  Convolution launches are grouped by the kernel the dispatcher selects; for the family with the
                   largest total time: achieved = sum of algorithmic FLOPs (2*N*OH*OW*Cout*KH*KW*Cin) / sum of durations,
@@ -91,8 +97,9 @@ def graphs_on():
 
 
 def build_step(workload, dev, world):
-    """Returns (step callable, HR pixels per rank and step).  `step.eager` is the un-captured form (roofline leg),
-    `step.syncs` the GradSync objects (collective-wait timing), `step.modules` the trained networks."""
+    """Returns (step callable, HR pixels per rank and step).  The step returns {name: tensor}, what a caller of the path
+    receives (--dump-outputs).  `step.eager` is the un-captured form (roofline leg), `step.syncs` the GradSync objects
+    (collective-wait timing), `step.modules` the trained networks."""
     cfg = WORKLOADS[workload]
     Gm, optim, steps = P("models.GAN.generator"), P("optim"), P("steps")
     torch.manual_seed(0)                      # module-default init under seed 0 (SURVEY.md 8d)
@@ -109,7 +116,7 @@ def build_step(workload, dev, world):
         gen = Gm.Generator(8, 16).to(dev)
         img = torch.rand(1, 3, cfg["lr"], cfg["lr"], generator=torch.Generator().manual_seed(1)).to(dev)
         # ~90 small launches per image: replay them from a HIP graph
-        return finish(lambda: infer.super_resolve(gen, img), (cfg["lr"] * 8) ** 2, graphs_on())
+        return finish(lambda: {"sr": infer.super_resolve(gen, img)}, (cfg["lr"] * 8) ** 2, graphs_on())
     if workload == "dip_x2":
         M, Dn = P("models.DIP"), P("utils.downsampler")
         hr_sz = cfg["lr"] * 2
@@ -121,7 +128,7 @@ def build_step(workload, dev, world):
             lr_img = down(hr_img)
         z = (torch.rand(1, 32, hr_sz, hr_sz, generator=gcpu) * 0.1).to(dev)
         run = steps.DipRunner(net, down, z, lr_img, 0.01, 0.05)
-        return finish(lambda: run.step()[0], hr_sz * hr_sz, graphs_on())
+        return finish(lambda: dict(zip(("loss", "out_hr"), run.step())), hr_sz * hr_sz, graphs_on())
     gen = Gm.Generator(cfg["factor"], 16).to(dev).train()
     n, s, f = cfg["batch"], cfg["lr"], cfg["factor"]
     g = torch.Generator(device="cpu").manual_seed(1 + (dist.get_rank() if world > 1 else 0))
@@ -142,7 +149,7 @@ def build_step(workload, dev, world):
                 loss.backward()
             sync_g()
             opt_g.step()
-            return loss
+            return {"loss": loss.detach(), "fake": fake.detach()}
         # launch-bound workload (~500 launches per step): capture the whole step once, replay it per step
         out, px = finish(step, n * (s * f) ** 2, world == 1 and graphs_on())
         out.syncs, out.modules = [sync_g], [gen]
@@ -159,7 +166,8 @@ def build_step(workload, dev, world):
     overlap = os.environ.get("DSR_GAN_OVERLAP", "1") != "0"
 
     def step():
-        return steps.gan_step(gen, disc, perc, opt_g, opt_d, lr, hr, sync_g, sync_d, overlap=overlap)[1]
+        return dict(zip(("loss_d", "loss_g", "fake"),
+                        steps.gan_step(gen, disc, perc, opt_g, opt_d, lr, hr, sync_g, sync_d, overlap=overlap)))
     # the whole two-stream step replays from ONE HIP graph (DSR_GAN_GRAPH=0: eager); collectives are not captured
     out, px = finish(step, n * (s * f) ** 2, world == 1 and graphs_on() and os.environ.get("DSR_GAN_GRAPH", "1") != "0"
                      and os.environ.get("DSR_DIST_FORCE", "0") != "1")
@@ -503,6 +511,23 @@ def time_fed_from_patch_bank(step, dev, steps, px):
             "feed": "PatchBank.sample(32) from 100 HBM-resident uint8 pairs + copy into the step's inputs, every step"}
 
 
+DUMP_MAX_ELEMS = 1 << 22        # per array (16 MB in float32); no step returns more than three arrays
+
+
+def dump_outputs(outputs, path):
+    """--dump-outputs: every tensor the last timed step returned as <path>/<name>.npy (see the module docstring)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in outputs.items():
+        a = t.detach().cpu().to(torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes"
+
+
 def spawn_ranks(a):
     """`python bench.py --gpus N` without a launcher: start the N ranks as a CHILD process tree (this process has not
     touched the GPU and never will) and hand back rank 0's output and exit code."""
@@ -524,6 +549,9 @@ def main():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-psnr", action="store_true")
     ap.add_argument("--no-other-workloads", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra legs: roofline, PSNR delta, other workloads, CPU baseline")
     a = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -584,7 +612,7 @@ def main():
     t0 = time.perf_counter()
     L.check(L.lib().dsr_clock_sample(ctypes.c_void_p(clk.data_ptr()), st_ptr))
     for _ in range(a.steps):
-        step()
+        res = step()
     L.check(L.lib().dsr_clock_sample(ctypes.c_void_p(clk.data_ptr() + 128), st_ptr))
     t_issue = time.perf_counter() - t0          # host time to ISSUE the steps (GPU still running): launch-bound if ~ dt
     fence()
@@ -642,24 +670,27 @@ def main():
         out["collective_wait_ms_per_step"] = wait_all
 
     note(f"{ms:.2f} ms/step (host issue {t_issue / a.steps * 1e3:.2f} ms/step)")
-    if rank == 0 and world == 1 and not a.no_roofline:
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(res, a.dump_outputs)
+    extra = rank == 0 and world == 1 and a.full
+    if extra and not a.no_roofline:
         note("roofline leg")
         r = roofline(step, a.workload, ms)
         if r:
             out["roofline"] = r
-    if rank == 0 and world == 1 and not a.no_psnr:
+    if extra and not a.no_psnr:
         note("psnr delta (HIP vs oracle on the reduced configuration)")
         pd = psnr_delta(a.workload, dev)
         out["psnr_delta_db"] = pd["value"]
         out["psnr_delta"] = pd
-    if rank == 0 and world == 1 and not force and a.workload == "gan_x4" and not a.no_other_workloads:
+    if extra and not force and a.workload == "gan_x4" and not a.no_other_workloads:
         note("the same step fed from a PatchBank")
         out["fed_from_patch_bank"] = time_fed_from_patch_bank(step, dev, a.steps, px_per_rank)
         out["other_workloads"] = {}
         for name in ("gen_l1_x4", "infer_x8", "dip_x2"):
             note(f"other workload {name}")
             out["other_workloads"][name] = time_workload(name, dev)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if extra and not a.no_cpu_baseline:
         note("cpu baseline (oracle on host cores)")
         out["cpu_baseline"] = cpu_baseline(a.workload)
     if rank == 0:

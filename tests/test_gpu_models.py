@@ -1025,6 +1025,37 @@ def test_rccl_single_rank_gan_step(dev):
             assert abs(v - sums[tag][name]) <= 1e-6 * abs(v), (tag, name, v, sums[tag][name])
 
 
+def test_bench_plain_line_and_dump_outputs(dev, tmp_path):
+    """bench.py without --full runs none of the extra legs, and --dump-outputs writes what the last timed step returned;
+    two runs with the same arguments write the same arrays (seeded inputs and weights, deterministic reductions)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    dumps = []
+    for rep in range(2):
+        d = tmp_path / f"run{rep}"
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--workload", "gen_l1_x4", "--steps", "3", "--warmup", "1",
+               "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-6000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert not {"roofline", "psnr_delta", "psnr_delta_db", "fed_from_patch_bank", "other_workloads", "cpu_baseline"} & set(out)
+        assert sorted(os.listdir(d)) == ["fake.npy", "loss.npy"]
+        arrs = {k: np.load(d / (k + ".npy")) for k in ("fake", "loss")}
+        assert arrs["fake"].dtype == np.float32 and arrs["fake"].shape == (16, 3, 128, 128)
+        assert arrs["loss"].dtype == np.float32 and arrs["loss"].shape == ()
+        assert all(np.isfinite(a).all() for a in arrs.values()) and 0 < float(arrs["loss"]) < 2
+        dumps.append(arrs)
+    for k, a in dumps[0].items():
+        np.testing.assert_array_equal(a, dumps[1][k], err_msg=k)
+
+
 def test_full_size_batch_split_invariance(dev):
     """BASELINE config-3 sizes (batch 32, 128x128 -> 512x512), where no CPU oracle finishes in test time: in eval mode
     every image is independent, so the networks run on the whole batch (the launch shapes bench.py times: persistent

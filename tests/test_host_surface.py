@@ -1,6 +1,6 @@
-"""CPU: the host-side mirror of the reference's surface -- install_dropin(), utils/DIP helpers against the golden
-fixture and (when /root/reference is present, i.e. in the build container) against the reference's own functions,
-reference-format checkpoints through evaluate.save_model / load_model and the reference's own save_model / load_model.
+"""CPU: the host-side mirror of the reference's surface -- install_dropin() under the reference's package layout, utils/DIP
+helpers and reference-format checkpoints through evaluate.save_model / load_model against what the reference's own
+functions returned (tests/golden/host_surface.npz, written by tests/golden/make_golden.py).
 No device work: module construction, state_dicts and host glue only."""
 import importlib
 import os
@@ -14,29 +14,48 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = "deep-super-resolution_amd"
-REF = "/root/reference"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree exists only in the build container")
 
 
 def P(sub):
     return importlib.import_module(PKG + "." + sub)
 
 
-def run_py(code, with_ref):
-    """Run a snippet in a fresh interpreter (install_dropin edits sys.modules; keep that out of the pytest process)."""
+def run_py(code, tree=None):
+    """Run a snippet in a fresh interpreter (install_dropin edits sys.modules; keep that out of the pytest process), with
+    the package tree `tree` (the name TREE in the snippet) on sys.path in front of this repository when one is given."""
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    pre = f"import sys, importlib\nsys.path.insert(0, {ROOT!r})\n" + (f"sys.path.insert(0, {REF!r})\n" if with_ref else "")
+    pre = f"import sys, importlib\nsys.path.insert(0, {ROOT!r})\n" + (f"TREE = {tree!r}\nsys.path.insert(0, TREE)\n" if tree else "")
     r = subprocess.run([sys.executable, "-c", pre + textwrap.dedent(code)], capture_output=True, text=True, env=env,
                        cwd="/tmp", timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     return r.stdout
 
 
-@needs_ref
-def test_install_dropin_keeps_reference_packages():
+def standin_reference_tree(root):
+    """The reference's package layout with placeholder modules: `utils` and `models` are namespace packages (no
+    __init__.py), models/GAN and models/DIP regular ones, dataset.py a top-level module, utils/common.py the helpers only
+    the reference has.  Every module this package mirrors raises when imported, so a leaf install_dropin fails to alias
+    shows up as an ImportError."""
+    mirrored = ("models/GAN/generator.py", "models/GAN/discriminator.py", "models/DIP/__init__.py", "models/DIP/skip.py",
+                "models/DIP/utils.py", "utils/downsampler.py", "utils/GAN.py", "utils/DIP.py", "utils/degradation.py",
+                "dataset.py")
+    files = {f: "raise ImportError('placeholder: install_dropin serves this module')\n" for f in mirrored}
+    files["models/GAN/__init__.py"] = ""
+    files["utils/common.py"] = "".join(f"def {n}(*args, **kwargs):\n    pass\n" for n in
+                                       ("save_model", "load_model", "save_log", "np_to_torch"))
+    for rel, text in files.items():
+        path = os.path.join(root, rel)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(text)
+    return str(root)
+
+
+def test_install_dropin_keeps_reference_packages(tmp_path):
     """with the reference on sys.path, the lines of train_GAN.py:11-15 / DIP.py:11-15 / eval_GAN.py:11-14
     must all resolve: mirrored leaves to this package (since round 2 that includes utils.degradation and the top-level
-    dataset module, whose own version needs torchvision), everything else (utils.common) to the reference's own modules."""
+    dataset module, whose own version needs torchvision), everything else (utils.common) to the reference's own modules.
+    The reference is stood in for by its package layout (standin_reference_tree)."""
     out = run_py("""
         pk = importlib.import_module("deep-super-resolution_amd")
         names = pk.install_dropin()
@@ -48,7 +67,7 @@ def test_install_dropin_keeps_reference_packages():
         from models.DIP import get_net
         from utils.DIP import *
         import utils.common, utils.degradation, utils.DIP, models.DIP.skip, models.GAN.generator as gg
-        assert utils.common.__file__.startswith("/root/reference/"), utils.common.__file__
+        assert utils.common.__file__.startswith(TREE + "/"), utils.common.__file__
         assert utils.degradation.__name__ == "deep-super-resolution_amd.utils.degradation"
         from dataset import GANDIV2KDataset, DIV2KDataset, get_image_pair          # (train_GAN.py:12 `from dataset import *`)
         assert GANDIV2KDataset.__module__ == "deep-super-resolution_amd.dataset"
@@ -62,7 +81,7 @@ def test_install_dropin_keeps_reference_packages():
         g = Generator(factor=8, residual_blocks_count=1)
         assert type(g).__module__.startswith("deep-super-resolution_amd.")
         print("OK", len(names))
-    """, with_ref=True)
+    """, standin_reference_tree(tmp_path / "reference"))
     assert out.startswith("OK 10")
 
 
@@ -82,7 +101,7 @@ def test_install_dropin_standalone():
             import utils.common
         except ImportError:
             print("OK")
-    """, with_ref=False)
+    """)
     assert out.strip() == "OK"
 
 
@@ -110,34 +129,31 @@ def test_product_get_noise_matches_reference_fixture(golden):
         D.fill_noise(torch.zeros(2), "x")
 
 
-@needs_ref
-def test_dip_helpers_equal_reference_functions():
-    """get_noise (both methods), fill_noise and get_params against the reference's own functions, imported here."""
-    out = run_py("""
-        import torch, numpy as np
-        import utils.DIP as ref                                     # the reference's
-        ours = importlib.import_module("deep-super-resolution_amd.utils.DIP")
-        for args, kw in (((32, "noise", (8, 12)), {}), ((3, "noise", 16), dict(noise_type="n", var=0.25)),
-                         ((2, "meshgrid", (6, 9)), {})):
-            torch.manual_seed(5); a = ref.get_noise(*args, **kw)
-            torch.manual_seed(5); b = ours.get_noise(*args, **kw)
-            assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b), args
-        net = torch.nn.Sequential(torch.nn.Conv2d(2, 3, 1), torch.nn.BatchNorm2d(3))
-        down = torch.nn.Conv2d(3, 3, 2)
-        for spec in ("net", "net,input", "input", "net,down", "down,net"):
-            zi_a, zi_b = torch.zeros(1, 2, 4, 4), torch.zeros(1, 2, 4, 4)
-            pa, pb = ref.get_params(spec, net, zi_a, down), ours.get_params(spec, net, zi_b, down)
-            assert len(pa) == len(pb) and all(x is y or (x is zi_a and y is zi_b) for x, y in zip(pa, pb)), spec
-            assert zi_a.requires_grad == zi_b.requires_grad
-        for f in (ref.get_params, ours.get_params):
-            try:
-                f("bogus", net, None)
-                raise SystemExit("no assert")
-            except AssertionError:
-                pass
-        print("OK")
-    """, with_ref=True)
-    assert out.strip() == "OK"
+def test_dip_helpers_equal_reference_functions(golden):
+    """get_noise (both methods), fill_noise and get_params against what the reference's own functions returned for the
+    same calls (tests/golden/make_golden.py gen_host_surface: seed 5 draws, the objects get_params hands back per spec)."""
+    ref = golden("host_surface")
+    ours = P("utils.DIP")
+    for i, (args, kw) in enumerate((((32, "noise", (8, 12)), {}), ((3, "noise", 16), dict(noise_type="n", var=0.25)),
+                                    ((2, "meshgrid", (6, 9)), {}))):
+        torch.manual_seed(5)
+        b = ours.get_noise(*args, **kw)
+        assert str(b.dtype) == str(ref[f"noise{i}_dtype"]) and b.dtype == torch.from_numpy(ref[f"noise{i}"]).dtype, args
+        np.testing.assert_array_equal(b.numpy(), ref[f"noise{i}"], err_msg=str(args))
+    net = torch.nn.Sequential(torch.nn.Conv2d(2, 3, 1), torch.nn.BatchNorm2d(3))
+    down = torch.nn.Conv2d(3, 3, 2)
+
+    def which(x, zi):               # the encoding of make_golden.which
+        if x is zi:
+            return "input"
+        return next(f"{tag}.{i}" for tag, m in (("net", net), ("down", down)) for i, p in enumerate(m.parameters()) if x is p)
+    for spec in ("net", "net,input", "input", "net,down", "down,net"):
+        zi = torch.zeros(1, 2, 4, 4)
+        assert [which(x, zi) for x in ours.get_params(spec, net, zi, down)] == ref[f"params/{spec}"].tolist(), spec
+        assert zi.requires_grad == bool(ref[f"params_input_grad/{spec}"]), spec
+    assert bool(ref["params_bogus_asserts"])
+    with pytest.raises(AssertionError):
+        ours.get_params("bogus", net, None)
 
 
 def test_optimize_rejects_unknown_optimizer():
@@ -152,55 +168,48 @@ def _seeded(cls, *a, **kw):
     return cls(*a, **kw)
 
 
-@needs_ref
-def test_checkpoint_roundtrip_with_reference_classes(tmp_path):
-    """utils/common.py:11-18,46-60 both ways, with the reference's OWN classes and functions imported here:
-    (1) reference Generator/Discriminator/DIP net -> reference save_model -> this package's load_model into the mirror;
-    (2) the same file re-keyed with the DataParallel ``module.`` prefix;  (3) mirror -> evaluate.save_model -> reference
-    load_model into the reference class (strict load_state_dict).  Keys, order, shapes, dtypes and values identical."""
-    out = run_py(f"""
-        import torch, os
-        from collections import OrderedDict
-        from models.GAN.generator import Generator as RefG
-        from models.GAN.discriminator import Discriminator as RefD
-        from models.DIP import get_net as ref_get_net
-        import utils.common as refc
-        ev = importlib.import_module("deep-super-resolution_amd.evaluate")
-        G = importlib.import_module("deep-super-resolution_amd.models.GAN.generator").Generator
-        D = importlib.import_module("deep-super-resolution_amd.models.GAN.discriminator").Discriminator
-        get_net = importlib.import_module("deep-super-resolution_amd.models.DIP").get_net
-        tmp = {str(tmp_path)!r}
-        cases = [("g", lambda: RefG(8, 2), lambda: G(8, 2)), ("d", lambda: RefD((48, 32)), lambda: D((48, 32))),
-                 ("dip", lambda: ref_get_net(8, "skip", "reflection", "bilinear", skip_n33d=16, skip_n33u=16, skip_n11=4, num_scales=3),
-                  lambda: get_net(8, "skip", "reflection", "bilinear", skip_n33d=16, skip_n33u=16, skip_n11=4, num_scales=3))]
-        for tag, mk_ref, mk_ours in cases:
-            torch.manual_seed(7)
-            ref = mk_ref()
-            for b in ref.buffers():                       # non-trivial running statistics / counters
-                if b.dtype.is_floating_point: b.uniform_(0.5, 1.5)
-                else: b.fill_(3)
-            refc.save_model(ref, tag, tmp)                # the reference's own writer
-            path = os.path.join(tmp, tag + ".pth")
-            rsd = ref.state_dict()
-            ours = ev.load_model(mk_ours(), path)
-            osd = ours.state_dict()
-            assert list(osd.keys()) == list(rsd.keys()), tag
-            for k in rsd:
-                assert osd[k].dtype == rsd[k].dtype and osd[k].shape == rsd[k].shape and torch.equal(osd[k], rsd[k]), (tag, k)
-            # a checkpoint of a DataParallel/DDP-wrapped model: every key carries "module."
-            pref = os.path.join(tmp, tag + "_module.pth")
-            torch.save(OrderedDict(("module." + k, v) for k, v in rsd.items()), pref)
-            ours2 = ev.load_model(mk_ours(), pref)
-            assert all(torch.equal(ours2.state_dict()[k], rsd[k]) for k in rsd), tag
-            ref_via_ref = refc.load_model(mk_ref(), pref)  # the reference's reader agrees on that file
-            assert all(torch.equal(ref_via_ref.state_dict()[k], rsd[k]) for k in rsd), tag
-            # the other direction
-            back = ev.save_model(ours, tag + "_back", tmp)
-            ref2 = refc.load_model(mk_ref(), back)
-            assert all(torch.equal(ref2.state_dict()[k], rsd[k]) for k in rsd), tag
-        print("OK")
-    """, with_ref=True)
-    assert out.strip().endswith("OK")
+def test_checkpoint_roundtrip_with_reference_classes(golden, tmp_path):
+    """utils/common.py:11-18,46-60 both ways, against the state_dict layout (ordered keys, shapes, dtypes) of the
+    reference's OWN Generator(8, 2), Discriminator((48, 32)) and small skip net (golden host_surface):
+    (1) a checkpoint as the reference's save_model writes it (torch.save of that state_dict) -> this package's load_model
+    into the mirror;  (2) the same file re-keyed with the DataParallel ``module.`` prefix (the reference's load_model read
+    such a file back, golden);  (3) mirror -> evaluate.save_model -> what the reference's load_model reads
+    (torch.load(weights_only=True), then a strict load_state_dict into the reference class): exactly that layout.
+    Keys, order, shapes, dtypes and values identical."""
+    from collections import OrderedDict
+    ref = golden("host_surface")
+    ev = P("evaluate")
+    G, D = P("models.GAN.generator").Generator, P("models.GAN.discriminator").Discriminator
+    get_net = P("models.DIP").get_net
+    cases = [("g", lambda: G(8, 2)), ("d", lambda: D((48, 32))),
+             ("dip", lambda: get_net(8, "skip", "reflection", "bilinear", skip_n33d=16, skip_n33u=16, skip_n11=4, num_scales=3))]
+    gen = torch.Generator().manual_seed(7)
+    for tag, mk_ours in cases:
+        keys, dtypes = ref[f"ckpt_{tag}_keys"].tolist(), ref[f"ckpt_{tag}_dtypes"].tolist()
+        shapes = [tuple(int(n) for n in s.split(",") if n) for s in ref[f"ckpt_{tag}_shapes"].tolist()]
+        rsd = OrderedDict()                          # the reference module's state_dict, non-trivial values
+        for k, shp, dt in zip(keys, shapes, dtypes):
+            dtype = getattr(torch, dt.split(".")[1])
+            rsd[k] = torch.rand(shp, generator=gen) + 0.5 if dtype.is_floating_point else torch.full(shp, 3, dtype=dtype)
+        path = str(tmp_path / f"{tag}.pth")
+        torch.save(rsd, path)                        # what the reference's save_model writes
+        ours = ev.load_model(mk_ours(), path)
+        osd = ours.state_dict()
+        assert list(osd.keys()) == keys, tag
+        for k in rsd:
+            assert osd[k].dtype == rsd[k].dtype and osd[k].shape == rsd[k].shape and torch.equal(osd[k], rsd[k]), (tag, k)
+        # a checkpoint of a DataParallel/DDP-wrapped model: every key carries "module."
+        pref = str(tmp_path / f"{tag}_module.pth")
+        torch.save(OrderedDict(("module." + k, v) for k, v in rsd.items()), pref)
+        ours2 = ev.load_model(mk_ours(), pref)
+        assert all(torch.equal(ours2.state_dict()[k], rsd[k]) for k in rsd), tag
+        assert bool(ref[f"ckpt_{tag}_ref_reads_prefixed"]), tag     # the reference's reader agrees on that file
+        # the other direction
+        back = ev.save_model(ours, tag + "_back", str(tmp_path))
+        bsd = torch.load(back, weights_only=True)
+        assert list(bsd.keys()) == keys, tag
+        for k, shp, dt in zip(keys, shapes, dtypes):
+            assert tuple(bsd[k].shape) == shp and str(bsd[k].dtype) == dt and torch.equal(bsd[k], rsd[k]), (tag, k)
 
 
 def test_checkpoint_roundtrip_mirror_only(tmp_path):
@@ -261,6 +270,24 @@ def test_data_host_logic_matches_oracle():
     a, b = np.random.RandomState(9), np.random.RandomState(9)
     for _ in range(50):
         assert DS.train_patch_coords(170, 255, (128, 96), 4, a) == od.train_patch_coords(170, 255, 128, 96, 4, b)
+
+
+def test_bench_dump_outputs_sampling(tmp_path):
+    """bench.py --dump-outputs (host side): float64 stays float64, everything else is written as float32; an array of at
+    most 2^22 elements is written whole, a larger one as the sorted sample drawn by numpy default_rng(0)."""
+    import bench
+    g = torch.Generator().manual_seed(2)
+    big = torch.randn(2, 3, 1000, 1000, generator=g).to(torch.bfloat16)
+    small = torch.randn(4, 3, 8, 8, generator=g).to(torch.float16)
+    loss = torch.tensor(0.25, dtype=torch.float64)
+    bench.dump_outputs({"big": big, "small": small, "loss": loss}, str(tmp_path / "out"))
+    assert sorted(os.listdir(tmp_path / "out")) == ["big.npy", "loss.npy", "small.npy"]
+    a = {k: np.load(tmp_path / "out" / (k + ".npy")) for k in ("big", "small", "loss")}
+    assert a["loss"].dtype == np.float64 and a["loss"].shape == () and float(a["loss"]) == 0.25
+    np.testing.assert_array_equal(a["small"], small.float().numpy())
+    idx = np.sort(np.random.default_rng(0).choice(big.numel(), 1 << 22, replace=False))
+    assert a["big"].dtype == np.float32 and a["big"].shape == (1 << 22,)
+    np.testing.assert_array_equal(a["big"], big.float().numpy().reshape(-1)[idx])
 
 
 def test_act_link_and_batched_wgrad_contexts_without_gpu():
