@@ -93,18 +93,6 @@ static bool is_c64(const dsr_conv_desc* d) {
          d->pad_mode == DSR_PAD_ZERO;
 }
 
-extern "C" int dsr_conv_fwd_affine_supported(const dsr_conv_desc* d) {
-  return d && !check_desc(d) && (is_c64(d) || is_c64_wide(d));
-}
-
-extern "C" int dsr_conv_stats_rows(const dsr_conv_desc* d) {
-  int OH, OW;
-  if (dsr_conv_out_size(d, &OH, &OW)) return -1;
-  if (is_c64(d) || is_c64_wide(d)) return dsr_c64_stat_rows(d->N, OH, OW, r8(d->Cout));   // one statistics row per persistent block
-  long long M = (long long)d->N * OH * OW;
-  return (int)((M + 127) / 128);
-}
-
 extern "C" size_t dsr_conv_packed_elems(const dsr_conv_desc* d, int dgrad) {
   if (check_desc(d)) return 0;
   size_t T = (size_t)d->KH * d->KW;
@@ -135,18 +123,29 @@ static void finish_args(ConvGemmArgs& a, int N, int wslices) {
   a.fd_cu8 = fd_make((unsigned)((a.CU >> 3) > 0 ? (a.CU >> 3) : 1));
 }
 
-extern "C" int dsr_conv_fwd(const dsr_conv_desc* d, const void* x, const void* w_fwd, const dsr_epilogue* e, void* y,
-                            dsr_stream_t s) {
-  int rc = check_desc(d);
-  if (rc) return rc;
-  if (!x || !w_fwd || !e) return dsr_fail(DSR_E_ARG, "conv_fwd: null pointer");
-  if (!y && !e->out_nchw_f32) return dsr_fail(DSR_E_ARG, "conv_fwd: no output");
+// ---- dispatch: which kernel a forward / input-gradient call runs is decided by plan_fwd / plan_dgrad alone; the entry
+// points launch what the plan says and dsr_conv_kernel_name names it
+enum class ConvKernel { C64, Halo64, Cin8, Rgb9, SmallN, Toeplitz9, DgradS2, Gemm };
+struct ConvPlan {
+  ConvKernel k;
+  int c64_mode = 0;                      // C64: dsr_c64_mode()
+  GemmTile tile = GemmTile::T128x128;    // Gemm: the tile of the (first) gather-kernel launch
+};
+
+// (the folded BatchNorm / residual bits only ever reach conv_c64: dsr_conv_fwd refuses them on every other plan)
+static int fwd_flags(const dsr_epilogue* e) {
+  return (e->bias ? DSR_F_BIAS : 0) | (e->stats_partial ? DSR_F_STATS : 0) | (e->out_nchw_f32 ? DSR_F_OUT_NCHW_F32 : 0) |
+         ((e->act == DSR_ACT_PRELU && e->prelu) ? DSR_F_PRELU_PTR : 0) | (e->pixel_shuffle ? DSR_F_PIXSHUF : 0) |
+         (e->bn_scale ? DSR_F_AFFINE : 0) | (e->residual ? DSR_F_RESIDUAL : 0);
+}
+
+// the gather kernel's arguments of a forward call (null pointers: the plan is made on the same arguments)
+static void fwd_gemm_args(const dsr_conv_desc* d, const dsr_epilogue* e, const void* x, const void* w, void* y, ConvGemmArgs& a) {
   int OH, OW;
   dsr_conv_out_size(d, &OH, &OW);
-  ConvGemmArgs a;
   memset(&a, 0, sizeof(a));
   a.x = x;
-  a.w = w_fwd;
+  a.w = w;
   a.y = y;
   a.out_f32 = e->out_nchw_f32;
   a.bias = e->bias;
@@ -166,124 +165,169 @@ extern "C" int dsr_conv_fwd(const dsr_conv_desc* d, const void* x, const void* w
   a.pad_mode = d->pad_mode;
   a.act = e->act;
   a.slope = e->slope;
-  a.flags = (e->bias ? DSR_F_BIAS : 0) | (e->stats_partial ? DSR_F_STATS : 0) |
-            (e->out_nchw_f32 ? DSR_F_OUT_NCHW_F32 : 0) | ((e->act == DSR_ACT_PRELU && e->prelu) ? DSR_F_PRELU_PTR : 0);
-  if (e->act == DSR_ACT_PRELU && !e->prelu) return dsr_fail(DSR_E_ARG, "conv_fwd: PReLU needs its weight pointer");
-  if (e->pixel_shuffle) {
-    if (d->Cout % 4 || d->Cout < 32 || e->out_nchw_f32 || e->stats_partial)
-      return dsr_fail(DSR_E_UNSUPPORTED, "conv_fwd: pixel-shuffle epilogue needs Cout %% 4 == 0, Cout >= 32, 16-bit output");
-    a.flags |= DSR_F_PIXSHUF;
-    a.OH = 2 * OH;
-    a.OW = 2 * OW;
-    a.CoutP = r8(d->Cout / 4);
-  } else {
-    a.OH = OH;
-    a.OW = OW;
-    a.CoutP = r8(d->Cout);
-  }
-  const bool fold = e->bn_scale || e->bn_shift || e->residual;
-  if (fold && (!dsr_conv_fwd_affine_supported(d) || e->pixel_shuffle || e->out_nchw_f32 || e->stats_partial ||
-               (!e->bn_scale) != (!e->bn_shift)))
-    return dsr_fail(DSR_E_UNSUPPORTED, "conv_fwd: folded BatchNorm / residual epilogue not available for this layer");
-  if (!fold && !e->pixel_shuffle && !e->out_nchw_f32 && !e->stats_partial && d->Cout % 64 == 0 && d->Cout >= 128 &&
-      (e->act == DSR_ACT_NONE || e->act == DSR_ACT_RELU || e->act == DSR_ACT_LEAKY) &&
-      dsr_halo64_supported(d->KH, d->KW, d->stride, d->pad, d->pad_mode, d->H, d->W, r8(d->Cin), d->Cout)) {
-    // 128 outputs over >= 128 input channels without BatchNorm statistics (VGG conv2_2, utils/GAN.py:26): two 64-channel
-    // slices per spatial tile on the halo-staged kernel (conv_halo64.hip) instead of the gather kernel's 128x128 tile
-    Halo64Args q;
-    memset(&q, 0, sizeof(q));
-    q.x = x;
-    q.w = w_fwd;
-    q.y = y;
-    q.bias = e->bias;
-    q.H = d->H;
-    q.W = d->W;
-    q.CinP = r8(d->Cin);
-    q.cout_full = d->Cout;
-    q.mirror = 0;
-    q.act = e->act;
-    q.slope = e->slope;
-    q.flags = e->bias ? DSR_F_BIAS : 0;
-    dsr_launch_conv_halo64(q, d->N, d->dtype, s);
-    return dsr_launch_status("dsr_conv_fwd(halo64)");
-  }
-  if (((is_c64(d) && !e->pixel_shuffle) || is_c64_wide(d)) && !e->out_nchw_f32) {
-    C64Args c;
-    memset(&c, 0, sizeof(c));
-    c.CoutP = d->Cout;
-    c.scale = e->bn_scale;
-    c.shift = e->bn_shift;
-    c.res = e->residual;
-    c.x = x;
-    c.w = w_fwd;
-    c.y = y;
-    c.bias = e->bias;
-    c.prelu = e->prelu;
-    c.stats = e->stats_partial;
-    c.H = d->H;
-    c.W = d->W;
-    c.act = e->act;
-    c.slope = e->slope;
-    c.flags = a.flags | (e->bn_scale ? DSR_F_AFFINE : 0) | (e->residual ? DSR_F_RESIDUAL : 0);
-    for (int kh = 0; kh < 3; ++kh)
-      for (int kw = 0; kw < 3; ++kw) {
-        c.tap_y[kh * 3 + kw] = kh;
-        c.tap_x[kh * 3 + kw] = kw;
-      }
-    dsr_launch_conv_c64(c, d->N, d->dtype, s);
-    return dsr_launch_status("dsr_conv_fwd(c64)");
-  }
-  if (is_cin8(d, e) || is_rgb9(d, e)) {
-    Cin8Args c;
-    memset(&c, 0, sizeof(c));
-    c.x = x;
-    c.w = w_fwd;
-    c.y = y;
-    c.bias = e->bias;
-    c.prelu = (e->act == DSR_ACT_PRELU) ? e->prelu : nullptr;
-    c.H = d->H;
-    c.W = d->W;
-    c.act = e->act;
-    c.slope = e->slope;
-    if (is_rgb9(d, e)) {
-      dsr_launch_conv_rgb9(c, d->N, d->dtype, s);
-      return dsr_launch_status("dsr_conv_fwd(rgb9)");
-    }
-    dsr_launch_conv_cin8(c, d->N, d->dtype, s);
-    return dsr_launch_status("dsr_conv_fwd(cin8)");
-  }
-  if (d->Cout <= 16 && d->stride == 1 && d->pad_mode == DSR_PAD_ZERO && d->KH * d->KW >= 9 && !e->stats_partial &&
-      !e->pixel_shuffle) {
-    // few output channels + many taps: stage the input halo once instead of gathering it once per tap
-    SmallNArgs sn;
-    memset(&sn, 0, sizeof(sn));
-    sn.x = x;
-    sn.w = w_fwd;
-    sn.y = y;
-    sn.out_f32 = e->out_nchw_f32;
-    sn.bias = e->bias;
-    sn.prelu = (e->act == DSR_ACT_PRELU) ? e->prelu : nullptr;
-    sn.IH = d->H;
-    sn.IW = d->W;
-    sn.CinP = r8(d->Cin);
-    sn.OH = OH;
-    sn.OW = OW;
-    sn.CoutP = r8(d->Cout);
-    sn.NB = r8(d->Cout);
-    sn.cout = d->Cout;
-    sn.KH = d->KH;
-    sn.KW = d->KW;
-    sn.pad = d->pad;
-    sn.act = e->act;
-    sn.slope = e->slope;
-    if (dsr_launch_conv_smalln(sn, d->N, d->dtype, s)) return dsr_launch_status("dsr_conv_fwd(small-n)");
-  }
+  a.flags = fwd_flags(e);
+  const int ps = e->pixel_shuffle ? 2 : 1;
+  a.OH = ps * OH;
+  a.OW = ps * OW;
+  a.CoutP = r8(d->Cout / (ps * ps));
   a.ntaps = d->KH * d->KW;
   for (int kh = 0; kh < d->KH; ++kh)
     for (int kw = 0; kw < d->KW; ++kw) a.taps[kh * d->KW + kw] = pack_tap(kh - d->pad, kw - d->pad, kh * d->KW + kw);
   finish_args(a, d->N, d->KH * d->KW);
-  dsr_launch_conv_gemm(a, d->dtype, s);
-  return dsr_launch_status("dsr_conv_fwd");
+}
+
+static ConvPlan plan_fwd(const dsr_conv_desc* d, const dsr_epilogue* e) {
+  const bool fold = e->bn_scale || e->bn_shift || e->residual;
+  // 128 outputs over >= 128 input channels without BatchNorm statistics (VGG conv2_2, utils/GAN.py:26): two 64-channel
+  // slices per spatial tile on the halo-staged kernel (conv_halo64.hip) instead of the gather kernel's 128x128 tile
+  if (!fold && !e->pixel_shuffle && !e->out_nchw_f32 && !e->stats_partial && d->Cout % 64 == 0 && d->Cout >= 128 &&
+      (e->act == DSR_ACT_NONE || e->act == DSR_ACT_RELU || e->act == DSR_ACT_LEAKY) &&
+      dsr_halo64_supported(d->KH, d->KW, d->stride, d->pad, d->pad_mode, d->H, d->W, r8(d->Cin), d->Cout))
+    return {ConvKernel::Halo64};
+  if (((is_c64(d) && !e->pixel_shuffle) || is_c64_wide(d)) && !e->out_nchw_f32)
+    return {ConvKernel::C64, dsr_c64_mode(fwd_flags(e), e->act, d->Cout)};
+  if (is_rgb9(d, e)) return {ConvKernel::Rgb9};
+  if (is_cin8(d, e)) return {ConvKernel::Cin8};
+  // few output channels + many taps: stage the input halo once instead of gathering it once per tap
+  if (d->Cout <= 16 && d->stride == 1 && d->pad_mode == DSR_PAD_ZERO && d->KH * d->KW >= 9 && !e->stats_partial &&
+      !e->pixel_shuffle && dsr_smalln_fits(d->KH, d->KW, r8(d->Cin), d->Cout))
+    return {ConvKernel::SmallN};
+  ConvGemmArgs a;
+  fwd_gemm_args(d, e, nullptr, nullptr, nullptr, a);
+  return {ConvKernel::Gemm, 0, dsr_conv_gemm_plan(a)};
+}
+
+extern "C" int dsr_conv_fwd_affine_supported(const dsr_conv_desc* d) {
+  if (!d || check_desc(d)) return 0;
+  static const float one = 1.f;
+  dsr_epilogue e = {};
+  e.bn_scale = e.bn_shift = &one;
+  return plan_fwd(d, &e).k == ConvKernel::C64;
+}
+
+extern "C" int dsr_conv_stats_rows(const dsr_conv_desc* d) {
+  int OH, OW;
+  if (dsr_conv_out_size(d, &OH, &OW)) return -1;
+  float row;
+  dsr_epilogue e = {};
+  e.stats_partial = &row;
+  if (plan_fwd(d, &e).k == ConvKernel::C64) return dsr_c64_stat_rows(d->N, OH, OW, r8(d->Cout));   // one row per persistent block
+  long long M = (long long)d->N * OH * OW;
+  return (int)((M + 127) / 128);
+}
+
+extern "C" int dsr_conv_fwd(const dsr_conv_desc* d, const void* x, const void* w_fwd, const dsr_epilogue* e, void* y,
+                            dsr_stream_t s) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  if (!x || !w_fwd || !e) return dsr_fail(DSR_E_ARG, "conv_fwd: null pointer");
+  if (!y && !e->out_nchw_f32) return dsr_fail(DSR_E_ARG, "conv_fwd: no output");
+  if (e->act == DSR_ACT_PRELU && !e->prelu) return dsr_fail(DSR_E_ARG, "conv_fwd: PReLU needs its weight pointer");
+  if (e->pixel_shuffle && (d->Cout % 4 || d->Cout < 32 || e->out_nchw_f32 || e->stats_partial))
+    return dsr_fail(DSR_E_UNSUPPORTED, "conv_fwd: pixel-shuffle epilogue needs Cout %% 4 == 0, Cout >= 32, 16-bit output");
+  const ConvPlan p = plan_fwd(d, e);
+  if ((e->bn_scale || e->bn_shift || e->residual) &&
+      (p.k != ConvKernel::C64 || e->pixel_shuffle || e->out_nchw_f32 || e->stats_partial || (!e->bn_scale) != (!e->bn_shift)))
+    return dsr_fail(DSR_E_UNSUPPORTED, "conv_fwd: folded BatchNorm / residual epilogue not available for this layer");
+  switch (p.k) {
+    case ConvKernel::Halo64: {
+      Halo64Args q;
+      memset(&q, 0, sizeof(q));
+      q.x = x;
+      q.w = w_fwd;
+      q.y = y;
+      q.bias = e->bias;
+      q.H = d->H;
+      q.W = d->W;
+      q.CinP = r8(d->Cin);
+      q.cout_full = d->Cout;
+      q.mirror = 0;
+      q.act = e->act;
+      q.slope = e->slope;
+      q.flags = e->bias ? DSR_F_BIAS : 0;
+      dsr_launch_conv_halo64(q, d->N, d->dtype, s);
+      return dsr_launch_status("dsr_conv_fwd(halo64)");
+    }
+    case ConvKernel::C64: {
+      C64Args c;
+      memset(&c, 0, sizeof(c));
+      c.CoutP = d->Cout;
+      c.scale = e->bn_scale;
+      c.shift = e->bn_shift;
+      c.res = e->residual;
+      c.x = x;
+      c.w = w_fwd;
+      c.y = y;
+      c.bias = e->bias;
+      c.prelu = e->prelu;
+      c.stats = e->stats_partial;
+      c.H = d->H;
+      c.W = d->W;
+      c.act = e->act;
+      c.slope = e->slope;
+      c.flags = fwd_flags(e);
+      for (int kh = 0; kh < 3; ++kh)
+        for (int kw = 0; kw < 3; ++kw) {
+          c.tap_y[kh * 3 + kw] = kh;
+          c.tap_x[kh * 3 + kw] = kw;
+        }
+      dsr_launch_conv_c64(c, d->N, d->dtype, s);
+      return dsr_launch_status("dsr_conv_fwd(c64)");
+    }
+    case ConvKernel::Rgb9:
+    case ConvKernel::Cin8: {
+      Cin8Args c;
+      memset(&c, 0, sizeof(c));
+      c.x = x;
+      c.w = w_fwd;
+      c.y = y;
+      c.bias = e->bias;
+      c.prelu = (e->act == DSR_ACT_PRELU) ? e->prelu : nullptr;
+      c.H = d->H;
+      c.W = d->W;
+      c.act = e->act;
+      c.slope = e->slope;
+      if (p.k == ConvKernel::Rgb9) {
+        dsr_launch_conv_rgb9(c, d->N, d->dtype, s);
+        return dsr_launch_status("dsr_conv_fwd(rgb9)");
+      }
+      dsr_launch_conv_cin8(c, d->N, d->dtype, s);
+      return dsr_launch_status("dsr_conv_fwd(cin8)");
+    }
+    case ConvKernel::SmallN: {
+      int OH, OW;
+      dsr_conv_out_size(d, &OH, &OW);
+      SmallNArgs sn;
+      memset(&sn, 0, sizeof(sn));
+      sn.x = x;
+      sn.w = w_fwd;
+      sn.y = y;
+      sn.out_f32 = e->out_nchw_f32;
+      sn.bias = e->bias;
+      sn.prelu = (e->act == DSR_ACT_PRELU) ? e->prelu : nullptr;
+      sn.IH = d->H;
+      sn.IW = d->W;
+      sn.CinP = r8(d->Cin);
+      sn.OH = OH;
+      sn.OW = OW;
+      sn.CoutP = r8(d->Cout);
+      sn.NB = r8(d->Cout);
+      sn.cout = d->Cout;
+      sn.KH = d->KH;
+      sn.KW = d->KW;
+      sn.pad = d->pad;
+      sn.act = e->act;
+      sn.slope = e->slope;
+      dsr_launch_conv_smalln(sn, d->N, d->dtype, s);
+      return dsr_launch_status("dsr_conv_fwd(small-n)");
+    }
+    default: {
+      ConvGemmArgs a;
+      fwd_gemm_args(d, e, x, w_fwd, y, a);
+      dsr_launch_conv_gemm(a, p.tile, d->dtype, s);
+      return dsr_launch_status("dsr_conv_fwd");
+    }
+  }
 }
 
 // ---- reflect-padding adjoint: dx[i][j] = sum of dxp over the padded coordinates that mirror onto (i,j)
@@ -352,7 +396,78 @@ extern "C" size_t dsr_conv_dgrad_workspace(const dsr_conv_desc* d) {
   return (size_t)d->N * (d->H + 2 * d->pad) * (d->W + 2 * d->pad) * r8(d->Cin) * 2;
 }
 
-static bool dgrad_mask_supported(const dsr_conv_desc* d);
+// the gather kernel's arguments of output-parity class (ph, pw) of an input gradient; false if the class is empty.  With
+// reflect padding the gradient is first taken w.r.t. the PADDED input (a pad = 0 problem into the workspace), then folded.
+static bool dgrad_gemm_args(const dsr_conv_desc* d, int ph, int pw, const void* dy, const void* w, void* target,
+                            const void* mask_x, int mask_act, float mask_slope, ConvGemmArgs& a) {
+  int OH, OW;
+  dsr_conv_out_size(d, &OH, &OW);
+  const bool folded = d->pad_mode == DSR_PAD_REFLECT && d->pad > 0;
+  const int H = folded ? d->H + 2 * d->pad : d->H;
+  const int W = folded ? d->W + 2 * d->pad : d->W;
+  const int pad = folded ? 0 : d->pad;
+  const int st = d->stride;
+  const int GH = (H - ph + st - 1) / st, GW = (W - pw + st - 1) / st;
+  if (GH <= 0 || GW <= 0) return false;
+  memset(&a, 0, sizeof(a));
+  a.x = dy;
+  a.w = w;
+  a.y = target;
+  a.GH = GH;
+  a.GW = GW;
+  a.M = d->N * GH * GW;
+  a.IH = OH;
+  a.IW = OW;
+  a.CinP = r8(d->Cout);
+  a.NB = r8(d->Cin);
+  a.cout = d->Cin;
+  a.CoutP = r8(d->Cin);
+  a.OH = H;
+  a.OW = W;
+  a.isy = a.isx = 1;
+  a.osy = a.osx = st;
+  a.ooy = ph;
+  a.oox = pw;
+  a.pad_mode = DSR_PAD_ZERO;
+  a.act = DSR_ACT_NONE;
+  a.mask_x = mask_x;
+  a.mask_act = mask_act;
+  a.mask_slope = mask_slope;
+  int nt = 0;
+  for (int kh = 0; kh < d->KH; ++kh) {
+    if ((ph + pad - kh) % st != 0) continue;
+    for (int kw = 0; kw < d->KW; ++kw) {
+      if ((pw + pad - kw) % st != 0) continue;
+      // C '/' truncates toward zero, but (ph+pad-kh) is an exact multiple of st here
+      a.taps[nt++] = pack_tap((ph + pad - kh) / st, (pw + pad - kw) / st, kh * d->KW + kw);
+    }
+  }
+  a.ntaps = nt;
+  finish_args(a, d->N, d->KH * d->KW);
+  return true;
+}
+
+static ConvPlan plan_dgrad(const dsr_conv_desc* d, const void* mask_x) {
+  const bool folded = d->pad_mode == DSR_PAD_REFLECT && d->pad > 0;
+  // mirrored taps on the [tap][ci][co] weight image; dx = dgrad(dy) * act'(mask_x) rides on the residual-tile mode
+  if (is_c64(d)) return {ConvKernel::C64, dsr_c64_mode(mask_x ? DSR_F_RESIDUAL | DSR_F_MASK : 0, DSR_ACT_NONE, 64)};
+  // the generator's 9x9 64->3 tail: Toeplitz K = (kw, co) mapping (conv_smalln.hip)
+  if (is_tail9(d)) return {ConvKernel::Toeplitz9};
+  // few input channels (the RGB first layers, discriminator.py:22): dx = dy correlated with the mirrored kernel, a stride-1
+  // "forward" problem with Cin output channels -> the halo-staged small-N kernel
+  if (is_smalln_dgrad(d) && dsr_smalln_fits(d->KH, d->KW, r8(d->Cout), d->Cin)) return {ConvKernel::SmallN};
+  // 64 input channels of a layer with 128 / 256 outputs (PixelShuffle convs, D's 64 -> 128, VGG conv2_1): the gradient is a
+  // 64-output convolution over many channels -- halo staged per 32-channel K-block (conv_halo64.hip)
+  if (!folded && dsr_halo64_supported(d->KH, d->KW, d->stride, d->pad, d->pad_mode, d->H, d->W, r8(d->Cout), r8(d->Cin)))
+    return {ConvKernel::Halo64};
+  // 3x3 stride 2 (discriminator.py:29-35): all four output-parity classes from one staged dY tile, one launch
+  if (!folded && dsr_dgrad_s2_supported(d->KH, d->KW, d->stride, d->pad, d->pad_mode, d->H, d->W, r8(d->Cin), r8(d->Cout), d->N))
+    return {ConvKernel::DgradS2};
+  // the gather kernel: grid = the input pixels (stride 1) or one output-parity class of them per launch (stride 2)
+  ConvGemmArgs a;
+  dgrad_gemm_args(d, 0, 0, nullptr, nullptr, nullptr, mask_x, DSR_ACT_NONE, 0.f, a);
+  return {ConvKernel::Gemm, 0, dsr_conv_gemm_plan(a)};
+}
 
 // mask_x != null: dx = dgrad(dy) * act'(mask_x) (dsr_conv_dgrad_masked; the caller has checked dgrad_mask_supported)
 static int conv_dgrad_impl(const dsr_conv_desc* d, const void* dy, const void* w_dgrad, void* dx, void* workspace,
@@ -362,126 +477,83 @@ static int conv_dgrad_impl(const dsr_conv_desc* d, const void* dy, const void* w
   if (!dy || !w_dgrad || !dx) return dsr_fail(DSR_E_ARG, "conv_dgrad: null pointer");
   if (d->pad_mode == DSR_PAD_REPLICATE && d->pad > 0)
     return dsr_fail(DSR_E_UNSUPPORTED, "conv_dgrad: replicate padding has no consumer on the hot path");
-  int OH, OW;
-  dsr_conv_out_size(d, &OH, &OW);
   const bool folded = d->pad_mode == DSR_PAD_REFLECT && d->pad > 0;
-  // with reflect padding the gradient is first taken w.r.t. the PADDED input (pad = 0 problem), then folded
-  const int H = folded ? d->H + 2 * d->pad : d->H;
-  const int W = folded ? d->W + 2 * d->pad : d->W;
-  const int pad = folded ? 0 : d->pad;
   void* target = dx;
   if (folded) {
     size_t need = dsr_conv_dgrad_workspace(d);
     if (!workspace || ws_bytes < need) return dsr_fail(DSR_E_WORKSPACE, "conv_dgrad: workspace %zu < %zu", ws_bytes, need);
     target = workspace;
   }
-  if (is_c64(d)) {   // mirrored taps on the [tap][ci][co] weight image
-    launch_c64_dgrad(d, dy, w_dgrad, mask_x, dx, s, mask_act, mask_slope);
-    return dsr_launch_status("dsr_conv_dgrad(c64)");
+  switch (plan_dgrad(d, mask_x).k) {
+    case ConvKernel::C64:
+      launch_c64_dgrad(d, dy, w_dgrad, mask_x, dx, s, mask_act, mask_slope);
+      return dsr_launch_status("dsr_conv_dgrad(c64)");
+    case ConvKernel::Toeplitz9:
+      dsr_launch_dgrad_toeplitz(dy, w_dgrad, dx, d->N, d->H, d->W, d->dtype, s);
+      return dsr_launch_status("dsr_conv_dgrad(toeplitz)");
+    case ConvKernel::SmallN: {
+      int OH, OW;
+      dsr_conv_out_size(d, &OH, &OW);
+      SmallNArgs sn;
+      memset(&sn, 0, sizeof(sn));
+      sn.x = dy;
+      sn.w = w_dgrad;
+      sn.y = dx;
+      sn.IH = OH;
+      sn.IW = OW;
+      sn.CinP = r8(d->Cout);
+      sn.OH = d->H;
+      sn.OW = d->W;
+      sn.CoutP = r8(d->Cin);
+      sn.NB = r8(d->Cin);
+      sn.cout = d->Cin;
+      sn.KH = d->KH;
+      sn.KW = d->KW;
+      sn.pad = d->KH - 1 - d->pad;
+      sn.act = DSR_ACT_NONE;
+      sn.flip = 1;
+      dsr_launch_conv_smalln(sn, d->N, d->dtype, s);
+      return dsr_launch_status("dsr_conv_dgrad(small-n)");
+    }
+    case ConvKernel::Halo64: {
+      Halo64Args q;
+      memset(&q, 0, sizeof(q));
+      q.x = dy;
+      q.w = w_dgrad;
+      q.y = dx;
+      q.H = d->H;
+      q.W = d->W;
+      q.CinP = r8(d->Cout);
+      q.cout_full = r8(d->Cin);
+      q.mirror = 1;
+      q.act = DSR_ACT_NONE;
+      q.mask_x = mask_x;
+      q.mask_act = mask_act;
+      q.mask_slope = mask_slope;
+      dsr_launch_conv_halo64(q, d->N, d->dtype, s);
+      return dsr_launch_status("dsr_conv_dgrad(halo64)");
+    }
+    case ConvKernel::DgradS2: {
+      DgradS2Args q;
+      memset(&q, 0, sizeof(q));
+      q.dy = dy;
+      q.w = w_dgrad;
+      q.dx = dx;
+      q.H = d->H;
+      q.W = d->W;
+      q.CinP = r8(d->Cin);
+      q.CoutP = r8(d->Cout);
+      dsr_launch_dgrad_s2(q, d->N, d->dtype, s);
+      return dsr_launch_status("dsr_conv_dgrad(s2)");
+    }
+    default:
+      break;
   }
-  if (is_tail9(d)) {   // the generator's 9x9 64->3 tail: Toeplitz K = (kw, co) mapping (conv_smalln.hip)
-    dsr_launch_dgrad_toeplitz(dy, w_dgrad, dx, d->N, d->H, d->W, d->dtype, s);
-    return dsr_launch_status("dsr_conv_dgrad(toeplitz)");
-  }
-  if (is_smalln_dgrad(d)) {
-    // few input channels (the RGB first layers, discriminator.py:22): dx = dy correlated with the mirrored kernel,
-    // a stride-1 "forward" problem with Cin output channels -> the halo-staged small-N kernel
-    SmallNArgs sn;
-    memset(&sn, 0, sizeof(sn));
-    sn.x = dy;
-    sn.w = w_dgrad;
-    sn.y = dx;
-    sn.IH = OH;
-    sn.IW = OW;
-    sn.CinP = r8(d->Cout);
-    sn.OH = d->H;
-    sn.OW = d->W;
-    sn.CoutP = r8(d->Cin);
-    sn.NB = r8(d->Cin);
-    sn.cout = d->Cin;
-    sn.KH = d->KH;
-    sn.KW = d->KW;
-    sn.pad = d->KH - 1 - d->pad;
-    sn.act = DSR_ACT_NONE;
-    sn.flip = 1;
-    if (dsr_launch_conv_smalln(sn, d->N, d->dtype, s)) return dsr_launch_status("dsr_conv_dgrad(small-n)");
-  }
-  if (!folded && dsr_halo64_supported(d->KH, d->KW, d->stride, d->pad, d->pad_mode, d->H, d->W, r8(d->Cout), r8(d->Cin))) {
-    // 64 input channels of a layer with 128 / 256 outputs (PixelShuffle convs, D's 64 -> 128, VGG conv2_1): the gradient is a
-    // 64-output convolution over many channels -- halo staged per 32-channel K-block (conv_halo64.hip)
-    Halo64Args q;
-    memset(&q, 0, sizeof(q));
-    q.x = dy;
-    q.w = w_dgrad;
-    q.y = dx;
-    q.H = d->H;
-    q.W = d->W;
-    q.CinP = r8(d->Cout);
-    q.cout_full = r8(d->Cin);
-    q.mirror = 1;
-    q.act = DSR_ACT_NONE;
-    q.mask_x = mask_x;
-    q.mask_act = mask_act;
-    q.mask_slope = mask_slope;
-    dsr_launch_conv_halo64(q, d->N, d->dtype, s);
-    return dsr_launch_status("dsr_conv_dgrad(halo64)");
-  }
-  if (!folded && dsr_dgrad_s2_supported(d->KH, d->KW, d->stride, d->pad, d->pad_mode, d->H, d->W, r8(d->Cin), r8(d->Cout), d->N)) {
-    // 3x3 stride 2 (discriminator.py:29-35): all four output-parity classes from one staged dY tile, one launch
-    DgradS2Args q;
-    memset(&q, 0, sizeof(q));
-    q.dy = dy;
-    q.w = w_dgrad;
-    q.dx = dx;
-    q.H = d->H;
-    q.W = d->W;
-    q.CinP = r8(d->Cin);
-    q.CoutP = r8(d->Cout);
-    dsr_launch_dgrad_s2(q, d->N, d->dtype, s);
-    return dsr_launch_status("dsr_conv_dgrad(s2)");
-  }
-  const int st = d->stride;
-  for (int ph = 0; ph < st; ++ph)
-    for (int pw = 0; pw < st; ++pw) {
-      int GH = (H - ph + st - 1) / st, GW = (W - pw + st - 1) / st;
-      if (GH <= 0 || GW <= 0) continue;
+  for (int ph = 0; ph < d->stride; ++ph)
+    for (int pw = 0; pw < d->stride; ++pw) {
       ConvGemmArgs a;
-      memset(&a, 0, sizeof(a));
-      a.x = dy;
-      a.w = w_dgrad;
-      a.y = target;
-      a.GH = GH;
-      a.GW = GW;
-      a.M = d->N * GH * GW;
-      a.IH = OH;
-      a.IW = OW;
-      a.CinP = r8(d->Cout);
-      a.NB = r8(d->Cin);
-      a.cout = d->Cin;
-      a.CoutP = r8(d->Cin);
-      a.OH = H;
-      a.OW = W;
-      a.isy = a.isx = 1;
-      a.osy = a.osx = st;
-      a.ooy = ph;
-      a.oox = pw;
-      a.pad_mode = DSR_PAD_ZERO;
-      a.act = DSR_ACT_NONE;
-      a.mask_x = mask_x;
-      a.mask_act = mask_act;
-      a.mask_slope = mask_slope;
-      int nt = 0;
-      for (int kh = 0; kh < d->KH; ++kh) {
-        if ((ph + pad - kh) % st != 0) continue;
-        for (int kw = 0; kw < d->KW; ++kw) {
-          if ((pw + pad - kw) % st != 0) continue;
-          // C '/' truncates toward zero, but (ph+pad-kh) is an exact multiple of st here
-          a.taps[nt++] = pack_tap((ph + pad - kh) / st, (pw + pad - kw) / st, kh * d->KW + kw);
-        }
-      }
-      a.ntaps = nt;
-      finish_args(a, d->N, d->KH * d->KW);
-      dsr_launch_conv_gemm(a, d->dtype, s);
+      if (dgrad_gemm_args(d, ph, pw, dy, w_dgrad, target, mask_x, mask_act, mask_slope, a))
+        dsr_launch_conv_gemm(a, dsr_conv_gemm_plan(a), d->dtype, s);
     }
   if (folded) {
     size_t total = (size_t)d->N * d->H * d->W * (r8(d->Cin) / 8);
@@ -787,46 +859,22 @@ extern "C" int dsr_conv_wgrad_batched(int count, const dsr_conv_desc* descs, con
   return dsr_launch_status("dsr_conv_wgrad_batched");
 }
 
-// ---- measurement aid: the kernel family the dispatch above selects (kept next to it so the two cannot drift far)
-static const char* gemm_name(int nb, long long M = 0, bool fast = false, bool stats = true, int flags = 0) {
-  if (nb > 64 && dsr_conv_gemm_use_224(M, nb, fast, flags | (stats ? DSR_F_STATS : 0))) return "conv_gemm_kernel<224x256>";
-  if (nb > 64 && dsr_conv_gemm_use_256(M, nb, fast, stats)) return "conv_gemm_kernel<256x256>";
-  if (nb > 64 && dsr_conv_gemm_use_64(M, nb, fast, flags | (stats ? DSR_F_STATS : 0))) return "conv_gemm_kernel<64x128>";
-  return nb > 64 ? "conv_gemm_kernel<128x128>" : (nb > 16 ? "conv_gemm_kernel<128x64>" : "conv_gemm_kernel<128x16>");
+// ---- measurement aid: the kernel a call launches, named like the symbols of a rocprof summary (from the plans above)
+static const char* plan_name(const ConvPlan& p) {
+  static const char* const c64[] = {"conv_c64_kernel<0>", "conv_c64_kernel<1>", "conv_c64_kernel<2>", "conv_c64_kernel<3>"};
+  static const char* const kernel[] = {nullptr, "conv_halo64_kernel", "conv_cin8_kernel", "conv_rgb9_kernel", "conv_smalln_kernel",
+                                       "conv_dgrad_toeplitz9_kernel", "conv_dgrad_s2_kernel"};   // (ConvKernel order)
+  static const char* const tile[] = {"conv_gemm_persist_kernel", "conv_gemm_kernel<224x256>", "conv_gemm_kernel<256x256>",
+                                     "conv_gemm_kernel<64x128>", "conv_gemm_kernel<128x128>", "conv_gemm_kernel<128x64>",
+                                     "conv_gemm_kernel<128x16>"};   // (GemmTile order)
+  if (p.k == ConvKernel::C64) return c64[p.c64_mode];
+  return p.k == ConvKernel::Gemm ? tile[(int)p.tile] : kernel[(int)p.k];
 }
 extern "C" const char* dsr_conv_kernel_name(const dsr_conv_desc* d, int op, const dsr_epilogue* e) {
   if (!d || check_desc(d)) return "invalid";
-  const bool ps = e && e->pixel_shuffle, nchw = e && e->out_nchw_f32, stats = e && e->stats_partial;
-  if (op == 0) {
-    // (named like the symbols of a rocprof summary: <mode 0> statistics epilogue, <1> plain, <2> folded inference epilogue)
-    if (((is_c64(d) && !ps) || is_c64_wide(d)) && !nchw)
-      return (e && (e->bn_scale || e->residual)) ? "conv_c64_kernel<2>" : (stats ? "conv_c64_kernel<0>" : "conv_c64_kernel<1>");
-    if (!ps && !nchw && !stats && !(e && (e->bn_scale || e->residual)) && d->Cout % 64 == 0 && d->Cout >= 128 &&
-        (!e || e->act == DSR_ACT_NONE || e->act == DSR_ACT_RELU || e->act == DSR_ACT_LEAKY) &&
-        dsr_halo64_supported(d->KH, d->KW, d->stride, d->pad, d->pad_mode, d->H, d->W, r8(d->Cin), d->Cout))
-      return "conv_halo64_kernel";
-    if (is_cin8(d, e)) return "conv_cin8_kernel";
-    if (is_rgb9(d, e)) return "conv_rgb9_kernel";
-    if (d->Cout <= 16 && d->stride == 1 && d->pad_mode == DSR_PAD_ZERO && d->KH * d->KW >= 9 && !stats && !ps &&
-        d->KW == 9 && d->KH <= 9 && r8(d->Cin) == 64)
-      return "conv_smalln_kernel";
-    int OH, OW;
-    dsr_conv_out_size(d, &OH, &OW);
-    return gemm_name(r8(d->Cout), (long long)d->N * OH * OW, d->pad_mode == DSR_PAD_ZERO && r8(d->Cin) % 64 == 0, stats,
-                     (ps ? DSR_F_PIXSHUF : 0) | (nchw ? DSR_F_OUT_NCHW_F32 : 0));
-  }
-  if (op == 1) {
-    if (is_c64(d)) return "conv_c64_kernel<1>";
-    if (is_tail9(d)) return "conv_dgrad_toeplitz9_kernel";
-    if (is_smalln_dgrad(d)) return "conv_smalln_kernel";
-    if (dsr_halo64_supported(d->KH, d->KW, d->stride, d->pad, d->pad_mode, d->H, d->W, r8(d->Cout), r8(d->Cin)))
-      return "conv_halo64_kernel";
-    if (dsr_dgrad_s2_supported(d->KH, d->KW, d->stride, d->pad, d->pad_mode, d->H, d->W, r8(d->Cin), r8(d->Cout), d->N))
-      return "conv_dgrad_s2_kernel";
-    // input gradient on the gather kernel: grid = the input pixels (stride 1) or one output-parity class of them (stride 2)
-    const long long Mg = (long long)d->N * ((d->H + d->stride - 1) / d->stride) * ((d->W + d->stride - 1) / d->stride);
-    return gemm_name(r8(d->Cin), Mg, r8(d->Cout) % 64 == 0 && (d->pad_mode == DSR_PAD_ZERO || d->pad == 0), false);
-  }
+  static const dsr_epilogue none = {};
+  if (op == 0) return plan_name(plan_fwd(d, e ? e : &none));
+  if (op == 1) return plan_name(plan_dgrad(d, nullptr));
   if (is_rgb9_wgrad(d)) return "conv_rgb9_wgrad_kernel";
   WgradTileArgs t;
   bool taps = false;

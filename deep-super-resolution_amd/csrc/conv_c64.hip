@@ -533,14 +533,18 @@ static void c64_launch(const C64Args& a, dim3 grid, hipStream_t st) {
   hipLaunchKernelGGL(fn, grid, dim3(256), LDS, st, a);
 }
 
-void dsr_launch_conv_c64(C64Args& a, int N, int dtype, hipStream_t st) {
-  const int slices = a.CoutP / 64;                            // blockIdx.y: 64-channel slice of the output
-  const bool fold = (a.flags & (DSR_F_AFFINE | DSR_F_RESIDUAL)) != 0;
+int dsr_c64_mode(int flags, int act, int CoutP) {
+  const bool fold = (flags & (DSR_F_AFFINE | DSR_F_RESIDUAL)) != 0;
   // residual alone, no activation, no PixelShuffle, one 64-channel slice (the input gradient of a residual block): mode 3
   // (DSR_F_MASK rides on the same prefetch: the tile is then an activation output whose derivative multiplies the result)
-  const bool res_only = (a.flags & DSR_F_RESIDUAL) && !(a.flags & (DSR_F_AFFINE | DSR_F_PIXSHUF | DSR_F_STATS)) &&
-                        a.act == DSR_ACT_NONE && slices == 1;
-  const int mode = res_only ? 3 : (fold ? 2 : ((a.flags & DSR_F_STATS) ? 0 : 1));
+  const bool res_only = (flags & DSR_F_RESIDUAL) && !(flags & (DSR_F_AFFINE | DSR_F_PIXSHUF | DSR_F_STATS)) &&
+                        act == DSR_ACT_NONE && CoutP == 64;
+  return res_only ? 3 : (fold ? 2 : ((flags & DSR_F_STATS) ? 0 : 1));
+}
+
+void dsr_launch_conv_c64(C64Args& a, int N, int dtype, hipStream_t st) {
+  const int slices = a.CoutP / 64;                            // blockIdx.y: 64-channel slice of the output
+  const int mode = dsr_c64_mode(a.flags, a.act, a.CoutP);
   int tr = c64_tile_rows(mode);
   if (mode == 2) {
     // inference images are often a few tiles per block only: take the tile height (2 or 3 rows) with the shorter longest

@@ -35,10 +35,10 @@ struct ConvGemmLds {
 // pad = 'reflection'): the padded coordinate of every A row is recomputed per K-step (a dozen VALU instructions per piece)
 // instead of falling back to the register-staged generic loader -- 10.6 us against 23.6 us per 128 -> 128 layer at 128^2.
 template <int DT, int BM, int BN, int WGM, int WGN, bool FAST, bool DMA, int NSTAGE, bool SWAP, bool PADX = false>
-__global__ __launch_bounds__(64 * WGM * WGN, (NSTAGE == 3 || BM * BN >= 224 * 256) ? 2 : (WGM * WGN) / 2) void conv_gemm_kernel(const ConvGemmArgs a) {
+__global__ __launch_bounds__(64 * WGM * WGN, BM * BN >= 224 * 256 ? 2 : (WGM * WGN) / 2) void conv_gemm_kernel(const ConvGemmArgs a) {
   static_assert(!DMA || FAST, "the LDS-DMA loader exists for the fast path only");
   static_assert(!PADX || (DMA && NSTAGE == 2 && WGM * WGN == 4), "padded-coordinate form: 4-wave two-stage DMA kernels only");
-  static_assert(NSTAGE == 2 || (NSTAGE == 3 && DMA), "three stages: DMA ring only");
+  static_assert(NSTAGE == 2, "two LDS stages");
   constexpr int NW = WGM * WGN;                 // 4 or 8 waves; two blocks per CU either way
   constexpr int NT = 64 * NW;
   constexpr int RPP = NT / 8;                   // tile rows covered by one pass of the loader (8 lanes per row)
@@ -209,8 +209,6 @@ __global__ __launch_bounds__(64 * WGM * WGN, (NSTAGE == 3 || BM * BN >= 224 * 25
         __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, (lds_ptr)(sB + stage * B_STAGE + (wave * 8 + RPP * i) * 128), 16,
                                                  (unsigned)(b_base[i] + d.woff), 0, 0, 0);
   };
-  // LDS-DMA variant of load_step: `buffer_load_dwordx4 ... lds` writes 64 lanes x 16 B = 8 tile rows straight into
-  // the stage (an out-of-range offset writes zeros), so the operand tiles never pass through VGPRs.
   [[maybe_unused]] auto dma_step = [&](int s, int stage) { dma_issue(decode_step(s), stage); };
   int st_off[RA > RB ? RA : RB];
 #pragma unroll
@@ -285,24 +283,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (NSTAGE == 3 || BM * BN >= 224 * 25
   if constexpr (DMA) {
     // One barrier per K-step: {wait for my own DMA of step s; barrier: step s has landed for every wave and every
     // wave is done reading the other stage; start the DMA of step s+1 into that stage; 32 MFMAs on step s}.
-    auto compute_flat = [&](int cur) {
-      const unsigned char* pa = sA + cur * A_STAGE + (wm * WM + r16) * 128;
-      const unsigned char* pb = sB + cur * B_STAGE + (wn * WN + r16) * 128;
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const int slot = ((4 * kk + g) ^ sw) << 4;
-        U4 fa[TM], fb[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const U4*>(pa + i * 16 * 128 + slot);
-#pragma unroll
-        for (int k = 0; k < TN; ++k) fb[k] = *reinterpret_cast<const U4*>(pb + k * 16 * 128 + slot);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int k = 0; k < TN; ++k) acc[i][k] = SWAP ? mfma16<DT>(fb[k], fa[i], acc[i][k]) : mfma16<DT>(fa[i], fb[k], acc[i][k]);
-      }
-    };
-    if constexpr (NSTAGE == 2 && NW == 8) {
+    if constexpr (NW == 8) {
       // 256x256 tile, 8 waves of 128x64, ONE resident block per CU (two waves per SIMD, 256 registers each: 128 of them
       // accumulators).  Per K-step and wave: 24 ds_read_b128 and 64 MFMAs (0.375 reads per MFMA; the 64x64 wave tile
       // of the 128x128 variant needs 0.5 and saturates the LDS at full MFMA rate) and 8 DMA pieces per 64 MFMAs (half
@@ -356,7 +337,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (NSTAGE == 3 || BM * BN >= 224 * 25
           }
         }
       }
-    } else if constexpr (NSTAGE == 2) {
+    } else {
       dma_step(0, 0);
       TapStep nd = decode_step(ks > 1 ? 1 : 0);      // the tap table read of the NEXT step is kept out of the loop body's
       for (int s = 0; s < ks; ++s) {                 // head: it shares the LDS counter with the fragment reads
@@ -398,26 +379,6 @@ __global__ __launch_bounds__(64 * WGM * WGN, (NSTAGE == 3 || BM * BN >= 224 * 25
         for (int i = 0; i < TM; ++i)
 #pragma unroll
           for (int k = 0; k < TN; ++k) acc[i][k] = SWAP ? mfma16<DT>(fb2[k], fa2[i], acc[i][k]) : mfma16<DT>(fa2[i], fb2[k], acc[i][k]);
-      }
-    } else {
-      // three-stage ring, one resident block per CU: the DMA of step s+2 is issued before the MFMAs of step s, so a
-      // tile has two full compute phases to land.  At the top of step s the groups of steps s and s+1 are in
-      // flight; vmcnt(NDMA) retires the older one only (a wave issues exactly NDMA DMA instructions per step).
-      constexpr int NDMA = RA + (BN + RPP - 1) / RPP;
-      dma_step(0, 0);
-      if (ks > 1) dma_step(1, 1);
-      int cur = 0, nxt2 = 2;
-      for (int s = 0; s < ks; ++s) {
-        if (s + 1 < ks)
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDMA) : "memory");
-        else
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (s + 2 < ks) dma_step(s + 2, nxt2);
-        compute_flat(cur);
-        cur = cur == 2 ? 0 : cur + 1;
-        nxt2 = nxt2 == 2 ? 0 : nxt2 + 1;
       }
     }
     __syncthreads();   // the epilogue reuses the stages as its C tile
@@ -733,10 +694,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, (NSTAGE == 3 || BM * BN >= 224 * 25
   }
 }
 
-template <int DT, int BM, int BN, int WGM, int WGN, bool FAST, bool DMA, int NSTAGE, bool SWAP, bool PADX = false>
+template <int DT, int BM, int BN, int WGM, int WGN, bool FAST, bool DMA, bool SWAP, bool PADX = false>
 static void launch_swap(dim3 grid, const ConvGemmArgs& b, hipStream_t st) {
-  constexpr int LDS = ConvGemmLds<BM, BN, WGM, NSTAGE>::TOTAL;
-  auto* fn = conv_gemm_kernel<DT, BM, BN, WGM, WGN, FAST, DMA, NSTAGE, SWAP, PADX>;
+  constexpr int LDS = ConvGemmLds<BM, BN, WGM, 2>::TOTAL;
+  auto* fn = conv_gemm_kernel<DT, BM, BN, WGM, WGN, FAST, DMA, 2, SWAP, PADX>;
   if constexpr (LDS > 64 * 1024) {   // more than 64 KB of dynamic LDS needs the opt-in, once per kernel (not a stream op)
     static LdsOptIn optin;
     optin.ensure((const void*)fn, LDS);
@@ -746,92 +707,112 @@ static void launch_swap(dim3 grid, const ConvGemmArgs& b, hipStream_t st) {
 
 // Launches that want BatchNorm statistics keep the pixel-major accumulator layout (a channel's column sum is then an
 // in-lane sum plus two shuffles); all others use the channel-major one (SWAP: packed 8-byte C-tile writes).
-template <int DT, int BM, int BN, int WGM, int WGN, bool FAST, bool DMA, int NSTAGE, bool PADX = false>
+template <int DT, int BM, int BN, int WGM, int WGN, bool FAST, bool DMA, bool PADX = false>
 static void launch_variant(dim3 grid, const ConvGemmArgs& b, hipStream_t st) {
   if constexpr (DMA) {
     // (the 256x256 tile has no register room for the pixel-major epilogue: it takes its statistics from the
     //  channel-major accumulators -- 16-lane shuffle sums -- as well)
     if (!(b.flags & DSR_F_STATS) || BM >= 224) {
-      launch_swap<DT, BM, BN, WGM, WGN, FAST, DMA, NSTAGE, true, PADX>(grid, b, st);
+      launch_swap<DT, BM, BN, WGM, WGN, FAST, DMA, true, PADX>(grid, b, st);
       return;
     }
   }
   // statistics launches, and the register-staged variants (measured 10 % slower with the channel-major epilogue)
-  if constexpr (BM < 224) launch_swap<DT, BM, BN, WGM, WGN, FAST, DMA, NSTAGE, false, PADX>(grid, b, st);
+  if constexpr (BM < 224) launch_swap<DT, BM, BN, WGM, WGN, FAST, DMA, false, PADX>(grid, b, st);
 }
 
 static bool env_on(const char* name) {   // tuning switches, default on ("0" turns one off)
   const char* e = getenv(name);
   return !(e && e[0] == '0');
 }
+static int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+static bool dma_on() {
+  static const bool on = env_on("DSR_CONV_DMA");          // 0 = register-staged loader (the 8-wave tiles then are never taken)
+  return on;
+}
 
-template <int DT, int BM, int BN, int WGM, int WGN, int NSTAGE = 2>
+template <int DT, int BM, int BN, int WGM, int WGN>
 static void launch_one(const ConvGemmArgs& a, hipStream_t st) {
   ConvGemmArgs b = a;
   b.tiles_m = (a.M + BM - 1) / BM;
   b.tiles_n = (a.NB + BN - 1) / BN;
   dim3 grid(b.tiles_m * b.tiles_n);
-  const bool fast = a.pad_mode == DSR_PAD_ZERO && (a.CU & 7) == 0 && a.ntaps > 0;
-  if constexpr (NSTAGE == 3) {
-    launch_variant<DT, BM, BN, WGM, WGN, true, true, 3>(grid, b, st);
-    return;
-  } else {
-    if constexpr (BN >= 64) {
-      static const bool use_dma = env_on("DSR_CONV_DMA");      // 0 = register-staged loader
-      if (fast && use_dma) {
-        launch_variant<DT, BM, BN, WGM, WGN, true, true, 2>(grid, b, st);
+  const bool fast = dsr_conv_gemm_fast(a);
+  if constexpr (BN >= 64) {
+    if (fast && dma_on()) {
+      launch_variant<DT, BM, BN, WGM, WGN, true, true>(grid, b, st);
+      return;
+    }
+    if constexpr (BM == 128 && BN == 128) {                 // reflect / replicate padding on the DMA path (the 128-channel DIP layers)
+      const bool padx = env_on("DSR_CONV_PADX");            // 0 = the register-staged generic loader (read per call: a test compares the two)
+      if (padx && dma_on() && a.pad_mode != DSR_PAD_ZERO && (a.CU & 7) == 0 && a.ntaps > 0) {
+        launch_variant<DT, BM, BN, WGM, WGN, true, true, true>(grid, b, st);
         return;
       }
-      if constexpr (BM == 128 && BN == 128) {                 // reflect / replicate padding on the DMA path (the 128-channel DIP layers)
-        const bool padx = env_on("DSR_CONV_PADX");            // 0 = the register-staged generic loader (read per call: a test compares the two)
-        if (padx && use_dma && a.pad_mode != DSR_PAD_ZERO && (a.CU & 7) == 0 && a.ntaps > 0) {
-          launch_variant<DT, BM, BN, WGM, WGN, true, true, 2, true>(grid, b, st);
-          return;
-        }
-      }
-    }
-    if constexpr (BM < 224) {       // (the 8-wave tiles exist as the LDS-DMA fast path only; dispatch_dt guarantees it)
-      if (fast)
-        launch_variant<DT, BM, BN, WGM, WGN, true, false, 2>(grid, b, st);
-      else
-        launch_variant<DT, BM, BN, WGM, WGN, false, false, 2>(grid, b, st);
     }
   }
+  if constexpr (BM < 224) {       // (the 8-wave tiles exist as the LDS-DMA fast path only; dsr_conv_gemm_plan guarantees it)
+    if (fast)
+      launch_variant<DT, BM, BN, WGM, WGN, true, false>(grid, b, st);
+    else
+      launch_variant<DT, BM, BN, WGM, WGN, false, false>(grid, b, st);
+  }
+}
+
+// The tile of a launch, chosen on its own arguments (dsr_conv_kernel_name names launches by the same call).  The switches
+// are read per call: tests flip them inside one process.
+//  * 256x256, 8 waves of 128x64, one block per CU: half the LDS fragment reads per MFMA (0.375 ds_read_b128 instead of 0.5)
+//    and half the DMA pieces of the 128x128 tile.  N % 256 == 0 and at least DSR_CONV_BIG_TILES tiles (default 150: a
+//    196-tile launch on 256 CUs still beats four times as many 128x128 tiles, VGG 512->512 at 28x28).  DSR_CONV_BIG=0: never.
+//  * 224x256 (7 m-tiles per wave): a launch whose 256-row tiles leave most of the chip idle in their last round (VGG19 at
+//    batch 32: 196 or 392 tiles on 256 CUs) runs as many rounds of tiles with 7/8 the work each.  Taken when that lowers
+//    rounds x rows per tile.  DSR_CONV_BM224: 0 = never, 1 (default) = by that cost, 2 = wherever 256x256 would be taken.
+//  * 64x128 (4 waves of 64x32): launches whose 128x128 tiles do not give every CU one block (VGG conv5_x at batch 32: 196).
+//    DSR_CONV_BM64: 0 = never, 1 (default) = fewer than 256 tiles of 128x128, 2 = wherever 128x128 would be taken.
+//  The 224- and 64-row tiles take no BatchNorm statistics (one row per 128 tile rows), PixelShuffle or NCHW stores.
+//  (8 waves of 64x32 on a 128x128 tile: LDS-bound, 35 % slower.)
+GemmTile dsr_conv_gemm_plan(const ConvGemmArgs& a) {
+  // (the persistent kernels keep a DMA in flight across their epilogue: no masked form)
+  if (!a.mask_x && dsr_conv_gemm_persist_fits(a)) return GemmTile::Persist64;
+  if (a.NB <= 16) return GemmTile::T128x16;
+  if (a.NB <= 64) return GemmTile::T128x64;
+  const bool dma_fast = dsr_conv_gemm_fast(a) && dma_on();
+  const bool plain = !(a.flags & (DSR_F_STATS | DSR_F_PIXSHUF | DSR_F_OUT_NCHW_F32));
+  const long long M = a.M, nt = (a.NB + 255) / 256;
+  if (env_on("DSR_CONV_BIG") && dma_fast && a.NB % 256 == 0 && ((M + 255) / 256) * nt >= env_int("DSR_CONV_BIG_TILES", 150)) {
+    const int bm224 = env_int("DSR_CONV_BM224", 1);
+    if (bm224 == 0 || !plain) return GemmTile::T256x256;
+    if (bm224 == 2) return GemmTile::T224x256;
+    const long long cus = 256;     // (a constant: names are asked for on hosts without a GPU too)
+    const long long r256 = (((M + 255) / 256) * nt + cus - 1) / cus, r224 = (((M + 223) / 224) * nt + cus - 1) / cus;
+    return r224 * 7 < r256 * 8 ? GemmTile::T224x256 : GemmTile::T256x256;
+  }
+  const int bm64 = env_int("DSR_CONV_BM64", 1);
+  if (bm64 != 0 && dma_fast && a.NB % 128 == 0 && plain && (bm64 == 2 || ((M + 127) / 128) * (a.NB / 128) < 256))
+    return GemmTile::T64x128;
+  return GemmTile::T128x128;
 }
 
 template <int DT>
-static void dispatch_dt(const ConvGemmArgs& a, hipStream_t st) {
-  if (a.NB > 64) {
-    // big problems: 256x128 tiles, 8 waves, three-stage DMA ring, one block per CU (needs >= 2 blocks per CU of work)
-    // measured: 5-12 % SLOWER than two resident 128x128 blocks on every config-3 layer, so it is off unless asked for
-    const bool use_big = true;
-    const bool fast = a.pad_mode == DSR_PAD_ZERO && (a.CU & 7) == 0 && a.ntaps > 0;
-    const long long big_tiles = (long long)((a.M + 255) / 256) * ((a.NB + 127) / 128);
-    // 256x256 tile, 8 waves of 128x64 (2 x 4), two stages, one block per CU: per MFMA half the LDS fragment reads
-    // (0.375 ds_read_b128 per MFMA instead of 0.5) and half the DMA pieces of the 128x128 tile
-    const int big_mode = dsr_conv_big_mode();
-    if (dsr_conv_gemm_use_224(a.M, a.NB, fast && env_on("DSR_CONV_DMA"), a.flags))
-      launch_one<DT, 224, 256, 2, 4>(a, st);
-    else if (dsr_conv_gemm_use_256(a.M, a.NB, fast && env_on("DSR_CONV_DMA"), (a.flags & DSR_F_STATS) != 0))
-      launch_one<DT, 256, 256, 2, 4>(a, st);
-    else if (use_big && big_mode == 1 && fast && big_tiles >= 512)
-      launch_one<DT, 256, 128, 4, 2, 3>(a, st);
-    else if (dsr_conv_gemm_use_64(a.M, a.NB, fast && env_on("DSR_CONV_DMA"), a.flags))
-      launch_one<DT, 64, 128, 1, 4>(a, st);        // few 128-row tiles (VGG conv5_x at batch 32: 196 blocks on 256 CUs): twice as many half-height tiles
-    else
-      launch_one<DT, 128, 128, 2, 2>(a, st);      // (8 waves of 64x32 were tried: LDS-bound, 35 % slower)
-  } else if (a.NB > 16)
-    launch_one<DT, 128, 64, 2, 2>(a, st);
-  else
-    launch_one<DT, 128, 16, 4, 1>(a, st);
+static void dispatch_dt(const ConvGemmArgs& a, GemmTile t, hipStream_t st) {
+  switch (t) {
+    case GemmTile::T224x256: launch_one<DT, 224, 256, 2, 4>(a, st); break;
+    case GemmTile::T256x256: launch_one<DT, 256, 256, 2, 4>(a, st); break;
+    case GemmTile::T64x128: launch_one<DT, 64, 128, 1, 4>(a, st); break;
+    case GemmTile::T128x128: launch_one<DT, 128, 128, 2, 2>(a, st); break;
+    case GemmTile::T128x64: launch_one<DT, 128, 64, 2, 2>(a, st); break;
+    default: launch_one<DT, 128, 16, 4, 1>(a, st); break;
+  }
 }
 
-void dsr_launch_conv_gemm(const ConvGemmArgs& a, int dtype, hipStream_t st) {
-  if (!a.mask_x) {          // (the persistent kernels keep a DMA in flight across their epilogue: no masked form)
-    if (dsr_launch_conv_gemm_persist(a, dtype, st)) return;   // many-tile fast-path launches: persistent kernel
-  }
-  if (dtype == DSR_DTYPE_BF16)
-    dispatch_dt<DSR_DTYPE_BF16>(a, st);
+void dsr_launch_conv_gemm(const ConvGemmArgs& a, GemmTile t, int dtype, hipStream_t st) {
+  if (t == GemmTile::Persist64)
+    dsr_launch_conv_gemm_persist(a, dtype, st);
+  else if (dtype == DSR_DTYPE_BF16)
+    dispatch_dt<DSR_DTYPE_BF16>(a, t, st);
   else
-    dispatch_dt<DSR_DTYPE_F16>(a, st);
+    dispatch_dt<DSR_DTYPE_F16>(a, t, st);
 }

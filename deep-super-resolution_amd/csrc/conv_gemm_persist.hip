@@ -385,25 +385,29 @@ static void launch_p(const ConvGemmArgs& b, int blocks, hipStream_t st) {
   hipLaunchKernelGGL(fn, dim3(blocks), dim3(256), LDS, st, b);
 }
 
-// returns false when the launch does not qualify (caller falls through to the one-tile-per-block kernel)
-bool dsr_launch_conv_gemm_persist(const ConvGemmArgs& a, int dtype, hipStream_t st) {
+static int persist_blocks(const ConvGemmArgs& a) {
+  return a.ksteps >= 24 ? 512 : 768;         // resident blocks per CU: 2 for long K loops, 3 otherwise; multiples of 8
+}
+
+// Measured on one box, persistent vs one-tile-per-block (profiles/r01_persist_ab.txt): 64-wide tiles gain (PixelShuffle
+// conv dgrad 256->64: +27 %, 64->64 stride 2: +8 %), 128-wide tiles do not (-1..-2 %: their fixed cost is epilogue
+// arithmetic, which persistence does not overlap).  So: fast-path launches 17..64 wide, with at least two tiles per
+// resident block (fewer: nothing to overlap).
+bool dsr_conv_gemm_persist_fits(const ConvGemmArgs& a) {
   static const bool enabled = [] {
     const char* e = getenv("DSR_CONV_PERSIST");          // tuning switch, default on
     return !(e && e[0] == '0');
   }();
-  const bool fast = a.pad_mode == DSR_PAD_ZERO && (a.CU & 7) == 0 && a.ntaps > 0;
-  if (!enabled || !fast || a.NB <= 16 || (a.flags & DSR_F_OUT_NCHW_F32)) return false;
-  // Measured on one box, persistent vs one-tile-per-block (profiles/r01_persist_ab.txt): 64-wide tiles gain (PixelShuffle
-  // conv dgrad 256->64: +27 %, 64->64 stride 2: +8 %), 128-wide tiles do not (-1..-2 %: their fixed cost is epilogue
-  // arithmetic, which persistence does not overlap).  So: BN = 64 only.
-  if (a.NB > 64) return false;
+  if (!enabled || !dsr_conv_gemm_fast(a) || a.NB <= 16 || a.NB > 64 || (a.flags & DSR_F_OUT_NCHW_F32)) return false;
+  return (long long)((a.M + 127) / 128) * ((a.NB + 63) / 64) >= 2 * persist_blocks(a);
+}
+
+void dsr_launch_conv_gemm_persist(const ConvGemmArgs& a, int dtype, hipStream_t st) {
   constexpr int BN = 64;
   ConvGemmArgs b = a;
   b.tiles_m = (a.M + 127) / 128;
   b.tiles_n = (a.NB + BN - 1) / BN;
-  const long long total = (long long)b.tiles_m * b.tiles_n;
-  const int blocks = a.ksteps >= 24 ? 512 : 768;         // resident blocks per CU: 2 for long K loops, 3 otherwise; multiples of 8
-  if (total < 2 * blocks) return false;                  // fewer than two tiles per resident block: nothing to overlap
+  const int blocks = persist_blocks(a);
   const bool swap = !(a.flags & DSR_F_STATS);
   if (dtype == DSR_DTYPE_BF16) {
     if (swap) launch_p<DSR_DTYPE_BF16, BN, true>(b, blocks, st);
@@ -412,5 +416,4 @@ bool dsr_launch_conv_gemm_persist(const ConvGemmArgs& a, int dtype, hipStream_t 
     if (swap) launch_p<DSR_DTYPE_F16, BN, true>(b, blocks, st);
     else launch_p<DSR_DTYPE_F16, BN, false>(b, blocks, st);
   }
-  return true;
 }

@@ -360,12 +360,18 @@ __global__ void zero_pad_channels_kernel(unsigned short* __restrict__ y, size_t 
 
 static LdsOptIn g_smalln_optin[4];
 
-int dsr_launch_conv_smalln(SmallNArgs& a, int N, int dtype, hipStream_t st) {
+static size_t smalln_lds(int KH, int KW, int cout) {   // halo tile + weights
+  const int HR = 8 + KH - 1, HC = (32 + KW - 1 + 7) & ~7;
+  return (size_t)HR * HC * 128 + (size_t)KH * KW * ((cout + 3) & ~3) * 128;
+}
+bool dsr_smalln_fits(int KH, int KW, int CinP, int cout) {
+  return smalln_lds(KH, KW, cout) <= 160 * 1024 && (KW == 9 || KW == 3) && KH <= 9 && CinP == 64;
+}
+
+void dsr_launch_conv_smalln(SmallNArgs& a, int N, int dtype, hipStream_t st) {
   a.tiles_y = (a.OH + 7) / 8;
   a.tiles_x = (a.OW + 31) / 32;
-  const int HR = 8 + a.KH - 1, HC = (32 + a.KW - 1 + 7) & ~7;
-  const size_t lds = (size_t)HR * HC * 128 + (size_t)a.KH * a.KW * ((a.cout + 3) & ~3) * 128;
-  if (lds > 160 * 1024 || (a.KW != 9 && a.KW != 3) || a.KH > 9 || a.CinP != 64) return 0;
+  const size_t lds = smalln_lds(a.KH, a.KW, a.cout);
   a.ntiles = N * a.tiles_y * a.tiles_x;
   a.x_bytes = (unsigned)((size_t)N * a.IH * a.IW * 128);
   const int per_cu = lds <= 80 * 1024 ? 2 : 1;
@@ -376,48 +382,35 @@ int dsr_launch_conv_smalln(SmallNArgs& a, int N, int dtype, hipStream_t st) {
                    : di == 2 ? (const void*)conv_smalln_kernel<DSR_DTYPE_BF16, 3>
                              : (const void*)conv_smalln_kernel<DSR_DTYPE_F16, 3>;
   g_smalln_optin[di].ensure(fn, 160 * 1024);   // > 64 KB of dynamic LDS needs the opt-in once per kernel and device (not a stream operation)
-  const size_t P = (size_t)N * a.OH * a.OW;
-  const bool zpad = !a.out_f32 && a.cout < a.CoutP;
+  const bool bf = dtype == DSR_DTYPE_BF16;
   if (a.KW == 9 && a.KH == 9 && a.cout <= 3 && a.pad == 4 && !a.flip) {   // the generator's tail: Toeplitz mapping
     static LdsOptIn toeplitz_optin[2];
-    const int dj = dtype == DSR_DTYPE_BF16 ? 0 : 1;
     const size_t tl = 18 * 16 * 128 + 2 * 24 * 40 * 64;      // weights + two one-K-block halo stages
-    const void* tf = dj == 0 ? (const void*)conv_toeplitz9_kernel<DSR_DTYPE_BF16> : (const void*)conv_toeplitz9_kernel<DSR_DTYPE_F16>;
-    toeplitz_optin[dj].ensure(tf, 160 * 1024);
+    const void* tf = bf ? (const void*)conv_toeplitz9_kernel<DSR_DTYPE_BF16> : (const void*)conv_toeplitz9_kernel<DSR_DTYPE_F16>;
+    toeplitz_optin[bf ? 0 : 1].ensure(tf, 160 * 1024);
     a.tiles_y = (a.OH + 15) / 16;                              // (this kernel's tiles are 16 rows x 32 columns)
     a.ntiles = N * a.tiles_y * a.tiles_x;
     dim3 tg(a.ntiles < 256 ? a.ntiles : 256);
-    if (dj == 0) {
+    if (bf)
       hipLaunchKernelGGL((conv_toeplitz9_kernel<DSR_DTYPE_BF16>), tg, block, tl, st, a);
-      if (zpad)
-        hipLaunchKernelGGL((zero_pad_channels_kernel<DSR_DTYPE_BF16>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st,
-                           (unsigned short*)a.y, P, a.cout, a.CoutP);
-    } else {
+    else
       hipLaunchKernelGGL((conv_toeplitz9_kernel<DSR_DTYPE_F16>), tg, block, tl, st, a);
-      if (zpad)
-        hipLaunchKernelGGL((zero_pad_channels_kernel<DSR_DTYPE_F16>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st,
-                           (unsigned short*)a.y, P, a.cout, a.CoutP);
-    }
-    return 1;
-  }
-  if (dtype == DSR_DTYPE_BF16) {
-    if (a.KW == 9)
-      hipLaunchKernelGGL((conv_smalln_kernel<DSR_DTYPE_BF16, 9>), grid, block, lds, st, a);
+  } else if (di == 0)
+    hipLaunchKernelGGL((conv_smalln_kernel<DSR_DTYPE_BF16, 9>), grid, block, lds, st, a);
+  else if (di == 1)
+    hipLaunchKernelGGL((conv_smalln_kernel<DSR_DTYPE_F16, 9>), grid, block, lds, st, a);
+  else if (di == 2)
+    hipLaunchKernelGGL((conv_smalln_kernel<DSR_DTYPE_BF16, 3>), grid, block, lds, st, a);
+  else
+    hipLaunchKernelGGL((conv_smalln_kernel<DSR_DTYPE_F16, 3>), grid, block, lds, st, a);
+  if (!a.out_f32 && a.cout < a.CoutP) {
+    const size_t P = (size_t)N * a.OH * a.OW;
+    const dim3 zg((unsigned)((P + 255) / 256));
+    if (bf)
+      hipLaunchKernelGGL((zero_pad_channels_kernel<DSR_DTYPE_BF16>), zg, dim3(256), 0, st, (unsigned short*)a.y, P, a.cout, a.CoutP);
     else
-      hipLaunchKernelGGL((conv_smalln_kernel<DSR_DTYPE_BF16, 3>), grid, block, lds, st, a);
-    if (zpad)
-      hipLaunchKernelGGL((zero_pad_channels_kernel<DSR_DTYPE_BF16>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st,
-                         (unsigned short*)a.y, P, a.cout, a.CoutP);
-  } else {
-    if (a.KW == 9)
-      hipLaunchKernelGGL((conv_smalln_kernel<DSR_DTYPE_F16, 9>), grid, block, lds, st, a);
-    else
-      hipLaunchKernelGGL((conv_smalln_kernel<DSR_DTYPE_F16, 3>), grid, block, lds, st, a);
-    if (zpad)
-      hipLaunchKernelGGL((zero_pad_channels_kernel<DSR_DTYPE_F16>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st,
-                         (unsigned short*)a.y, P, a.cout, a.CoutP);
+      hipLaunchKernelGGL((zero_pad_channels_kernel<DSR_DTYPE_F16>), zg, dim3(256), 0, st, (unsigned short*)a.y, P, a.cout, a.CoutP);
   }
-  return 1;
 }
 
 // ------------------------------------------------------------------ weight gradient, wide tap rows, few channels
@@ -1028,7 +1021,7 @@ void dsr_launch_dgrad_toeplitz(const void* dy, const void* w_dgrad, void* dx, in
   a.dyu = dyu;
   a.ps_partial = ps_partial;
   if (ps) {
-    static LdsOptIn optin[2];   // 76 KB of static LDS: above the 64 KB default
+    // (76 KB of static LDS: the code object declares it, so no opt-in is needed -- that is for dynamic LDS above 64 KB)
     if (dtype == DSR_DTYPE_BF16)
       hipLaunchKernelGGL((conv_dgrad_toeplitz9_kernel<DSR_DTYPE_BF16, true>), dim3(blocks), dim3(256), 0, st, a);
     else

@@ -2,7 +2,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #define DSR_MAX_TAPS 96
 #define DSR_WGRAD_SCRATCH_SLABS 16
@@ -66,50 +65,16 @@ struct ConvGemmArgs {
   int taps[DSR_MAX_TAPS];   // (dy & 0xff) | (dx & 0xff) << 8 | widx << 16
 };
 
-void dsr_launch_conv_gemm(const ConvGemmArgs& a, int dtype, hipStream_t st);
-// 256x256-tile variant of the gather kernel (conv_gemm.hip): LDS-DMA fast path, N a multiple of 256 and at least one
-// tile per CU.  Shared by the dispatcher and by dsr_conv_kernel_name().
-// DSR_CONV_BIG: 0 = 128x128 tiles only, 1 = the 256x128 three-stage experiment, 2 (default) = 256x256 where it applies.
-static inline int dsr_conv_big_mode(void) {
-  const char* e = getenv("DSR_CONV_BIG");            // read per call: tests switch it inside one process
-  return e ? atoi(e) : 2;
+// fast path of the gather kernel: zero padding and Cin a multiple of 64 (the 8 units of a K-step share one tap)
+static inline bool dsr_conv_gemm_fast(const ConvGemmArgs& a) {
+  return a.pad_mode == DSR_PAD_ZERO && (a.CU & 7) == 0 && a.ntaps > 0;
 }
-static inline bool dsr_conv_gemm_use_256(long long M, int NB, bool fast, bool stats) {
-  const long long tiles = ((M + 255) / 256) * ((NB + 255) / 256);
-  (void)stats;   // both epilogues exist on the 256x256 tile (statistics from the channel-major accumulators)
-  const char* t = getenv("DSR_CONV_BIG_TILES");      // tuning switch: fewest 256x256 tiles worth taking (default 150: a 196-tile launch on 256 CUs still beats four times as many 128x128 tiles, measured on VGG 512->512 at 28x28)
-  return dsr_conv_big_mode() == 2 && fast && NB % 256 == 0 && tiles >= (t ? atoi(t) : 150);
-}
-
-// 224x256 tile (the same 8-wave kernel with 7 m-tiles per wave): a launch whose 256-row tiles leave most of the chip idle in
-// their last round -- VGG19 at batch 32: 196 tiles (512 channels at 28x28) or 392 tiles (256 channels at 56x56) on the 256
-// CUs of an MI355X, i.e. 77 % of the slots of one / two rounds -- runs 224 / 448 tiles of 7/8 the work each instead: the same
-// number of rounds, every round 12.5 % shorter.  Taken when it lowers rounds x rows per tile, for launches without BatchNorm
-// statistics (one statistics row per 128 tile rows has no place in a 224-row tile) and without PixelShuffle stores.
-// DSR_CONV_BM224: 0 = never, 1 (default) = by that cost, 2 = wherever the 256x256 tile would be taken (tests).
-static inline bool dsr_conv_gemm_use_224(long long M, int NB, bool fast, int flags) {
-  const char* e = getenv("DSR_CONV_BM224");          // read per call: tests switch it inside one process
-  const int mode = e ? atoi(e) : 1;
-  if (mode == 0 || (flags & (DSR_F_STATS | DSR_F_PIXSHUF | DSR_F_OUT_NCHW_F32))) return false;
-  if (!dsr_conv_gemm_use_256(M, NB, fast, false)) return false;
-  if (mode == 2) return true;
-  const long long cus = 256, nt = NB / 256;
-  const long long r256 = (((M + 255) / 256) * nt + cus - 1) / cus, r224 = (((M + 223) / 224) * nt + cus - 1) / cus;
-  return r224 * 7 < r256 * 8;
-}
-
-// 64x128 tile (4 waves of 64x32): launches whose 128x128 tiles do not even give every CU one block (VGG conv5_x at batch 32:
-// M = 6,272 -> 49 x 4 = 196 blocks).  Without statistics only (a statistics row covers 128 tile rows).
-// DSR_CONV_BM64: 0 = never, 1 (default) = fewer than 256 tiles of 128x128, 2 = every launch the 128x128 tile would take (tests).
-static inline bool dsr_conv_gemm_use_64(long long M, int NB, bool fast, int flags) {
-  const char* e = getenv("DSR_CONV_BM64");
-  const int mode = e ? atoi(e) : 1;
-  if (mode == 0 || !fast || NB % 128 != 0 || (flags & (DSR_F_STATS | DSR_F_PIXSHUF | DSR_F_OUT_NCHW_F32))) return false;
-  if (mode == 2) return true;
-  return ((M + 127) / 128) * (NB / 128) < 256;
-}
-
-bool dsr_launch_conv_gemm_persist(const ConvGemmArgs& a, int dtype, hipStream_t st);   // conv_gemm_persist.hip
+// kernel / tile of a gather-kernel launch: the persistent 64-wide kernel (conv_gemm_persist.hip) or a BMxBN tile
+enum class GemmTile { Persist64, T224x256, T256x256, T64x128, T128x128, T128x64, T128x16 };
+GemmTile dsr_conv_gemm_plan(const ConvGemmArgs& a);                                       // conv_gemm.hip
+void dsr_launch_conv_gemm(const ConvGemmArgs& a, GemmTile t, int dtype, hipStream_t st);   // t = dsr_conv_gemm_plan(a)
+bool dsr_conv_gemm_persist_fits(const ConvGemmArgs& a);                                    // conv_gemm_persist.hip
+void dsr_launch_conv_gemm_persist(const ConvGemmArgs& a, int dtype, hipStream_t st);
 
 struct WgradArgs {
   const void* x;    // [N][IH][IW][CinP]
@@ -180,7 +145,9 @@ struct SmallNArgs {
   int flip;           // read weight slice ntaps-1-t for tap t (input gradient = correlation with the mirrored kernel)
   unsigned x_bytes;
 };
-int dsr_launch_conv_smalln(SmallNArgs& a, int N, int dtype, hipStream_t st);   // returns 0 if the halo does not fit
+// whether the kernel takes a problem: KW 3 or 9, KH <= 9, CinP 64, and the halo tile fits in 160 KB of LDS
+bool dsr_smalln_fits(int KH, int KW, int CinP, int cout);
+void dsr_launch_conv_smalln(SmallNArgs& a, int N, int dtype, hipStream_t st);   // dsr_smalln_fits() must hold
 
 // 64 -> 64 channel 3x3 stride-1 zero-pad conv, weights register-resident, persistent (conv_c64.hip)
 struct C64Args {
@@ -206,6 +173,8 @@ struct C64Args {
 };
 int dsr_c64_tiles(int N, int H, int W, int tile_rows);
 int dsr_c64_stat_rows(int N, int H, int W, int CoutP);
+// kernel mode of a launch: 0 statistics epilogue, 1 plain, 2 folded inference epilogue, 3 residual / mask tile only
+int dsr_c64_mode(int flags, int act, int CoutP);
 void dsr_launch_conv_c64(C64Args& a, int N, int dtype, hipStream_t st);
 
 struct Cin8Args {

@@ -208,3 +208,87 @@ def test_ops_fail_loudly_without_gpu():
     g = gen.Generator(4, 1)
     with pytest.raises(RuntimeError):
         g(torch.zeros(1, 3, 8, 8))
+
+
+# Kernel names of tools/microbench_conv.py's layers (fwd with that script's epilogue: BatchNorm statistics when Cout > 16 and
+# Cin > 8; dgrad; wgrad), as the launch code picks them.  bench.py's roofline leg groups time and FLOPs by these names.
+MICROBENCH_NAMES = {
+    "G.trunk 64->64 @128": ("conv_c64_kernel<0>", "conv_c64_kernel<1>", "conv_wgrad_dma_kernel"),
+    "G.ps0 64->256 @128": ("conv_c64_kernel<0>", "conv_halo64_kernel", "conv_wgrad_dma_kernel"),
+    "G.ps1 64->256 @256": ("conv_c64_kernel<0>", "conv_halo64_kernel", "conv_wgrad_dma_kernel"),
+    "G.conv1 9x9 3->64 @128": ("conv_rgb9_kernel", "conv_smalln_kernel", "conv_rgb9_wgrad_kernel"),
+    "G.conv3 9x9 64->3 @512": ("conv_smalln_kernel", "conv_dgrad_toeplitz9_kernel", "conv_wgrad_toeplitz9_kernel"),
+    "D.conv 3->64 @512": ("conv_cin8_kernel", "conv_smalln_kernel", "conv_wgrad_dma_kernel"),
+    "D.b0 64->64 s2 @512": ("conv_gemm_persist_kernel", "conv_dgrad_s2_kernel", "conv_wgrad_dma_s2_kernel"),
+    "D.b1 64->128 @256": ("conv_c64_kernel<0>", "conv_halo64_kernel", "conv_wgrad_dma_kernel"),
+    "D.b2 128->128 s2 @256": ("conv_gemm_kernel<128x128>", "conv_dgrad_s2_kernel", "conv_wgrad_dma_s2_kernel"),
+    "D.b3 128->256 @128": ("conv_gemm_kernel<256x256>", "conv_gemm_kernel<128x128>", "conv_wgrad_dma_kernel"),
+    "D.b4 256->256 s2 @128": ("conv_gemm_kernel<256x256>", "conv_dgrad_s2_kernel", "conv_wgrad_dma_s2_kernel"),
+    "D.b5 256->512 @64": ("conv_gemm_kernel<256x256>", "conv_gemm_kernel<256x256>", "conv_wgrad_dma_kernel"),
+    "D.b6 512->512 s2 @64": ("conv_gemm_kernel<256x256>", "conv_dgrad_s2_kernel", "conv_wgrad_dma_s2_kernel"),
+    "V.3->64 @224": ("conv_cin8_kernel", "conv_smalln_kernel", "conv_wgrad_dma_kernel"),
+    "V.64->64 @224": ("conv_c64_kernel<0>", "conv_c64_kernel<1>", "conv_wgrad_dma_kernel"),
+    "V.64->128 @112": ("conv_c64_kernel<0>", "conv_halo64_kernel", "conv_wgrad_dma_kernel"),
+    "V.128->128 @112": ("conv_gemm_kernel<128x128>", "conv_gemm_kernel<128x128>", "conv_wgrad_dma_kernel"),
+    "V.128->256 @56": ("conv_gemm_kernel<256x256>", "conv_gemm_kernel<128x128>", "conv_wgrad_dma_kernel"),
+    "V.256->256 @56": ("conv_gemm_kernel<256x256>", "conv_gemm_kernel<224x256>", "conv_wgrad_dma_kernel"),
+    "V.256->512 @28": ("conv_gemm_kernel<256x256>", "conv_gemm_kernel<128x128>", "conv_wgrad_dma_kernel"),
+    "V.512->512 @28": ("conv_gemm_kernel<256x256>", "conv_gemm_kernel<224x256>", "conv_wgrad_dma_kernel"),
+    "V.512->512 @14": ("conv_gemm_kernel<128x128>", "conv_gemm_kernel<64x128>", "conv_wgrad_dma_kernel"),
+}
+
+# (layer or (N, H, W, Cin, Cout, k, stride, pad, pad_mode), op, switches, name).  op: "fwd" = microbench epilogue, "fwd0" =
+# no epilogue.  The first rows are the launches whose names once disagreed with the kernel the launch code runs.
+NAME_CASES = [
+    ((32, 128, 128, 64, 16, 3, 1, 1, 0), "fwd0", {}, "conv_smalln_kernel"),            # small-N takes 3x3 as well as 9x9
+    ((32, 128, 128, 64, 16, 9, 1, 4, 0), "fwd0", {}, "conv_gemm_kernel<128x16>"),       # its halo needs 247 KB > 160 KB
+    ((32, 128, 128, 16, 64, 9, 1, 4, 0), "dgrad", {}, "conv_gemm_kernel<128x16>"),      # the same, input gradient
+    ((32, 256, 256, 128, 64, 3, 1, 1, 0), "fwd0", {}, "conv_gemm_persist_kernel"),      # many 64-wide tiles
+    ((1, 256, 256, 128, 128, 3, 2, 1, 1), "dgrad", {}, "conv_gemm_kernel<64x128>"),     # reflect pad: the fast path after the fold
+    ("V.512->512 @28", "fwd", {"DSR_CONV_BIG": "0"}, "conv_gemm_kernel<128x128>"),
+    ("V.256->256 @56", "dgrad", {"DSR_CONV_BIG": "0"}, "conv_gemm_kernel<128x128>"),
+    ("V.512->512 @28", "fwd", {"DSR_CONV_BIG": "1"}, "conv_gemm_kernel<256x256>"),
+    ("V.256->256 @56", "dgrad", {"DSR_CONV_BIG": "1"}, "conv_gemm_kernel<224x256>"),
+    ("V.512->512 @28", "fwd", {"DSR_CONV_BIG": "2"}, "conv_gemm_kernel<256x256>"),
+    ("G.ps0 64->256 @128", "dgrad", {"DSR_CONV_HALO64": "0"}, "conv_gemm_persist_kernel"),
+    ("V.128->128 @112", "fwd0", {"DSR_CONV_HALO64": "2"}, "conv_halo64_kernel"),
+    ("V.128->128 @112", "dgrad", {"DSR_CONV_HALO64": "2"}, "conv_halo64_kernel"),
+    ("V.128->128 @112", "dgrad", {"DSR_CONV_HALO64": "3"}, "conv_gemm_kernel<128x128>"),
+    ("D.b3 128->256 @128", "dgrad", {"DSR_CONV_HALO64": "3"}, "conv_gemm_kernel<128x128>"),
+    ("D.b5 256->512 @64", "dgrad", {"DSR_CONV_BM224": "2"}, "conv_gemm_kernel<224x256>"),
+    ("V.128->128 @112", "dgrad", {"DSR_CONV_BM64": "2"}, "conv_gemm_kernel<64x128>"),
+    ("D.b2 128->128 s2 @256", "dgrad", {"DSR_DGRAD_S2": "0"}, "conv_gemm_kernel<128x128>"),
+    ("D.b0 64->64 s2 @512", "dgrad", {"DSR_DGRAD_S2": "0"}, "conv_gemm_persist_kernel"),
+]
+
+
+def microbench_shapes():
+    import ast
+    src = open(os.path.join(ROOT, "tools", "microbench_conv.py")).read()
+    i = src.index("SHAPES = [")
+    return {s[0]: s[1:] for s in ast.literal_eval(src[i + len("SHAPES = "):src.index("]\n", i) + 1])}
+
+
+def test_conv_kernel_names_follow_the_dispatch(so, monkeypatch):
+    """dsr_conv_kernel_name reads the plan the launch code follows (conv_api.hip): the name of every microbench layer and
+    switch setting is the kernel that runs.  Host only: planning launches nothing."""
+    L = importlib.import_module(PKG + "._lib")
+    lib = L.lib()
+    shapes = microbench_shapes()
+    assert set(shapes) == set(MICROBENCH_NAMES)
+    stats = (ctypes.c_float * 4)()
+
+    def name(shape, op):
+        n, h, w, cin, cout, k, s, p = shape[:8]
+        d = L.ConvDesc(L.BF16, n, h, w, cin, cout, k, k, s, p, shape[8] if len(shape) > 8 else 0)
+        ep = L.Epilogue(0, 0.0, None, None, ctypes.addressof(stats) if (cout > 16 and cin > 8) else None, 0, None)
+        code = {"fwd": 0, "fwd0": 0, "dgrad": 1, "wgrad": 2}[op]
+        return lib.dsr_conv_kernel_name(ctypes.byref(d), code, ctypes.byref(ep) if op == "fwd" else None).decode()
+
+    for layer, want in MICROBENCH_NAMES.items():
+        assert tuple(name(shapes[layer], op) for op in ("fwd", "dgrad", "wgrad")) == want, layer
+    for layer, op, env, want in NAME_CASES:
+        with monkeypatch.context() as m:
+            for k, v in env.items():
+                m.setenv(k, v)
+            assert name(shapes.get(layer, layer), op) == want, (layer, op, env)

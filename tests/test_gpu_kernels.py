@@ -826,12 +826,11 @@ def test_first_two_layers_fused_forward(dev, n, h, w, keep):
 
 
 @pytest.mark.parametrize("b,hw,c,cp,bp", [(5, 72, 100, 128, 8), (64, 1024, 512, 512, 64), (3, 8, 64, 64, 16)])
-def test_flatten_tile_kernel_equals_strided_form(dev, b, hw, c, cp, bp):
+def test_flatten_tile_kernel_equals_strided_form(dev, b, hw, c, cp, bp, monkeypatch):
     """dsr_flatten (NHWC <-> the CHW-flattened operand of the dense head, discriminator.py:37-39,60-62) has a tile form that
     goes through LDS with 16-byte accesses on both sides; DSR_FLATTEN_TILE=0 keeps the strided form.  Pure data movement:
     the two must agree bit for bit in all three modes, and with torch's permute."""
     import ctypes as C
-    import os
     L = P("_lib")
     lib = L.lib()
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -841,23 +840,16 @@ def test_flatten_tile_kernel_equals_strided_form(dev, b, hw, c, cp, bp):
     act = act.to(dev)
     flat_src = (torch.rand(b, c * hw, generator=g) - 0.5).to(torch.bfloat16).to(dev)
     res = {}
-    old = os.environ.get("DSR_FLATTEN_TILE")
-    try:
-        for tag in ("1", "0"):
-            os.environ["DSR_FLATTEN_TILE"] = tag
-            flat = torch.full((b, c * hw), float("nan"), dtype=torch.bfloat16, device=dev)
-            L.check(lib.dsr_flatten(L.BF16, act.data_ptr(), flat.data_ptr(), b, hw, c, cp, 0, 0, st))
-            flat_t = torch.full((c * hw, bp), float("nan"), dtype=torch.bfloat16, device=dev)
-            L.check(lib.dsr_flatten(L.BF16, act.data_ptr(), flat_t.data_ptr(), b, hw, c, cp, bp, 1, st))
-            back = torch.full((b, hw, cp), float("nan"), dtype=torch.bfloat16, device=dev)
-            L.check(lib.dsr_flatten(L.BF16, flat_src.data_ptr(), back.data_ptr(), b, hw, c, cp, 0, 2, st))
-            torch.cuda.synchronize()
-            res[tag] = (flat, flat_t, back)
-    finally:
-        if old is None:
-            os.environ.pop("DSR_FLATTEN_TILE", None)
-        else:
-            os.environ["DSR_FLATTEN_TILE"] = old
+    for tag in ("1", "0"):
+        monkeypatch.setenv("DSR_FLATTEN_TILE", tag)
+        flat = torch.full((b, c * hw), float("nan"), dtype=torch.bfloat16, device=dev)
+        L.check(lib.dsr_flatten(L.BF16, act.data_ptr(), flat.data_ptr(), b, hw, c, cp, 0, 0, st))
+        flat_t = torch.full((c * hw, bp), float("nan"), dtype=torch.bfloat16, device=dev)
+        L.check(lib.dsr_flatten(L.BF16, act.data_ptr(), flat_t.data_ptr(), b, hw, c, cp, bp, 1, st))
+        back = torch.full((b, hw, cp), float("nan"), dtype=torch.bfloat16, device=dev)
+        L.check(lib.dsr_flatten(L.BF16, flat_src.data_ptr(), back.data_ptr(), b, hw, c, cp, 0, 2, st))
+        torch.cuda.synchronize()
+        res[tag] = (flat, flat_t, back)
     for u, v in zip(res["1"], res["0"]):
         assert torch.isfinite(u.float()).all()
         assert torch.equal(u, v)
@@ -870,12 +862,11 @@ def test_flatten_tile_kernel_equals_strided_form(dev, b, hw, c, cp, bp):
 
 
 @pytest.mark.parametrize("pmode,stride", [(1, 1), (1, 2), (2, 1)])
-def test_padded_coordinate_dma_path_equals_generic_loader(dev, pmode, stride):
+def test_padded_coordinate_dma_path_equals_generic_loader(dev, pmode, stride, monkeypatch):
     """Reflect (1) / replicate (2) padding with Cin % 64 == 0 runs on the LDS-DMA kernel, which recomputes the padded
     coordinate of every tile row per K-step; DSR_CONV_PADX=0 sends the same launch through the register-staged generic loader.
     Same K order, same tile: the two must agree BIT FOR BIT (models/DIP/utils.py:83-105, pad='reflection')."""
     import ctypes as C
-    import os
     L = P("_lib")
     lib = L.lib()
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -890,20 +881,13 @@ def test_padded_coordinate_dma_path_equals_generic_loader(dev, pmode, stride):
     x = (torch.rand(n, h, w, cin, generator=g) - 0.5).to(torch.float16).to(dev)
     bias = (torch.rand(cout, generator=g) - 0.5).to(dev)
     outs = []
-    old = os.environ.get("DSR_CONV_PADX")
-    try:
-        for mode in ("0", "1"):
-            os.environ["DSR_CONV_PADX"] = mode
-            y = torch.full((n, oh, ow, cout), float("nan"), dtype=torch.float16, device=dev)
-            ep = L.Epilogue(1, 0.2, None, bias.data_ptr(), None, 0, None, None, None, None)
-            L.check(lib.dsr_conv_fwd(C.byref(d), x.data_ptr(), wf.data_ptr(), C.byref(ep), y.data_ptr(), st))
-            torch.cuda.synchronize()
-            outs.append(y)
-    finally:
-        if old is None:
-            os.environ.pop("DSR_CONV_PADX", None)
-        else:
-            os.environ["DSR_CONV_PADX"] = old
+    for mode in ("0", "1"):
+        monkeypatch.setenv("DSR_CONV_PADX", mode)
+        y = torch.full((n, oh, ow, cout), float("nan"), dtype=torch.float16, device=dev)
+        ep = L.Epilogue(1, 0.2, None, bias.data_ptr(), None, 0, None, None, None, None)
+        L.check(lib.dsr_conv_fwd(C.byref(d), x.data_ptr(), wf.data_ptr(), C.byref(ep), y.data_ptr(), st))
+        torch.cuda.synchronize()
+        outs.append(y)
     assert torch.isfinite(outs[0].float()).all()
     assert torch.equal(outs[0], outs[1])
     # and against torch on the padded image
@@ -914,7 +898,7 @@ def test_padded_coordinate_dma_path_equals_generic_loader(dev, pmode, stride):
 
 
 @pytest.mark.parametrize("op", ["fwd", "fwd_stats", "dgrad", "dgrad_masked", "dgrad_s2"])
-def test_conv_256x256_tile_equals_128x128(dev, op):
+def test_conv_256x256_tile_equals_128x128(dev, op, monkeypatch):
     """The big-tile variants of the gather kernel (8 waves, one block per CU; conv_gemm.hip) at a shape that dispatches to them
     (314 tiles of 256 rows): the 256x256 tile and the 224x256 tile (7 instead of 8 m-tiles per wave: taken by launches
     without BatchNorm statistics whose 256-row tiles would leave the last round of the chip mostly idle) walk K in the same
@@ -922,7 +906,6 @@ def test_conv_256x256_tile_equals_128x128(dev, op):
     same op on the same bf16 operands (conv2d / conv_transpose2d on the CPU; BatchNorm sums of the REFERENCE's output), which
     is what ties the dominant kernel of the batch-32 step to something other than another kernel of this library."""
     import ctypes as C
-    import os
     L = P("_lib")
     lib = L.lib()
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -940,46 +923,38 @@ def test_conv_256x256_tile_equals_128x128(dev, op):
     dy = (torch.rand(n, oh, ow, cout, generator=g) - 0.5).to(torch.bfloat16).to(dev)
     bias = (torch.rand(cout, generator=g) - 0.5).to(dev)
     outs, stats = {}, {}
-    keys = ("DSR_CONV_BIG", "DSR_DGRAD_S2", "DSR_CONV_BM224", "DSR_CONV_BM64")
-    old = {k: os.environ.get(k) for k in keys}
-    os.environ["DSR_DGRAD_S2"] = "0"       # this test is about the gather kernel's tiles: keep stride-2 dgrads on it
-    try:
-        # DSR_CONV_BM224: 0 = never, 1 = where it saves rounds (default), 2 = wherever the 256x256 tile would be taken
-        # DSR_CONV_BM64: 0 = never, 1 = launches of fewer than 256 tiles (default), 2 = wherever the 128x128 tile would be taken
-        for mode, big, b224, b64, want in (("t128", "0", "0", "0", "128x128"), ("t256", "2", "0", "0", "256x256"),
-                                           ("t224", "2", "2", "0", "224x256"), ("t64", "0", "0", "2", "64x128")):
-            if mode in ("t224", "t64") and op == "fwd_stats":
-                continue                   # (the 224- and 64-row tiles carry no statistics epilogue)
-            os.environ["DSR_CONV_BIG"], os.environ["DSR_CONV_BM224"], os.environ["DSR_CONV_BM64"] = big, b224, b64
-            if op in ("fwd", "fwd_stats"):
-                y = torch.full((n, oh, ow, cout), float("nan"), dtype=torch.bfloat16, device=dev)
-                rows = lib.dsr_conv_stats_rows(C.byref(d))
-                part = torch.full(((rows + 64) * 2 * cout,), float("nan"), dtype=torch.float32, device=dev)
-                ep = L.Epilogue(L.ACT_RELU if op == "fwd" else L.ACT_NONE, 0.0, None, bias.data_ptr(),
-                                part.data_ptr() if op == "fwd_stats" else None, 0, None)
-                name = lib.dsr_conv_kernel_name(C.byref(d), 0, C.byref(ep)).decode()
-                L.check(lib.dsr_conv_fwd(C.byref(d), x.data_ptr(), wf.data_ptr(), C.byref(ep), y.data_ptr(), st))
-                outs[mode] = y
-                if op == "fwd_stats":     # BatchNorm statistics: per-channel sum and sum of squares over all pixels
-                    stats[mode] = part[:rows * 2 * cout].reshape(rows, 2, cout).double().sum(0)
+    monkeypatch.setenv("DSR_DGRAD_S2", "0")       # this test is about the gather kernel's tiles: keep stride-2 dgrads on it
+    # DSR_CONV_BM224: 0 = never, 1 = where it saves rounds (default), 2 = wherever the 256x256 tile would be taken
+    # DSR_CONV_BM64: 0 = never, 1 = launches of fewer than 256 tiles (default), 2 = wherever the 128x128 tile would be taken
+    for mode, big, b224, b64, want in (("t128", "0", "0", "0", "128x128"), ("t256", "2", "0", "0", "256x256"),
+                                       ("t224", "2", "2", "0", "224x256"), ("t64", "0", "0", "2", "64x128")):
+        if mode in ("t224", "t64") and op == "fwd_stats":
+            continue                   # (the 224- and 64-row tiles carry no statistics epilogue)
+        for k, v in (("DSR_CONV_BIG", big), ("DSR_CONV_BM224", b224), ("DSR_CONV_BM64", b64)):
+            monkeypatch.setenv(k, v)
+        if op in ("fwd", "fwd_stats"):
+            y = torch.full((n, oh, ow, cout), float("nan"), dtype=torch.bfloat16, device=dev)
+            rows = lib.dsr_conv_stats_rows(C.byref(d))
+            part = torch.full(((rows + 64) * 2 * cout,), float("nan"), dtype=torch.float32, device=dev)
+            ep = L.Epilogue(L.ACT_RELU if op == "fwd" else L.ACT_NONE, 0.0, None, bias.data_ptr(),
+                            part.data_ptr() if op == "fwd_stats" else None, 0, None)
+            name = lib.dsr_conv_kernel_name(C.byref(d), 0, C.byref(ep)).decode()
+            L.check(lib.dsr_conv_fwd(C.byref(d), x.data_ptr(), wf.data_ptr(), C.byref(ep), y.data_ptr(), st))
+            outs[mode] = y
+            if op == "fwd_stats":     # BatchNorm statistics: per-channel sum and sum of squares over all pixels
+                stats[mode] = part[:rows * 2 * cout].reshape(rows, 2, cout).double().sum(0)
+        else:
+            dx = torch.full((n, h, w, cin), float("nan"), dtype=torch.bfloat16, device=dev)
+            name = lib.dsr_conv_kernel_name(C.byref(d), 1, None).decode()
+            if op == "dgrad_masked":       # dx * relu'(x): the activation mask folded into the store loop
+                L.check(lib.dsr_conv_dgrad_masked(C.byref(d), dy.data_ptr(), wd.data_ptr(), x.data_ptr(), L.ACT_RELU, 0.0,
+                                                  dx.data_ptr(), st))
             else:
-                dx = torch.full((n, h, w, cin), float("nan"), dtype=torch.bfloat16, device=dev)
-                name = lib.dsr_conv_kernel_name(C.byref(d), 1, None).decode()
-                if op == "dgrad_masked":       # dx * relu'(x): the activation mask folded into the store loop
-                    L.check(lib.dsr_conv_dgrad_masked(C.byref(d), dy.data_ptr(), wd.data_ptr(), x.data_ptr(), L.ACT_RELU, 0.0,
-                                                      dx.data_ptr(), st))
-                else:
-                    wsz = lib.dsr_conv_dgrad_workspace(C.byref(d))
-                    ws = torch.empty(max(wsz, 16), dtype=torch.uint8, device=dev)
-                    L.check(lib.dsr_conv_dgrad(C.byref(d), dy.data_ptr(), wd.data_ptr(), dx.data_ptr(), ws.data_ptr(), wsz, st))
-                outs[mode] = dx
-            assert want in name, (mode, name)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+                wsz = lib.dsr_conv_dgrad_workspace(C.byref(d))
+                ws = torch.empty(max(wsz, 16), dtype=torch.uint8, device=dev)
+                L.check(lib.dsr_conv_dgrad(C.byref(d), dy.data_ptr(), wd.data_ptr(), dx.data_ptr(), ws.data_ptr(), wsz, st))
+            outs[mode] = dx
+        assert want in name, (mode, name)
     torch.cuda.synchronize()
     assert all(torch.isfinite(o.float()).all() for o in outs.values())
     assert torch.equal(outs["t128"], outs["t256"])
@@ -1010,14 +985,13 @@ def test_conv_256x256_tile_equals_128x128(dev, op):
 
 
 @pytest.mark.parametrize("n,h,w,cout", [(3, 40, 100, 256), (2, 8, 32, 128), (1, 67, 130, 192), (40, 16, 64, 256)])
-def test_conv_halo64_dgrad_vs_gather_kernel_and_fp32(dev, n, h, w, cout):
+def test_conv_halo64_dgrad_vs_gather_kernel_and_fp32(dev, n, h, w, cout, monkeypatch):
     """conv_halo64_kernel (input gradient of a 3x3 stride-1 layer with 64 inputs and `cout` = 128 / 192 / 256 outputs: a
     64-output convolution over `cout` channels, halo staged per 32-channel K-block; generator.py:30, discriminator.py:31)
     against the gather kernel it replaces (DSR_CONV_HALO64=0: the same products, summed tap-major there and channel-block-major
     here, so equal within fp32 summation order) and against a float64 conv_transpose2d of the same bf16 operands.  Shapes:
     ragged right / bottom tiles, the smallest admitted map, 192 = six K-blocks, and 640 tiles on 256 persistent blocks."""
     import ctypes as C
-    import os
     L = P("_lib")
     lib = L.lib()
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -1031,20 +1005,13 @@ def test_conv_halo64_dgrad_vs_gather_kernel_and_fp32(dev, n, h, w, cout):
     dy = bfr(torch.rand(n, cout, h, w, generator=g) - 0.5)
     dyg = dy.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16).to(dev)
     outs = {}
-    old = os.environ.get("DSR_CONV_HALO64")
-    try:
-        for mode in ("1", "0"):
-            os.environ["DSR_CONV_HALO64"] = mode
-            name = lib.dsr_conv_kernel_name(C.byref(d), 1, None).decode()
-            assert ("halo64" in name) == (mode == "1"), (mode, name)
-            dx = torch.full((n, h, w, cin), float("nan"), dtype=torch.bfloat16, device=dev)
-            L.check(lib.dsr_conv_dgrad(C.byref(d), dyg.data_ptr(), wd.data_ptr(), dx.data_ptr(), None, 0, st))
-            outs[mode] = dx
-    finally:
-        if old is None:
-            os.environ.pop("DSR_CONV_HALO64", None)
-        else:
-            os.environ["DSR_CONV_HALO64"] = old
+    for mode in ("1", "0"):
+        monkeypatch.setenv("DSR_CONV_HALO64", mode)
+        name = lib.dsr_conv_kernel_name(C.byref(d), 1, None).decode()
+        assert ("halo64" in name) == (mode == "1"), (mode, name)
+        dx = torch.full((n, h, w, cin), float("nan"), dtype=torch.bfloat16, device=dev)
+        L.check(lib.dsr_conv_dgrad(C.byref(d), dyg.data_ptr(), wd.data_ptr(), dx.data_ptr(), None, 0, st))
+        outs[mode] = dx
     torch.cuda.synchronize()
     assert torch.isfinite(outs["1"].float()).all()
     ref = TF.conv_transpose2d(dy.double(), wt.double(), padding=1)
@@ -1055,14 +1022,13 @@ def test_conv_halo64_dgrad_vs_gather_kernel_and_fp32(dev, n, h, w, cout):
 
 
 @pytest.mark.parametrize("n,h,w,cin,cout", [(2, 40, 100, 128, 128), (1, 67, 130, 256, 128), (3, 16, 64, 128, 256), (36, 16, 64, 128, 128)])
-def test_conv_halo64_two_slices_of_64_outputs(dev, n, h, w, cin, cout):
+def test_conv_halo64_two_slices_of_64_outputs(dev, n, h, w, cin, cout, monkeypatch):
     """conv_halo64_kernel on a layer with 128 outputs (forward: VGG conv2_2, utils/GAN.py:26, with bias + ReLU in the epilogue)
     or 128 inputs (input gradient, plain and with the ReLU mask of the activation in front folded into its stores): two
     64-channel slices per spatial tile (opt-in, DSR_CONV_HALO64=2: faster launch by launch, slower inside the two-stream step).
     Against the gather kernel (the default for these layers: the same products in another order) and float64 conv2d / conv_transpose2d on the same bf16 operands.  Ragged tiles, K = 128 and 256,
     more (tile, slice) pairs than persistent blocks."""
     import ctypes as C
-    import os
     L = P("_lib")
     F = P("functional")
     lib = L.lib()
@@ -1080,34 +1046,27 @@ def test_conv_halo64_two_slices_of_64_outputs(dev, n, h, w, cin, cout):
     ep = L.Epilogue(L.ACT_RELU, 0.0, None, bg.data_ptr(), None, 0, None)
     do_fwd, do_dgrad = cout == 128, cin == 128
     outs = {}
-    old = os.environ.get("DSR_CONV_HALO64")
-    try:
-        for mode in ("2", "1"):
-            os.environ["DSR_CONV_HALO64"] = mode
-            res = {}
-            if do_fwd:
-                name = lib.dsr_conv_kernel_name(C.byref(d), 0, C.byref(ep)).decode()
-                assert ("halo64" in name) == (mode == "2"), (mode, name)
-                y = torch.full((n, h, w, cout), float("nan"), dtype=torch.bfloat16, device=dev)
-                L.check(lib.dsr_conv_fwd(C.byref(d), xg.data_ptr(), wf.data_ptr(), C.byref(ep), y.data_ptr(), st))
-                res["y"] = y
-            if do_dgrad:
-                name = lib.dsr_conv_kernel_name(C.byref(d), 1, None).decode()
-                assert ("halo64" in name) == (mode == "2"), (mode, name)
-                dx = torch.full((n, h, w, cin), float("nan"), dtype=torch.bfloat16, device=dev)
-                L.check(lib.dsr_conv_dgrad(C.byref(d), dyg.data_ptr(), wd.data_ptr(), dx.data_ptr(), None, 0, st))
-                res["dx"] = dx
-                if lib.dsr_conv_dgrad_masked_supported(C.byref(d)):
-                    dxm = torch.full((n, h, w, cin), float("nan"), dtype=torch.bfloat16, device=dev)
-                    L.check(lib.dsr_conv_dgrad_masked(C.byref(d), dyg.data_ptr(), wd.data_ptr(), xg.data_ptr(), L.ACT_RELU, 0.0,
-                                                      dxm.data_ptr(), st))
-                    res["dxm"] = dxm
-            outs[mode] = res
-    finally:
-        if old is None:
-            os.environ.pop("DSR_CONV_HALO64", None)
-        else:
-            os.environ["DSR_CONV_HALO64"] = old
+    for mode in ("2", "1"):
+        monkeypatch.setenv("DSR_CONV_HALO64", mode)
+        res = {}
+        if do_fwd:
+            name = lib.dsr_conv_kernel_name(C.byref(d), 0, C.byref(ep)).decode()
+            assert ("halo64" in name) == (mode == "2"), (mode, name)
+            y = torch.full((n, h, w, cout), float("nan"), dtype=torch.bfloat16, device=dev)
+            L.check(lib.dsr_conv_fwd(C.byref(d), xg.data_ptr(), wf.data_ptr(), C.byref(ep), y.data_ptr(), st))
+            res["y"] = y
+        if do_dgrad:
+            name = lib.dsr_conv_kernel_name(C.byref(d), 1, None).decode()
+            assert ("halo64" in name) == (mode == "2"), (mode, name)
+            dx = torch.full((n, h, w, cin), float("nan"), dtype=torch.bfloat16, device=dev)
+            L.check(lib.dsr_conv_dgrad(C.byref(d), dyg.data_ptr(), wd.data_ptr(), dx.data_ptr(), None, 0, st))
+            res["dx"] = dx
+            if lib.dsr_conv_dgrad_masked_supported(C.byref(d)):
+                dxm = torch.full((n, h, w, cin), float("nan"), dtype=torch.bfloat16, device=dev)
+                L.check(lib.dsr_conv_dgrad_masked(C.byref(d), dyg.data_ptr(), wd.data_ptr(), xg.data_ptr(), L.ACT_RELU, 0.0,
+                                                  dxm.data_ptr(), st))
+                res["dxm"] = dxm
+        outs[mode] = res
     torch.cuda.synchronize()
     refs = {}
     if do_fwd:
@@ -1125,12 +1084,11 @@ def test_conv_halo64_two_slices_of_64_outputs(dev, n, h, w, cin, cout):
 
 
 @pytest.mark.parametrize("n,h,w,cin,cout", [(2, 64, 96, 64, 64), (1, 50, 38, 128, 192), (3, 32, 32, 256, 64)])
-def test_conv_dgrad_s2_single_launch_equals_four_launches(dev, n, h, w, cin, cout):
+def test_conv_dgrad_s2_single_launch_equals_four_launches(dev, n, h, w, cin, cout, monkeypatch):
     """conv_dgrad_s2_kernel (3x3 stride 2 pad 1 input gradient, all four output-parity classes from one staged dY tile;
     discriminator.py:29-35) against the four gather-kernel launches it replaces: same products in the same order, so BIT FOR
     BIT equal, ragged M tail included; and against a float64 conv_transpose on the same bf16 operands."""
     import ctypes as C
-    import os
     L = P("_lib")
     lib = L.lib()
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -1145,20 +1103,13 @@ def test_conv_dgrad_s2_single_launch_equals_four_launches(dev, n, h, w, cin, cou
     dy = bfr(torch.rand(n, cout, oh, ow, generator=g) - 0.5)
     dyd = dy.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16).to(dev)
     outs = []
-    old = os.environ.get("DSR_DGRAD_S2")
-    try:
-        for mode in ("0", "2"):        # 0: four parity-class launches, 2: the single-launch kernel whatever the grid size
-            os.environ["DSR_DGRAD_S2"] = mode
-            dx = torch.full((n, h, w, cin), float("nan"), dtype=torch.bfloat16, device=dev)
-            name = lib.dsr_conv_kernel_name(C.byref(d), 1, None).decode()
-            assert (name == "conv_dgrad_s2_kernel") == (mode == "2"), (mode, name)
-            L.check(lib.dsr_conv_dgrad(C.byref(d), dyd.data_ptr(), wd.data_ptr(), dx.data_ptr(), None, 0, st))
-            outs.append(dx)
-    finally:
-        if old is None:
-            os.environ.pop("DSR_DGRAD_S2", None)
-        else:
-            os.environ["DSR_DGRAD_S2"] = old
+    for mode in ("0", "2"):        # 0: four parity-class launches, 2: the single-launch kernel whatever the grid size
+        monkeypatch.setenv("DSR_DGRAD_S2", mode)
+        dx = torch.full((n, h, w, cin), float("nan"), dtype=torch.bfloat16, device=dev)
+        name = lib.dsr_conv_kernel_name(C.byref(d), 1, None).decode()
+        assert (name == "conv_dgrad_s2_kernel") == (mode == "2"), (mode, name)
+        L.check(lib.dsr_conv_dgrad(C.byref(d), dyd.data_ptr(), wd.data_ptr(), dx.data_ptr(), None, 0, st))
+        outs.append(dx)
     torch.cuda.synchronize()
     assert torch.isfinite(outs[1].float()).all()
     assert torch.equal(outs[0], outs[1])
@@ -1232,13 +1183,12 @@ def test_conv_wgrad_batched_equals_per_layer_launches(dev):
 
 
 @pytest.mark.parametrize("n,h,w,cin,cout", [(2, 40, 48, 64, 128), (1, 33, 70, 128, 256), (3, 16, 16, 192, 384)])
-def test_conv_wgrad_stride2_128_channel_blocks(dev, n, h, w, cin, cout):
+def test_conv_wgrad_stride2_128_channel_blocks(dev, n, h, w, cin, cout, monkeypatch):
     """conv_wgrad_dma_s2_kernel<COH = 2> (3x3 stride-2 weight gradient with 128 output channels per 8-wave block, so that the
     input halo is fetched once per 128 instead of once per 64 output channels; discriminator.py:31 at config 3) against the
     64-channel form (DSR_WGRAD_S2_CO128=0: the same per-wave products, a different pixel partition) and a float64
     torch.nn.grad.conv2d_weight of the same bf16 operands.  Odd sizes, a ragged last column tile, 192 input channels."""
     import ctypes as C
-    import os
     L = P("_lib")
     lib = L.lib()
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -1251,20 +1201,13 @@ def test_conv_wgrad_stride2_128_channel_blocks(dev, n, h, w, cin, cout):
     xg = x.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16).to(dev)
     dyg = dy.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16).to(dev)
     outs = {}
-    old = os.environ.get("DSR_WGRAD_S2_CO128")
-    try:
-        for mode in ("2", "0"):
-            os.environ["DSR_WGRAD_S2_CO128"] = mode
-            dw = torch.full((cout, cin, 3, 3), float("nan"), dtype=torch.float32, device=dev)
-            wsz = lib.dsr_conv_wgrad_workspace(C.byref(d))
-            ws = torch.empty(wsz, dtype=torch.uint8, device=dev)
-            L.check(lib.dsr_conv_wgrad(C.byref(d), xg.data_ptr(), dyg.data_ptr(), dw.data_ptr(), ws.data_ptr(), wsz, st))
-            outs[mode] = dw.cpu().double()
-    finally:
-        if old is None:
-            os.environ.pop("DSR_WGRAD_S2_CO128", None)
-        else:
-            os.environ["DSR_WGRAD_S2_CO128"] = old
+    for mode in ("2", "0"):
+        monkeypatch.setenv("DSR_WGRAD_S2_CO128", mode)
+        dw = torch.full((cout, cin, 3, 3), float("nan"), dtype=torch.float32, device=dev)
+        wsz = lib.dsr_conv_wgrad_workspace(C.byref(d))
+        ws = torch.empty(wsz, dtype=torch.uint8, device=dev)
+        L.check(lib.dsr_conv_wgrad(C.byref(d), xg.data_ptr(), dyg.data_ptr(), dw.data_ptr(), ws.data_ptr(), wsz, st))
+        outs[mode] = dw.cpu().double()
     scale = float(ref.abs().max())
     for mode, got in outs.items():
         assert torch.isfinite(got).all(), mode
