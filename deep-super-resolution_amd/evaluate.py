@@ -10,6 +10,7 @@ Counterparts of the reference's host glue, kept format-compatible so that ``.pth
 PSNR is 10*log10(range^2 / MSE) (torchmetrics' definition; that package is absent here, so the formula is restated --
 "parity unpinned").  ``data_range=None`` infers max-min of the target like ``PeakSignalNoiseRatio()`` does.
 The MSE is reduced on the device by the HIP loss kernel; only the final scalar crosses to the host.
+LPIPS is ``lpips.LPIPS`` (AlexNet trunk on the HIP path); ``lpips()`` below is the reference's helper around it.
 """
 import math
 import os
@@ -77,6 +78,12 @@ def ssim(pred, target, data_range=1.0):
     return float(total)
 
 
+def lpips(im0, im1, lpips_model):
+    """utils/common.py:105-109: host float of ``lpips_model(im0, im1)`` under ``no_grad`` (an ``lpips.LPIPS``)."""
+    with torch.no_grad():
+        return float(lpips_model(im0, im1))
+
+
 def to_uint8_image(img):
     """[3,H,W] float in [0,1] -> [H,W,3] uint8 numpy (eval_GAN.py:55-56; values are clipped first, the reference's bare
     ``astype(np.uint8)`` wraps out-of-range values)."""
@@ -84,14 +91,15 @@ def to_uint8_image(img):
 
 
 def evaluate_generator(gen, pairs, tile=None, out_dir=None, data_range=None, dtype=torch.float16, to_unit=None,
-                       with_ssim=True):
+                       with_ssim=True, lpips_model=None):
     """eval_GAN.py:21-69 for an iterable of (LR [1,3,h,w], HR [1,3,H,W], name) on the device.
 
-    Returns {'avg_psnr': ..., 'psnr': {name: value}, 'avg_ssim': ..., 'ssim': {name: value}} (LPIPS needs a downloaded
-    AlexNet and is out of reach offline).  ``out_dir`` (optional) receives <out_dir>/images/<name>.png like
+    Returns {'avg_psnr': ..., 'psnr': {name: value}, 'avg_ssim': ..., 'ssim': {name: value}}, and with ``lpips_model`` (an
+    ``lpips.LPIPS``; eval_GAN.py:32,49) also 'avg_lpips' (the reference's key, :66) and 'lpips': {name: value}; its numbers
+    are the trained metric's only when the model was given the AlexNet and head weights.  ``out_dir`` (optional) receives <out_dir>/images/<name>.png like
     save_image (utils/common.py:20-33); ``to_unit`` maps the network's output range to [0,1] for the PNG (default:
     identity, as in the reference)."""
-    per, ssims = OrderedDict(), OrderedDict()
+    per, ssims, lps = OrderedDict(), OrderedDict(), OrderedDict()
     for lr_image, hr_image, name in pairs:
         if isinstance(name, (list, tuple)):
             name = name[0]                                  # DataLoader collation of a batch of one (eval_GAN.py:40)
@@ -99,6 +107,8 @@ def evaluate_generator(gen, pairs, tile=None, out_dir=None, data_range=None, dty
         per[name] = psnr(resolved, hr_image, data_range)
         if with_ssim:
             ssims[name] = ssim(resolved, hr_image, 1.0)          # SSIM(data_range=1.) as at eval_GAN.py:31
+        if lpips_model is not None:
+            lps[name] = lpips(resolved, hr_image, lpips_model)   # eval_GAN.py:49
         if out_dir is not None:
             from PIL import Image
             img_dir = os.path.join(out_dir, "images")
@@ -108,4 +118,6 @@ def evaluate_generator(gen, pairs, tile=None, out_dir=None, data_range=None, dty
     out = {"avg_psnr": sum(per.values()) / max(len(per), 1), "psnr": per}
     if with_ssim:
         out.update(avg_ssim=sum(ssims.values()) / max(len(ssims), 1), ssim=ssims)
+    if lpips_model is not None:
+        out.update(avg_lpips=sum(lps.values()) / max(len(lps), 1), lpips=lps)
     return out

@@ -314,6 +314,30 @@ int dsr_ssim_blocks(int planes, int H, int W);
 int dsr_ssim_f32(const float* img1, const float* img2, int planes, int H, int W, float data_range, float* partial,
                  dsr_stream_t s);
 
+/* LPIPS with the AlexNet trunk (torchmetrics LearnedPerceptualImagePatchSimilarity(net_type='alex') at train_GAN.py:32,112,
+ * eval_GAN.py:32,49, DIP.py:75,185; csrc/lpips.hip).  The five convolutions are dsr_conv_fwd calls; these are the rest.
+ * dsr_lpips_tap_sizes: hw[2k], hw[2k+1] = height, width of tap k (relu1..relu5) for an H x W image; DSR_E_ARG if the trunk
+ * would produce an empty map.
+ * dsr_lpips_stem_prep: fp32 NCHW [N][3][H][W] img1, img2 -> out [2N][h1+2][w1+2][64] 16-bit NHWC (img1 first): optional
+ * x -> 2x - 1 (normalize), the scaling layer, zero padding 2, then the 4x4 space-to-depth, channel (py*4 + px)*3 + c of block
+ * (by, bx) = padded pixel (4by + py, 4bx + px) of channel c; channels 48..63 and pixels past the padded image are 0.  The stem
+ * is then a 3x3 / stride-1 / pad-0 conv of 64 -> 64 channels.  range[2] (device, preset to 0xffffffff, 0) receives the
+ * atomic min / max of the raw input values as order-preserving keys (f >= 0: bits | 0x80000000, f < 0: ~bits).
+ * dsr_maxpool3s2_fwd: nn.MaxPool2d(3, 2) (floor mode, no padding) on NHWC 16-bit; H, W = INPUT size (>= 3).
+ * dsr_lpips_distance: taps k < ntaps (HOST tables): feats[k] = [2N][hw[k]][cp[k]] 16-bit, lin_w[k] = [c[k]] fp32 device;
+ * partial gets dsr_lpips_distance_blocks(ntaps, hw, N) block sums of sum_c w[c] (n1[c] - n2[c])^2, n = f / sqrt(1e-8 + |f|^2).
+ * dsr_lpips_finalize: per_image[N] = sum_k (1/hw[k]) * (tap k's sums of image n); total[0] (+= if accumulate) =
+ * total_scale * sum_n per_image[n]. */
+int dsr_lpips_tap_sizes(int H, int W, int* hw);
+int dsr_lpips_stem_prep(int dtype, const float* img1, const float* img2, int N, int H, int W, int normalize, void* out,
+                        unsigned* range, dsr_stream_t s);
+int dsr_maxpool3s2_fwd(int dtype, const void* x, void* y, int N, int H, int W, int Cp, dsr_stream_t s);
+int dsr_lpips_distance_blocks(int ntaps, const int* hw, int N);
+int dsr_lpips_distance(int dtype, int ntaps, const void* const* feats, const float* const* lin_w, const int* hw, const int* cp,
+                       const int* c, int N, float* partial, dsr_stream_t s);
+int dsr_lpips_finalize(int ntaps, const int* hw, int N, const float* partial, float* per_image, float* total, float total_scale,
+                       int accumulate, dsr_stream_t s);
+
 /* measurement aid: out16[2x] = shader-clock cycle counter (s_memtime) and out16[2x+1] = 100 MHz real-time counter
  * (s_memrealtime) of XCD x (8 pairs; zero-fill before), read when the stream reaches this launch; two samples give the average
  * shader clock of what ran between them (difference pairs of the same XCD only: the cycle counters are per XCD) */
