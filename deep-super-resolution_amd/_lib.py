@@ -132,6 +132,10 @@ SIGNATURES = {
     "dsr_lpips_distance": (_I, [_I, _I, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(_I), C.POINTER(_I),
                                 C.POINTER(_I), _I, _P, _P]),
     "dsr_lpips_finalize": (_I, [_I, C.POINTER(_I), _I, _P, _P, _P, _F, _I, _P]),
+    "dsr_lpips_distance_bwd": (_I, [_I, _I, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(_I), C.POINTER(_I),
+                                    C.POINTER(_I), _I, _P, _F, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _P]),
+    "dsr_maxpool3s2_bwd": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "dsr_lpips_stem_prep_bwd": (_I, [_I, _P, _I, _I, _I, _I, _F, _P, _P]),
 }
 
 _lib = None

@@ -19,6 +19,17 @@ space-to-depth to 64 channels, input range), the five convolutions on dsr_conv_f
 fp32 accumulation; the batch of 2N images runs the trunk once), two 3x3 / stride-2 max-pool launches, one distance launch for
 all five taps and one finalise launch.  Only the [N] / scalar result and the input's (min, max) key pair leave the device.
 
+Backward (LPIPS as a training loss, ``loss = l1 + 0.1 * lpips(fake, hr)``): when grad mode is on and an input requires a
+gradient, the call goes through one autograd node that keeps the five tap tensors and runs, per trunk pass,
+  dsr_lpips_distance_bwd   the distance's closed-form derivative at all five taps, times each tap's ReLU mask;
+  dsr_conv_dgrad_masked    conv5 and conv4 (the mask of relu4 / relu3 in the epilogue) + dsr_pw_add of that tap's distance part;
+  dsr_conv_dgrad           conv3, conv2 and the stem (as the 3x3 / pad-0 conv over the space-to-depth input);
+  dsr_maxpool3s2_bwd       twice: pool backward + ReLU mask + the distance part of relu2 / relu1 in one pass;
+  dsr_lpips_stem_prep_bwd  16-bit gradient of the stem input -> fp32 NCHW image gradient.
+The weights are frozen buffers: there is no weight gradient.  If only one image requires a gradient (the training case: img2 is
+the HR target) every launch after the first covers that half of the batch only.  Nothing on the path reads a device value on
+the host; with ``validate_range=False`` the forward does not either, and forward + backward can be captured in a HIP graph.
+
 The 11x11 / stride-4 stem has 121 taps, more than the conv kernels take; after the space-to-depth it is an exact 3x3 / stride-1
 / pad-0 conv over 64 channels (48 real + 16 zero), whose weight is the 11x11 kernel zero-padded to 12x12 and regrouped once on
 the host (``stem_weight_s2d``).  64 rather than 48 input channels keep the conv on the gather kernels' 64-channel fast path.
@@ -28,6 +39,7 @@ downloaded here.  Like ``Vgg19Loss(state_dict=...)``, ``LPIPS(net_weights=..., l
 (or state dicts) the caller provides; otherwise deterministic stand-ins are used and ``pretrained`` is False.
 """
 import ctypes as C
+import math
 import os
 import struct
 from collections.abc import Mapping
@@ -146,10 +158,14 @@ class LPIPS(nn.Module):
     ``forward(img1, img2)`` -> 0-dim fp32 device tensor (``.item()`` works as in the reference); ``per_image`` -> [N];
     ``update`` / ``compute`` / ``reset`` keep a running sum and image count on the device (torchmetrics' ``sum_scores`` /
     ``total``).  ``net_weights`` / ``lin_weights``: path or state dict (see load_net_state / load_lin_state); stand-ins
-    otherwise.  ``dtype``: 16-bit storage of the trunk (fp32 accumulation)."""
+    otherwise.  ``dtype``: 16-bit storage of the trunk (fp32 accumulation).  ``validate_range=False`` skips the range check and
+    with it the call's one host read (needed inside a captured graph).  ``grad_scale``: static loss scale of the 16-bit
+    gradients (a power of two; None: chosen from the shapes, see ``_grad_scale``).
+
+    ``forward`` and ``per_image`` are differentiable with respect to either image; ``update`` never is (as in torchmetrics)."""
 
     def __init__(self, net_type="alex", reduction="mean", normalize=False, net_weights=None, lin_weights=None,
-                 dtype=torch.float16):
+                 dtype=torch.float16, validate_range=True, grad_scale=None):
         super().__init__()
         if net_type in ("vgg", "squeeze"):
             raise NotImplementedError(f"LPIPS: net_type '{net_type}' is not built here; only 'alex' is")
@@ -159,7 +175,11 @@ class LPIPS(nn.Module):
             raise ValueError(f"LPIPS: reduction must be 'mean' or 'sum', got {reduction!r}")
         if dtype not in (torch.float16, torch.bfloat16):
             raise ValueError(f"LPIPS: dtype must be torch.float16 or torch.bfloat16, got {dtype}")
+        if grad_scale is not None and not (float(grad_scale) > 0 and math.isfinite(float(grad_scale))):
+            raise ValueError(f"LPIPS: grad_scale must be a positive finite number, got {grad_scale!r}")
         self.net_type, self.reduction, self.normalize, self.dtype = net_type, reduction, bool(normalize), dtype
+        self.validate_range = bool(validate_range)
+        self.grad_scale = None if grad_scale is None else float(grad_scale)
         self.pretrained = net_weights is not None and lin_weights is not None
         net = load_net_state(net_weights if net_weights is not None else _standin_alex_state())
         lin = load_lin_state(lin_weights if lin_weights is not None else _standin_lin_state())
@@ -170,6 +190,7 @@ class LPIPS(nn.Module):
             self.register_buffer(f"lin{k + 1}", lin[k].contiguous())
         self.max_pairs_per_launch = None       # None: as many image pairs per trunk pass as keep every tensor below 2 GiB
         self._packed = {}
+        self._packed_dgrad = {}
         self.reset()
 
     # ---- running state (torchmetrics Metric surface)
@@ -200,12 +221,18 @@ class LPIPS(nn.Module):
 
     # ---- one-shot evaluation
     def forward(self, img1, img2):
-        _, tot = self._run(img1, img2, None)
+        _, tot = self._run_or_apply(img1, img2)
         return tot.reshape(())
 
     def per_image(self, img1, img2):
-        per, _ = self._run(img1, img2, None)
+        per, _ = self._run_or_apply(img1, img2)
         return per
+
+    def _run_or_apply(self, img1, img2):
+        if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (img1, img2)):
+            self._check_inputs(img1, img2)
+            return _LPIPSFunction.apply(self, img1, img2)
+        return self._run(img1, img2, None)
 
     # ---- the device path
     def _check_inputs(self, img1, img2):
@@ -258,9 +285,55 @@ class LPIPS(nn.Module):
             pairs = min(pairs, int(self.max_pairs_per_launch))
         return max(pairs, 1)
 
-    def _run(self, img1, img2, total_scale):
+    def _weights_dgrad(self, device):
+        """The packed input-gradient weight images [tap][Cin][Cout], made at the first backward."""
+        key = (str(device), self.dtype)
+        hit = self._packed_dgrad.get(key)
+        if hit is not None:
+            return hit
+        lib = _lib.lib()
+        dt = F16 if self.dtype == torch.float16 else BF16
+        packed = []
+        for k, (_, cout, cin, ks, _, _) in enumerate(ALEX_CONVS):
+            w = getattr(self, f"w{k + 1}")
+            cin_d, ks_d = (STEM_CP, 3) if k == 0 else (cin, ks)
+            d = ConvDesc(dt, 1, 16, 16, cin_d, cout, ks_d, ks_d, 1, 0, PAD_ZERO)
+            wf = torch.empty(lib.dsr_conv_packed_elems(C.byref(d), 0), dtype=self.dtype, device=device)
+            wd = torch.empty(lib.dsr_conv_packed_elems(C.byref(d), 1), dtype=self.dtype, device=device)
+            check(lib.dsr_conv_pack_weight(C.byref(d), _ptr(w), _ptr(wf), _ptr(wd), _stream()))
+            packed.append(wd)
+        self._packed_dgrad = {key: packed}
+        return packed
+
+    def _total_scale(self, n):
+        return 1.0 / n if self.reduction == "mean" else 1.0
+
+    def _grad_scale(self, n, sizes):
+        """The static loss scale S of the backward: every 16-bit gradient is S times the true one, the image gradient is
+        divided by S again (dsr_lpips_stem_prep_bwd), so a power of two changes nothing but the range.
+
+        Why it is needed: the distance gradient at tap k is 2 w (n1 - n2) / (s N hw_k) per element.  At the training size of the
+        step recipes (32 pairs of 512 x 512: hw_1 = 127^2, hw_5 = 31^2) with w ~ 4 / C, |n1 - n2| ~ 0.1 / sqrt(C) and a feature
+        norm s of a few units this is ~4e-9 at relu1 and ~1e-8 at relu5 -- below fp16's smallest subnormal (6e-8), four
+        thousand times below its normal range (6.1e-5).  The elements scale with 1 / (N hw_1), so the default is
+            S = 16 * 2^ceil(log2(N hw_1))        (N = 1 for reduction='sum': each image's value then has weight 1)
+        which puts the typical relu1 element of an unrelated pair near 32 w |n1 - n2| / s ~ 1e-2 and the relu5 one (hw_1 / hw_5
+        ~ 17 times larger) near 0.2, whatever the batch and image size: some 2^8 above fp16's normal limit and 2^16 below its
+        maximum (a close pair, with |n1 - n2| ten times smaller, sits that much lower: see the measurement below).  The
+        distance kernel saturates at the fp16 maximum instead of writing inf (a feature vector of norm ~1e-4 divides by it).
+        bf16 storage has fp32's range; the same S is used and is harmless.  Measured on the MI355X at that size (stand-in
+        weights, a noise-perturbed pair): unscaled, every element of all five taps rounds to zero in fp16; with the default
+        S = 2^23 the medians are 3e-3 (relu1) and 2e-4 ... 6e-4 (relu2 ... relu5), the largest element 0.14, none is zero
+        and 2 - 20 % per tap remain subnormal ("LPIPS backward")."""
+        if self.grad_scale is not None:
+            return self.grad_scale
+        n_eff = n if self.reduction == "mean" else 1
+        return float(2.0 ** (4 + math.ceil(math.log2(n_eff * sizes[0][0] * sizes[0][1]))))
+
+    def _run(self, img1, img2, total_scale, keep=None):
         """(per_image [N], total [1]); total = total_scale * sum (None: the module's reduction).  Raises ValueError on
-        out-of-range inputs before returning anything."""
+        out-of-range inputs before returning anything.  keep: a list that receives (first pair, last pair + 1, the five tap
+        tensors) of every trunk pass, for the backward."""
         self._check_inputs(img1, img2)
         n, _, h, w = img1.shape
         sizes = self.tap_sizes(h, w)
@@ -269,15 +342,19 @@ class LPIPS(nn.Module):
         img2 = img2.detach().contiguous().float()
         wf = self._weights(dev)
         if total_scale is None:
-            total_scale = 1.0 / n if self.reduction == "mean" else 1.0
+            total_scale = self._total_scale(n)
         per = torch.empty(n, dtype=torch.float32, device=dev)
         tot = torch.empty(1, dtype=torch.float32, device=dev)
         rng = torch.zeros(2, dtype=torch.int32, device=dev)
-        rng[0] = -1                                               # min key 0xffffffff, max key 0
+        rng[:1].fill_(-1)                                         # min key 0xffffffff, max key 0 (a fill: no host copy)
         step = self._pairs_per_launch(h, w, sizes)
         for i0 in range(0, n, step):
             i1 = min(n, i0 + step)
-            self._trunk(img1[i0:i1], img2[i0:i1], sizes, wf, per[i0:i1], tot, total_scale, i0 > 0, rng)
+            feats = self._trunk(img1[i0:i1], img2[i0:i1], sizes, wf, per[i0:i1], tot, total_scale, i0 > 0, rng)
+            if keep is not None:
+                keep.append((i0, i1, feats))
+        if not self.validate_range:
+            return per, tot
         lo_k, hi_k = rng.tolist()                                 # the one host read of the call
         lo, hi = _decode_key(lo_k), _decode_key(hi_k)
         lo_ok, hi_ok = (0.0, 1.0) if self.normalize else (-1.0, 1.0)
@@ -321,3 +398,112 @@ class LPIPS(nn.Module):
         lw = (C.c_void_p * 5)(*[getattr(self, f"lin{k + 1}").data_ptr() for k in range(5)])
         check(lib.dsr_lpips_distance(dt, 5, fp, lw, hw, cp, cp, n, _ptr(partial), st))
         check(lib.dsr_lpips_finalize(5, hw, n, _ptr(partial), _ptr(per), _ptr(tot), float(total_scale), int(accumulate), st))
+        return feats
+
+    def _upstream(self, gper, gtot, n, dev):
+        """fp32 [n]: d loss / d per_image[i] = gper[i] + total_scale * gtot, formed on the device."""
+        lib = _lib.lib()
+        g = None
+        if gtot is not None:
+            ones = torch.ones(n, dtype=torch.float32, device=dev)
+            g = torch.empty(n, dtype=torch.float32, device=dev)
+            check(lib.dsr_pw_axpby_f32(_ptr(ones), None, self._total_scale(n), 0.0, _ptr(gtot.contiguous().float()), _ptr(g), n,
+                                       _stream()))
+        if gper is not None:
+            gper = gper.contiguous().float()
+            if g is None:
+                return gper
+            both = torch.empty(n, dtype=torch.float32, device=dev)
+            check(lib.dsr_pw_axpby_f32(_ptr(gper), _ptr(g), 1.0, 1.0, None, _ptr(both), n, _stream()))
+            return both
+        return g
+
+    def _dgrad(self, k, m, ih, iw, dy, wd, x_act=None):
+        """Input gradient of conv k+1 over m images of ih x iw inputs; x_act: the ReLU output that is this conv's input, whose
+        mask then rides in the launch's epilogue."""
+        lib = _lib.lib()
+        _, cout, cin, ks, _, pad = ALEX_CONVS[k]
+        cin_d, ks_d, pad_d = (STEM_CP, 3, 0) if k == 0 else (cin, ks, pad)
+        d = ConvDesc(F16 if self.dtype == torch.float16 else BF16, m, ih, iw, cin_d, cout, ks_d, ks_d, 1, pad_d, PAD_ZERO)
+        dx = torch.empty((m, ih, iw, cin_d), dtype=self.dtype, device=dy.device)
+        if x_act is None:
+            check(lib.dsr_conv_dgrad(C.byref(d), _ptr(dy), _ptr(wd[k]), _ptr(dx), None, 0, _stream()))
+        else:
+            check(lib.dsr_conv_dgrad_masked(C.byref(d), _ptr(dy), _ptr(wd[k]), _ptr(x_act), ACT_RELU, 0.0, _ptr(dx), _stream()))
+        return dx
+
+    def _trunk_bwd(self, feats, n, h, w, sizes, g, which, out1, out2, scale):
+        """Backward of one trunk pass.  feats: its five taps [2n]...; g: fp32 [n] upstream gradient per image; which: 1 = image
+        1, 2 = image 2, 3 = both; out1 / out2: fp32 [n,3,h,w] slices that receive the image gradients."""
+        lib = _lib.lib()
+        st = _stream()
+        dt = F16 if self.dtype == torch.float16 else BF16
+        dev = feats[0].device
+        wd = self._weights_dgrad(dev)
+        m = 2 * n if which == 3 else n
+        half = slice(n, 2 * n) if which == 2 else slice(0, m)       # the images the chain below runs on
+        f = [t[half] for t in feats]
+        dist = [torch.empty_like(t) for t in f]                     # the distance part of each tap's gradient
+        hw = (C.c_int * 5)(*[y * x_ for y, x_ in sizes])
+        cp = (C.c_int * 5)(*LIN_CHANNELS)
+        fp = (C.c_void_p * 5)(*[t.data_ptr() for t in feats])
+        lw = (C.c_void_p * 5)(*[getattr(self, f"lin{k + 1}").data_ptr() for k in range(5)])
+        d1 = (C.c_void_p * 5)(*[t.data_ptr() for t in dist]) if which & 1 else None
+        d2 = (C.c_void_p * 5)(*[t[m - n:].data_ptr() for t in dist]) if which & 2 else None
+        check(lib.dsr_lpips_distance_bwd(dt, 5, fp, lw, hw, cp, cp, n, _ptr(g), float(scale), d1, d2, st))
+
+        def add(a, b):
+            out = torch.empty_like(a)
+            check(lib.dsr_pw_add(dt, _ptr(a), _ptr(b), _ptr(out), a.numel() // 8, st))
+            return out
+
+        def pool_bwd(x, dy, addend):
+            _, ih, iw, c = x.shape
+            dx = torch.empty_like(x)
+            check(lib.dsr_maxpool3s2_bwd(dt, _ptr(x), _ptr(dy), _ptr(addend), _ptr(dx), m, ih, iw, c, 1, st))
+            return dx
+
+        (h1, w1), (h2, w2), (h3, w3) = sizes[0], sizes[1], sizes[2]
+        gk = dist[4]                                                       # at conv5's output
+        gk = add(self._dgrad(4, m, h3, w3, gk, wd, x_act=f[3]), dist[3])  # at conv4's output
+        gk = add(self._dgrad(3, m, h3, w3, gk, wd, x_act=f[2]), dist[2])  # at conv3's output
+        gk = pool_bwd(f[1], self._dgrad(2, m, h3, w3, gk, wd), dist[1])   # through pool2 to conv2's output
+        gk = pool_bwd(f[0], self._dgrad(1, m, h2, w2, gk, wd), dist[0])   # through pool1 to conv1's output
+        gk = self._dgrad(0, m, h1 + 2, w1 + 2, gk, wd)                    # at the space-to-depth stem input
+        if which & 1:
+            check(lib.dsr_lpips_stem_prep_bwd(dt, _ptr(gk), n, h, w, int(self.normalize), float(scale), _ptr(out1), st))
+        if which & 2:
+            check(lib.dsr_lpips_stem_prep_bwd(dt, _ptr(gk[m - n:]), n, h, w, int(self.normalize), float(scale), _ptr(out2), st))
+
+
+class _LPIPSFunction(torch.autograd.Function):
+    """(per_image [N], total [1]) of LPIPS._run with the image gradients of LPIPS._trunk_bwd; the module's weights are
+    constants of the node."""
+
+    @staticmethod
+    def forward(ctx, mod, img1, img2):
+        chunks = []
+        per, tot = mod._run(img1, img2, None, keep=chunks)
+        ctx.mod, ctx.chunks = mod, chunks
+        ctx.shape, ctx.dtypes = tuple(img1.shape), (img1.dtype, img2.dtype)
+        ctx.set_materialize_grads(False)
+        return per, tot
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gper, gtot):
+        mod = ctx.mod
+        n, _, h, w = ctx.shape
+        which = (1 if ctx.needs_input_grad[1] else 0) | (2 if ctx.needs_input_grad[2] else 0)
+        if which == 0 or (gper is None and gtot is None):
+            return None, None, None
+        dev = ctx.chunks[0][2][0].device
+        sizes = mod.tap_sizes(h, w)
+        g = mod._upstream(gper, gtot, n, dev)
+        scale = mod._grad_scale(n, sizes)
+        out = [torch.empty(ctx.shape, dtype=torch.float32, device=dev) if which & b else None for b in (1, 2)]
+        for i0, i1, feats in ctx.chunks:
+            mod._trunk_bwd(feats, i1 - i0, h, w, sizes, g[i0:i1], which, None if out[0] is None else out[0][i0:i1],
+                           None if out[1] is None else out[1][i0:i1], scale)
+        out = [o if o is None or o.dtype == dt else o.to(dt) for o, dt in zip(out, ctx.dtypes)]
+        return None, out[0], out[1]

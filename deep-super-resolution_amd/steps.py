@@ -1,6 +1,7 @@
 """The timed step recipes on the HIP path.
 
 gen_l1_step : BASELINE config 2 (generator-only x4, L1, Adam) -- defined by SURVEY.md 8(d).
+gen_lpips_step : the same step with the perceptual fine-tuning loss l1_weight * L1 + lpips_weight * LPIPS(fake, hr).
 gan_step    : train_GAN.py:38-71 (do_epoch): D step, then G step with the detached adversarial term.
 dip_step    : DIP.py:47-95 closure + utils/DIP.py:33-40 Adam iteration.
 """
@@ -19,6 +20,24 @@ def gen_l1_step(gen, opt, lr_patches, hr_patches):
         loss.backward()
     opt.step()
     return loss.detach(), fake.detach()
+
+
+def gen_lpips_step(gen, opt, lpips, lr_patches, hr_patches, l1_weight=1.0, lpips_weight=0.1):
+    """Perceptual fine-tuning of a PSNR-trained generator: loss = l1_weight * L1 + lpips_weight * LPIPS(fake, hr).
+
+    `lpips`: an lpips.LPIPS with normalize=False (the generator ends in tanh and scale_images targets live in [-1, 1]); only
+    `fake` requires a gradient, so the LPIPS backward runs on that half of the trunk's batch.  Returns the two unweighted terms
+    and `fake` as device tensors (no host sync here).  Inside GraphedStep the module needs validate_range=False: the range
+    check is the one host read of the call."""
+    fake = gen(lr_patches)
+    l1 = F.l1_loss(fake, hr_patches)
+    lp = lpips(fake, hr_patches)
+    loss = F.add_losses(F.scale_loss(l1, float(l1_weight)), F.scale_loss(lp, float(lpips_weight)))
+    opt.zero_grad()
+    with F.batched_wgrad():
+        loss.backward()
+    opt.step()
+    return l1.detach(), lp.detach(), fake.detach()
 
 
 _side_streams = {}

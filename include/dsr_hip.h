@@ -338,6 +338,25 @@ int dsr_lpips_distance(int dtype, int ntaps, const void* const* feats, const flo
 int dsr_lpips_finalize(int ntaps, const int* hw, int N, const float* partial, float* per_image, float* total, float total_scale,
                        int accumulate, dsr_stream_t s);
 
+/* The backward of the same path (LPIPS as a training loss; the five input gradients are dsr_conv_dgrad /
+ * dsr_conv_dgrad_masked calls).  All gradients are 16-bit NHWC and carry the caller's static loss `scale` (a power of two keeps
+ * it exact), which dsr_lpips_stem_prep_bwd divides out again.
+ * dsr_lpips_distance_bwd: tables as dsr_lpips_distance; g[N] (device fp32) = upstream gradient of each image's value.  With
+ * s = sqrt(1e-8 + |f|^2), n = f / s, u[c] = 2 w[c] (n1[c] - n2[c]) g[image] scale / hw[k]:  d1[k] = (u - n1 <u, n1>) / s1 * (f1 > 0),
+ * d2[k] = -(u - n2 <u, n2>) / s2 * (f2 > 0), each [N][hw[k]][cp[k]]: the gradient at the pre-activation of the tap's ReLU.  d1 or
+ * d2 may be NULL (that half is not written), not both.
+ * dsr_maxpool3s2_bwd: dx [N][H][W][Cp] = autograd of nn.MaxPool2d(3, 2) for dy [N][OH][OW][Cp] with the windows' arg-max
+ * recomputed from x (torch's tie rule: row-major scan, first maximum), fp32 sum of the at most four dy a pixel wins; times
+ * (x > 0) if relu_mask; plus addend (same shape as x, nullable); one rounding.
+ * dsr_lpips_stem_prep_bwd: dx [N][h1+2][w1+2][64] (gradient of dsr_lpips_stem_prep's output, one image set) -> dimg fp32
+ * [N][3][H][W] = dx gathered back, / scaling-layer scale[c], * 2 if normalize, / scale. */
+int dsr_lpips_distance_bwd(int dtype, int ntaps, const void* const* feats, const float* const* lin_w, const int* hw, const int* cp,
+                           const int* c, int N, const float* g, float scale, void* const* d1, void* const* d2, dsr_stream_t s);
+int dsr_maxpool3s2_bwd(int dtype, const void* x, const void* dy, const void* addend, void* dx, int N, int H, int W, int Cp,
+                       int relu_mask, dsr_stream_t s);
+int dsr_lpips_stem_prep_bwd(int dtype, const void* dx, int N, int H, int W, int normalize, float scale, float* dimg,
+                            dsr_stream_t s);
+
 /* measurement aid: out16[2x] = shader-clock cycle counter (s_memtime) and out16[2x+1] = 100 MHz real-time counter
  * (s_memrealtime) of XCD x (8 pairs; zero-fill before), read when the stream reaches this launch; two samples give the average
  * shader clock of what ran between them (difference pairs of the same XCD only: the cycle counters are per XCD) */
