@@ -136,6 +136,14 @@ SIGNATURES = {
                                     C.POINTER(_I), _I, _P, _F, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _P]),
     "dsr_maxpool3s2_bwd": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dsr_lpips_stem_prep_bwd": (_I, [_I, _P, _I, _I, _I, _I, _F, _P, _P]),
+    "dsr_ssim_img_blocks": (_I, [_I, _I, _I, _I]),
+    "dsr_ssim_img_f32": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _F, _I, _P]),
+    "dsr_ssim_bwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P]),
+    "dsr_psnr_blocks": (_I, [_I, _I]),
+    "dsr_psnr_stats_f32": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "dsr_psnr_finalize": (_I, [_P, _P, _I, _I, _I, _F, _F, _P, _P, _F, _P, _P]),
+    "dsr_metric_accumulate": (_I, [_P, _I, _P, _P]),
+    "dsr_metric_compute": (_I, [_P, _I, _I, _F, _F, _P, _P]),
 }
 
 _lib = None
@@ -146,7 +154,8 @@ LAUNCH_LOG = None
 _NO_LAUNCH = ("dsr_last_error", "dsr_abi_version", "dsr_conv_dgrad_ps_supported", "dsr_conv_dgrad_ps_rows", "dsr_conv_dgrad_bn_supported", "dsr_conv_dgrad_bn_rows", "dsr_conv_dgrad_first_bwd_supported", "dsr_conv_dgrad_first_bwd_workspace", "dsr_conv_kernel_name", "dsr_conv_wgrad_batchable", "dsr_conv_wgrad_batched_workspace", "dsr_conv_dgrad_add_supported", "dsr_conv_dgrad_masked_supported", "dsr_conv_fwd_affine_supported",
               "dsr_conv_first2_supported", "dsr_conv_first2_stats_rows", "dsr_conv_first_bwd_supported", "dsr_conv_first_bwd_workspace", "dsr_conv_out_size", "dsr_conv_stats_rows",
               "dsr_conv_packed_elems", "dsr_conv_dgrad_workspace", "dsr_conv_wgrad_workspace", "dsr_pw_scratch_rows",
-              "dsr_pw_reduce_blocks", "dsr_linear_fwd_workspace", "dsr_ssim_blocks", "dsr_lpips_tap_sizes", "dsr_lpips_distance_blocks")
+              "dsr_pw_reduce_blocks", "dsr_linear_fwd_workspace", "dsr_ssim_blocks", "dsr_lpips_tap_sizes", "dsr_lpips_distance_blocks",
+              "dsr_ssim_img_blocks", "dsr_psnr_blocks")
 
 
 class _Lib:

@@ -1,0 +1,339 @@
+"""PSNR and SSIM as metric modules on the HIP path: the two objects the reference's scripts build next to LPIPS
+(torchmetrics ``PeakSignalNoiseRatio()`` and ``StructuralSimilarityIndexMeasure(data_range=1.0)``: train_GAN.py:30-31,110-111,
+eval_GAN.py:30-31,47-48, DIP.py:73-74,157-158,183-184).
+
+torchmetrics is absent here, so both restate its documented behaviour -- PARITY UNPINNED, as for ``lpips.LPIPS`` and
+``evaluate.psnr``:
+  PSNR  10 / ln(base) * (2 ln(range) - ln(SSE / count)); with ``dim=None`` over the whole batch (and every batch added by
+        ``update``), with ``dim=(1, 2, 3)`` per image, then reduced.  ``data_range=None`` takes the range from the target as
+        max(running max, target max) - min(running min, target min), the running pair starting at 0.
+  SSIM  Wang, Bovik, Sheikh, Simoncelli 2004 with a Gaussian 11x11 window (sigma 1.5), K1 = 0.01, K2 = 0.03, per channel, the
+        mean over every window position inside the image (torchmetrics reflect-pads by 5 and crops that border again: the same
+        positions), per image; then the batch mean, sum, or the [N] values (``reduction``).
+
+Both behave like a torchmetrics ``Metric`` with ``full_state_update=False``: ``forward`` returns the batch's value from a fresh
+state and adds the batch to the running state; ``update`` / ``compute`` / ``reset`` keep that state on the device (sums, counts
+and PSNR's running min / max, in float64).  Nothing here reads a device value on the host, so a call can be captured in a HIP
+graph (steps.GraphedStep).
+
+Device work (csrc/metrics.hip, include/dsr_hip.h):
+  dsr_ssim_img_f32     per-image SSIM: separable row / column passes over an LDS tile, one partial per block, a one-block fold;
+  dsr_ssim_bwd_f32     its input gradient for either image or both in one launch, the moments recomputed per tile;
+  dsr_psnr_stats_f32   one pass: per-block squared-error sums and the target's min / max as order-preserving keys;
+  dsr_psnr_finalize    per-image or whole-batch PSNR and the running-state update;
+  dsr_metric_accumulate / dsr_metric_compute   the running state.
+SSIM is differentiable (a loss term such as ``1 - ssim(x, y)``); PSNR is not.
+"""
+import ctypes as C
+import math
+import numbers
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+from ._lib import check
+
+_WIN = 11
+_REDUCTIONS = ("elementwise_mean", "sum", "none", None)
+
+
+def _ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _check_pair(name, preds, target):
+    """Both inputs 4-D tensors of one shape, at least 11 x 11, on the device.  Returns (N, C, H, W)."""
+    for t in (preds, target):
+        if not torch.is_tensor(t) or t.dim() != 4:
+            raise ValueError(f"{name}: expected two [N, C, H, W] tensors, got "
+                             f"{tuple(preds.shape) if torch.is_tensor(preds) else type(preds).__name__} and "
+                             f"{tuple(target.shape) if torch.is_tensor(target) else type(target).__name__}")
+    if preds.shape != target.shape:
+        raise ValueError(f"{name}: the two inputs must have one shape, got {tuple(preds.shape)} and {tuple(target.shape)}")
+    n, c, h, w = preds.shape
+    if n < 1 or c < 1:
+        raise ValueError(f"{name}: empty batch {tuple(preds.shape)}")
+    if h < _WIN or w < _WIN:
+        raise ValueError(f"{name}: images of {h}x{w} are smaller than 11x11")
+    if not (preds.is_floating_point() and target.is_floating_point()):
+        raise ValueError(f"{name}: expected floating-point inputs, got {preds.dtype} and {target.dtype}")
+    if not (preds.is_cuda and target.is_cuda):
+        raise RuntimeError("deep-super-resolution_amd: tensors must live on the MI355X (cuda device); "
+                           "there is no CPU implementation of this path")
+    return n, c, h, w
+
+
+def _f32(t):
+    """fp32 contiguous view of t, detached (fp16 / bf16 / fp64 inputs are computed in fp32)."""
+    return t.detach().contiguous().float()
+
+
+def _positive_float(name, what, v):
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not (float(v) > 0 and math.isfinite(float(v))):
+        raise ValueError(f"{name}: {what} must be a positive finite number, got {v!r}")
+    return float(v)
+
+
+def _check_reduction(name, reduction):
+    if reduction not in _REDUCTIONS:
+        raise ValueError(f"{name}: reduction must be one of 'elementwise_mean', 'sum', 'none' or None, got {reduction!r}")
+    return "none" if reduction is None else reduction
+
+
+class _RunningState:
+    """float64 [4] device state (see dsr_psnr_finalize / dsr_metric_accumulate) and, for reduction 'none', the per-image
+    values of every update.  ``updated`` is a host flag set by the calls themselves: no device read."""
+
+    def __init__(self):
+        self.buf = None
+        self.values = []
+        self.updated = False
+
+    def get(self, dev):
+        if self.buf is None or self.buf.device != dev:
+            self.buf = torch.zeros(4, dtype=torch.float64, device=dev)     # PSNR's running min / max start at 0
+        return self.buf
+
+
+class PeakSignalNoiseRatio(nn.Module):
+    """torchmetrics ``PeakSignalNoiseRatio(data_range, base, reduction, dim)`` on the HIP path (not differentiable).
+
+    ``dim``: None (one value over everything seen) or (1, 2, 3) (per image, then ``reduction``: 'elementwise_mean', 'sum',
+    'none' / None; needs ``data_range``).  ``data_range``: a positive number, or None to infer it from the targets as above.
+    A tuple ``data_range`` (torchmetrics clamps the inputs to it) and other ``dim``s are not built here.  Inputs are [N,C,H,W]
+    of one shape and at least 11 x 11, like SSIM's (the two modules take the same batches at every call site)."""
+
+    def __init__(self, data_range=None, base=10.0, reduction="elementwise_mean", dim=None):
+        super().__init__()
+        if isinstance(data_range, (tuple, list)):
+            raise NotImplementedError("PeakSignalNoiseRatio: data_range as a (min, max) tuple (clamping the inputs) is not "
+                                      "built here; pass a number or None")
+        if dim is not None:
+            d = (dim,) if isinstance(dim, int) else tuple(dim)
+            if tuple(sorted(d)) != (1, 2, 3):
+                raise NotImplementedError(f"PeakSignalNoiseRatio: dim={dim!r} is not built here; only None and (1, 2, 3) are")
+            if data_range is None:
+                raise ValueError("PeakSignalNoiseRatio: the `data_range` must be given when `dim` is not None")
+        self.dim = None if dim is None else (1, 2, 3)
+        self.data_range = None if data_range is None else _positive_float("PeakSignalNoiseRatio", "data_range", data_range)
+        b = _positive_float("PeakSignalNoiseRatio", "base", base)
+        if b == 1.0:
+            raise ValueError("PeakSignalNoiseRatio: base must not be 1")
+        self.base = b
+        self.log_scale = 10.0 / math.log(b)
+        self.reduction = _check_reduction("PeakSignalNoiseRatio", reduction)
+        self._st = _RunningState()
+
+    # ---- running state
+    def reset(self):
+        self._st = _RunningState()
+
+    def update(self, preds, target):
+        self._batch(preds, target)
+
+    def forward(self, preds, target):
+        return self._batch(preds, target)
+
+    def compute(self):
+        st = self._st
+        if not st.updated:
+            raise RuntimeError("PeakSignalNoiseRatio.compute() called before update()")
+        if self.dim is not None and self.reduction == "none":
+            return torch.cat(st.values)
+        out = torch.empty(1, dtype=torch.float32, device=st.buf.device)
+        if self.dim is None:
+            mode = 2
+        else:
+            mode = 1 if self.reduction == "elementwise_mean" else 0
+        check(_lib.lib().dsr_metric_compute(_ptr(st.buf), mode, int(self.data_range is None), self._range(), self.log_scale,
+                                            _ptr(out), _stream()))
+        return out.reshape(())
+
+    # ---- the device path
+    def _range(self):
+        return 1.0 if self.data_range is None else self.data_range       # (ignored when inferred)
+
+    def _batch(self, preds, target):
+        """The batch's value from a fresh state; the batch is added to the running state."""
+        n, c, h, w = _check_pair("PeakSignalNoiseRatio", preds, target)
+        e = c * h * w
+        lib = _lib.lib()
+        st = _stream()
+        dev = preds.device
+        p, t = _f32(preds), _f32(target)
+        blocks = lib.dsr_psnr_blocks(n, e)
+        if blocks <= 0:
+            raise RuntimeError(f"PeakSignalNoiseRatio: {n} images of {e} elements are too many for one launch")
+        sse = torch.empty(blocks, dtype=torch.float32, device=dev)
+        keys = torch.empty(2 * blocks, dtype=torch.int32, device=dev)
+        check(lib.dsr_psnr_stats_f32(_ptr(p), _ptr(t), n, e, _ptr(sse), _ptr(keys), st))
+        state = self._st.get(dev)
+        if self.dim is None:
+            val = torch.empty(1, dtype=torch.float32, device=dev)
+            check(lib.dsr_psnr_finalize(_ptr(sse), _ptr(keys), n, e, int(self.data_range is None), self._range(),
+                                        self.log_scale, None, _ptr(val), 1.0, _ptr(state), st))
+            out = val.reshape(())
+        else:
+            per = torch.empty(n, dtype=torch.float32, device=dev)
+            val = None if self.reduction == "none" else torch.empty(1, dtype=torch.float32, device=dev)
+            scale = 1.0 / n if self.reduction == "elementwise_mean" else 1.0
+            check(lib.dsr_psnr_finalize(_ptr(sse), _ptr(keys), n, e, 0, self.data_range, self.log_scale, _ptr(per), _ptr(val),
+                                        scale, _ptr(state), st))
+            if self.reduction == "none":
+                self._st.values.append(per.clone())
+                out = per
+            else:
+                out = val.reshape(())
+        self._st.updated = True
+        return out
+
+
+class StructuralSimilarityIndexMeasure(nn.Module):
+    """torchmetrics ``StructuralSimilarityIndexMeasure`` on the HIP path, for what the reference uses: the Gaussian 11x11 window
+    with sigma 1.5 and a positive ``data_range`` (the reference passes 1.0).  ``reduction``: 'elementwise_mean' (0-dim),
+    'sum' (0-dim) or 'none' / None ([N], one value per image).
+
+    ``forward`` is differentiable with respect to either input or both when grad mode is on and an input requires a gradient:
+    ``1 - ssim(x, y)`` is a loss term.  ``update`` never is."""
+
+    def __init__(self, gaussian_kernel=True, sigma=1.5, kernel_size=11, reduction="elementwise_mean", data_range=1.0,
+                 k1=0.01, k2=0.03, return_full_image=False, return_contrast_sensitivity=False):
+        super().__init__()
+        name = "StructuralSimilarityIndexMeasure"
+        if not gaussian_kernel:
+            raise NotImplementedError(f"{name}: gaussian_kernel=False (a uniform window) is not built here")
+        sig = tuple(sigma) if isinstance(sigma, (tuple, list)) else (sigma, sigma)
+        if len(sig) != 2 or any(isinstance(s, bool) or not isinstance(s, numbers.Real) or float(s) != 1.5 for s in sig):
+            raise NotImplementedError(f"{name}: sigma={sigma!r} is not built here; only 1.5 is")
+        ks = tuple(kernel_size) if isinstance(kernel_size, (tuple, list)) else (kernel_size, kernel_size)
+        if len(ks) != 2 or any(isinstance(k, bool) or k != _WIN for k in ks):
+            raise NotImplementedError(f"{name}: kernel_size={kernel_size!r} is not built here; only 11 is")
+        if return_full_image:
+            raise NotImplementedError(f"{name}: return_full_image=True is not built here")
+        if return_contrast_sensitivity:
+            raise NotImplementedError(f"{name}: return_contrast_sensitivity=True is not built here")
+        if data_range is None:
+            raise NotImplementedError(f"{name}: data_range=None (inferred from the inputs) is not built here; pass a number")
+        if isinstance(data_range, (tuple, list)):
+            raise NotImplementedError(f"{name}: data_range as a (min, max) tuple (clamping the inputs) is not built here")
+        self.data_range = _positive_float(name, "data_range", data_range)
+        self.k1 = _positive_float(name, "k1", k1)
+        self.k2 = _positive_float(name, "k2", k2)
+        self.reduction = _check_reduction(name, reduction)
+        self.c1 = (self.k1 * self.data_range) ** 2
+        self.c2 = (self.k2 * self.data_range) ** 2
+        if not (0 < float(C.c_float(self.c1).value) < math.inf and 0 < float(C.c_float(self.c2).value) < math.inf):
+            raise ValueError(f"{name}: (k * data_range)^2 leaves the fp32 range")
+        self._st = _RunningState()
+
+    # ---- running state
+    def reset(self):
+        self._st = _RunningState()
+
+    def update(self, preds, target):
+        _check_pair("StructuralSimilarityIndexMeasure", preds, target)
+        per, _ = self._run(preds, target)
+        self._accumulate(per)
+
+    def compute(self):
+        st = self._st
+        if not st.updated:
+            raise RuntimeError("StructuralSimilarityIndexMeasure.compute() called before update()")
+        if self.reduction == "none":
+            return torch.cat(st.values)
+        out = torch.empty(1, dtype=torch.float32, device=st.buf.device)
+        mode = 1 if self.reduction == "elementwise_mean" else 0
+        check(_lib.lib().dsr_metric_compute(_ptr(st.buf), mode, 0, 1.0, 1.0, _ptr(out), _stream()))
+        return out.reshape(())
+
+    def forward(self, preds, target):
+        _check_pair("StructuralSimilarityIndexMeasure", preds, target)
+        if torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad):
+            per, tot = _SSIMFunction.apply(self, preds, target)
+        else:
+            per, tot = self._run(preds, target)
+        self._accumulate(per.detach())
+        return per if self.reduction == "none" else tot.reshape(())
+
+    # ---- the device path
+    def _total_scale(self, n):
+        return 1.0 / n if self.reduction == "elementwise_mean" else 1.0
+
+    def _accumulate(self, per):
+        st = self._st
+        check(_lib.lib().dsr_metric_accumulate(_ptr(per), per.shape[0], _ptr(st.get(per.device)), _stream()))
+        if self.reduction == "none":
+            st.values.append(per.clone())
+        st.updated = True
+
+    def _run(self, preds, target, a=None, b=None):
+        """(per_image [N], total [1] = the reduction's scale * sum) of fp32 copies a, b of the inputs."""
+        n, c, h, w = preds.shape
+        a = _f32(preds) if a is None else a
+        b = _f32(target) if b is None else b
+        lib = _lib.lib()
+        blocks = lib.dsr_ssim_img_blocks(n, c, h, w)
+        if blocks <= 0:
+            raise RuntimeError(f"StructuralSimilarityIndexMeasure: {tuple(preds.shape)} needs too many window tiles")
+        dev = a.device
+        partial = torch.empty(blocks, dtype=torch.float32, device=dev)
+        per = torch.empty(n, dtype=torch.float32, device=dev)
+        tot = torch.empty(1, dtype=torch.float32, device=dev)
+        check(lib.dsr_ssim_img_f32(_ptr(a), _ptr(b), n, c, h, w, self.c1, self.c2, _ptr(partial), _ptr(per), _ptr(tot),
+                                   self._total_scale(n), 0, _stream()))
+        return per, tot
+
+    def _upstream(self, gper, gtot, n, dev):
+        """fp32 [n]: d loss / d per_image[i] = gper[i] + total_scale * gtot, formed on the device."""
+        lib = _lib.lib()
+        g = None
+        if gtot is not None:
+            ones = torch.ones(n, dtype=torch.float32, device=dev)
+            g = torch.empty(n, dtype=torch.float32, device=dev)
+            check(lib.dsr_pw_axpby_f32(_ptr(ones), None, self._total_scale(n), 0.0, _ptr(gtot.contiguous().float()), _ptr(g), n,
+                                       _stream()))
+        if gper is not None:
+            gper = gper.contiguous().float()
+            if g is None:
+                return gper
+            both = torch.empty(n, dtype=torch.float32, device=dev)
+            check(lib.dsr_pw_axpby_f32(_ptr(gper), _ptr(g), 1.0, 1.0, None, _ptr(both), n, _stream()))
+            return both
+        return g
+
+
+class _SSIMFunction(torch.autograd.Function):
+    """(per_image [N], total [1]) of StructuralSimilarityIndexMeasure._run, with dsr_ssim_bwd_f32 as the backward."""
+
+    @staticmethod
+    def forward(ctx, mod, preds, target):
+        a, b = _f32(preds), _f32(target)
+        per, tot = mod._run(preds, target, a, b)
+        ctx.mod, ctx.a, ctx.b = mod, a, b
+        ctx.dtypes = (preds.dtype, target.dtype)
+        ctx.set_materialize_grads(False)
+        return per, tot
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gper, gtot):
+        want1, want2 = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if not (want1 or want2) or (gper is None and gtot is None):
+            return None, None, None
+        mod, a, b = ctx.mod, ctx.a, ctx.b
+        n, c, h, w = a.shape
+        g = mod._upstream(gper, gtot, n, a.device)
+        g1 = torch.empty_like(a) if want1 else None
+        g2 = torch.empty_like(b) if want2 else None
+        check(_lib.lib().dsr_ssim_bwd_f32(_ptr(a), _ptr(b), n, c, h, w, mod.c1, mod.c2, _ptr(g), _ptr(g1), _ptr(g2), _stream()))
+        out = [o if o is None or o.dtype == dt else o.to(dt) for o, dt in zip((g1, g2), ctx.dtypes)]
+        return None, out[0], out[1]
+
+
+PSNR = PeakSignalNoiseRatio
+SSIM = StructuralSimilarityIndexMeasure

@@ -314,6 +314,36 @@ int dsr_ssim_blocks(int planes, int H, int W);
 int dsr_ssim_f32(const float* img1, const float* img2, int planes, int H, int W, float data_range, float* partial,
                  dsr_stream_t s);
 
+/* The metric modules of metrics.py (same window and formula; c1 = (k1 range)^2, c2 = (k2 range)^2, both > 0 and finite).
+ * dsr_ssim_img_f32: fp32 NCHW img1, img2 [N][C][H][W] -> per_image[N] = mean SSIM over the image's C x (H-10) x (W-10) window
+ * positions (nullable), total[0] (+= if accumulate; nullable) = total_scale * sum_n per_image[n]; partial: scratch of
+ * dsr_ssim_img_blocks(N, C, H, W) floats.  Two launches (tiles, then a one-block fold in a fixed order).
+ * dsr_ssim_bwd_f32: g[N] (device) = upstream gradient of each per-image value -> grad1 / grad2 (fp32 NCHW, either nullable, not
+ * both) = g[n] d per_image[n] / d img, one launch; the moments are recomputed per tile.
+ * dsr_psnr_stats_f32: preds, target fp32 [N][E] -> per block of dsr_psnr_blocks(N, E) (blocks of one image are consecutive):
+ * partial_sse[b] = sum of squared errors, partial_keys[2b], [2b+1] = order-preserving keys of the target's min, max
+ * (f >= 0: bits | 0x80000000, f < 0: ~bits).
+ * dsr_psnr_finalize: log_scale = 10 / ln(base).  per_image != null: per_image[n] = log_scale (2 ln data_range - ln(SSE_n / E)),
+ * value (nullable) = value_scale * sum_n per_image[n], state[0] += that sum, state[1] += N.  per_image == null: value = PSNR of the
+ * whole batch with range = data_range, or (infer_range) max(target max, 0) - min(target min, 0); state (nullable, double[4]:
+ * SSE, count, running min, running max) += the batch's SSE and N E, min / max folded in.
+ * dsr_metric_accumulate: state[0] += sum_n per_image[n], state[1] += N (double[2]).
+ * dsr_metric_compute: out[0] = state[0] (mode 0), state[0] / state[1] (mode 1), or the PSNR of a dsr_psnr_finalize batch state
+ * (mode 2; range = data_range, or state[3] - state[2] with infer_range). */
+int dsr_ssim_img_blocks(int N, int C, int H, int W);
+int dsr_ssim_img_f32(const float* img1, const float* img2, int N, int C, int H, int W, float c1, float c2, float* partial,
+                     float* per_image, float* total, float total_scale, int accumulate, dsr_stream_t s);
+int dsr_ssim_bwd_f32(const float* img1, const float* img2, int N, int C, int H, int W, float c1, float c2, const float* g,
+                     float* grad1, float* grad2, dsr_stream_t s);
+int dsr_psnr_blocks(int N, int E);
+int dsr_psnr_stats_f32(const float* preds, const float* target, int N, int E, float* partial_sse, unsigned* partial_keys,
+                       dsr_stream_t s);
+int dsr_psnr_finalize(const float* partial_sse, const unsigned* partial_keys, int N, int E, int infer_range, float data_range,
+                      float log_scale, float* per_image, float* value, float value_scale, double* state, dsr_stream_t s);
+int dsr_metric_accumulate(const float* per_image, int N, double* state, dsr_stream_t s);
+int dsr_metric_compute(const double* state, int mode, int infer_range, float data_range, float log_scale, float* out,
+                       dsr_stream_t s);
+
 /* LPIPS with the AlexNet trunk (torchmetrics LearnedPerceptualImagePatchSimilarity(net_type='alex') at train_GAN.py:32,112,
  * eval_GAN.py:32,49, DIP.py:75,185; csrc/lpips.hip).  The five convolutions are dsr_conv_fwd calls; these are the rest.
  * dsr_lpips_tap_sizes: hw[2k], hw[2k+1] = height, width of tap k (relu1..relu5) for an H x W image; DSR_E_ARG if the trunk
