@@ -144,6 +144,12 @@ SIGNATURES = {
     "dsr_psnr_finalize": (_I, [_P, _P, _I, _I, _I, _F, _F, _P, _P, _F, _P, _P]),
     "dsr_metric_accumulate": (_I, [_P, _I, _P, _P]),
     "dsr_metric_compute": (_I, [_P, _I, _I, _F, _F, _P, _P]),
+    "dsr_lbfgs_workspace": (_Z, [_I, _Z, _I]),
+    "dsr_lbfgs_vector_floats": (_Z, [_I, _Z]),
+    "dsr_lbfgs_gather": (_I, [_I, C.POINTER(C.c_void_p), C.POINTER(_Z), _P, _Z, _P, _I, _Z, _P]),
+    "dsr_lbfgs_dots": (_I, [_P, _Z, _P, _I, _Z, _I, _P]),
+    "dsr_lbfgs_scalar": (_I, [_P, _Z, _I, _Z, _I, _P, _I, _P, C.c_double, _I, _I, C.c_double, C.c_double, _P]),
+    "dsr_lbfgs_combine": (_I, [_I, C.POINTER(C.c_void_p), C.POINTER(_Z), _P, _Z, _P, _I, _Z, _P]),
 }
 
 _lib = None
@@ -155,7 +161,7 @@ _NO_LAUNCH = ("dsr_last_error", "dsr_abi_version", "dsr_conv_dgrad_ps_supported"
               "dsr_conv_first2_supported", "dsr_conv_first2_stats_rows", "dsr_conv_first_bwd_supported", "dsr_conv_first_bwd_workspace", "dsr_conv_out_size", "dsr_conv_stats_rows",
               "dsr_conv_packed_elems", "dsr_conv_dgrad_workspace", "dsr_conv_wgrad_workspace", "dsr_pw_scratch_rows",
               "dsr_pw_reduce_blocks", "dsr_linear_fwd_workspace", "dsr_ssim_blocks", "dsr_lpips_tap_sizes", "dsr_lpips_distance_blocks",
-              "dsr_ssim_img_blocks", "dsr_psnr_blocks")
+              "dsr_ssim_img_blocks", "dsr_psnr_blocks", "dsr_lbfgs_workspace", "dsr_lbfgs_vector_floats")
 
 
 class _Lib:

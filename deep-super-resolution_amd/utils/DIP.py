@@ -6,7 +6,7 @@ Host-side glue: the closure the caller passes in runs the HIP network; nothing h
 import numpy as np
 import torch
 
-from ..optim import FusedAdam
+from ..optim import FusedAdam, FusedLBFGS
 
 # utils/DIP.py:21 -- the LBFGS branch first takes 100 Adam steps at this fixed rate
 LBFGS_WARMUP_STEPS = 100
@@ -23,16 +23,17 @@ def _adam_loop(parameters, closure, learning_rate, steps):
     optimizer.zero_grad(set_to_none=True)
 
 
-def _lbfgs(parameters, closure, learning_rate, num_iter):
+def _lbfgs(parameters, closure, learning_rate, num_iter, fused=False):
     """utils/DIP.py:19-31: Adam warm-up, then ONE torch.optim.LBFGS.step of ``max_iter=num_iter`` inner iterations
-    with both tolerances disabled.  The closure (forward, loss, backward) is the HIP path; the two-loop recursion
-    itself is torch's own vector arithmetic on the flattened parameters, exactly as in the reference.  LBFGS writes
-    the parameters in place through torch ops, which bumps their version counters, so the packed 16-bit weight
-    images are refreshed on the next forward."""
+    with both tolerances disabled.  The closure (forward, loss, backward) is the HIP path; by default the two-loop
+    recursion itself is torch's own vector arithmetic on the flattened parameters, exactly as in the reference.  LBFGS
+    writes the parameters in place through torch ops, which bumps their version counters, so the packed 16-bit weight
+    images are refreshed on the next forward.  ``fused``: the same step by ``optim.FusedLBFGS`` (csrc/lbfgs.hip), which
+    refreshes those images itself after each update."""
     parameters = list(parameters)
     _adam_loop(parameters, closure, LBFGS_WARMUP_LR, LBFGS_WARMUP_STEPS)
-    optimizer = torch.optim.LBFGS(parameters, max_iter=num_iter, lr=learning_rate, tolerance_grad=-1,
-                                  tolerance_change=-1)
+    cls = FusedLBFGS if fused else torch.optim.LBFGS
+    optimizer = cls(parameters, max_iter=num_iter, lr=learning_rate, tolerance_grad=-1, tolerance_change=-1)
 
     def closure2():
         optimizer.zero_grad()
@@ -41,10 +42,11 @@ def _lbfgs(parameters, closure, learning_rate, num_iter):
     optimizer.step(closure2)
 
 
-def optimize(optimizer_type, parameters, closure, learning_rate, num_iter):
-    """Run the optimisation loop: ``'adam'`` (what DIP.py:99 selects) or ``'LBFGS'``; anything else asserts."""
+def optimize(optimizer_type, parameters, closure, learning_rate, num_iter, *, fused_lbfgs=False):
+    """Run the optimisation loop: ``'adam'`` (what DIP.py:99 selects) or ``'LBFGS'``; anything else asserts.
+    ``fused_lbfgs=True`` runs the LBFGS branch's L-BFGS phase on ``optim.FusedLBFGS`` instead of torch.optim.LBFGS."""
     runners = {'adam': lambda: _adam_loop(list(parameters), closure, learning_rate, num_iter),
-               'LBFGS': lambda: _lbfgs(parameters, closure, learning_rate, num_iter)}
+               'LBFGS': lambda: _lbfgs(parameters, closure, learning_rate, num_iter, fused=fused_lbfgs)}
     assert optimizer_type in runners
     runners[optimizer_type]()
 

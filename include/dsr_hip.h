@@ -416,6 +416,27 @@ int dsr_scale_images_f32(float* x, size_t n, int mode, dsr_stream_t s);
 int dsr_patch_batch_u8(int count, const unsigned char* const* images, const int* heights, const int* widths, const int* tops,
                        const int* lefts, int ph, int pw, int mode, float* out, dsr_stream_t s);
 
+/* ------------------------------------------------------------------ L-BFGS (lbfgs.hip)
+ * torch.optim.LBFGS with line_search_fn=None (utils/DIP.py:24-31) in the vector-free form (Chen, Wang & Zhou, NIPS 2014):
+ * the two-loop recursion runs on the Gram matrix of the basis {s_i, y_i, g} in fp64; the vectors are read by two streaming
+ * passes.  A flat vector of n fp32 elements is split into `count` tensors (HOST tables of device pointers and element counts,
+ * read before the call returns, summing to n).  history: 1 .. 1024 pairs.
+ * ws: dsr_lbfgs_workspace(history, n, count) bytes, zero-filled before the first call (that is the fresh state); vecs:
+ * dsr_lbfgs_vector_floats(history, n) floats, zero-filled.  The pair (ws, vecs) is the optimizer's whole state; the first
+ * five ints of ws are n_iter, func_evals, n_iter of the running step, closure calls of the running step, live pairs.
+ * Per closure call: dsr_lbfgs_gather (the .grad tensors; NULL entries are zero gradients), dsr_lbfgs_dots, dsr_lbfgs_scalar
+ * (loss: the closure's device scalar; first = 1 for the first closure of a step()), dsr_lbfgs_combine (the parameters).
+ * The scalar pass writes stop[0] = 1 when torch would not call the closure again (every break of lbfgs.py). */
+size_t dsr_lbfgs_workspace(int history, size_t n, int count);
+size_t dsr_lbfgs_vector_floats(int history, size_t n);
+int dsr_lbfgs_gather(int count, const float* const* grads, const size_t* numel, void* ws, size_t ws_bytes, float* vecs,
+                     int history, size_t n, dsr_stream_t s);
+int dsr_lbfgs_dots(void* ws, size_t ws_bytes, const float* vecs, int history, size_t n, int count, dsr_stream_t s);
+int dsr_lbfgs_scalar(void* ws, size_t ws_bytes, int history, size_t n, int count, const float* loss, int first, int* stop,
+                     double lr, int max_iter, int max_eval, double tolerance_grad, double tolerance_change, dsr_stream_t s);
+int dsr_lbfgs_combine(int count, float* const* params, const size_t* numel, void* ws, size_t ws_bytes, float* vecs,
+                      int history, size_t n, dsr_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
