@@ -99,6 +99,11 @@ SIGNATURES = {
     "dsr_pw_adam": (_I, [_P, _P, _P, _P, _Z, _F, _F, _F, _F, _P, _F, _P, _P]),
     "dsr_pw_adam_multi": (_I, [_I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _P, _F, _P]),
     "dsr_pw_incr": (_I, [_P, _P]),
+    "dsr_amp_check": (_I, [_I, C.POINTER(C.c_void_p), C.POINTER(_Z), _P, _P]),
+    "dsr_pw_adam_amp": (_I, [_P, _P, _P, _P, _Z, _F, _F, _F, _F, _P, _P, _P, _P, _P]),
+    "dsr_pw_adam_multi_amp": (_I, [_I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _P, _P, _P, _P]),
+    "dsr_pw_incr_unless": (_I, [_P, _P, _P]),
+    "dsr_amp_update": (_I, [_P, _P, _P, _F, _F, _I, _P, _P]),
     "dsr_cast16": (_I, [_I, _P, _P, _Z, _P]),
     "dsr_flatten": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dsr_linear_fwd_workspace": (_Z, [_I, _Z, _I]),

@@ -997,14 +997,24 @@ __global__ void bce_const_kernel(const float* __restrict__ p, int n, float targe
 
 // ------------------------------------------------------------------ Adam (torch.optim.Adam defaults, no weight decay)
 // step counter lives on the device so the launch is graph-capturable.
+// AMP (dynamic loss scale, optim.DynamicLossScaler): the same arithmetic, predicated on the device.  found_inf[0] != 0
+// means some gradient of this step is not finite: the kernel returns before it touches p, m, v or the shadow.  Otherwise
+// the gradient multiplier is 1 / loss_scale[0] -- exact, the scale is a power of two -- in place of the host's grad_scale.
+template <bool AMP>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
                                                    float b1, float b2, float eps, const int* __restrict__ step,
-                                                   float grad_scale, unsigned short* __restrict__ shadow16) {
+                                                   float grad_scale, unsigned short* __restrict__ shadow16,
+                                                   const float* __restrict__ loss_scale,
+                                                   const float* __restrict__ found_inf) {
   // A pure stream (28 B per parameter, nothing re-read): two 16-byte vectors per thread and tensor in flight and
   // nontemporal accesses measured 6.3 TB/s against 5.8 for the one-vector cached form (537 M parameters).
   typedef __attribute__((ext_vector_type(4))) float F4;
   typedef __attribute__((ext_vector_type(2))) unsigned U2;
+  if constexpr (AMP) {
+    if (found_inf[0] != 0.f) return;
+    grad_scale = 1.f / loss_scale[0];
+  }
   const AdamCoef co = adam_coef(step, lr, b1, b2, eps, grad_scale);
   const size_t n4 = n / 4;
   const size_t stride = (size_t)gridDim.x * 512;
@@ -1055,6 +1065,73 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
 }
 __global__ void incr_kernel(int* step) { *step += 1; }
+__global__ void incr_unless_kernel(int* step, const float* found_inf) {
+  if (found_inf[0] == 0.f) *step += 1;
+}
+
+// ------------------------------------------------------------------ dynamic loss scale (optim.DynamicLossScaler)
+// State: scale (fp32, a power of two), growth_tracker (int32), found_inf (fp32 0 / 1), all on the device.
+// amp_check_kernel: one streaming read of up to 64 fp32 gradient tensors.  A tensor's 16-byte aligned body is cut into
+// chunks of DSR_AMP_CHUNK elements, one block each; the tensor's first block also reads the scalar head (a view may start
+// 4, 8 or 12 bytes off a 16-byte boundary) and tail.  Inf and NaN are the values whose exponent bits are all ones.  Every
+// writer stores the same 1, so the store needs neither an atomic nor an order; 0 is never written here.
+#define DSR_AMP_GROUP 64
+#define DSR_AMP_CHUNK 8192   // elements per block: 8 16-byte vectors per thread
+struct AmpGroup {
+  const float* g[DSR_AMP_GROUP];
+  size_t n[DSR_AMP_GROUP];
+  unsigned first_block[DSR_AMP_GROUP + 1];
+  int count;
+};
+static_assert(sizeof(AmpGroup) <= 4096, "kernel arguments are limited to 4 KB");
+__device__ __forceinline__ bool amp_nonfinite(unsigned bits) { return (bits & 0x7f800000u) == 0x7f800000u; }
+static __host__ __device__ inline size_t amp_head(const float* g, size_t n) {
+  const size_t h = ((16 - ((size_t)(uintptr_t)g & 15)) & 15) / 4;
+  return h < n ? h : n;
+}
+__global__ __launch_bounds__(256) void amp_check_kernel(const AmpGroup a, float* __restrict__ found_inf) {
+  int t = 0;
+  while (t + 1 < a.count && blockIdx.x >= a.first_block[t + 1]) ++t;      // wave-uniform scan of <= 64 entries
+  const unsigned blk = blockIdx.x - a.first_block[t];
+  const unsigned* __restrict__ g = reinterpret_cast<const unsigned*>(a.g[t]);
+  const size_t n = a.n[t], head = amp_head(a.g[t], n), nvec = (n - head) / 4;
+  const U4* __restrict__ body = reinterpret_cast<const U4*>(g + head);
+  const size_t v0 = (size_t)blk * (DSR_AMP_CHUNK / 4);
+  const size_t v1 = v0 + DSR_AMP_CHUNK / 4 < nvec ? v0 + DSR_AMP_CHUNK / 4 : nvec;
+  bool bad = false;
+#pragma unroll 4
+  for (size_t i = v0 + threadIdx.x; i < v1; i += 256) {
+    const U4 x = __builtin_nontemporal_load(body + i);
+    bad |= amp_nonfinite(x.x) | amp_nonfinite(x.y) | amp_nonfinite(x.z) | amp_nonfinite(x.w);
+  }
+  if (blk == 0) {
+    const size_t tail0 = head + nvec * 4;
+    if (threadIdx.x < head) bad |= amp_nonfinite(g[threadIdx.x]);
+    if (tail0 + threadIdx.x < n) bad |= amp_nonfinite(g[tail0 + threadIdx.x]);
+  }
+  if (__ballot(bad) != 0 && (threadIdx.x & 63) == 0) found_inf[0] = 1.f;
+}
+
+// torch's _amp_update_scale_ (one thread), then found_inf = 0 for the next step.  stats (nullable): steps taken, skipped.
+__global__ void amp_update_kernel(float* scale, int* growth_tracker, float* found_inf, float growth, float backoff,
+                                  int interval, int* stats) {
+  if (found_inf[0] != 0.f) {
+    scale[0] *= backoff;
+    growth_tracker[0] = 0;
+    if (stats) stats[1] += 1;
+  } else {
+    const int successful = growth_tracker[0] + 1;
+    if (successful == interval) {
+      const float grown = scale[0] * growth;
+      if ((__float_as_uint(grown) & 0x7f800000u) != 0x7f800000u) scale[0] = grown;   // growth to Inf is refused
+      growth_tracker[0] = 0;
+    } else {
+      growth_tracker[0] = successful;
+    }
+    if (stats) stats[0] += 1;
+  }
+  found_inf[0] = 0.f;
+}
 
 // ================================================================== host launchers
 #define DT_SWITCH(dtype, CALL)                 \
@@ -1325,9 +1402,19 @@ extern "C" int dsr_pw_adam(float* p, const float* g, float* m, float* v, size_t 
   DSR_REQUIRE(p && g && m && v && step && n > 0, "adam: null pointer or empty tensor");
   size_t want = (n / 4 + 511) / 512;
   unsigned blocks = (unsigned)(want < 1 ? 1 : (want > 65536 ? 65536 : want));
-  hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, step, grad_scale,
-                     (unsigned short*)shadow_bf16);
+  hipLaunchKernelGGL(adam_kernel<false>, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, step, grad_scale,
+                     (unsigned short*)shadow_bf16, (const float*)nullptr, (const float*)nullptr);
   return dsr_launch_status("dsr_pw_adam");
+}
+extern "C" int dsr_pw_adam_amp(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2,
+                               float eps, const int* step, const float* scale, const float* found_inf, void* shadow_bf16,
+                               hipStream_t st) {
+  DSR_REQUIRE(p && g && m && v && step && scale && found_inf && n > 0, "adam_amp: null pointer or empty tensor");
+  size_t want = (n / 4 + 511) / 512;
+  unsigned blocks = (unsigned)(want < 1 ? 1 : (want > 65536 ? 65536 : want));
+  hipLaunchKernelGGL(adam_kernel<true>, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, step, 1.f,
+                     (unsigned short*)shadow_bf16, scale, found_inf);
+  return dsr_launch_status("dsr_pw_adam_amp");
 }
 // ---- multi-tensor Adam: the generator and discriminator hold ~100 small tensors each; one launch per 64 of them.
 #define DSR_ADAM_GROUP 64
@@ -1341,8 +1428,15 @@ struct AdamGroup {
   unsigned first_block[DSR_ADAM_GROUP + 1];
   int count;
 };
+template <bool AMP>
 __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamGroup a, float lr, float b1, float b2, float eps,
-                                                         const int* __restrict__ step, float grad_scale) {
+                                                         const int* __restrict__ step, float grad_scale,
+                                                         const float* __restrict__ loss_scale,
+                                                         const float* __restrict__ found_inf) {
+  if constexpr (AMP) {          // see adam_kernel
+    if (found_inf[0] != 0.f) return;
+    grad_scale = 1.f / loss_scale[0];
+  }
   int t = 0;
   while (t + 1 < a.count && blockIdx.x >= a.first_block[t + 1]) ++t;      // wave-uniform scan of <= 64 entries
   const unsigned base = (blockIdx.x - a.first_block[t]) * DSR_ADAM_CHUNK;
@@ -1361,10 +1455,10 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamGroup a, floa
     p[i] = pk;
   }
 }
-extern "C" int dsr_pw_adam_multi(int count, float* const* p, const float* const* g, float* const* m, float* const* v,
-                                 const size_t* n, float lr, float b1, float b2, float eps, const int* step,
-                                 float grad_scale, hipStream_t st) {
-  if (count < 0 || (count && (!p || !g || !m || !v || !n))) return dsr_fail(DSR_E_ARG, "adam_multi: null table");
+template <bool AMP>
+static int adam_multi_launch(const char* what, int count, float* const* p, const float* const* g, float* const* m,
+                             float* const* v, const size_t* n, float lr, float b1, float b2, float eps, const int* step,
+                             float grad_scale, const float* loss_scale, const float* found_inf, hipStream_t st) {
   for (int i0 = 0; i0 < count; i0 += DSR_ADAM_GROUP) {
     AdamGroup a;
     a.count = count - i0 < DSR_ADAM_GROUP ? count - i0 : DSR_ADAM_GROUP;
@@ -1380,12 +1474,78 @@ extern "C" int dsr_pw_adam_multi(int count, float* const* p, const float* const*
       blocks += (unsigned)((n[i0 + j] + DSR_ADAM_CHUNK - 1) / DSR_ADAM_CHUNK);
     }
     a.first_block[a.count] = blocks;
-    if (blocks) hipLaunchKernelGGL(adam_multi_kernel, dim3(blocks), dim3(256), 0, st, a, lr, b1, b2, eps, step, grad_scale);
+    if (blocks)
+      hipLaunchKernelGGL(adam_multi_kernel<AMP>, dim3(blocks), dim3(256), 0, st, a, lr, b1, b2, eps, step, grad_scale,
+                         loss_scale, found_inf);
   }
-  return dsr_launch_status("dsr_pw_adam_multi");
+  return dsr_launch_status(what);
+}
+extern "C" int dsr_pw_adam_multi(int count, float* const* p, const float* const* g, float* const* m, float* const* v,
+                                 const size_t* n, float lr, float b1, float b2, float eps, const int* step,
+                                 float grad_scale, hipStream_t st) {
+  if (count < 0 || (count && (!p || !g || !m || !v || !n))) return dsr_fail(DSR_E_ARG, "adam_multi: null table");
+  return adam_multi_launch<false>("dsr_pw_adam_multi", count, p, g, m, v, n, lr, b1, b2, eps, step, grad_scale, nullptr,
+                                  nullptr, st);
+}
+extern "C" int dsr_pw_adam_multi_amp(int count, float* const* p, const float* const* g, float* const* m, float* const* v,
+                                     const size_t* n, float lr, float b1, float b2, float eps, const int* step,
+                                     const float* scale, const float* found_inf, hipStream_t st) {
+  DSR_REQUIRE(count > 0 && p && g && m && v && n && step && scale && found_inf, "adam_multi_amp: null pointer or no tensors");
+  for (int i = 0; i < count; ++i)
+    DSR_REQUIRE(p[i] && g[i] && m[i] && v[i] && n[i] > 0, "adam_multi_amp: null or empty tensor %d", i);
+  return adam_multi_launch<true>("dsr_pw_adam_multi_amp", count, p, g, m, v, n, lr, b1, b2, eps, step, 1.f, scale,
+                                 found_inf, st);
 }
 extern "C" int dsr_pw_incr(int* step, hipStream_t st) {
   DSR_REQUIRE(step, "incr: null pointer");
   hipLaunchKernelGGL(incr_kernel, dim3(1), dim3(1), 0, st, step);
   return dsr_launch_status("dsr_pw_incr");
+}
+extern "C" int dsr_pw_incr_unless(int* step, const float* found_inf, hipStream_t st) {
+  DSR_REQUIRE(step && found_inf, "incr_unless: null pointer");
+  hipLaunchKernelGGL(incr_unless_kernel, dim3(1), dim3(1), 0, st, step, found_inf);
+  return dsr_launch_status("dsr_pw_incr_unless");
+}
+extern "C" int dsr_amp_check(int count, const float* const* grads, const size_t* numel, float* found_inf, hipStream_t st) {
+  DSR_REQUIRE(count > 0 && grads && numel && found_inf, "amp_check: null pointer or no tensors");
+  for (int i = 0; i < count; ++i)      // NULL = no gradient, skipped; a launch holds < 2^31 blocks of DSR_AMP_CHUNK elements
+    DSR_REQUIRE(!grads[i] || (numel[i] > 0 && numel[i] < ((size_t)1 << 43) && ((uintptr_t)grads[i] & 3) == 0),
+                "amp_check: tensor %d is empty, too large or not 4-byte aligned", i);
+  AmpGroup a;
+  a.count = 0;
+  size_t blocks = 0;
+  auto flush = [&]() {
+    if (!a.count) return;
+    a.first_block[a.count] = (unsigned)blocks;
+    hipLaunchKernelGGL(amp_check_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, found_inf);
+    a.count = 0;
+    blocks = 0;
+  };
+  for (int i = 0; i < count; ++i) {
+    if (!grads[i]) continue;
+    const size_t nvec = (numel[i] - amp_head(grads[i], numel[i])) / 4;
+    const size_t nb = nvec ? (nvec + DSR_AMP_CHUNK / 4 - 1) / (DSR_AMP_CHUNK / 4) : 1;
+    if (a.count == DSR_AMP_GROUP || blocks + nb > 0x7fffffffull) flush();
+    a.g[a.count] = grads[i];
+    a.n[a.count] = numel[i];
+    a.first_block[a.count] = (unsigned)blocks;
+    blocks += nb;
+    ++a.count;
+  }
+  flush();
+  return dsr_launch_status("dsr_amp_check");
+}
+static bool amp_pow2(float x) {
+  int e;
+  return x > 0.f && x <= 3.4e38f && frexpf(x, &e) == 0.5f;
+}
+extern "C" int dsr_amp_update(float* scale, int* growth_tracker, float* found_inf, float growth_factor,
+                              float backoff_factor, int growth_interval, int* stats, hipStream_t st) {
+  DSR_REQUIRE(scale && growth_tracker && found_inf, "amp_update: null pointer");
+  DSR_REQUIRE(amp_pow2(growth_factor) && growth_factor > 1.f, "amp_update: growth_factor must be a power of two above 1");
+  DSR_REQUIRE(amp_pow2(backoff_factor) && backoff_factor < 1.f, "amp_update: backoff_factor must be a power of two below 1");
+  DSR_REQUIRE(growth_interval >= 1, "amp_update: growth_interval must be at least 1");
+  hipLaunchKernelGGL(amp_update_kernel, dim3(1), dim3(1), 0, st, scale, growth_tracker, found_inf, growth_factor,
+                     backoff_factor, growth_interval, stats);
+  return dsr_launch_status("dsr_amp_update");
 }

@@ -478,24 +478,28 @@ class ToNHWC(torch.autograd.Function):
 
 
 class ToNCHW(torch.autograd.Function):
-    """16-bit NHWC -> fp32 NCHW with the first `c` channels."""
+    """16-bit NHWC -> fp32 NCHW with the first `c` channels.  `net_output`: this is where a network hands its result back
+    (a net that ends without an activation), so its backward is where an ambient loss scale enters (ambient_loss_scale)."""
 
     @staticmethod
-    def forward(ctx, x, c):
+    def forward(ctx, x, c, net_output=False):
         x = x.contiguous()
         n, h, w, cp = x.shape
         out = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
         check(_lib.lib().dsr_pw_nhwc_to_nchw(_dt(x), _ptr(x), _ptr(out), n, c, h, w, cp, _stream()))
         ctx.dtype = x.dtype
+        ctx.net_output = net_output
         return out
 
     @staticmethod
     def backward(ctx, g):
         g = g.contiguous().float()
+        if ctx.net_output:
+            g = _ambient_scaled(g)
         n, c, h, w = g.shape
         out = torch.empty((n, h, w, r8(c)), dtype=ctx.dtype, device=g.device)
         check(_lib.lib().dsr_pw_nchw_to_nhwc(_dt(out), _ptr(g), _ptr(out), n, c, h, w, r8(c), _stream()))
-        return out, None
+        return out, None, None
 
 
 # ----------------------------------------------------------------------------- conv + bias + activation
@@ -882,7 +886,7 @@ class ConvOutNCHW(torch.autograd.Function):
     def backward(ctx, dout):
         x, out, wd = ctx.saved_tensors
         desc = ctx.desc
-        dout = dout.contiguous().float()
+        dout = _ambient_scaled(dout.contiguous().float())
         n, c, h, w = out.shape
         dy = torch.empty((n, h, w, r8(c)), dtype=x.dtype, device=x.device)
         check(_lib.lib().dsr_pw_act_bwd_nchw(_dt(x), _ptr(dout), _ptr(out), _ptr(dy), n, c, h, w, r8(c), ctx.act,
@@ -1018,6 +1022,49 @@ class ScaleLoss(torch.autograd.Function):
 
 def scale_loss(loss, s):
     return loss if s == 1.0 else ScaleLoss.apply(loss, s)
+
+
+class ScaleLossDevice(torch.autograd.Function):
+    """scale[0] * loss for a one-element device tensor (optim.DynamicLossScaler): nothing is read on the host.  Backward
+    reads the live tensor, which is correct because the scaler's update() runs after backward()."""
+
+    @staticmethod
+    def forward(ctx, loss, scale):
+        ctx.scale = scale
+        return axpby(loss.reshape(1), None, 1.0, 0.0, scale).reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        return axpby(g.reshape(1), None, 1.0, 0.0, ctx.scale).reshape(()), None
+
+
+_ambient_scale = None    # the open ambient_loss_scale context's device scalar (per process, like _wgrad_batch)
+
+
+class ambient_loss_scale:
+    """While open, the backward of a network's fp32 output op (ConvOutNCHW; ToNCHW where a net ends without an activation)
+    multiplies the incoming gradient by scale[0] before it is rounded to 16 bits.  For callers whose loss this package
+    never sees (utils.DIP.optimize: the closure calls backward() itself); everything downstream is then identical to a
+    scaled loss, because a power of two commutes with the fp32 arithmetic in front of that op.  `scale`: a one-element
+    fp32 device tensor, or None (no-op)."""
+
+    def __init__(self, scale):
+        self.scale = scale
+
+    def __enter__(self):
+        global _ambient_scale
+        self.prev, _ambient_scale = _ambient_scale, self.scale
+        return self
+
+    def __exit__(self, *exc):
+        global _ambient_scale
+        _ambient_scale = self.prev
+        return False
+
+
+def _ambient_scaled(g):
+    """The fp32 gradient entering 16-bit storage, times the ambient loss scale when one is set."""
+    return g if _ambient_scale is None else axpby(g, None, 1.0, 0.0, _ambient_scale)
 
 
 # ----------------------------------------------------------------------------- discriminator dense head

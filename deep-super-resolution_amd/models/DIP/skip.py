@@ -19,7 +19,7 @@ class SkipNet(nn.Sequential):
     def forward(self, x):
         out, c_out = run_fused(self, F.ToNHWC.apply(x, self.compute_dtype), x.shape[1], self.training)
         if out.dtype != torch.float32:      # need_sigmoid=False: hand back fp32 NCHW like the reference would
-            out = F.ToNCHW.apply(out, c_out)
+            out = F.ToNCHW.apply(out, c_out, True)
         return out
 
 

@@ -3,6 +3,7 @@ HIP kernel per tensor; the step counter lives on the device so a whole train ste
 in a HIP graph.  L-BFGS with torch.optim.LBFGS's semantics (utils/DIP.py:24-31) as four HIP passes
 per closure call, its whole state on the device."""
 import ctypes as C
+import math
 
 import torch
 
@@ -42,10 +43,25 @@ class FusedAdam:
             elif p.grad is not None:
                 p.grad.zero_()
 
-    def step(self):
+    def step(self, scaler=None):
+        """One Adam update.  `scaler` (a DynamicLossScaler whose check of this step's gradients has run; use
+        ``scaler.step(optimizer)``): the predicated kernels -- gradients times 1 / scale read on the device, and nothing
+        moves, the step counter included, when the scaler's overflow flag is set.  The launch sequence is the same either way."""
         lib = _lib.lib()
         st = _stream()
-        check(lib.dsr_pw_incr(_ptr(self.step_t), st))
+        amp = scaler is not None and scaler.enabled
+        if amp:
+            if self.grad_scale != 1.0:
+                raise ValueError(f"FusedAdam(grad_scale={self.grad_scale}) under a DynamicLossScaler would un-scale the "
+                                 "gradients twice: leave grad_scale at 1.0")
+            if self.fuse_dense_head:
+                raise ValueError("FusedAdam(fuse_dense_head=True) takes no DynamicLossScaler: the dense head's gradient "
+                                 "never exists as a tensor that could be checked for overflow, and the bf16 GAN step it "
+                                 "serves needs no loss scale")
+            scale, found = scaler._state(self.step_t.device)
+            check(lib.dsr_pw_incr_unless(_ptr(self.step_t), _ptr(found), st))
+        else:
+            check(lib.dsr_pw_incr(_ptr(self.step_t), st))
         small, keep = [], []
         for p, m, v in zip(self.params, self.m, self.v):
             pending = getattr(p, "_dsr_grad_factors", None)
@@ -75,6 +91,9 @@ class FusedAdam:
             sh = shadow_for_update(p)        # bf16 image kept by DenseHead for this matrix (or None)
             if sh is None and p.numel() <= self.MULTI_MAX and p.is_contiguous():
                 small.append((p, g, m, v))
+            elif amp:
+                check(lib.dsr_pw_adam_amp(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), self.lr, self.betas[0],
+                                          self.betas[1], self.eps, _ptr(self.step_t), _ptr(scale), _ptr(found), _ptr(sh), st))
             else:
                 check(lib.dsr_pw_adam(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), self.lr, self.betas[0],
                                       self.betas[1], self.eps, _ptr(self.step_t), self.grad_scale, _ptr(sh), st))
@@ -85,9 +104,151 @@ class FusedAdam:
             k = len(small)
             arr = [(C.c_void_p * k)(*[t[i].data_ptr() for t in small]) for i in range(4)]
             ns = (C.c_size_t * k)(*[t[0].numel() for t in small])
-            check(lib.dsr_pw_adam_multi(k, arr[0], arr[1], arr[2], arr[3], ns, self.lr, self.betas[0], self.betas[1],
-                                        self.eps, _ptr(self.step_t), self.grad_scale, st))
-        repack_cached(self.params)           # packed 16-bit conv weight images follow in one launch, not one per layer
+            if amp:
+                check(lib.dsr_pw_adam_multi_amp(k, arr[0], arr[1], arr[2], arr[3], ns, self.lr, self.betas[0],
+                                                self.betas[1], self.eps, _ptr(self.step_t), _ptr(scale), _ptr(found), st))
+            else:
+                check(lib.dsr_pw_adam_multi(k, arr[0], arr[1], arr[2], arr[3], ns, self.lr, self.betas[0], self.betas[1],
+                                            self.eps, _ptr(self.step_t), self.grad_scale, st))
+        # packed 16-bit conv weight images follow in one launch, not one per layer (after a skipped step the same bits again:
+        # the launch sequence stays fixed for graph replay)
+        repack_cached(self.params)
+
+
+def _pow2_exponent(x):
+    """k with x == 2**k, or None."""
+    x = float(x)
+    if not (x > 0 and math.isfinite(x)):
+        return None
+    m, e = math.frexp(x)
+    return e - 1 if m == 0.5 else None
+
+
+class DynamicLossScaler:
+    """torch.amp.GradScaler for the 16-bit HIP training paths (the fp16 DIP net above all), with nothing read on the host:
+    scale, growth counter and overflow flag are three device words, the skipped step is decided inside the kernels, so a
+    whole step stays capturable in a HIP graph (steps.GraphedStep).  Constructor names, defaults and ``state_dict()`` keys
+    are GradScaler's; a checkpoint moves between the two.
+
+        scaler.scale(loss).backward(); scaler.step(optimizer); scaler.update()
+
+    ``step`` = one pass over the gradients that raises the flag if any element is Inf / NaN (dsr_amp_check), then
+    ``optimizer.step(scaler=self)``: gradients times 1 / scale, or nothing at all when the flag is up.  ``update`` applies
+    torch's rule (overflow: scale *= backoff_factor; ``growth_interval`` clean steps in a row: scale *= growth_factor) and
+    clears the flag.  All three factors must be powers of two: un-scaling is then exact, a run under the scaler is bit for bit
+    the run under the static scale it sits at.  The state is created on the device of the first loss.
+
+    Under data parallelism the check runs inside step(), after the gradient all-reduce, so every rank sees the same flag.
+    FusedLBFGS is not served: its closure values and curvature pairs do not survive skipped steps.  ``get_scale()`` and
+    ``counts()`` are the only host reads."""
+
+    def __init__(self, init_scale=2.0 ** 16, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, enabled=True):
+        kg, kb = _pow2_exponent(growth_factor), _pow2_exponent(backoff_factor)
+        if _pow2_exponent(init_scale) is None:
+            raise ValueError(f"init_scale must be a power of two, got {init_scale!r}")
+        if kg is None or kg < 1:
+            raise ValueError(f"growth_factor must be 2**k with k >= 1, got {growth_factor!r}")
+        if kb is None or kb > -1:
+            raise ValueError(f"backoff_factor must be 2**-k with k >= 1, got {backoff_factor!r}")
+        if isinstance(growth_interval, bool) or int(growth_interval) != growth_interval or growth_interval < 1:
+            raise ValueError(f"growth_interval must be a positive integer, got {growth_interval!r}")
+        self.enabled = bool(enabled)
+        self._init_scale, self._init_growth_tracker = float(init_scale), 0
+        self._growth_factor, self._backoff_factor = float(growth_factor), float(backoff_factor)
+        self._growth_interval = int(growth_interval)
+        self._scale = self._growth_tracker = self._found_inf = self._stats = None
+
+    def _state(self, device):
+        """(scale, found_inf) device tensors, created on first use."""
+        if self._scale is None:
+            self._scale = torch.full((1,), self._init_scale, dtype=torch.float32, device=device)
+            self._growth_tracker = torch.full((1,), self._init_growth_tracker, dtype=torch.int32, device=device)
+            self._found_inf = torch.zeros(1, dtype=torch.float32, device=device)
+            self._stats = torch.zeros(2, dtype=torch.int32, device=device)
+        return self._scale, self._found_inf
+
+    def scale(self, loss):
+        """loss * scale as a differentiable device scalar (functional.ScaleLossDevice)."""
+        if not self.enabled:
+            return loss
+        from .functional import ScaleLossDevice
+        return ScaleLossDevice.apply(loss, self._state(loss.device)[0])
+
+    def ambient(self, device):
+        """Context for callers whose loss never reaches scale(): the scale enters at the network output's backward."""
+        from .functional import ambient_loss_scale
+        return ambient_loss_scale(self._state(device)[0] if self.enabled else None)
+
+    def step(self, optimizer):
+        if not self.enabled:
+            return optimizer.step()
+        if not isinstance(optimizer, FusedAdam):
+            raise TypeError("DynamicLossScaler.step drives optim.FusedAdam (FusedLBFGS and torch optimizers are not served)")
+        grads, keep = [], []
+        for p in optimizer.params:
+            g = p.grad
+            if g is not None and g.numel() and (g.dtype != torch.float32 or not g.is_contiguous()):
+                g = p.grad = g.float().contiguous()      # what FusedAdam.step would make of it; checked and applied alike
+            grads.append(g if g is not None and g.numel() else None)
+        _, found = self._state(optimizer.step_t.device)
+        k = len(grads)
+        check(_lib.lib().dsr_amp_check(k, (C.c_void_p * k)(*[None if g is None else g.data_ptr() for g in grads]),
+                                       (C.c_size_t * k)(*[0 if g is None else g.numel() for g in grads]), _ptr(found),
+                                       _stream()))
+        return optimizer.step(scaler=self)
+
+    def update(self):
+        if not self.enabled:
+            return
+        if self._scale is None:
+            raise RuntimeError("DynamicLossScaler.update() before any scale() or step()")
+        check(_lib.lib().dsr_amp_update(_ptr(self._scale), _ptr(self._growth_tracker), _ptr(self._found_inf),
+                                        self._growth_factor, self._backoff_factor, self._growth_interval,
+                                        _ptr(self._stats), _stream()))
+
+    def get_scale(self):
+        """The current scale as a host float (synchronises)."""
+        if not self.enabled:
+            return 1.0
+        return self._init_scale if self._scale is None else float(self._scale.item())
+
+    def counts(self):
+        """(steps taken, steps skipped) over all update() calls so far (one host read)."""
+        if self._stats is None:
+            return (0, 0)
+        t, s = self._stats.tolist()
+        return (t, s)
+
+    def get_growth_factor(self):
+        return self._growth_factor
+
+    def get_backoff_factor(self):
+        return self._backoff_factor
+
+    def get_growth_interval(self):
+        return self._growth_interval
+
+    def state_dict(self):
+        """torch.amp.GradScaler.state_dict()'s keys and meaning (empty when disabled, as there)."""
+        if not self.enabled:
+            return {}
+        tracker = self._init_growth_tracker if self._growth_tracker is None else int(self._growth_tracker.item())
+        return {"scale": self.get_scale(), "growth_factor": self._growth_factor, "backoff_factor": self._backoff_factor,
+                "growth_interval": self._growth_interval, "_growth_tracker": tracker}
+
+    def load_state_dict(self, state_dict):
+        if not self.enabled:
+            return
+        if not state_dict:
+            raise RuntimeError("The source state dict is empty, possibly because it was saved from a disabled scaler.")
+        probe = DynamicLossScaler(state_dict["scale"], state_dict["growth_factor"], state_dict["backoff_factor"],
+                                  state_dict["growth_interval"])      # the same argument checks
+        self._init_scale, self._init_growth_tracker = probe._init_scale, int(state_dict["_growth_tracker"])
+        self._growth_factor, self._backoff_factor = probe._growth_factor, probe._backoff_factor
+        self._growth_interval = probe._growth_interval
+        if self._scale is not None:
+            self._scale.fill_(self._init_scale)
+            self._growth_tracker.fill_(self._init_growth_tracker)
 
 
 class FusedLBFGS:

@@ -12,31 +12,40 @@ import torch
 from . import functional as F
 
 
-def gen_l1_step(gen, opt, lr_patches, hr_patches):
+def _backward_and_step(loss, opt, scaler):
+    """loss.backward(); opt.step() -- under an optim.DynamicLossScaler: scaled loss, checked and predicated step, update."""
+    with F.batched_wgrad():              # e.g. the 35 3x3 weight gradients of the generator: one grouped launch at the end
+        (loss if scaler is None else scaler.scale(loss)).backward()
+    if scaler is None:
+        opt.step()
+    else:
+        scaler.step(opt)
+        scaler.update()
+
+
+def gen_l1_step(gen, opt, lr_patches, hr_patches, *, scaler=None):
+    """`scaler`: an optim.DynamicLossScaler for a generator with fp16 storage (the default bf16 needs none)."""
     fake = gen(lr_patches)
     loss = F.l1_loss(fake, hr_patches)
     opt.zero_grad()
-    with F.batched_wgrad():              # the 35 3x3 weight gradients of the generator: one grouped launch at the end
-        loss.backward()
-    opt.step()
+    _backward_and_step(loss, opt, scaler)
     return loss.detach(), fake.detach()
 
 
-def gen_lpips_step(gen, opt, lpips, lr_patches, hr_patches, l1_weight=1.0, lpips_weight=0.1):
+def gen_lpips_step(gen, opt, lpips, lr_patches, hr_patches, l1_weight=1.0, lpips_weight=0.1, *, scaler=None):
     """Perceptual fine-tuning of a PSNR-trained generator: loss = l1_weight * L1 + lpips_weight * LPIPS(fake, hr).
 
     `lpips`: an lpips.LPIPS with normalize=False (the generator ends in tanh and scale_images targets live in [-1, 1]); only
     `fake` requires a gradient, so the LPIPS backward runs on that half of the trunk's batch.  Returns the two unweighted terms
     and `fake` as device tensors (no host sync here).  Inside GraphedStep the module needs validate_range=False: the range
-    check is the one host read of the call."""
+    check is the one host read of the call.  `scaler`: an optim.DynamicLossScaler around the summed loss (the LPIPS trunk
+    keeps its own internal grad_scale)."""
     fake = gen(lr_patches)
     l1 = F.l1_loss(fake, hr_patches)
     lp = lpips(fake, hr_patches)
     loss = F.add_losses(F.scale_loss(l1, float(l1_weight)), F.scale_loss(lp, float(lpips_weight)))
     opt.zero_grad()
-    with F.batched_wgrad():
-        loss.backward()
-    opt.step()
+    _backward_and_step(loss, opt, scaler)
     return l1.detach(), lp.detach(), fake.detach()
 
 
@@ -179,10 +188,19 @@ class DipRunner:
     """DIP.py:22-123 state: fixed noise input, jitter buffer, Lanczos downsampler, Adam over the net."""
 
     def __init__(self, net, downsampler, net_input, lr_image, learning_rate, reg_noise_std, loss_scale=None):
-        from .optim import FusedAdam
-        # fp16 storage (the DIP default, see models/DIP/skip.py) needs a static loss scale so that activation
+        from .optim import DynamicLossScaler, FusedAdam
+        # fp16 storage (the DIP default, see models/DIP/skip.py) needs a loss scale so that activation
         # gradients (~1e-5 at the MSE) stay out of fp16's subnormal range; Adam un-scales on the fly.
-        if loss_scale is None:
+        # None: static 1024 (tuned at HR 128x128, x2); a number: that static scale; "dynamic" or an
+        # optim.DynamicLossScaler: the scale follows the gradients on the device, overflowing steps are skipped.
+        self.scaler = None
+        if isinstance(loss_scale, str):
+            if loss_scale != "dynamic":
+                raise ValueError(f"loss_scale: a number, None, 'dynamic' or a DynamicLossScaler, got {loss_scale!r}")
+            loss_scale = DynamicLossScaler()
+        if isinstance(loss_scale, DynamicLossScaler):
+            self.scaler, loss_scale = loss_scale, 1.0
+        elif loss_scale is None:
             loss_scale = 1024.0 if getattr(net, "compute_dtype", None) == torch.float16 else 1.0
         self.loss_scale = float(loss_scale)
         self.net, self.down = net, downsampler
@@ -204,6 +222,9 @@ class DipRunner:
         out_hr = self.net(self.net_input)                        # :60
         out_lr = self.down(out_hr)                               # :62
         loss = F.mse_loss(out_lr, self.lr_image)                 # :65
+        if self.scaler is not None:
+            _backward_and_step(loss, self.opt, self.scaler)      # :68 under the dynamic scale
+            return loss.detach(), out_hr.detach()
         with F.batched_wgrad():
             F.scale_loss(loss, self.loss_scale).backward()       # :68
         self.opt.step()

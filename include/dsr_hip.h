@@ -238,6 +238,30 @@ int dsr_pw_adam_multi(int count, float* const* p, const float* const* g, float* 
                       dsr_stream_t s);
 int dsr_pw_incr(int* step, dsr_stream_t s);
 
+/* ------------------------------------------------------------------ dynamic loss scale (optim.DynamicLossScaler)
+ * What torch.amp.GradScaler is to torch.optim, with nothing read on the host: the state is three device words, scale
+ * (fp32, always a power of two, so that un-scaling is exact), growth_tracker (int32) and found_inf (fp32, 0 or 1), and the
+ * skipped step is decided inside the kernels.  Order within a step: dsr_amp_check, dsr_pw_incr_unless, the _amp Adam
+ * launches, dsr_amp_update.
+ * dsr_amp_check: found_inf[0] = 1 if any element of the `count` fp32 tensors is Inf or NaN (HOST tables of device pointers
+ * and element counts, read before the call returns; a NULL entry is a parameter without a gradient and is skipped; 64 tensors
+ * per launch).  Never writes 0: dsr_amp_update clears the flag.
+ * dsr_pw_adam_amp / dsr_pw_adam_multi_amp: dsr_pw_adam / dsr_pw_adam_multi with the gradient multiplied by 1 / scale[0],
+ * and no write at all to p, m, v or the shadow when found_inf[0] != 0.  dsr_pw_incr_unless: the step counter likewise.
+ * dsr_amp_update: torch's _amp_update_scale_ -- found_inf: scale *= backoff_factor, tracker = 0; otherwise tracker += 1 and,
+ * when it reaches growth_interval, scale *= growth_factor (unless that is not finite) and tracker = 0 -- then found_inf = 0.
+ * growth_factor = 2^k, backoff_factor = 2^-k, k >= 1; growth_interval >= 1.  stats (nullable): int32[2], steps taken and
+ * steps skipped, incremented here. */
+int dsr_amp_check(int count, const float* const* grads, const size_t* numel, float* found_inf, dsr_stream_t s);
+int dsr_pw_adam_amp(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps,
+                    const int* step, const float* scale, const float* found_inf, void* shadow_bf16, dsr_stream_t s);
+int dsr_pw_adam_multi_amp(int count, float* const* p, const float* const* g, float* const* m, float* const* v,
+                          const size_t* n, float lr, float b1, float b2, float eps, const int* step, const float* scale,
+                          const float* found_inf, dsr_stream_t s);
+int dsr_pw_incr_unless(int* step, const float* found_inf, dsr_stream_t s);
+int dsr_amp_update(float* scale, int* growth_tracker, float* found_inf, float growth_factor, float backoff_factor,
+                   int growth_interval, int* stats, dsr_stream_t s);
+
 /* ------------------------------------------------------------------ discriminator dense head (linear.hip)
  * models/GAN/discriminator.py:37-45,65-72: flatten(C,H,W) -> Linear(K,O) -> LeakyReLU(0.2) -> Linear(O,1) -> Sigmoid */
 /* 16-bit shadow copy of an fp32 tensor (n % 8 == 0) */
