@@ -104,6 +104,11 @@ SIGNATURES = {
     "dsr_pw_adam_multi_amp": (_I, [_I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _P, _P, _P, _P]),
     "dsr_pw_incr_unless": (_I, [_P, _P, _P]),
     "dsr_amp_update": (_I, [_P, _P, _P, _F, _F, _I, _P, _P]),
+    "dsr_clip_sumsq_partials": (_Z, [_I, C.POINTER(C.c_void_p), C.POINTER(_Z)]),
+    "dsr_clip_sumsq": (_I, [_I, C.POINTER(C.c_void_p), C.POINTER(_Z), _P, _Z, _P]),
+    "dsr_clip_finalize": (_I, [_P, _I, _P, _I, _F, _P, _F, _P, _F, _P, _P, _P, _P]),
+    "dsr_pw_adam_hyper": (_I, [_P, _P, _P, _P, _Z, _P, _F, _F, _F, _P, _F, _P, _P, _P, _P]),
+    "dsr_pw_adam_multi_hyper": (_I, [_I, _P, _P, _P, _P, _P, _P, _F, _F, _F, _P, _F, _P, _P, _P]),
     "dsr_cast16": (_I, [_I, _P, _P, _Z, _P]),
     "dsr_flatten": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dsr_linear_fwd_workspace": (_Z, [_I, _Z, _I]),
@@ -112,6 +117,10 @@ SIGNATURES = {
     "dsr_linear_wgrad": (_I, [_I, _P, _P, _P, _I, _I, _Z, _P]),
     "dsr_linear_wgrad_gathered": (_I, [_I, _P, _P, _P, _I, _I, _Z, _I, _F, _P]),
     "dsr_linear_wgrad_adam": (_I, [_I, _P, _P, _I, _I, _Z, _I, _F, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _P]),
+    "dsr_linear_factor_gram_workspace": (_Z, [_I, _I, _Z, _I]),
+    "dsr_linear_factor_gram_dots": (_I, [_I, _I]),
+    "dsr_linear_factor_gram": (_I, [_I, _P, _P, _I, _I, _Z, _I, _F, _P, _Z, _P]),
+    "dsr_linear_wgrad_adam_hyper": (_I, [_I, _P, _P, _I, _I, _Z, _I, _F, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _P, _P, _P]),
     "dsr_dense2_fwd": (_I, [_P, _P, _P, _I, _I, _P, _P]),
     "dsr_dense2_bwd": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
     "dsr_maxpool2_fwd": (_I, [_I, _P, _P, _I, _I, _I, _I, _P]),
@@ -166,7 +175,8 @@ _NO_LAUNCH = ("dsr_last_error", "dsr_abi_version", "dsr_conv_dgrad_ps_supported"
               "dsr_conv_first2_supported", "dsr_conv_first2_stats_rows", "dsr_conv_first_bwd_supported", "dsr_conv_first_bwd_workspace", "dsr_conv_out_size", "dsr_conv_stats_rows",
               "dsr_conv_packed_elems", "dsr_conv_dgrad_workspace", "dsr_conv_wgrad_workspace", "dsr_pw_scratch_rows",
               "dsr_pw_reduce_blocks", "dsr_linear_fwd_workspace", "dsr_ssim_blocks", "dsr_lpips_tap_sizes", "dsr_lpips_distance_blocks",
-              "dsr_ssim_img_blocks", "dsr_psnr_blocks", "dsr_lbfgs_workspace", "dsr_lbfgs_vector_floats")
+              "dsr_ssim_img_blocks", "dsr_psnr_blocks", "dsr_lbfgs_workspace", "dsr_lbfgs_vector_floats", "dsr_clip_sumsq_partials",
+              "dsr_linear_factor_gram_workspace", "dsr_linear_factor_gram_dots")
 
 
 class _Lib:

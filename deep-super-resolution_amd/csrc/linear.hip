@@ -474,11 +474,13 @@ struct AdamFused {
   const int* step;
   float lr, b1, b2, eps, grad_scale;
 };
+// (the tile loop, shared by linear_wgrad_adam_kernel and linear_wgrad_adam_hyper_kernel, which differ only in where the
+// Adam coefficients come from)
 template <int DT, int BP>
-__global__ __launch_bounds__(256, 2) void linear_wgrad_adam_kernel(const unsigned short* __restrict__ dyT,
-                                                                   const unsigned short* __restrict__ xT, int O, size_t K,
-                                                                   int R, float scale, int kpairs_per_block,
-                                                                   const AdamFused a) {
+__device__ __forceinline__ void linear_wgrad_adam_tiles(const unsigned short* __restrict__ dyT,
+                                                        const unsigned short* __restrict__ xT, int O, size_t K, int R,
+                                                        float scale, int kpairs_per_block, const AdamFused& a,
+                                                        const AdamCoef& co) {
   typedef __attribute__((ext_vector_type(4))) float F4;
   typedef __attribute__((ext_vector_type(2))) unsigned U2;
   constexpr int RS = 72;                         // tile row pitch in floats: 4 * RS = 32 (mod 64 banks), so the two half-waves
@@ -490,7 +492,6 @@ __global__ __launch_bounds__(256, 2) void linear_wgrad_adam_kernel(const unsigne
   // per row and tensor at a time (rows are K * 4 bytes = 2 MB apart)
   const int o0 = blockIdx.y * 64;
   constexpr int KS = BP / 16;
-  const AdamCoef co = adam_coef(a.step, a.lr, a.b1, a.b2, a.eps, a.grad_scale);
   float* my = tile[wave];                        // (no block-level barrier below: a wave owns its slice of `tile`)
   const size_t kp0 = (size_t)blockIdx.x * kpairs_per_block;
   for (int t = 0; t < kpairs_per_block; ++t) {
@@ -573,6 +574,141 @@ __global__ __launch_bounds__(256, 2) void linear_wgrad_adam_kernel(const unsigne
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       __builtin_amdgcn_wave_barrier();           // the tile is free again
     }
+  }
+}
+template <int DT, int BP>
+__global__ __launch_bounds__(256, 2) void linear_wgrad_adam_kernel(const unsigned short* __restrict__ dyT,
+                                                                   const unsigned short* __restrict__ xT, int O, size_t K,
+                                                                   int R, float scale, int kpairs_per_block,
+                                                                   const AdamFused a) {
+  linear_wgrad_adam_tiles<DT, BP>(dyT, xT, O, K, R, scale, kpairs_per_block, a,
+                                  adam_coef(a.step, a.lr, a.b1, a.b2, a.eps, a.grad_scale));
+}
+// Device-resident hyper-parameters (pointwise.hip adam_hyper_kernel): hyper = {lr, clipping coefficient}; loss_scale and
+// found_inf nullable, with the dynamic loss scaler's meaning.
+template <int DT, int BP>
+__global__ __launch_bounds__(256, 2) void linear_wgrad_adam_hyper_kernel(
+    const unsigned short* __restrict__ dyT, const unsigned short* __restrict__ xT, int O, size_t K, int R, float scale,
+    int kpairs_per_block, const AdamFused a, const float* __restrict__ hyper, const float* __restrict__ loss_scale,
+    const float* __restrict__ found_inf) {
+  if (found_inf != nullptr && found_inf[0] != 0.f) return;
+  const float gs = loss_scale != nullptr ? 1.f / loss_scale[0] : a.grad_scale;
+  linear_wgrad_adam_tiles<DT, BP>(dyT, xT, O, K, R, scale, kpairs_per_block, a,
+                                  adam_coef(a.step, hyper[0], a.b1, a.b2, a.eps, gs * hyper[1]));
+}
+
+// ------------------------------------------------------------------ norm of the factored gradient (gradient clipping)
+// dW = s * sum_{(r,b)} dyT[r][:,b] (x) xT[r][:,b] is a sum of N = R * Bp outer products, so
+//   |dW|_F^2 = s^2 * sum_{i,j} Gx[i][j] * Gdy[i][j],   Gx = X X^T, Gdy = dY dY^T  (N x N Gram matrices, i = (r, b)):
+// one read of the two factor tables (67 MB + 128 KB at config 3) instead of the 2.17 GB gradient.
+// factor_gram_kernel: G += T^T T over this block's rows of one table T [R][rows][Bp] (16-bit, row-major: the batch is the
+// contiguous index).  The rows are a pure stream: 16-byte loads into registers, staged [row][N] in LDS (row pitch 2 N + 32
+// bytes: an odd multiple of 32, so the eight 32-byte row segments of a transposing read's half-wave fall on disjoint banks),
+// the next stage's loads in flight while this one is multiplied.  ds_read_b64_tr_b16 hands a lane 4 rows of one column, two
+// reads = the 16x16x32 MFMA fragment of a 16-column block, and since G is T^T T the SAME fragment serves as the A operand of
+// its block row and the B operand of its block column (row slots permuted alike in both, which a contraction does not see).
+// A wave owns one 16-row block of G and up to 8 of its 16-column blocks (8 accumulators); blockIdx.y walks those units.
+// Output: this block's fp32 partial of G at out[blockIdx.x][N][N] -- plain stores, summed in fp64 by factor_gram_dot_kernel.
+#define DSR_GRAM_MAX_N 512
+template <int DT>
+__global__ __launch_bounds__(256) void factor_gram_kernel(const unsigned short* __restrict__ T, size_t rows, int Bp, int R,
+                                                          int nsub, size_t rows_per_block, float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char gram_smem[];
+  const int N = R * Bp, NB = N / 16, CG = (NB + 7) / 8, RP = 2 * N + 32, CPR = N / 8;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l16 = lane & 15, g = lane >> 4;
+  const int unit = blockIdx.y * 4 + wave;
+  const int mb = unit / CG, cg = unit % CG;
+  const bool active = mb < NB;                                   // wave-uniform
+  const size_t r0 = (size_t)blockIdx.x * rows_per_block;
+  const size_t r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
+  const int srows = 32 * nsub;                                   // rows per stage
+  const int chunks = srows * CPR;                                // 16-byte chunks per stage: at most 8 per thread
+  f32x4 acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  U4 v[8];
+  auto gload = [&](size_t s0) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int c = tid + 256 * i;
+      const int row = c / CPR, n = (c - row * CPR) * 8;
+      const int r = n / Bp, b = n - r * Bp;
+      const bool ok = c < chunks && s0 + row < r1;
+      v[i] = load16_or_zero(T, ((size_t)r * rows + s0 + row) * Bp + b, ok);
+    }
+  };
+  auto sstore = [&]() {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int c = tid + 256 * i;
+      const int row = c / CPR, cn = c - row * CPR;
+      if (c < chunks) *reinterpret_cast<U4*>(gram_smem + row * RP + cn * 16) = v[i];
+    }
+  };
+  const int q = l16 >> 2, cc = 4 * (l16 & 3);
+  auto frag = [&](int sub, int cb) {                             // every lane of the wave takes part (full EXEC)
+    const unsigned char* base = gram_smem + (32 * sub + 4 * g + q) * RP + (cb * 16 + cc) * 2;
+    const s16x4 lo = lds_tr_read16(base), hi = lds_tr_read16(base + 16 * RP);
+    return __builtin_bit_cast(U4, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+  };
+  if (r0 < r1) gload(r0);
+  for (size_t s0 = r0; s0 < r1; s0 += srows) {
+    sstore();
+    __syncthreads();
+    if (s0 + srows < r1) gload(s0 + srows);
+    if (active) {
+      for (int sub = 0; sub < nsub; ++sub) {
+        if (s0 + 32 * (size_t)sub >= r1) break;                  // (block-uniform)
+        const U4 fa = frag(sub, mb);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int nb = cg * 8 + j;
+          if (nb < NB) acc[j] = mfma16<DT>(fa, frag(sub, nb), acc[j]);
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (!active) return;
+  float* o = out + (size_t)blockIdx.x * N * N;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int nb = cg * 8 + j;
+    if (nb >= NB) continue;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[(size_t)(mb * 16 + 4 * g + i) * N + nb * 16 + l16] = acc[j][i];
+  }
+}
+// dots[blockIdx.x] = s^2 * sum over this block's 16 entries e of (sum_c gx[c][e]) * (sum_c gy[c][e]), all in fp64 and in a
+// fixed order: 16 entries x 16 partial-lanes per block, lane q sums partials q, q + 16, ... ; lanes and entries are then
+// added in index order.  The products are signed (off-diagonal entries), which is why nothing here is fp32.
+__global__ __launch_bounds__(256) void factor_gram_dot_kernel(const float* __restrict__ gx, int sx, const float* __restrict__ gy,
+                                                              int sy, int nn, double scale2, double* __restrict__ dots) {
+  __shared__ double red[2][16][16];
+  const int cx = threadIdx.x & 15, ry = threadIdx.x >> 4;
+  const int e = blockIdx.x * 16 + cx;
+  double a = 0.0, b = 0.0;
+  if (e < nn) {
+    for (int c = ry; c < sx; c += 16) a += (double)gx[(size_t)c * nn + e];
+    for (int c = ry; c < sy; c += 16) b += (double)gy[(size_t)c * nn + e];
+  }
+  red[0][ry][cx] = a;
+  red[1][ry][cx] = b;
+  __syncthreads();
+  if (threadIdx.x < 16) {
+    double ta = 0.0, tb = 0.0;
+    for (int qq = 0; qq < 16; ++qq) {
+      ta += red[0][qq][cx];
+      tb += red[1][qq][cx];
+    }
+    red[0][0][cx] = ta * tb;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int i = 0; i < 16; ++i) t += red[0][0][i];
+    dots[blockIdx.x] = t * scale2;
   }
 }
 
@@ -885,4 +1021,123 @@ extern "C" int dsr_dense2_bwd(int dtype, const float* dout, const float* out, co
     hipLaunchKernelGGL((dense2_bwd_kernel<DSR_DTYPE_F16>), grid, block, 0, st, dout, out, h, w2, B, K1, Bp, slope, dw2,
                        db2, db1, (unsigned short*)dy16, (unsigned short*)dyT16);
   return dsr_launch_status("dsr_dense2_bwd");
+}
+
+// ---- norm of the factored gradient + the device-hyper form of dsr_linear_wgrad_adam
+struct GramPlan {
+  int N, nsub, gy;          // Gram size, 32-row sub-stages per stage, grid.y (units of 4 waves)
+  int sx, sy;               // row chunks (blocks along x) of the X and the dY table
+  size_t rpbx, rpby;        // rows per block
+  size_t dots, fx, fy;      // element counts of the three workspace parts
+};
+static void gram_split(size_t rows, int nsub, int gy, int* s, size_t* rpb) {
+  const size_t srows = (size_t)32 * nsub;
+  size_t want = 512 / gy;
+  if (want < 1) want = 1;
+  size_t per = (rows + want - 1) / want;
+  per = (per + srows - 1) / srows * srows;
+  *rpb = per;
+  *s = (int)((rows + per - 1) / per);
+}
+static bool gram_plan(int Bp, int O, size_t K, int R, GramPlan* g) {
+  if ((Bp != 32 && Bp != 64) || O <= 0 || K == 0 || R < 1 || (long long)R * Bp > DSR_GRAM_MAX_N) return false;
+  if (K > ((size_t)1 << 40)) return false;
+  g->N = R * Bp;
+  g->nsub = 512 / g->N;
+  if (g->nsub > 8) g->nsub = 8;
+  const int NB = g->N / 16, CG = (NB + 7) / 8;
+  g->gy = (NB * CG + 3) / 4;
+  gram_split(K, g->nsub, g->gy, &g->sx, &g->rpbx);
+  gram_split((size_t)O, g->nsub, g->gy, &g->sy, &g->rpby);
+  g->dots = ((size_t)g->N * g->N + 15) / 16;
+  g->fx = (size_t)g->sx * g->N * g->N;
+  g->fy = (size_t)g->sy * g->N * g->N;
+  return true;
+}
+extern "C" size_t dsr_linear_factor_gram_workspace(int Bp, int O, size_t K, int R) {
+  GramPlan g;
+  if (!gram_plan(Bp, O, K, R, &g)) return 0;
+  return g.dots * sizeof(double) + (g.fx + g.fy) * sizeof(float);
+}
+extern "C" int dsr_linear_factor_gram_dots(int Bp, int R) {
+  if ((Bp != 32 && Bp != 64) || R < 1 || (long long)R * Bp > DSR_GRAM_MAX_N) return 0;
+  return (R * Bp) * (R * Bp) / 16;
+}
+extern "C" int dsr_linear_factor_gram(int dtype, const void* dyT16_all, const void* xT16_all, int Bp, int O, size_t K, int R,
+                                      float scale, void* workspace, size_t ws_bytes, dsr_stream_t st) {
+  DSR_REQUIRE(dyT16_all && xT16_all && workspace && DSR_DTYPE_OK(dtype) && K > 0 && O > 0,
+              "linear_factor_gram: null pointer or bad shape");
+  if (Bp != 32 && Bp != 64) return dsr_fail(DSR_E_UNSUPPORTED, "linear_factor_gram: padded batch must be 32 or 64");
+  if (R < 1) return dsr_fail(DSR_E_ARG, "linear_factor_gram: R < 1");
+  if ((long long)R * Bp > DSR_GRAM_MAX_N)
+    return dsr_fail(DSR_E_UNSUPPORTED, "linear_factor_gram: R * Bp = %lld > %d (materialise the gradient instead)",
+                    (long long)R * Bp, DSR_GRAM_MAX_N);
+  DSR_REQUIRE((((uintptr_t)dyT16_all | (uintptr_t)xT16_all | (uintptr_t)workspace) & 15) == 0,
+              "linear_factor_gram: tables and workspace must be 16-byte aligned");
+  DSR_REQUIRE(scale == scale, "linear_factor_gram: scale is NaN");
+  GramPlan g;
+  if (!gram_plan(Bp, O, K, R, &g)) return dsr_fail(DSR_E_UNSUPPORTED, "linear_factor_gram: shape");
+  if (ws_bytes < g.dots * sizeof(double) + (g.fx + g.fy) * sizeof(float))
+    return dsr_fail(DSR_E_WORKSPACE, "linear_factor_gram: workspace");
+  double* dots = (double*)workspace;
+  float* fx = (float*)(dots + g.dots);
+  float* fy = fx + g.fx;
+  const size_t lds = (size_t)32 * g.nsub * (2 * g.N + 32);
+  const unsigned short* DYT = (const unsigned short*)dyT16_all;
+  const unsigned short* XT = (const unsigned short*)xT16_all;
+#define LAUNCH_GRAM(DTV)                                                                                                   \
+  do {                                                                                                                     \
+    hipLaunchKernelGGL((factor_gram_kernel<DTV>), dim3(g.sx, g.gy), dim3(256), lds, st, XT, K, Bp, R, g.nsub, g.rpbx, fx); \
+    hipLaunchKernelGGL((factor_gram_kernel<DTV>), dim3(g.sy, g.gy), dim3(256), lds, st, DYT, (size_t)O, Bp, R, g.nsub,     \
+                       g.rpby, fy);                                                                                        \
+  } while (0)
+  if (dtype == DSR_BF16) LAUNCH_GRAM(DSR_DTYPE_BF16); else LAUNCH_GRAM(DSR_DTYPE_F16);
+#undef LAUNCH_GRAM
+  hipLaunchKernelGGL(factor_gram_dot_kernel, dim3((unsigned)g.dots), dim3(256), 0, st, fx, g.sx, fy, g.sy, g.N * g.N,
+                     (double)scale * (double)scale, dots);
+  return dsr_launch_status("dsr_linear_factor_gram");
+}
+
+extern "C" int dsr_linear_wgrad_adam_hyper(int dtype, const void* dyT16_all, const void* xT16_all, int Bp, int O, size_t K,
+                                           int R, float scale, float* p, float* m, float* v, void* shadow_bf16,
+                                           const int* step, const float* hyper, float b1, float b2, float eps,
+                                           float grad_scale, const float* loss_scale, const float* found_inf,
+                                           dsr_stream_t st) {
+  DSR_REQUIRE(dyT16_all && xT16_all && p && m && v && step && hyper && DSR_DTYPE_OK(dtype) && K > 0 && O > 0,
+              "linear_wgrad_adam_hyper: null pointer or bad shape");
+  if (Bp != 32 && Bp != 64) return dsr_fail(DSR_E_UNSUPPORTED, "linear_wgrad_adam_hyper: padded batch must be 32 or 64");
+  if (R < 1) return dsr_fail(DSR_E_ARG, "linear_wgrad_adam_hyper: R < 1");
+  if (K % 64) return dsr_fail(DSR_E_UNSUPPORTED, "linear_wgrad_adam_hyper: K %% 64 (use dsr_linear_wgrad + dsr_pw_adam_hyper)");
+  DSR_REQUIRE((((uintptr_t)dyT16_all | (uintptr_t)xT16_all | (uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) == 0 &&
+                  ((uintptr_t)shadow_bf16 & 7) == 0 &&
+                  (((uintptr_t)step | (uintptr_t)hyper | (uintptr_t)loss_scale | (uintptr_t)found_inf) & 3) == 0,
+              "linear_wgrad_adam_hyper: misaligned pointer");
+  const char* e = getenv("DSR_WGRAD_ADAM_KPB");      // the tuning switch of dsr_linear_wgrad_adam
+  const int kpb = e ? atoi(e) : 1;
+  if (kpb < 1) return dsr_fail(DSR_E_ARG, "linear_wgrad_adam_hyper: DSR_WGRAD_ADAM_KPB < 1");
+  const size_t kgroups = (K + 255) / 256;
+  dim3 grid((unsigned)((kgroups + kpb - 1) / kpb), (O + 63) / 64), block(256);
+  const unsigned short* DYT = (const unsigned short*)dyT16_all;
+  const unsigned short* XT = (const unsigned short*)xT16_all;
+  AdamFused a;
+  a.p = p;
+  a.m = m;
+  a.v = v;
+  a.shadow = (unsigned short*)shadow_bf16;
+  a.step = step;
+  a.lr = 0.f;
+  a.b1 = b1;
+  a.b2 = b2;
+  a.eps = eps;
+  a.grad_scale = grad_scale;
+#define LAUNCH_WGAH(DTV, BPV)                                                                                            \
+  hipLaunchKernelGGL((linear_wgrad_adam_hyper_kernel<DTV, BPV>), grid, block, 0, st, DYT, XT, O, K, R, scale, kpb, a, hyper, \
+                     loss_scale, found_inf)
+  if (dtype == DSR_BF16) {
+    if (Bp == 32) LAUNCH_WGAH(DSR_DTYPE_BF16, 32); else LAUNCH_WGAH(DSR_DTYPE_BF16, 64);
+  } else {
+    if (Bp == 32) LAUNCH_WGAH(DSR_DTYPE_F16, 32); else LAUNCH_WGAH(DSR_DTYPE_F16, 64);
+  }
+#undef LAUNCH_WGAH
+  return dsr_launch_status("dsr_linear_wgrad_adam_hyper");
 }

@@ -1000,22 +1000,15 @@ __global__ void bce_const_kernel(const float* __restrict__ p, int n, float targe
 // AMP (dynamic loss scale, optim.DynamicLossScaler): the same arithmetic, predicated on the device.  found_inf[0] != 0
 // means some gradient of this step is not finite: the kernel returns before it touches p, m, v or the shadow.  Otherwise
 // the gradient multiplier is 1 / loss_scale[0] -- exact, the scale is a power of two -- in place of the host's grad_scale.
-template <bool AMP>
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
-                                                   float b1, float b2, float eps, const int* __restrict__ step,
-                                                   float grad_scale, unsigned short* __restrict__ shadow16,
-                                                   const float* __restrict__ loss_scale,
-                                                   const float* __restrict__ found_inf) {
+// The streaming loop of the per-tensor launch, shared by adam_kernel and adam_hyper_kernel (which differ only in where the
+// coefficients come from).
+__device__ __forceinline__ void adam_stream(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                            float* __restrict__ v, size_t n, unsigned short* __restrict__ shadow16,
+                                            const AdamCoef& co) {
   // A pure stream (28 B per parameter, nothing re-read): two 16-byte vectors per thread and tensor in flight and
   // nontemporal accesses measured 6.3 TB/s against 5.8 for the one-vector cached form (537 M parameters).
   typedef __attribute__((ext_vector_type(4))) float F4;
   typedef __attribute__((ext_vector_type(2))) unsigned U2;
-  if constexpr (AMP) {
-    if (found_inf[0] != 0.f) return;
-    grad_scale = 1.f / loss_scale[0];
-  }
-  const AdamCoef co = adam_coef(step, lr, b1, b2, eps, grad_scale);
   const size_t n4 = n / 4;
   const size_t stride = (size_t)gridDim.x * 512;
   for (size_t i0 = (size_t)blockIdx.x * 512 + threadIdx.x; i0 < n4; i0 += stride) {
@@ -1063,6 +1056,43 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     p[i] = pk;
     if (shadow16) shadow16[i] = f2h<DSR_DTYPE_BF16>(pk);
   }
+}
+template <bool AMP>
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                   float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
+                                                   float b1, float b2, float eps, const int* __restrict__ step,
+                                                   float grad_scale, unsigned short* __restrict__ shadow16,
+                                                   const float* __restrict__ loss_scale,
+                                                   const float* __restrict__ found_inf) {
+  if constexpr (AMP) {
+    if (found_inf[0] != 0.f) return;
+    grad_scale = 1.f / loss_scale[0];
+  }
+  adam_stream(p, g, m, v, n, shadow16, adam_coef(step, lr, b1, b2, eps, grad_scale));
+}
+// Device-resident hyper-parameters (FusedAdam(lr=<tensor>, max_grad_norm=c)): hyper[0] is the learning rate, hyper[1] the
+// clipping coefficient of this step (dsr_clip_finalize writes both).  The gradient multiplier is ONE fp32 product
+// grad_scale * hyper[1], so a coefficient of exactly 1 leaves the bits of the kernels above; loss_scale / found_inf
+// (both nullable) are the dynamic loss scaler's words, with adam_kernel<true>'s meaning.
+__device__ __forceinline__ bool adam_hyper_coef(const float* __restrict__ hyper, float b1, float b2, float eps,
+                                                const int* __restrict__ step, float grad_scale,
+                                                const float* __restrict__ loss_scale,
+                                                const float* __restrict__ found_inf, AdamCoef& co) {
+  if (found_inf != nullptr && found_inf[0] != 0.f) return false;
+  if (loss_scale != nullptr) grad_scale = 1.f / loss_scale[0];
+  co = adam_coef(step, hyper[0], b1, b2, eps, grad_scale * hyper[1]);
+  return true;
+}
+__global__ __launch_bounds__(256) void adam_hyper_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                         float* __restrict__ m, float* __restrict__ v, size_t n,
+                                                         const float* __restrict__ hyper, float b1, float b2, float eps,
+                                                         const int* __restrict__ step, float grad_scale,
+                                                         unsigned short* __restrict__ shadow16,
+                                                         const float* __restrict__ loss_scale,
+                                                         const float* __restrict__ found_inf) {
+  AdamCoef co;
+  if (!adam_hyper_coef(hyper, b1, b2, eps, step, grad_scale, loss_scale, found_inf, co)) return;
+  adam_stream(p, g, m, v, n, shadow16, co);
 }
 __global__ void incr_kernel(int* step) { *step += 1; }
 __global__ void incr_unless_kernel(int* step, const float* found_inf) {
@@ -1131,6 +1161,83 @@ __global__ void amp_update_kernel(float* scale, int* growth_tracker, float* foun
     if (stats) stats[0] += 1;
   }
   found_inf[0] = 0.f;
+}
+
+// ------------------------------------------------------------------ gradient-norm clipping (optim.FusedAdam(max_grad_norm=c))
+// torch.nn.utils.clip_grad_norm_(params, c, norm_type=2) with nothing read on the host and no gradient rewritten: one
+// streaming read forms the sum of squares, dsr_clip_finalize turns it into the coefficient, the _hyper Adam kernels apply it.
+// clip_sumsq_kernel: amp_check_kernel's layout (<= 64 tensors per launch, DSR_AMP_CHUNK elements of a tensor's 16-byte
+// aligned body per block, scalar head and tail in the tensor's first block).  A thread squares and adds at most 32 body
+// elements (8 vectors x 4) and 2 head / tail elements in fp32, in a fixed order; from there on everything is fp64 (butterfly
+// over the wave, the four wave sums in order), and the block stores ONE fp32 partial at its own index: no atomics, the same
+// bits on every run.
+__global__ __launch_bounds__(256) void clip_sumsq_kernel(const AmpGroup a, float* __restrict__ partial) {
+  typedef __attribute__((ext_vector_type(4))) float F4;
+  __shared__ double red[4];
+  int t = 0;
+  while (t + 1 < a.count && blockIdx.x >= a.first_block[t + 1]) ++t;      // wave-uniform scan of <= 64 entries
+  const unsigned blk = blockIdx.x - a.first_block[t];
+  const float* __restrict__ g = a.g[t];
+  const size_t n = a.n[t], head = amp_head(a.g[t], n), nvec = (n - head) / 4;
+  const F4* __restrict__ body = reinterpret_cast<const F4*>(g + head);
+  const size_t v0 = (size_t)blk * (DSR_AMP_CHUNK / 4);
+  const size_t v1 = v0 + DSR_AMP_CHUNK / 4 < nvec ? v0 + DSR_AMP_CHUNK / 4 : nvec;
+  float s = 0.f;
+  {
+#pragma clang fp contract(off)
+#pragma unroll 4
+    for (size_t i = v0 + threadIdx.x; i < v1; i += 256) {
+      const F4 x = __builtin_nontemporal_load(body + i);
+      s += x.x * x.x;
+      s += x.y * x.y;
+      s += x.z * x.z;
+      s += x.w * x.w;
+    }
+    if (blk == 0) {
+      const size_t tail0 = head + nvec * 4;
+      if (threadIdx.x < head) s += g[threadIdx.x] * g[threadIdx.x];
+      if (tail0 + threadIdx.x < n) s += g[tail0 + threadIdx.x] * g[tail0 + threadIdx.x];
+    }
+  }
+  double d = (double)s;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = d;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = (float)(((red[0] + red[1]) + red[2]) + red[3]);
+}
+
+// One block: every partial summed in fp64 in a fixed order (thread i takes partials i, i + 256, ...; the 256 thread sums are
+// added in index order), then  norm = sqrt(sum) * |grad_scale|  (or / loss_scale[0]),  coef = min(1, max_norm / (norm + 1e-6))
+// in fp32 as torch forms it (a NaN norm gives a NaN coefficient: the comparison keeps it), and the hyper block {lr, coef}.
+// max_norm <= 0: no clipping, coef = 1 (the launch then only carries a tensor lr into the hyper block).
+__global__ __launch_bounds__(256) void clip_finalize_kernel(const float* __restrict__ partial, int n_partial,
+                                                            const double* __restrict__ gram, int n_gram, float grad_scale,
+                                                            const float* __restrict__ loss_scale, float max_norm,
+                                                            const float* __restrict__ lr_dev, float lr_host,
+                                                            float* __restrict__ grad_norm, float* __restrict__ clip_coef,
+                                                            float* __restrict__ hyper) {
+  __shared__ double red[256];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n_partial; i += 256) s += (double)partial[i];
+  for (int i = threadIdx.x; i < n_gram; i += 256) s += gram[i];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double tot = 0.0;
+  for (int i = 0; i < 256; ++i) tot += red[i];
+  double nd = sqrt(tot);
+  nd = loss_scale != nullptr ? nd / (double)loss_scale[0] : nd * fabs((double)grad_scale);
+  const float norm = (float)nd;
+  float coef = 1.f;
+  if (max_norm > 0.f) {
+    coef = max_norm / (norm + 1e-6f);
+    coef = coef > 1.f ? 1.f : coef;
+  }
+  if (grad_norm) grad_norm[0] = norm;
+  if (clip_coef) clip_coef[0] = coef;
+  hyper[0] = lr_dev != nullptr ? lr_dev[0] : lr_host;
+  hyper[1] = coef;
 }
 
 // ================================================================== host launchers
@@ -1428,15 +1535,8 @@ struct AdamGroup {
   unsigned first_block[DSR_ADAM_GROUP + 1];
   int count;
 };
-template <bool AMP>
-__global__ __launch_bounds__(256) void adam_multi_kernel(const AdamGroup a, float lr, float b1, float b2, float eps,
-                                                         const int* __restrict__ step, float grad_scale,
-                                                         const float* __restrict__ loss_scale,
-                                                         const float* __restrict__ found_inf) {
-  if constexpr (AMP) {          // see adam_kernel
-    if (found_inf[0] != 0.f) return;
-    grad_scale = 1.f / loss_scale[0];
-  }
+// this block's chunk of its tensor (shared by adam_multi_kernel and adam_multi_hyper_kernel)
+__device__ __forceinline__ void adam_multi_chunk(const AdamGroup& a, const AdamCoef& co) {
   int t = 0;
   while (t + 1 < a.count && blockIdx.x >= a.first_block[t + 1]) ++t;      // wave-uniform scan of <= 64 entries
   const unsigned base = (blockIdx.x - a.first_block[t]) * DSR_ADAM_CHUNK;
@@ -1445,7 +1545,6 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamGroup a, floa
   const float* __restrict__ g = a.g[t];
   float* __restrict__ m = a.m[t];
   float* __restrict__ v = a.v[t];
-  const AdamCoef co = adam_coef(step, lr, b1, b2, eps, grad_scale);
 #pragma unroll 4
   for (unsigned i = base + threadIdx.x; i < base + DSR_ADAM_CHUNK && i < n; i += 256) {
     float pk = p[i], mk = m[i], vk = v[i];
@@ -1456,9 +1555,29 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamGroup a, floa
   }
 }
 template <bool AMP>
+__global__ __launch_bounds__(256) void adam_multi_kernel(const AdamGroup a, float lr, float b1, float b2, float eps,
+                                                         const int* __restrict__ step, float grad_scale,
+                                                         const float* __restrict__ loss_scale,
+                                                         const float* __restrict__ found_inf) {
+  if constexpr (AMP) {          // see adam_kernel
+    if (found_inf[0] != 0.f) return;
+    grad_scale = 1.f / loss_scale[0];
+  }
+  adam_multi_chunk(a, adam_coef(step, lr, b1, b2, eps, grad_scale));
+}
+__global__ __launch_bounds__(256) void adam_multi_hyper_kernel(const AdamGroup a, const float* __restrict__ hyper, float b1,
+                                                               float b2, float eps, const int* __restrict__ step,
+                                                               float grad_scale, const float* __restrict__ loss_scale,
+                                                               const float* __restrict__ found_inf) {
+  AdamCoef co;
+  if (!adam_hyper_coef(hyper, b1, b2, eps, step, grad_scale, loss_scale, found_inf, co)) return;
+  adam_multi_chunk(a, co);
+}
+template <bool AMP>
 static int adam_multi_launch(const char* what, int count, float* const* p, const float* const* g, float* const* m,
                              float* const* v, const size_t* n, float lr, float b1, float b2, float eps, const int* step,
-                             float grad_scale, const float* loss_scale, const float* found_inf, hipStream_t st) {
+                             float grad_scale, const float* loss_scale, const float* found_inf, hipStream_t st,
+                             const float* hyper = nullptr) {
   for (int i0 = 0; i0 < count; i0 += DSR_ADAM_GROUP) {
     AdamGroup a;
     a.count = count - i0 < DSR_ADAM_GROUP ? count - i0 : DSR_ADAM_GROUP;
@@ -1474,7 +1593,10 @@ static int adam_multi_launch(const char* what, int count, float* const* p, const
       blocks += (unsigned)((n[i0 + j] + DSR_ADAM_CHUNK - 1) / DSR_ADAM_CHUNK);
     }
     a.first_block[a.count] = blocks;
-    if (blocks)
+    if (blocks && hyper)
+      hipLaunchKernelGGL(adam_multi_hyper_kernel, dim3(blocks), dim3(256), 0, st, a, hyper, b1, b2, eps, step, grad_scale,
+                         loss_scale, found_inf);
+    else if (blocks)
       hipLaunchKernelGGL(adam_multi_kernel<AMP>, dim3(blocks), dim3(256), 0, st, a, lr, b1, b2, eps, step, grad_scale,
                          loss_scale, found_inf);
   }
@@ -1548,4 +1670,99 @@ extern "C" int dsr_amp_update(float* scale, int* growth_tracker, float* found_in
   hipLaunchKernelGGL(amp_update_kernel, dim3(1), dim3(1), 0, st, scale, growth_tracker, found_inf, growth_factor,
                      backoff_factor, growth_interval, stats);
   return dsr_launch_status("dsr_amp_update");
+}
+
+// ------------------------------------------------------------------ clipping + device hyper-parameters: C ABI
+static bool clip_tables_ok(int count, const float* const* grads, const size_t* numel) {
+  if (count <= 0 || !grads || !numel) return false;
+  for (int i = 0; i < count; ++i)
+    if (grads[i] && !(numel[i] > 0 && numel[i] < ((size_t)1 << 43) && ((uintptr_t)grads[i] & 3) == 0)) return false;
+  return true;
+}
+static size_t clip_tensor_blocks(const float* g, size_t n) {
+  const size_t nvec = (n - amp_head(g, n)) / 4;
+  return nvec ? (nvec + DSR_AMP_CHUNK / 4 - 1) / (DSR_AMP_CHUNK / 4) : 1;
+}
+extern "C" size_t dsr_clip_sumsq_partials(int count, const float* const* grads, const size_t* numel) {
+  if (!clip_tables_ok(count, grads, numel)) return 0;
+  size_t blocks = 0;
+  for (int i = 0; i < count; ++i)
+    if (grads[i]) blocks += clip_tensor_blocks(grads[i], numel[i]);
+  return blocks;
+}
+extern "C" int dsr_clip_sumsq(int count, const float* const* grads, const size_t* numel, float* partials, size_t n_partials,
+                              hipStream_t st) {
+  DSR_REQUIRE(count > 0 && grads && numel && partials, "clip_sumsq: null pointer or no tensors");
+  DSR_REQUIRE(((uintptr_t)partials & 3) == 0, "clip_sumsq: partials not 4-byte aligned");
+  for (int i = 0; i < count; ++i)      // NULL = no gradient, skipped
+    DSR_REQUIRE(!grads[i] || (numel[i] > 0 && numel[i] < ((size_t)1 << 43) && ((uintptr_t)grads[i] & 3) == 0),
+                "clip_sumsq: tensor %d is empty, too large or not 4-byte aligned", i);
+  const size_t need = dsr_clip_sumsq_partials(count, grads, numel);
+  if (need == 0) return dsr_fail(DSR_E_ARG, "clip_sumsq: every table entry is NULL");
+  if (n_partials < need || need > 0x7fffffffull)
+    return dsr_fail(DSR_E_WORKSPACE, "clip_sumsq: %zu partials needed, %zu given", need, n_partials);
+  AmpGroup a;
+  a.count = 0;
+  size_t blocks = 0, base = 0;
+  auto flush = [&]() {
+    if (!a.count) return;
+    a.first_block[a.count] = (unsigned)blocks;
+    hipLaunchKernelGGL(clip_sumsq_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, partials + base);
+    base += blocks;
+    a.count = 0;
+    blocks = 0;
+  };
+  for (int i = 0; i < count; ++i) {
+    if (!grads[i]) continue;
+    const size_t nb = clip_tensor_blocks(grads[i], numel[i]);
+    if (a.count == DSR_AMP_GROUP || blocks + nb > 0x7fffffffull) flush();
+    a.g[a.count] = grads[i];
+    a.n[a.count] = numel[i];
+    a.first_block[a.count] = (unsigned)blocks;
+    blocks += nb;
+    ++a.count;
+  }
+  flush();
+  return dsr_launch_status("dsr_clip_sumsq");
+}
+extern "C" int dsr_clip_finalize(const float* partials, int n_partials, const double* gram_partials, int n_gram,
+                                 float grad_scale, const float* scale, float max_norm, const float* lr_dev, float lr_host,
+                                 float* grad_norm, float* clip_coef, float* hyper, hipStream_t st) {
+  DSR_REQUIRE(hyper && n_partials >= 0 && n_gram >= 0, "clip_finalize: null hyper block or negative count");
+  DSR_REQUIRE((n_partials == 0 || partials) && (n_gram == 0 || gram_partials), "clip_finalize: null partials");
+  DSR_REQUIRE(((uintptr_t)partials & 3) == 0 && ((uintptr_t)gram_partials & 7) == 0 && ((uintptr_t)hyper & 3) == 0 &&
+                  ((uintptr_t)scale & 3) == 0 && ((uintptr_t)lr_dev & 3) == 0 && ((uintptr_t)grad_norm & 3) == 0 &&
+                  ((uintptr_t)clip_coef & 3) == 0,
+              "clip_finalize: misaligned pointer");
+  DSR_REQUIRE(max_norm == max_norm && grad_scale == grad_scale, "clip_finalize: max_norm or grad_scale is NaN");
+  DSR_REQUIRE(lr_dev || lr_host == lr_host, "clip_finalize: lr is NaN");
+  hipLaunchKernelGGL(clip_finalize_kernel, dim3(1), dim3(256), 0, st, partials, n_partials, gram_partials, n_gram,
+                     grad_scale, scale, max_norm, lr_dev, lr_host, grad_norm, clip_coef, hyper);
+  return dsr_launch_status("dsr_clip_finalize");
+}
+extern "C" int dsr_pw_adam_hyper(float* p, const float* g, float* m, float* v, size_t n, const float* hyper, float b1,
+                                 float b2, float eps, const int* step, float grad_scale, const float* scale,
+                                 const float* found_inf, void* shadow_bf16, hipStream_t st) {
+  DSR_REQUIRE(p && g && m && v && step && hyper && n > 0, "adam_hyper: null pointer or empty tensor");
+  DSR_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 3) == 0 && ((uintptr_t)shadow_bf16 & 1) == 0 &&
+                  (((uintptr_t)hyper | (uintptr_t)step | (uintptr_t)scale | (uintptr_t)found_inf) & 3) == 0,
+              "adam_hyper: misaligned pointer");
+  size_t want = (n / 4 + 511) / 512;
+  unsigned blocks = (unsigned)(want < 1 ? 1 : (want > 65536 ? 65536 : want));
+  hipLaunchKernelGGL(adam_hyper_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, hyper, b1, b2, eps, step, grad_scale,
+                     (unsigned short*)shadow_bf16, scale, found_inf);
+  return dsr_launch_status("dsr_pw_adam_hyper");
+}
+extern "C" int dsr_pw_adam_multi_hyper(int count, float* const* p, const float* const* g, float* const* m, float* const* v,
+                                       const size_t* n, const float* hyper, float b1, float b2, float eps, const int* step,
+                                       float grad_scale, const float* scale, const float* found_inf, hipStream_t st) {
+  DSR_REQUIRE(count > 0 && p && g && m && v && n && step && hyper, "adam_multi_hyper: null pointer or no tensors");
+  DSR_REQUIRE((((uintptr_t)hyper | (uintptr_t)step | (uintptr_t)scale | (uintptr_t)found_inf) & 3) == 0,
+              "adam_multi_hyper: misaligned pointer");
+  for (int i = 0; i < count; ++i)
+    DSR_REQUIRE(p[i] && g[i] && m[i] && v[i] && n[i] > 0 &&
+                    (((uintptr_t)p[i] | (uintptr_t)g[i] | (uintptr_t)m[i] | (uintptr_t)v[i]) & 3) == 0,
+                "adam_multi_hyper: null, empty or misaligned tensor %d", i);
+  return adam_multi_launch<false>("dsr_pw_adam_multi_hyper", count, p, g, m, v, n, 0.f, b1, b2, eps, step, grad_scale, scale,
+                                  found_inf, st, hyper);
 }

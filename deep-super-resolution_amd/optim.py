@@ -14,10 +14,44 @@ from .functional import _ptr, _stream, bump, check, mark_shadow_current, repack_
 class FusedAdam:
     MULTI_MAX = 1 << 20      # tensors up to this many elements go through the multi-tensor launch
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, fuse_dense_head=False):
+    GRAM_MAX_ROWS = 512      # ranks x padded batch up to which the factored gradient's norm comes from the Gram identity
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, fuse_dense_head=False,
+                 max_grad_norm=None, norm_type=2.0):
+        """``lr``: a float, or a one-element tensor (torch.optim.Adam's capturable form): cast to fp32 on the parameters'
+        device and kept as ``self.lr``; every Adam launch reads it on the device, so ``opt.lr.fill_(x)`` takes effect at the
+        next ``step()`` and at the next replay of a captured step (steps.GraphedStep).  A tensor holding the fp32 value of a
+        float gives that float's bits.
+
+        ``max_grad_norm=c``: ``torch.nn.utils.clip_grad_norm_(params, c, norm_type=2.0, error_if_nonfinite=False)`` followed
+        by Adam, on the device: ``step()`` forms the global 2-norm over every parameter of this optimiser that has a gradient
+        -- the dense head's deferred gradient included, from its two factors, which torch's function cannot see -- and the
+        Adam kernels apply ``clip_coef = min(1, c / (grad_norm + 1e-6))``.  The gradients themselves are NOT rewritten:
+        ``p.grad`` after ``step()`` holds the unclipped gradient.  ``self.grad_norm`` / ``self.clip_coef`` (fp32 device
+        tensors [1]) hold this step's norm of the TRUE gradient -- a static ``grad_scale`` and a DynamicLossScaler's scale
+        are taken out -- before clipping, and the coefficient; a non-finite norm gives a NaN coefficient and NaN parameters, as
+        in torch.  After a step the scaler skipped they may hold anything, finite or not.  Only the 2-norm is offered.
+        With neither option ``step()`` issues the launches it always did."""
+        if norm_type is None or isinstance(norm_type, bool) or not isinstance(norm_type, (int, float)) or float(norm_type) != 2.0:
+            raise NotImplementedError(f"FusedAdam: norm_type={norm_type!r} is not implemented; only the 2-norm "
+                                      "(norm_type=2.0) runs on the HIP path")
+        if max_grad_norm is not None:
+            if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)):
+                raise ValueError(f"max_grad_norm must be a positive number or None, got {max_grad_norm!r}")
+            if not max_grad_norm > 0:          # (NaN fails the comparison too)
+                raise ValueError(f"max_grad_norm must be a positive number or None, got {max_grad_norm!r}")
+            max_grad_norm = float(max_grad_norm)
+        self.max_grad_norm = max_grad_norm
         self.params = [p for p in params]
         if not self.params:
             raise ValueError("optimizer got an empty parameter list")   # torch.optim raises the same
+        dev = self.params[0].device
+        if isinstance(lr, torch.Tensor):
+            if lr.numel() != 1:
+                raise ValueError(f"a tensor lr must have one element, got shape {tuple(lr.shape)}")
+            self.lr = lr.detach().to(device=dev, dtype=torch.float32).reshape(1)      # (the caller's own storage when it fits)
+        else:
+            self.lr = float(lr)
         # fuse_dense_head: the dense head's big matrix (discriminator.py:54, marked `_dsr_dense_head`) gets its gradient as
         # two 16-bit factors (functional.GradFactors) instead of a `.grad` tensor, and step() applies Adam inside the
         # weight-gradient contraction (dsr_linear_wgrad_adam).  Same arithmetic, bit for bit; `.grad` of that one tensor
@@ -27,12 +61,16 @@ class FusedAdam:
             for p in self.params:
                 if getattr(p, "_dsr_dense_head", False):
                     p._dsr_defer_wgrad = True
-        self.lr, self.betas, self.eps = float(lr), betas, float(eps)
+        self.betas, self.eps = betas, float(eps)
         self.grad_scale = float(grad_scale)     # gradients are multiplied by this first (1/S for a loss scale S)
-        dev = self.params[0].device
         self.m = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
         self.v = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
         self.step_t = torch.zeros(1, dtype=torch.int32, device=dev)
+        # the device hyper block {lr, clip_coef} the _hyper kernels read; dsr_clip_finalize writes it every step
+        self.grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.clip_coef = torch.ones(1, dtype=torch.float32, device=dev)
+        self._hyper = torch.zeros(2, dtype=torch.float32, device=dev)
+        self._partials = self._gram_ws = None
 
     def zero_grad(self, set_to_none=True):
         for p in self.params:
@@ -43,13 +81,61 @@ class FusedAdam:
             elif p.grad is not None:
                 p.grad.zero_()
 
+    def _device_hyper(self):
+        """True when the Adam launches read lr / the clipping coefficient from the device (the _hyper kernels)."""
+        return self.max_grad_norm is not None or isinstance(self.lr, torch.Tensor)
+
+    def _buffer(self, name, nbytes):
+        buf = getattr(self, name)
+        if buf is None or buf.numel() < nbytes:
+            buf = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=self.step_t.device)
+            setattr(self, name, buf)
+        return buf
+
+    def _write_hyper(self, grads, factors, scale):
+        """The norm pass and dsr_clip_finalize: grad_norm, clip_coef and the hyper block of this step.  `grads`: the fp32
+        gradient tensors, `factors`: the deferred GradFactors (already waited for), `scale`: the loss scaler's device word."""
+        lib = _lib.lib()
+        st = _stream()
+        npart, parts, ndots, dots = 0, None, 0, None
+        if self.max_grad_norm is not None:
+            keep = []
+            for f in factors:
+                if len(factors) == 1 and f.ranks * f.bp <= self.GRAM_MAX_ROWS:
+                    nbytes = lib.dsr_linear_factor_gram_workspace(f.bp, f.o, f.k, f.ranks)
+                    ws = self._buffer("_gram_ws", nbytes)
+                    check(lib.dsr_linear_factor_gram(f.dt, _ptr(f.dyt), _ptr(f.xt), f.bp, f.o, f.k, f.ranks, f.scale, _ptr(ws),
+                                                     nbytes, st))
+                    ndots, dots = lib.dsr_linear_factor_gram_dots(f.bp, f.ranks), ws
+                else:           # more rows than the Gram kernel takes (or a second factored tensor): the tensor pass
+                    keep.append(f.materialize())
+            grads = [g for g in list(grads) + keep if g.numel()]
+            if grads:
+                k = len(grads)
+                ptrs = (C.c_void_p * k)(*[g.data_ptr() for g in grads])
+                ns = (C.c_size_t * k)(*[g.numel() for g in grads])
+                npart = lib.dsr_clip_sumsq_partials(k, ptrs, ns)
+                parts = self._buffer("_partials", 4 * npart)
+                check(lib.dsr_clip_sumsq(k, ptrs, ns, _ptr(parts), npart, st))
+        tensor_lr = isinstance(self.lr, torch.Tensor)
+        check(lib.dsr_clip_finalize(_ptr(parts), npart, _ptr(dots), ndots, self.grad_scale, _ptr(scale),
+                                    self.max_grad_norm or 0.0, _ptr(self.lr) if tensor_lr else None,
+                                    0.0 if tensor_lr else self.lr, _ptr(self.grad_norm), _ptr(self.clip_coef),
+                                    _ptr(self._hyper), st))
+
     def step(self, scaler=None):
         """One Adam update.  `scaler` (a DynamicLossScaler whose check of this step's gradients has run; use
         ``scaler.step(optimizer)``): the predicated kernels -- gradients times 1 / scale read on the device, and nothing
-        moves, the step counter included, when the scaler's overflow flag is set.  The launch sequence is the same either way."""
+        moves, the step counter included, when the scaler's overflow flag is set.  The launch sequence is the same either way.
+
+        With ``max_grad_norm`` or a tensor ``lr`` the Adam launches wait until the norm pass and dsr_clip_finalize have
+        written this step's hyper block -- after the overflow check, after a data-parallel run's gradient averaging and the
+        dense head's factor gather, so every rank forms the same coefficient -- and read lr and coefficient on the device."""
         lib = _lib.lib()
         st = _stream()
         amp = scaler is not None and scaler.enabled
+        hyper = self._device_hyper()
+        scale = found = None
         if amp:
             if self.grad_scale != 1.0:
                 raise ValueError(f"FusedAdam(grad_scale={self.grad_scale}) under a DynamicLossScaler would un-scale the "
@@ -62,6 +148,21 @@ class FusedAdam:
             check(lib.dsr_pw_incr_unless(_ptr(self.step_t), _ptr(found), st))
         else:
             check(lib.dsr_pw_incr(_ptr(self.step_t), st))
+        b1, b2 = self.betas
+        hp = _ptr(self._hyper)
+        deferred, grads, factors = [], [], []     # device hyper block: the Adam launches follow the norm pass
+
+        def launch(fn, p, sh):
+            def run():
+                check(fn())
+                bump(p)
+                if sh is not None:           # after bump(): the shadow written by this launch IS the new version
+                    mark_shadow_current(p)
+            if hyper:
+                deferred.append(run)
+            else:
+                run()
+
         small, keep = [], []
         for p, m, v in zip(self.params, self.m, self.v):
             pending = getattr(p, "_dsr_grad_factors", None)
@@ -71,12 +172,16 @@ class FusedAdam:
                     f = pending[0]
                     f.wait()
                     sh = shadow_for_update(p)
-                    check(lib.dsr_linear_wgrad_adam(f.dt, _ptr(f.dyt), _ptr(f.xt), f.bp, f.o, f.k, f.ranks, f.scale, _ptr(p),
-                                                    _ptr(m), _ptr(v), _ptr(sh), _ptr(self.step_t), self.lr, self.betas[0],
-                                                    self.betas[1], self.eps, self.grad_scale, st))
-                    bump(p)
-                    if sh is not None:
-                        mark_shadow_current(p)
+                    if hyper:
+                        factors.append(f)
+                        launch(lambda f=f, p=p, m=m, v=v, sh=sh: lib.dsr_linear_wgrad_adam_hyper(
+                            f.dt, _ptr(f.dyt), _ptr(f.xt), f.bp, f.o, f.k, f.ranks, f.scale, _ptr(p), _ptr(m), _ptr(v),
+                            _ptr(sh), _ptr(self.step_t), hp, b1, b2, self.eps, self.grad_scale, _ptr(scale), _ptr(found),
+                            st), p, sh)
+                    else:
+                        launch(lambda f=f, p=p, m=m, v=v, sh=sh: lib.dsr_linear_wgrad_adam(
+                            f.dt, _ptr(f.dyt), _ptr(f.xt), f.bp, f.o, f.k, f.ranks, f.scale, _ptr(p), _ptr(m), _ptr(v),
+                            _ptr(sh), _ptr(self.step_t), self.lr, b1, b2, self.eps, self.grad_scale, st), p, sh)
                     continue
                 # several backward passes since zero_grad (or a .grad from elsewhere): accumulate like autograd would
                 for f in pending:
@@ -88,23 +193,36 @@ class FusedAdam:
             if g.dtype != torch.float32 or not g.is_contiguous():
                 g = g.float().contiguous()
                 keep.append(g)
+            grads.append(g)
             sh = shadow_for_update(p)        # bf16 image kept by DenseHead for this matrix (or None)
             if sh is None and p.numel() <= self.MULTI_MAX and p.is_contiguous():
                 small.append((p, g, m, v))
+                bump(p)                      # (rewritten by the multi-tensor launch below, before anything reads it)
+                continue
+            if hyper:
+                launch(lambda p=p, g=g, m=m, v=v, sh=sh: lib.dsr_pw_adam_hyper(
+                    _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), hp, b1, b2, self.eps, _ptr(self.step_t),
+                    self.grad_scale, _ptr(scale), _ptr(found), _ptr(sh), st), p, sh)
             elif amp:
-                check(lib.dsr_pw_adam_amp(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), self.lr, self.betas[0],
-                                          self.betas[1], self.eps, _ptr(self.step_t), _ptr(scale), _ptr(found), _ptr(sh), st))
+                launch(lambda p=p, g=g, m=m, v=v, sh=sh: lib.dsr_pw_adam_amp(
+                    _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), self.lr, b1, b2, self.eps, _ptr(self.step_t),
+                    _ptr(scale), _ptr(found), _ptr(sh), st), p, sh)
             else:
-                check(lib.dsr_pw_adam(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), self.lr, self.betas[0],
-                                      self.betas[1], self.eps, _ptr(self.step_t), self.grad_scale, _ptr(sh), st))
-            bump(p)
-            if sh is not None:               # after bump(): the shadow written by this launch IS the new version
-                mark_shadow_current(p)
+                launch(lambda p=p, g=g, m=m, v=v, sh=sh: lib.dsr_pw_adam(
+                    _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), self.lr, b1, b2, self.eps, _ptr(self.step_t),
+                    self.grad_scale, _ptr(sh), st), p, sh)
+        if hyper:
+            self._write_hyper(grads, factors, scale)
+            for run in deferred:
+                run()
         if small:                            # every small tensor in one launch per 64 (dsr_pw_adam_multi)
             k = len(small)
             arr = [(C.c_void_p * k)(*[t[i].data_ptr() for t in small]) for i in range(4)]
             ns = (C.c_size_t * k)(*[t[0].numel() for t in small])
-            if amp:
+            if hyper:
+                check(lib.dsr_pw_adam_multi_hyper(k, arr[0], arr[1], arr[2], arr[3], ns, hp, b1, b2, self.eps,
+                                                  _ptr(self.step_t), self.grad_scale, _ptr(scale), _ptr(found), st))
+            elif amp:
                 check(lib.dsr_pw_adam_multi_amp(k, arr[0], arr[1], arr[2], arr[3], ns, self.lr, self.betas[0],
                                                 self.betas[1], self.eps, _ptr(self.step_t), _ptr(scale), _ptr(found), st))
             else:

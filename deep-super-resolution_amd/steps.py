@@ -187,12 +187,14 @@ class GraphedStep:
 class DipRunner:
     """DIP.py:22-123 state: fixed noise input, jitter buffer, Lanczos downsampler, Adam over the net."""
 
-    def __init__(self, net, downsampler, net_input, lr_image, learning_rate, reg_noise_std, loss_scale=None):
+    def __init__(self, net, downsampler, net_input, lr_image, learning_rate, reg_noise_std, loss_scale=None,
+                 max_grad_norm=None):
         from .optim import DynamicLossScaler, FusedAdam
         # fp16 storage (the DIP default, see models/DIP/skip.py) needs a loss scale so that activation
         # gradients (~1e-5 at the MSE) stay out of fp16's subnormal range; Adam un-scales on the fly.
         # None: static 1024 (tuned at HR 128x128, x2); a number: that static scale; "dynamic" or an
         # optim.DynamicLossScaler: the scale follows the gradients on the device, overflowing steps are skipped.
+        # max_grad_norm: FusedAdam's device-side clipping of the global gradient norm (of the un-scaled gradients).
         self.scaler = None
         if isinstance(loss_scale, str):
             if loss_scale != "dynamic":
@@ -209,8 +211,8 @@ class DipRunner:
         self.net_input = net_input
         self.lr_image = lr_image
         self.sigma = reg_noise_std
-        self.opt = FusedAdam(list(net.parameters()), lr=learning_rate,
-                             grad_scale=1.0 / self.loss_scale)       # get_params('net') + utils/DIP.py:34
+        self.opt = FusedAdam(list(net.parameters()), lr=learning_rate, grad_scale=1.0 / self.loss_scale,
+                             max_grad_norm=max_grad_norm)            # get_params('net') + utils/DIP.py:34
 
     def step(self, noise=None):
         """optimizer.zero_grad(); closure(); optimizer.step()  (utils/DIP.py:35-38, DIP.py:47-68)."""

@@ -23,15 +23,16 @@ def _scaler(loss_scale):
     raise ValueError(f"loss_scale: None, 'dynamic' or an optim.DynamicLossScaler, got {loss_scale!r}")
 
 
-def _adam_loop(parameters, closure, learning_rate, steps, scaler=None):
+def _adam_loop(parameters, closure, learning_rate, steps, scaler=None, max_grad_norm=None):
     """zero_grad(); closure(); step()  `steps` times with the fused multi-tensor Adam kernel (utils/DIP.py:33-38).
 
     ``scaler``: the closure calls backward() itself on a loss this function never sees, so the scale is applied where the
     fp32 gradient enters the net's 16-bit storage (functional.ambient_loss_scale) -- the same numbers as a scaled loss.
     On that route the closure's 3x3 weight gradients are also grouped into one launch as steps.DipRunner groups them
     (functional.batched_wgrad: nothing in the closure may read a weight's .grad), so the two routes give the same bits; the
-    route without a scaler keeps its launches, and its bits, as they were."""
-    optimizer = FusedAdam(parameters, lr=learning_rate)
+    route without a scaler keeps its launches, and its bits, as they were.  ``max_grad_norm``: FusedAdam's device-side
+    clipping of the global gradient norm."""
+    optimizer = FusedAdam(parameters, lr=learning_rate, max_grad_norm=max_grad_norm)
     for _ in range(steps):
         optimizer.zero_grad()
         if scaler is None:
@@ -45,15 +46,15 @@ def _adam_loop(parameters, closure, learning_rate, steps, scaler=None):
     optimizer.zero_grad(set_to_none=True)
 
 
-def _lbfgs(parameters, closure, learning_rate, num_iter, fused=False, scaler=None):
+def _lbfgs(parameters, closure, learning_rate, num_iter, fused=False, scaler=None, max_grad_norm=None):
     """utils/DIP.py:19-31: Adam warm-up, then ONE torch.optim.LBFGS.step of ``max_iter=num_iter`` inner iterations
     with both tolerances disabled.  The closure (forward, loss, backward) is the HIP path; by default the two-loop
     recursion itself is torch's own vector arithmetic on the flattened parameters, exactly as in the reference.  LBFGS
     writes the parameters in place through torch ops, which bumps their version counters, so the packed 16-bit weight
     images are refreshed on the next forward.  ``fused``: the same step by ``optim.FusedLBFGS`` (csrc/lbfgs.hip), which
-    refreshes those images itself after each update.  ``scaler`` serves the Adam warm-up only."""
+    refreshes those images itself after each update.  ``scaler`` and ``max_grad_norm`` serve the Adam warm-up only."""
     parameters = list(parameters)
-    _adam_loop(parameters, closure, LBFGS_WARMUP_LR, LBFGS_WARMUP_STEPS, scaler)
+    _adam_loop(parameters, closure, LBFGS_WARMUP_LR, LBFGS_WARMUP_STEPS, scaler, max_grad_norm)
     cls = FusedLBFGS if fused else torch.optim.LBFGS
     optimizer = cls(parameters, max_iter=num_iter, lr=learning_rate, tolerance_grad=-1, tolerance_change=-1)
 
@@ -64,17 +65,22 @@ def _lbfgs(parameters, closure, learning_rate, num_iter, fused=False, scaler=Non
     optimizer.step(closure2)
 
 
-def optimize(optimizer_type, parameters, closure, learning_rate, num_iter, *, fused_lbfgs=False, loss_scale=None):
+def optimize(optimizer_type, parameters, closure, learning_rate, num_iter, *, fused_lbfgs=False, loss_scale=None,
+             max_grad_norm=None):
     """Run the optimisation loop: ``'adam'`` (what DIP.py:99 selects) or ``'LBFGS'``; anything else asserts.
     ``fused_lbfgs=True`` runs the LBFGS branch's L-BFGS phase on ``optim.FusedLBFGS`` instead of torch.optim.LBFGS.
 
     ``loss_scale="dynamic"`` (or an ``optim.DynamicLossScaler``): the fp16 net's gradients are computed under a loss scale
     that follows them on the device; steps whose gradients overflow are skipped.  The closure stays as it is.  Without it
     the gradients are unscaled, as before.  With ``'LBFGS'`` it applies to the 100-step Adam warm-up only: the L-BFGS phase
-    takes no loss scale (closure values and curvature pairs do not survive skipped steps)."""
+    takes no loss scale (closure values and curvature pairs do not survive skipped steps).
+
+    ``max_grad_norm=c``: the Adam steps clip the global 2-norm of the gradients to ``c`` on the device
+    (``optim.FusedAdam(max_grad_norm=c)``); with ``'LBFGS'`` that is the warm-up only, FusedLBFGS takes no clipping."""
     scaler = _scaler(loss_scale)
-    runners = {'adam': lambda: _adam_loop(list(parameters), closure, learning_rate, num_iter, scaler),
-               'LBFGS': lambda: _lbfgs(parameters, closure, learning_rate, num_iter, fused=fused_lbfgs, scaler=scaler)}
+    runners = {'adam': lambda: _adam_loop(list(parameters), closure, learning_rate, num_iter, scaler, max_grad_norm),
+               'LBFGS': lambda: _lbfgs(parameters, closure, learning_rate, num_iter, fused=fused_lbfgs, scaler=scaler,
+                                       max_grad_norm=max_grad_norm)}
     assert optimizer_type in runners
     runners[optimizer_type]()
 

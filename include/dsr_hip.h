@@ -262,6 +262,34 @@ int dsr_pw_incr_unless(int* step, const float* found_inf, dsr_stream_t s);
 int dsr_amp_update(float* scale, int* growth_tracker, float* found_inf, float growth_factor, float backoff_factor,
                    int growth_interval, int* stats, dsr_stream_t s);
 
+/* ------------------------------------------------------------------ gradient-norm clipping and a device-resident learning rate
+ * (optim.FusedAdam(lr=<tensor>, max_grad_norm=c)).  torch.nn.utils.clip_grad_norm_(params, c, norm_type=2) followed by
+ * torch.optim.Adam, with nothing read on the host and no gradient rewritten: the coefficient is applied inside the Adam
+ * kernels.  Order within a step: (dsr_amp_check,) dsr_pw_incr[_unless], dsr_clip_sumsq and / or dsr_linear_factor_gram,
+ * dsr_clip_finalize, the _hyper Adam launches.
+ * dsr_clip_sumsq: one fp32 partial sum of squares per block over `count` fp32 tensors (HOST tables as dsr_amp_check takes
+ * them: a NULL entry is skipped, 64 tensors per launch, views 4 / 8 / 12 bytes off a 16-byte boundary are fine), written
+ * with plain stores at partials[0 .. dsr_clip_sumsq_partials()): no atomics, bit-reproducible.
+ * dsr_clip_finalize: sums partials (fp32) and gram_partials (fp64) in fp64 in a fixed order; norm = sqrt(sum) * |grad_scale|,
+ * or sqrt(sum) / scale[0] when scale (the dynamic loss scaler's word) is non-NULL; coef = min(1, max_norm / (norm + 1e-6)),
+ * torch's formula (max_norm <= 0: coef = 1, no clipping); writes grad_norm[0], clip_coef[0] (both nullable) and the hyper
+ * block hyper[0] = lr (lr_dev[0] when lr_dev is non-NULL, else lr_host), hyper[1] = coef.  Either count may be 0.
+ * dsr_pw_adam_hyper / dsr_pw_adam_multi_hyper: dsr_pw_adam / dsr_pw_adam_multi with lr = hyper[0] and the gradient multiplied
+ * by the ONE fp32 product grad_scale * hyper[1] (scale non-NULL: (1 / scale[0]) * hyper[1]); found_inf non-NULL and set:
+ * no write at all.  hyper[1] == 1 gives the bits of the kernels they shadow. */
+size_t dsr_clip_sumsq_partials(int count, const float* const* grads, const size_t* numel);
+int dsr_clip_sumsq(int count, const float* const* grads, const size_t* numel, float* partials, size_t n_partials,
+                   dsr_stream_t s);
+int dsr_clip_finalize(const float* partials, int n_partials, const double* gram_partials, int n_gram, float grad_scale,
+                      const float* scale, float max_norm, const float* lr_dev, float lr_host, float* grad_norm,
+                      float* clip_coef, float* hyper, dsr_stream_t s);
+int dsr_pw_adam_hyper(float* p, const float* g, float* m, float* v, size_t n, const float* hyper, float b1, float b2,
+                      float eps, const int* step, float grad_scale, const float* scale, const float* found_inf,
+                      void* shadow_bf16, dsr_stream_t s);
+int dsr_pw_adam_multi_hyper(int count, float* const* p, const float* const* g, float* const* m, float* const* v,
+                            const size_t* n, const float* hyper, float b1, float b2, float eps, const int* step,
+                            float grad_scale, const float* scale, const float* found_inf, dsr_stream_t s);
+
 /* ------------------------------------------------------------------ discriminator dense head (linear.hip)
  * models/GAN/discriminator.py:37-45,65-72: flatten(C,H,W) -> Linear(K,O) -> LeakyReLU(0.2) -> Linear(O,1) -> Sigmoid */
 /* 16-bit shadow copy of an fp32 tensor (n % 8 == 0) */
@@ -288,6 +316,21 @@ int dsr_linear_wgrad_gathered(int dtype, const void* dyT16_all, const void* xT16
 int dsr_linear_wgrad_adam(int dtype, const void* dyT16_all, const void* xT16_all, int Bp, int O, size_t K, int R, float scale,
                           float* p, float* m, float* v, void* shadow_bf16, const int* step, float lr, float b1, float b2,
                           float eps, float grad_scale, dsr_stream_t s);
+/* squared Frobenius norm of the factored gradient dW = scale * sum_{(r,b)} dyT[r][:,b] (x) xT[r][:,b] WITHOUT forming it:
+ * |dW|^2 = scale^2 * sum_{i,j} Gx[i][j] Gdy[i][j] over the (R Bp)^2 Gram matrices of the two tables (same arguments as
+ * dsr_linear_wgrad_adam).  The workspace (16-byte aligned, dsr_linear_factor_gram_workspace() bytes) starts with
+ * dsr_linear_factor_gram_dots() fp64 partial sums -- what dsr_clip_finalize takes as gram_partials -- followed by the
+ * per-block fp32 Gram partials they were combined from (in fp64).  R * Bp > 512: DSR_E_UNSUPPORTED (both queries answer 0). */
+size_t dsr_linear_factor_gram_workspace(int Bp, int O, size_t K, int R);
+int dsr_linear_factor_gram_dots(int Bp, int R);
+int dsr_linear_factor_gram(int dtype, const void* dyT16_all, const void* xT16_all, int Bp, int O, size_t K, int R, float scale,
+                           void* workspace, size_t ws_bytes, dsr_stream_t s);
+/* dsr_linear_wgrad_adam with the device hyper block (lr = hyper[0], gradient multiplier grad_scale * hyper[1]; loss_scale and
+ * found_inf nullable, as in dsr_pw_adam_hyper) */
+int dsr_linear_wgrad_adam_hyper(int dtype, const void* dyT16_all, const void* xT16_all, int Bp, int O, size_t K, int R,
+                                float scale, float* p, float* m, float* v, void* shadow_bf16, const int* step,
+                                const float* hyper, float b1, float b2, float eps, float grad_scale, const float* loss_scale,
+                                const float* found_inf, dsr_stream_t s);
 /* out[b] = sigmoid(h[b][:] . w2 + b2) */
 int dsr_dense2_fwd(const float* h, const float* w2, const float* b2, int B, int K1, float* out, dsr_stream_t s);
 /* backward of the fp32 tail; also emits the 16-bit dy / dy^T operands of the two dense1 GEMMs */
