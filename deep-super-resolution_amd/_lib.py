@@ -137,6 +137,10 @@ SIGNATURES = {
     "dsr_box_copy": (_I, [_P, _P] + [_I] * 16 + [_P]),
     "dsr_downsample_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dsr_downsample_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "dsr_downsample_dense_fwd": (_I, [_P, _P, _P, _P] + [_I] * 7 + [_P]),
+    "dsr_downsample_dense_dgrad": (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
+    "dsr_downsample_dense_wgrad_workspace": (_Z, [_I] * 7),
+    "dsr_downsample_dense_wgrad": (_I, [_P, _P, _P, _P, _P, _Z] + [_I] * 7 + [_P]),
     "dsr_ssim_blocks": (_I, [_I, _I, _I]),
     "dsr_ssim_f32": (_I, [_P, _P, _I, _I, _I, _F, _P, _P]),
     "dsr_lpips_tap_sizes": (_I, [_I, _I, C.POINTER(_I)]),
@@ -176,7 +180,7 @@ _NO_LAUNCH = ("dsr_last_error", "dsr_abi_version", "dsr_conv_dgrad_ps_supported"
               "dsr_conv_packed_elems", "dsr_conv_dgrad_workspace", "dsr_conv_wgrad_workspace", "dsr_pw_scratch_rows",
               "dsr_pw_reduce_blocks", "dsr_linear_fwd_workspace", "dsr_ssim_blocks", "dsr_lpips_tap_sizes", "dsr_lpips_distance_blocks",
               "dsr_ssim_img_blocks", "dsr_psnr_blocks", "dsr_lbfgs_workspace", "dsr_lbfgs_vector_floats", "dsr_clip_sumsq_partials",
-              "dsr_linear_factor_gram_workspace", "dsr_linear_factor_gram_dots")
+              "dsr_linear_factor_gram_workspace", "dsr_linear_factor_gram_dots", "dsr_downsample_dense_wgrad_workspace")
 
 
 class _Lib:

@@ -1496,3 +1496,55 @@ class Downsample(torch.autograd.Function):
         dx = torch.empty((n, c, h, w), dtype=torch.float32, device=dy.device)
         check(_lib.lib().dsr_downsample_bwd(_ptr(dy), _ptr(kern), _ptr(dx), n * c, h, w, k, factor, pad, _stream()))
         return dx, None, None, None
+
+
+class DownsampleDense(torch.autograd.Function):
+    """The Downsampler as the dense layer it is in the reference: ReplicationPad2d(pad) + Conv2d(C, C, k, stride=factor)
+    + bias on fp32 NCHW with every filter live (csrc/downsample_dense.hip).  Gradients for x, weight and bias, each
+    computed only when asked for.  Under an ambient loss scale (utils.DIP.optimize(loss_scale=...)) the scale enters
+    the backward pass at the net's output, i.e. after this op: dx passes on unscaled and gets scaled there, so dw and db
+    are multiplied by the scale here to arrive at the optimiser scaled like every other gradient."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, factor, pad):
+        _need_gpu(x)
+        x = x.contiguous().float()
+        w = weight.detach().contiguous().float()
+        b = None if bias is None else bias.detach().contiguous().float()
+        n, c, h, wd = x.shape
+        if w.dim() != 4 or w.shape[0] != c or w.shape[1] != c or w.shape[2] != w.shape[3]:
+            raise RuntimeError(f"DownsampleDense: weight {tuple(w.shape)} does not fit an input of {c} planes")
+        k = w.shape[2]
+        oh, ow = (h + 2 * pad - k) // factor + 1, (wd + 2 * pad - k) // factor + 1
+        y = torch.empty((n, c, max(oh, 0), max(ow, 0)), dtype=torch.float32, device=x.device)
+        check(_lib.lib().dsr_downsample_dense_fwd(_ptr(x), _ptr(w), _ptr(b), _ptr(y), n, c, h, wd, k, factor, pad,
+                                                  _stream()))
+        ctx.args = (n, c, h, wd, k, factor, pad, bias is not None)
+        ctx.save_for_backward(x, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        n, c, h, wd, k, factor, pad, has_bias = ctx.args
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_db = has_bias and ctx.needs_input_grad[2]
+        dy = dy.contiguous().float()
+        lib = _lib.lib()
+        dx = dw = db = None
+        if need_dx:
+            dx = torch.empty_like(x)
+            check(lib.dsr_downsample_dense_dgrad(_ptr(dy), _ptr(w), _ptr(dx), n, c, h, wd, k, factor, pad, _stream()))
+        if need_dw or need_db:
+            nbytes = lib.dsr_downsample_dense_wgrad_workspace(n, c, h, wd, k, factor, pad)
+            ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=x.device)
+            dw = torch.empty_like(w)
+            db = torch.empty(c, dtype=torch.float32, device=x.device) if need_db else None
+            check(lib.dsr_downsample_dense_wgrad(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), nbytes, n, c, h, wd, k,
+                                                 factor, pad, _stream()))
+            if _ambient_scale is not None:
+                dw = axpby(dw, None, 1.0, 0.0, _ambient_scale)
+                db = None if db is None else axpby(db, None, 1.0, 0.0, _ambient_scale)
+            if not need_dw:
+                dw = None
+        return dx, dw, db, None, None

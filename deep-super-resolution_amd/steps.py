@@ -188,7 +188,7 @@ class DipRunner:
     """DIP.py:22-123 state: fixed noise input, jitter buffer, Lanczos downsampler, Adam over the net."""
 
     def __init__(self, net, downsampler, net_input, lr_image, learning_rate, reg_noise_std, loss_scale=None,
-                 max_grad_norm=None):
+                 max_grad_norm=None, learn_downsampler=False):
         from .optim import DynamicLossScaler, FusedAdam
         # fp16 storage (the DIP default, see models/DIP/skip.py) needs a loss scale so that activation
         # gradients (~1e-5 at the MSE) stay out of fp16's subnormal range; Adam un-scales on the fly.
@@ -211,8 +211,13 @@ class DipRunner:
         self.net_input = net_input
         self.lr_image = lr_image
         self.sigma = reg_noise_std
-        self.opt = FusedAdam(list(net.parameters()), lr=learning_rate, grad_scale=1.0 / self.loss_scale,
-                             max_grad_norm=max_grad_norm)            # get_params('net') + utils/DIP.py:34
+        params = list(net.parameters())                          # get_params('net')
+        if learn_downsampler:
+            # blind super-resolution: the downsampler's weight and bias join the same Adam (and its loss scale / clipping)
+            downsampler.set_learnable(True)
+            params = params + list(downsampler.parameters())
+        self.opt = FusedAdam(params, lr=learning_rate, grad_scale=1.0 / self.loss_scale,
+                             max_grad_norm=max_grad_norm)            # utils/DIP.py:34
 
     def step(self, noise=None):
         """optimizer.zero_grad(); closure(); optimizer.step()  (utils/DIP.py:35-38, DIP.py:47-68)."""

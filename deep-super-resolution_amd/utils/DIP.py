@@ -89,13 +89,16 @@ def get_params(opt_over, net, net_input, downsampler=None):
     """Tensors to optimise over for a comma-separated ``opt_over`` of 'net', 'down', 'input' (utils/DIP.py:44-68).
 
     Bug-compatible with the reference on one point: 'down' REPLACES whatever was collected before it instead of
-    extending it (utils/DIP.py:61 assigns), so "net,down" yields the downsampler's parameters only."""
+    extending it (utils/DIP.py:61 assigns), so "net,down" yields the downsampler's parameters only.  'down' also
+    switches a utils.downsampler.Downsampler to its dense, differentiable forward (``set_learnable(True)``)."""
     params = []
     for what in opt_over.split(','):
         if what == 'net':
             params = params + list(net.parameters())
         elif what == 'down':
             assert downsampler is not None
+            if hasattr(downsampler, 'set_learnable'):
+                downsampler.set_learnable(True)       # forward through the dense op: these parameters get gradients
             params = list(downsampler.parameters())
         elif what == 'input':
             net_input.requires_grad = True

@@ -2,7 +2,8 @@
 
 Same constructor arguments, assertions and attributes (``kernel`` float64 numpy, ``downsampler_``
 nn.Conv2d holding the dense-diagonal weight so state_dicts/``.parameters()`` match, ``padding``,
-``preserve_size``, ``x``).  The reference's Conv2d(n, n, k, stride=f) has only its n diagonal filters
+``preserve_size``, ``x``), plus the opt-in ``learnable`` / ``set_learnable()``: the dense layer with gradients for
+weight and bias (csrc/downsample_dense.hip), which is what ``get_params('down')`` needs.  The reference's Conv2d(n, n, k, stride=f) has only its n diagonal filters
 non-zero and zero bias (:44-50), i.e. it is a depthwise correlation with one k x k kernel -- that is what
 the device kernel computes (from ``downsampler_.weight[0, 0]``, the float32 copy the reference makes at :48-50).
 get_kernel (:73-135) is restated vectorised in numpy; it is host-side construction-time work.
@@ -16,7 +17,7 @@ from .. import functional as F
 
 class Downsampler(nn.Module):
     def __init__(self, n_planes, factor, kernel_type, phase=0, kernel_width=None, support=None, sigma=None,
-                 preserve_size=False):
+                 preserve_size=False, *, learnable=False):
         super(Downsampler, self).__init__()
 
         assert phase in [0, 0.5], 'phase should be 0 or 0.5'
@@ -57,11 +58,40 @@ class Downsampler(nn.Module):
 
         self.preserve_size = preserve_size
         self.factor = factor
+        # dense: forward runs the full Conv2d (every filter and the bias, with gradients for both) instead of the
+        # depthwise kernel below.  Set by learnable=True / set_learnable(), and after load_state_dict() of a checkpoint
+        # whose weight or bias is no longer the constructor's diagonal kernel / zero bias.
+        self.dense = bool(learnable)
+        self.register_load_state_dict_post_hook(_after_load)
+
+    def set_learnable(self, flag=True):
+        """Route forward through the dense op (functional.DownsampleDense) so that ``downsampler_.weight`` and
+        ``downsampler_.bias`` are what is computed with and receive gradients; False returns to the fixed kernel."""
+        self.dense = bool(flag)
+        return self
+
+    def is_pristine(self):
+        """True while weight and bias are the constructor's values (one host comparison; not for a hot loop)."""
+        w = self.downsampler_.weight.detach().cpu()
+        ref = torch.zeros_like(w)
+        kernel_torch = torch.from_numpy(self.kernel).to(w.dtype)
+        for i in range(w.shape[0]):
+            ref[i, i] = kernel_torch
+        return bool(torch.equal(w, ref)) and not bool(self.downsampler_.bias.detach().cpu().any())
 
     def forward(self, input):
         self.x = input          # the reference caches the (padded) input here (:70); the pad is fused on device
+        if self.dense:
+            return F.DownsampleDense.apply(input, self.downsampler_.weight, self.downsampler_.bias, self.factor,
+                                           self.pad if self.preserve_size else 0)
         kern = self.downsampler_.weight[0, 0].detach().contiguous()
         return F.Downsample.apply(input, kern, self.factor, self.pad if self.preserve_size else 0)
+
+
+def _after_load(module, incompatible_keys):
+    # a learned checkpoint (this package's or the reference's) must not be evaluated with the fixed depthwise kernel
+    if not module.is_pristine():
+        module.dense = True
 
 
 def get_kernel(factor, kernel_type, phase, kernel_width, support=None, sigma=None):

@@ -373,6 +373,25 @@ int dsr_downsample_fwd(const float* x, const float* kern, float* y, int NC, int 
 int dsr_downsample_bwd(const float* dy, const float* kern, float* dx, int NC, int H, int W, int k, int f, int p,
                        dsr_stream_t s);
 
+/* Dense (learnable) Downsampler: ReplicationPad2d(p) + Conv2d(C, C, k, stride=f) + bias, every filter live -- what
+ * get_params('down') optimises (utils/DIP.py:59-61).  fp32 NCHW, contiguous; w is OIHW [C][C][k][k]; 1 <= C <= 4
+ * (more: DSR_E_UNSUPPORTED); OH = (H + 2p - k) / f + 1 (an empty output is DSR_E_ARG).  fp32 FMA throughout.
+ *   fwd  : y[n][co][oy][ox] = b[co] + sum_ci sum_ij w[co][ci][i][j] x[n][ci][clamp(oy f + i - p)][clamp(ox f + j - p)];
+ *          b may be NULL (no bias)
+ *   dgrad: dx = the adjoint with respect to x, the replicate pad's included (border pixels collect what the pad copied
+ *          from them); dx is written, not accumulated
+ *   wgrad: dw[co][ci][i][j] = sum_{n,oy,ox} dy[n][co][oy][ox] x[n][ci][clamp(..)][clamp(..)], db[co] = sum dy (db may be
+ *          NULL); both written, not accumulated.  Deterministic: per-slab partials in `workspace`
+ *          (dsr_downsample_dense_wgrad_workspace bytes, a pure host query; too small: DSR_E_WORKSPACE) summed in index
+ *          order by a second launch, no float atomics -- two calls on the same inputs give the same bits. */
+int dsr_downsample_dense_fwd(const float* x, const float* w, const float* b, float* y, int N, int C, int H, int W, int k,
+                             int f, int p, dsr_stream_t s);
+int dsr_downsample_dense_dgrad(const float* dy, const float* w, float* dx, int N, int C, int H, int W, int k, int f, int p,
+                               dsr_stream_t s);
+size_t dsr_downsample_dense_wgrad_workspace(int N, int C, int H, int W, int k, int f, int p);
+int dsr_downsample_dense_wgrad(const float* x, const float* dy, float* dw, float* db, void* workspace,
+                               size_t workspace_bytes, int N, int C, int H, int W, int k, int f, int p, dsr_stream_t s);
+
 /* SSIM as the reference's scripts measure it (torchmetrics StructuralSimilarityIndexMeasure at train_GAN.py:31,111,
  * eval_GAN.py:31,48): Gaussian 11x11 sigma 1.5 window, K1 0.01, K2 0.03, per plane (planes = N*C fp32 H x W images),
  * window positions inside the image.  Writes dsr_ssim_blocks(planes, H, W) partial sums; their total divided by
