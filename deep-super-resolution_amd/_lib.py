@@ -157,6 +157,14 @@ SIGNATURES = {
     "dsr_ssim_img_blocks": (_I, [_I, _I, _I, _I]),
     "dsr_ssim_img_f32": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _F, _I, _P]),
     "dsr_ssim_bwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P]),
+    "dsr_msssim_min_size": (_I, [_I]),
+    "dsr_msssim_pyramid_floats": (_Z, [_I, _I, _I, _I, _I]),
+    "dsr_ssim_cs_img_blocks": (_I, [_I, _I, _I, _I]),
+    "dsr_ssim_cs_img_f32": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P]),
+    "dsr_avgpool2_pair_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "dsr_msssim_combine": (_I, [_P, _I, _I, C.POINTER(_F), _I, _P, _P, _P, _F, _P, _P]),
+    "dsr_msssim_bwd_blocks": (_I, [_I, _I, _I, _I]),
+    "dsr_msssim_bwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dsr_psnr_blocks": (_I, [_I, _I]),
     "dsr_psnr_stats_f32": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "dsr_psnr_finalize": (_I, [_P, _P, _I, _I, _I, _F, _F, _P, _P, _F, _P, _P]),
@@ -180,7 +188,8 @@ _NO_LAUNCH = ("dsr_last_error", "dsr_abi_version", "dsr_conv_dgrad_ps_supported"
               "dsr_conv_packed_elems", "dsr_conv_dgrad_workspace", "dsr_conv_wgrad_workspace", "dsr_pw_scratch_rows",
               "dsr_pw_reduce_blocks", "dsr_linear_fwd_workspace", "dsr_ssim_blocks", "dsr_lpips_tap_sizes", "dsr_lpips_distance_blocks",
               "dsr_ssim_img_blocks", "dsr_psnr_blocks", "dsr_lbfgs_workspace", "dsr_lbfgs_vector_floats", "dsr_clip_sumsq_partials",
-              "dsr_linear_factor_gram_workspace", "dsr_linear_factor_gram_dots", "dsr_downsample_dense_wgrad_workspace")
+              "dsr_linear_factor_gram_workspace", "dsr_linear_factor_gram_dots", "dsr_downsample_dense_wgrad_workspace",
+              "dsr_msssim_min_size", "dsr_msssim_pyramid_floats", "dsr_ssim_cs_img_blocks", "dsr_msssim_bwd_blocks")
 
 
 class _Lib:

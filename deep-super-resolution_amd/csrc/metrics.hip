@@ -103,6 +103,12 @@ extern "C" int dsr_ssim_f32(const float* img1, const float* img2, int planes, in
 // (metrics.py).  Same window and unclamped formula as ssim_kernel; c1 = (k1 range)^2, c2 = (k2 range)^2 are arguments.
 // Reductions are deterministic: one partial per block (plain stores), folded in a fixed order by a one-block finalise launch.
 
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 static SsimWindow ssim_gauss_window() {
   SsimWindow win;
   double s = 0.0, g[SSIM_K];
@@ -124,17 +130,33 @@ __device__ __forceinline__ float ssim_of_moments(float ma, float mb, float saa, 
   return ((2.f * mab + c1) * (2.f * cab + c2)) / ((maa + mbb + c1) * (va + vb + c2));
 }
 
+// The same position as its two factors: the contrast-structure term cs = (2 cab + c2) / (va + vb + c2) and
+// ssim = cs * (2 mab + c1) / (maa + mbb + c1) (torchmetrics' return_contrast_sensitivity pair, which multi-scale SSIM
+// folds per scale).  Same rules as above: no contraction, products formed once, so swapped images give the same bits
+// and identical images give exactly cs = 1 and ssim = 1 * 1.
+__device__ __forceinline__ void ssim_cs_of_moments(float ma, float mb, float saa, float sbb, float sab, float c1, float c2,
+                                                   float& ssim, float& cs) {
+#pragma clang fp contract(off)
+  const float maa = ma * ma, mbb = mb * mb, mab = ma * mb;
+  const float va = saa - maa, vb = sbb - mbb, cab = sab - mab;
+  cs = (2.f * cab + c2) / (va + vb + c2);
+  ssim = cs * ((2.f * mab + c1) / (maa + mbb + c1));
+}
+
 // ---- forward: a block owns SF_TH x SF_TW window positions of one plane; separable passes over a (SF_TH+10) x (SF_TW+10)
-// tile of both images in LDS (11 row taps x 5 moments per staged row, then 11 column taps x 5 moments per position)
+// tile of both images in LDS (11 row taps x 5 moments per staged row, then 11 column taps x 5 moments per position).
+// CS = false: one partial per block, the SSIM sum (partial[block]).  CS = true: two, the SSIM sum and the sum of the
+// contrast-structure term (partial[2 block], partial[2 block + 1]).
 #define SF_TW 64
 #define SF_TH 16
+template <bool CS>
 __global__ __launch_bounds__(256) void ssim_img_kernel(const float* __restrict__ a, const float* __restrict__ b, int H, int W,
                                                        int tiles_x, int tiles_y, float c1, float c2, SsimWindow win,
                                                        float* __restrict__ partial) {
   constexpr int SR = SF_TH + SSIM_K - 1, SC = SF_TW + SSIM_K - 1;
   __shared__ float sa[SR][SC + 1], sb[SR][SC + 1];
   __shared__ float hm[5][SR][SF_TW + 1];
-  __shared__ float red[4];
+  __shared__ float red[CS ? 8 : 4];
   const int plane = blockIdx.x / (tiles_x * tiles_y);
   const int t = blockIdx.x % (tiles_x * tiles_y);
   const int y0 = (t / tiles_x) * SF_TH, x0 = (t % tiles_x) * SF_TW;
@@ -170,7 +192,7 @@ __global__ __launch_bounds__(256) void ssim_img_kernel(const float* __restrict__
   __syncthreads();
   const int OH = H - SSIM_K + 1, OW = W - SSIM_K + 1;
   const int c = threadIdx.x % SF_TW;
-  float v = 0.f;
+  float v = 0.f, vcs = 0.f;
   for (int r = threadIdx.x / SF_TW; r < SF_TH; r += 256 / SF_TW) {
     if (y0 + r < OH && x0 + c < OW) {
       float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
@@ -180,13 +202,31 @@ __global__ __launch_bounds__(256) void ssim_img_kernel(const float* __restrict__
 #pragma unroll
         for (int k = 0; k < 5; ++k) m[k] = fmaf(g, hm[k][r + dy][c], m[k]);
       }
-      v += ssim_of_moments(m[0], m[1], m[2], m[3], m[4], c1, c2);
+      if constexpr (CS) {
+        float s, q;
+        ssim_cs_of_moments(m[0], m[1], m[2], m[3], m[4], c1, c2, s, q);
+        v += s;
+        vcs += q;
+      } else {
+        v += ssim_of_moments(m[0], m[1], m[2], m[3], m[4], c1, c2);
+      }
     }
   }
   v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  if constexpr (CS) vcs = wave_sum(vcs);
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = v;
+    if constexpr (CS) red[4 + (threadIdx.x >> 6)] = vcs;
+  }
   __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  if (threadIdx.x == 0) {
+    if constexpr (CS) {
+      partial[2 * (size_t)blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+      partial[2 * (size_t)blockIdx.x + 1] = (red[4] + red[5]) + (red[6] + red[7]);
+    } else {
+      partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    }
+  }
 }
 
 // per_image[n] = inv_count * (the nblk partials of image n, folded in a fixed order); total (+)= total_scale * sum_n per_image
@@ -240,7 +280,7 @@ extern "C" int dsr_ssim_img_f32(const float* img1, const float* img2, int N, int
   DSR_REQUIRE(blocks > 0, "ssim_img: too many window tiles");
   const int OH = H - SSIM_K + 1, OW = W - SSIM_K + 1;
   const int tiles_y = (OH + SF_TH - 1) / SF_TH, tiles_x = (OW + SF_TW - 1) / SF_TW;
-  hipLaunchKernelGGL(ssim_img_kernel, dim3(blocks), dim3(256), 0, st, img1, img2, H, W, tiles_x, tiles_y, c1, c2,
+  hipLaunchKernelGGL(ssim_img_kernel<false>, dim3(blocks), dim3(256), 0, st, img1, img2, H, W, tiles_x, tiles_y, c1, c2,
                      ssim_gauss_window(), partial);
   const int rc = dsr_launch_status("dsr_ssim_img_f32");
   if (rc) return rc;
@@ -259,6 +299,14 @@ extern "C" int dsr_ssim_img_f32(const float* img1, const float* img2, int N, int
 //   4. transposed row taps, (T+10) x T;                        5. transposed column taps per pixel, and
 //   da = k (W'cmu_a + 2 a W'cE2 + b W'cEab),  db = k (W'cmu_b + 2 b W'cE2 + a W'cEab),  k = g[n] / (C OH OW).
 // Buffers of passes 1 / 3 and 2 / 4 share LDS (each is dead before its partner is written): 73.6 KB, two blocks per CU.
+//
+// MS = true is one scale of the multi-scale backward (dsr_msssim_bwd_f32).  Each image carries two upstream weights,
+// k_sim = g[n] w_sim[n] / (C OH OW) for its SSIM mean and k_cs = g[n] w_cs[n] / (C OH OW) for its contrast-structure mean
+// (a null weight array is 0).  With l = A1 / B1, cs = A2 / B2, S = l cs, the maps of pass 3 are those of k_sim S + k_cs cs
+//   = u d cs + t d l,   u = k_sim l + k_cs,  t = k_sim cs:
+//   d/dmu_a = 2 u (mu_a cs - mu_b) / B2 + 2 t (mu_b - l mu_a) / B1,   d/dE[a^2] = -u cs / B2,   d/dE[ab] = 2 u / B2,
+// so pass 5 multiplies by nothing more; its epilogue adds the gradient that arrived at the next coarser scale spread back
+// through the 2x2 mean pool, 0.25 coarse[y/2][x/2] for pixels inside the pooled extent (a dropped odd row / column gets none).
 #define SB_T 32
 #define SB_SR (SB_T + 2 * (SSIM_K - 1))        // staged rows / columns
 #define SB_PR (SB_T + SSIM_K - 1)              // window positions per row / column
@@ -267,10 +315,13 @@ extern "C" int dsr_ssim_img_f32(const float* img1, const float* img2, int N, int
 static_assert(SB_R1 >= 2 * SB_SR * (SB_SR + 1), "ssim_bwd LDS layout");
 static_assert(SB_R2 >= 4 * SB_PR * (SB_T + 1), "ssim_bwd LDS layout");
 
+template <bool MS>
 __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b, int C, int H,
                                                        int W, int tiles_x, int tiles_y, float c1, float c2, SsimWindow win,
                                                        const float* __restrict__ g, float inv_count, float* __restrict__ ga,
-                                                       float* __restrict__ gb) {
+                                                       float* __restrict__ gb, const float* __restrict__ w_sim,
+                                                       const float* __restrict__ w_cs, const float* __restrict__ coarse_a,
+                                                       const float* __restrict__ coarse_b) {
   __shared__ float r1[SB_R1];
   __shared__ float r2[SB_R2];
   // r1 as the stage [2][SB_SR][SB_SR+1], then as the coefficient maps [4][SB_PR][SB_PR+1]
@@ -288,6 +339,7 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__
   const float* pa = a + (size_t)plane * H * W;
   const float* pb = b + (size_t)plane * H * W;
   const float k = g[plane / C] * inv_count;
+  const float k_sim = (MS && w_sim) ? k * w_sim[plane / C] : 0.f, k_cs = (MS && w_cs) ? k * w_cs[plane / C] : 0.f;
   // 1. stage pixel (y0 - 10 + sy, x0 - 10 + sx); zero outside the image (those only feed positions that do not exist)
   for (int i = threadIdx.x; i < SB_SR * SB_SR; i += 256) {
     const int sy = i / SB_SR, sx = i % SB_SR;
@@ -336,13 +388,23 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__
       const float maa = ma * ma, mbb = mb * mb, mab = ma * mb;
       const float A1 = 2.f * mab + c1, A2 = 2.f * (m[4] - mab) + c2;
       const float B1 = maa + mbb + c1, B2 = (m[2] - maa) + (m[3] - mbb) + c2;
-      const float inv = 1.f / (B1 * B2);
-      const float S = A1 * A2 * inv;
-      const float d = 2.f * (A2 - A1) * inv, e = 2.f * S * (1.f / B1 - 1.f / B2);
-      cma = mb * d - ma * e;                      // dS/dmu_a
-      cmb = ma * d - mb * e;                      // dS/dmu_b
-      ce2 = -S / B2;                              // dS/dE[a^2] = dS/dE[b^2]
-      ceab = 2.f * A1 * inv;                      // dS/dE[ab]
+      if constexpr (MS) {
+        const float i1 = 1.f / B1, i2 = 1.f / B2;
+        const float l = A1 * i1, cs = A2 * i2;
+        const float u2 = 2.f * (k_sim * l + k_cs) * i2, t2 = 2.f * (k_sim * cs) * i1;
+        cma = u2 * (ma * cs - mb) + t2 * (mb - l * ma);
+        cmb = u2 * (mb * cs - ma) + t2 * (ma - l * mb);
+        ce2 = -0.5f * u2 * cs;
+        ceab = u2;
+      } else {
+        const float inv = 1.f / (B1 * B2);
+        const float S = A1 * A2 * inv;
+        const float d = 2.f * (A2 - A1) * inv, e = 2.f * S * (1.f / B1 - 1.f / B2);
+        cma = mb * d - ma * e;                      // dS/dmu_a
+        cmb = ma * d - mb * e;                      // dS/dmu_b
+        ce2 = -S / B2;                              // dS/dE[a^2] = dS/dE[b^2]
+        ceab = 2.f * A1 * inv;                      // dS/dE[ab]
+      }
     }
     CF(0, py, px) = want_a ? cma : cmb;
     CF(1, py, px) = ce2;
@@ -375,8 +437,17 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__
     }
     const size_t o = (size_t)plane * H * W + (size_t)y * W + x;
     const float va = pa[(size_t)y * W + x], vb = pb[(size_t)y * W + x];
-    if (want_a) ga[o] = k * (G[0] + 2.f * va * G[1] + vb * G[2]);
-    if (want_b) gb[o] = k * ((want_a ? G[3] : G[0]) + 2.f * vb * G[1] + va * G[2]);
+    if constexpr (MS) {
+      const int Hc = H >> 1, Wc = W >> 1;
+      const bool pooled = (y >> 1) < Hc && (x >> 1) < Wc;
+      const size_t oc = ((size_t)plane * Hc + (y >> 1)) * Wc + (x >> 1);
+      if (want_a) ga[o] = (G[0] + 2.f * va * G[1] + vb * G[2]) + ((coarse_a && pooled) ? 0.25f * coarse_a[oc] : 0.f);
+      if (want_b)
+        gb[o] = ((want_a ? G[3] : G[0]) + 2.f * vb * G[1] + va * G[2]) + ((coarse_b && pooled) ? 0.25f * coarse_b[oc] : 0.f);
+    } else {
+      if (want_a) ga[o] = k * (G[0] + 2.f * va * G[1] + vb * G[2]);
+      if (want_b) gb[o] = k * ((want_a ? G[3] : G[0]) + 2.f * vb * G[1] + va * G[2]);
+    }
   }
 #undef STG
 #undef CF
@@ -396,9 +467,217 @@ extern "C" int dsr_ssim_bwd_f32(const float* img1, const float* img2, int N, int
   DSR_REQUIRE(blocks < (1ll << 31), "ssim_bwd: too many tiles");
   const int OH = H - SSIM_K + 1, OW = W - SSIM_K + 1;
   const float inv_count = (float)(1.0 / ((double)C * OH * OW));
-  hipLaunchKernelGGL(ssim_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, img1, img2, C, H, W, tiles_x, tiles_y, c1, c2,
-                     ssim_gauss_window(), g, inv_count, grad1, grad2);
+  hipLaunchKernelGGL(ssim_bwd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, img1, img2, C, H, W, tiles_x, tiles_y,
+                     c1, c2, ssim_gauss_window(), g, inv_count, grad1, grad2, (const float*)nullptr, (const float*)nullptr,
+                     (const float*)nullptr, (const float*)nullptr);
   return dsr_launch_status("dsr_ssim_bwd_f32");
+}
+
+// ================================================================================ metrics.MultiScaleStructuralSimilarityIndexMeasure
+// Multi-scale SSIM (Wang, Simoncelli, Bovik 2003) as torchmetrics' MultiScaleStructuralSimilarityIndexMeasure states it: per
+// scale the per-image means of SSIM and of its contrast-structure term, both images halved by a 2x2 mean between scales, and
+// out[n] = prod_s v_s[n]^betas[s] over v = (cs_0 .. cs_{L-2}, ssim_{L-1}).  torchmetrics is absent here: PARITY UNPINNED.
+
+// sim[n], cs[n] (either nullable) = inv_count * (the nblk partial pairs of image n, folded in a fixed order)
+__global__ __launch_bounds__(1024) void ssim_cs_finalize_kernel(const float* __restrict__ partial, int N, int nblk,
+                                                                float inv_count, float* __restrict__ sim,
+                                                                float* __restrict__ cs) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int n = wave; n < N; n += 16) {
+    float s = 0.f, q = 0.f;
+    for (int k = lane; k < nblk; k += 64) {
+      const float2 p = reinterpret_cast<const float2*>(partial)[(size_t)n * nblk + k];
+      s += p.x;
+      q += p.y;
+    }
+    s = wave_sum(s) * inv_count;
+    q = wave_sum(q) * inv_count;
+    if (lane == 0) {
+      if (sim) sim[n] = s;
+      if (cs) cs[n] = q;
+    }
+  }
+}
+
+extern "C" int dsr_ssim_cs_img_blocks(int N, int C, int H, int W) { return dsr_ssim_img_blocks(N, C, H, W); }
+
+extern "C" int dsr_ssim_cs_img_f32(const float* img1, const float* img2, int N, int C, int H, int W, float c1, float c2,
+                                   float* partial, float* sim, float* cs, dsr_stream_t st) {
+  DSR_REQUIRE(img1 && img2 && partial, "ssim_cs_img: null pointer");
+  DSR_REQUIRE(sim || cs, "ssim_cs_img: neither the SSIM nor the contrast-structure means are asked for");
+  DSR_REQUIRE(((uintptr_t)partial & 7) == 0, "ssim_cs_img: partial must be 8-byte aligned");
+  DSR_REQUIRE(N >= 1 && C >= 1, "ssim_cs_img: %d images of %d planes", N, C);
+  DSR_REQUIRE(H >= SSIM_K && W >= SSIM_K, "ssim_cs_img: image %dx%d smaller than the 11x11 window", H, W);
+  DSR_REQUIRE(ssim_consts_ok(c1, c2), "ssim_cs_img: c1 and c2 must be positive and finite (data_range > 0)");
+  const int blocks = dsr_ssim_img_blocks(N, C, H, W);
+  DSR_REQUIRE(blocks > 0, "ssim_cs_img: too many window tiles");
+  const int OH = H - SSIM_K + 1, OW = W - SSIM_K + 1;
+  const int tiles_y = (OH + SF_TH - 1) / SF_TH, tiles_x = (OW + SF_TW - 1) / SF_TW;
+  hipLaunchKernelGGL(ssim_img_kernel<true>, dim3(blocks), dim3(256), 0, st, img1, img2, H, W, tiles_x, tiles_y, c1, c2,
+                     ssim_gauss_window(), partial);
+  const int rc = dsr_launch_status("dsr_ssim_cs_img_f32");
+  if (rc) return rc;
+  const float inv_count = (float)(1.0 / ((double)C * OH * OW));
+  hipLaunchKernelGGL(ssim_cs_finalize_kernel, dim3(1), dim3(1024), 0, st, partial, N, blocks / N, inv_count, sim, cs);
+  return dsr_launch_status("dsr_ssim_cs_img_f32");
+}
+
+// ---- both images to half size in one launch: out[y][x] = mean of in[2y .. 2y+1][2x .. 2x+1], F.avg_pool2d(x, 2) (an odd last
+// row / column is dropped).  Bandwidth-bound.  V4 (W % 4 == 0, 16-byte aligned planes): a thread loads one float4 of two
+// input rows and stores two outputs as a float2; otherwise one output per thread from four scalar loads.  blockIdx.y picks
+// the image.
+template <bool V4>
+__global__ __launch_bounds__(256) void avgpool2_pair_kernel(const float* __restrict__ in1, const float* __restrict__ in2,
+                                                            float* __restrict__ out1, float* __restrict__ out2, int H, int W,
+                                                            long long work) {
+  const float* __restrict__ in = blockIdx.y ? in2 : in1;
+  float* __restrict__ out = blockIdx.y ? out2 : out1;
+  const int Ho = H >> 1, Wo = W >> 1;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= work) return;
+  if constexpr (V4) {
+    const int W4 = W >> 2;
+    const int x4 = (int)(i % W4);
+    const long long r = i / W4;                               // plane * Ho + yo
+    const int yo = (int)(r % Ho);
+    const long long plane = r / Ho;
+    const float* row = in + ((size_t)plane * H + 2 * (size_t)yo) * W + 4 * (size_t)x4;
+    const float4 t = *reinterpret_cast<const float4*>(row), u = *reinterpret_cast<const float4*>(row + W);
+    float2 o;
+    o.x = 0.25f * ((t.x + t.y) + (u.x + u.y));
+    o.y = 0.25f * ((t.z + t.w) + (u.z + u.w));
+    *reinterpret_cast<float2*>(out + (size_t)r * Wo + 2 * (size_t)x4) = o;
+  } else {
+    const int xo = (int)(i % Wo);
+    const long long r = i / Wo;
+    const int yo = (int)(r % Ho);
+    const long long plane = r / Ho;
+    const float* row = in + ((size_t)plane * H + 2 * (size_t)yo) * W + 2 * (size_t)xo;
+    out[(size_t)r * Wo + xo] = 0.25f * ((row[0] + row[1]) + (row[W] + row[W + 1]));
+  }
+}
+
+extern "C" int dsr_avgpool2_pair_f32(const float* in1, const float* in2, float* out1, float* out2, int planes, int H, int W,
+                                     dsr_stream_t st) {
+  DSR_REQUIRE(in1 && in2 && out1 && out2, "avgpool2_pair: null pointer");
+  DSR_REQUIRE(planes >= 1 && H >= 2 && W >= 2, "avgpool2_pair: %d planes of %dx%d", planes, H, W);
+  const int Ho = H / 2, Wo = W / 2;
+  const bool v4 = W % 4 == 0 && (((uintptr_t)in1 | (uintptr_t)in2) & 15) == 0 && (((uintptr_t)out1 | (uintptr_t)out2) & 7) == 0;
+  const long long work = (long long)planes * Ho * (v4 ? W / 4 : Wo);
+  const long long blocks = (work + 255) / 256;
+  DSR_REQUIRE((long long)planes * H * W < (1ll << 40) && blocks < (1ll << 31), "avgpool2_pair: too many elements");
+  if (v4)
+    hipLaunchKernelGGL(avgpool2_pair_kernel<true>, dim3((unsigned)blocks, 2), dim3(256), 0, st, in1, in2, out1, out2, H, W, work);
+  else
+    hipLaunchKernelGGL(avgpool2_pair_kernel<false>, dim3((unsigned)blocks, 2), dim3(256), 0, st, in1, in2, out1, out2, H, W, work);
+  return dsr_launch_status("dsr_avgpool2_pair_f32");
+}
+
+// ---- the pyramid's sizes (host queries)
+extern "C" int dsr_msssim_min_size(int L) { return (L >= 1 && L <= DSR_MSSSIM_MAX_SCALES) ? SSIM_K << (L - 1) : 0; }
+
+static bool msssim_shape_ok(int N, int C, int H, int W, int L) {
+  const int m = dsr_msssim_min_size(L);
+  return N >= 1 && C >= 1 && m > 0 && H >= m && W >= m;
+}
+
+// floats of one image's pooled levels 1 .. L-1, each [N][C][H >> s][W >> s], level 1 first (0: bad sizes, or L == 1)
+extern "C" size_t dsr_msssim_pyramid_floats(int N, int C, int H, int W, int L) {
+  if (!msssim_shape_ok(N, C, H, W, L)) return 0;
+  size_t t = 0;
+  for (int s = 1; s < L; ++s) t += (size_t)N * C * (H >> s) * (W >> s);
+  return t;
+}
+
+// ---- combine: raw[s][n] = the cs mean of scale s < L-1, the SSIM mean of scale L-1.  One block; thread n strides the images.
+//   v = raw, max(raw, 0) (relu) or (raw + 1) / 2 (simple);  out[n] = prod_s v_s^betas[s] (double, s ascending);
+//   factors[s][n] = d out[n] / d raw[s][n] = betas[s] out / v_s (x 1/2 under simple); under relu 0 where v_s <= 0 -- the
+//   image's out is 0 there, and so are all its factors (torch autograd has 0 * inf = NaN at that point).
+struct MsssimBetas {
+  float b[DSR_MSSSIM_MAX_SCALES];
+};
+
+__global__ __launch_bounds__(256) void msssim_combine_kernel(const float* __restrict__ raw, int N, int L, MsssimBetas betas,
+                                                             int normalize, float* __restrict__ vals,
+                                                             float* __restrict__ per_image, float* __restrict__ total,
+                                                             float total_scale, float* __restrict__ factors) {
+  __shared__ double wsum[4];
+  double mine = 0.0;
+  for (int n = threadIdx.x; n < N; n += 256) {
+    double v[DSR_MSSSIM_MAX_SCALES];
+    double out = 1.0;
+#pragma unroll
+    for (int s = 0; s < DSR_MSSSIM_MAX_SCALES; ++s) {
+      if (s < L) {
+        const float r = raw[(size_t)s * N + n];
+        const float x = normalize == 1 ? fmaxf(r, 0.f) : normalize == 2 ? (r + 1.f) * 0.5f : r;
+        if (vals) vals[(size_t)s * N + n] = x;
+        v[s] = (double)x;
+        out *= pow(v[s], (double)betas.b[s]);
+      }
+    }
+    if (per_image) per_image[n] = (float)out;
+    if (factors) {
+#pragma unroll
+      for (int s = 0; s < DSR_MSSSIM_MAX_SCALES; ++s) {
+        if (s < L) {
+          double f = (double)betas.b[s] * out / v[s];
+          if (normalize == 1 && !(v[s] > 0.0)) f = 0.0;
+          if (normalize == 2) f *= 0.5;
+          factors[(size_t)s * N + n] = (float)f;
+        }
+      }
+    }
+    mine += (double)(float)out;
+  }
+  mine = wave_sum_f64(mine);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0 && total) total[0] = (float)((double)total_scale * ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])));
+}
+
+extern "C" int dsr_msssim_combine(const float* raw, int N, int L, const float* betas, int normalize, float* vals,
+                                  float* per_image, float* total, float total_scale, float* factors, dsr_stream_t st) {
+  DSR_REQUIRE(raw && betas, "msssim_combine: null pointer");
+  DSR_REQUIRE(per_image || total, "msssim_combine: neither per-image values nor a total are asked for");
+  DSR_REQUIRE(N >= 1, "msssim_combine: %d images", N);
+  DSR_REQUIRE(L >= 1 && L <= DSR_MSSSIM_MAX_SCALES, "msssim_combine: %d scales (1 .. %d)", L, DSR_MSSSIM_MAX_SCALES);
+  DSR_REQUIRE(normalize >= 0 && normalize <= 2, "msssim_combine: normalize %d (0 none, 1 relu, 2 simple)", normalize);
+  MsssimBetas bt;
+  for (int s = 0; s < DSR_MSSSIM_MAX_SCALES; ++s) {
+    bt.b[s] = s < L ? betas[s] : 1.f;
+    DSR_REQUIRE(bt.b[s] > 0.f && bt.b[s] < INFINITY, "msssim_combine: betas[%d] must be positive and finite", s);
+  }
+  hipLaunchKernelGGL(msssim_combine_kernel, dim3(1), dim3(256), 0, st, raw, N, L, bt, normalize, vals, per_image, total,
+                     total_scale, factors);
+  return dsr_launch_status("dsr_msssim_combine");
+}
+
+// ---- one scale of the backward (ssim_bwd_kernel<true>, see there)
+extern "C" int dsr_msssim_bwd_f32(const float* img1, const float* img2, int N, int C, int H, int W, float c1, float c2,
+                                  const float* g, const float* w_sim, const float* w_cs, const float* coarse1,
+                                  const float* coarse2, float* grad1, float* grad2, dsr_stream_t st) {
+  DSR_REQUIRE(img1 && img2 && g, "msssim_bwd: null pointer");
+  DSR_REQUIRE(w_sim || w_cs, "msssim_bwd: neither the SSIM nor the contrast-structure weights are given");
+  DSR_REQUIRE(grad1 || grad2, "msssim_bwd: neither image's gradient is asked for");
+  DSR_REQUIRE((!coarse1 || grad1) && (!coarse2 || grad2), "msssim_bwd: a coarse gradient without its image's gradient");
+  DSR_REQUIRE(N >= 1 && C >= 1, "msssim_bwd: %d images of %d planes", N, C);
+  DSR_REQUIRE(H >= SSIM_K && W >= SSIM_K, "msssim_bwd: image %dx%d smaller than the 11x11 window", H, W);
+  DSR_REQUIRE(ssim_consts_ok(c1, c2), "msssim_bwd: c1 and c2 must be positive and finite (data_range > 0)");
+  const int tiles_y = (H + SB_T - 1) / SB_T, tiles_x = (W + SB_T - 1) / SB_T;
+  const long long blocks = (long long)N * C * tiles_y * tiles_x;
+  DSR_REQUIRE(blocks < (1ll << 31), "msssim_bwd: too many tiles");
+  const int OH = H - SSIM_K + 1, OW = W - SSIM_K + 1;
+  const float inv_count = (float)(1.0 / ((double)C * OH * OW));
+  hipLaunchKernelGGL(ssim_bwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, img1, img2, C, H, W, tiles_x, tiles_y,
+                     c1, c2, ssim_gauss_window(), g, inv_count, grad1, grad2, w_sim, w_cs, coarse1, coarse2);
+  return dsr_launch_status("dsr_msssim_bwd_f32");
+}
+
+extern "C" int dsr_msssim_bwd_blocks(int N, int C, int H, int W) {
+  if (N < 1 || C < 1 || H < SSIM_K || W < SSIM_K) return 0;
+  const long long b = (long long)N * C * ((H + SB_T - 1) / SB_T) * ((W + SB_T - 1) / SB_T);
+  return b < (1ll << 31) ? (int)b : 0;
 }
 
 // ================================================================================ metrics.PeakSignalNoiseRatio
@@ -474,12 +753,6 @@ __global__ __launch_bounds__(256) void psnr_stats_kernel(const float* __restrict
     partial_keys[2 * blockIdx.x] = min(min(rmin[0], rmin[1]), min(rmin[2], rmin[3]));
     partial_keys[2 * blockIdx.x + 1] = max(max(rmax[0], rmax[1]), max(rmax[2], rmax[3]));
   }
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // per_image mode (per_image != null): per[n] = log_scale (2 ln range - ln(SSE_n / E)); value = value_scale * sum_n per[n];

@@ -1007,6 +1007,23 @@ def add_losses(a, b):
     return AddScalars.apply(a, b)
 
 
+class OneMinus(torch.autograd.Function):
+    """1 - x for a scalar similarity (1 - SSIM, 1 - MS-SSIM as a loss term)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        one = torch.ones(1, dtype=torch.float32, device=x.device)
+        return axpby(x.reshape(1).float(), one, -1.0, 1.0).reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        return axpby(g.reshape(1), None, -1.0, 0.0).reshape(())
+
+
+def one_minus(x):
+    return OneMinus.apply(x)
+
+
 class ScaleLoss(torch.autograd.Function):
     """s * loss for a host constant s (the static loss scale of the fp16 DIP path)."""
 

@@ -23,6 +23,18 @@ Device work (csrc/metrics.hip, include/dsr_hip.h):
   dsr_psnr_finalize    per-image or whole-batch PSNR and the running-state update;
   dsr_metric_accumulate / dsr_metric_compute   the running state.
 SSIM is differentiable (a loss term such as ``1 - ssim(x, y)``); PSNR is not.
+
+``MultiScaleStructuralSimilarityIndexMeasure`` (alias ``MS_SSIM``) restates torchmetrics' module of that name in the same way
+-- PARITY UNPINNED too.  Per scale s = 0 .. L-1 (L = len(betas)) the current pair of images gives, over the same window positions
+as SSIM, the per-image means of ``cs = (2 cov + c2) / (var_a + var_b + c2)`` and of ``ssim = cs * (2 mu_a mu_b + c1) /
+(mu_a^2 + mu_b^2 + c1)``; ``normalize='relu'`` clamps both at 0; then both images are replaced by their 2x2 mean at stride 2
+(``F.avg_pool2d(x, 2)``: an odd last row or column is dropped).  With v = (cs_0, .., cs_{L-2}, ssim_{L-1}), halved to
+(v + 1) / 2 under ``normalize='simple'``, the per-image value is prod_s v_s ** betas[s].  Device work:
+  dsr_ssim_cs_img_f32     the two per-image means of one scale (the SSIM tile kernel with two partials per block, one fold);
+  dsr_avgpool2_pair_f32   both images to half size in one launch;
+  dsr_msssim_combine      normalised values, powers, product, the reduction's total and d out / d (per-scale mean), one launch;
+  dsr_msssim_bwd_f32      one scale of the backward: each image carries a weight for its SSIM mean and one for its cs mean, and
+                          the epilogue adds the coarser scale's gradient spread back through the pool -- L launches, coarse to fine.
 """
 import ctypes as C
 import math
@@ -193,57 +205,20 @@ class PeakSignalNoiseRatio(nn.Module):
         return out
 
 
-class StructuralSimilarityIndexMeasure(nn.Module):
-    """torchmetrics ``StructuralSimilarityIndexMeasure`` on the HIP path, for what the reference uses: the Gaussian 11x11 window
-    with sigma 1.5 and a positive ``data_range`` (the reference passes 1.0).  ``reduction``: 'elementwise_mean' (0-dim),
-    'sum' (0-dim) or 'none' / None ([N], one value per image).
+class _PerImageMetric(nn.Module):
+    """The running state, reduction and upstream gradient shared by the metrics that fold one fp32 value per image."""
 
-    ``forward`` is differentiable with respect to either input or both when grad mode is on and an input requires a gradient:
-    ``1 - ssim(x, y)`` is a loss term.  ``update`` never is."""
-
-    def __init__(self, gaussian_kernel=True, sigma=1.5, kernel_size=11, reduction="elementwise_mean", data_range=1.0,
-                 k1=0.01, k2=0.03, return_full_image=False, return_contrast_sensitivity=False):
-        super().__init__()
-        name = "StructuralSimilarityIndexMeasure"
-        if not gaussian_kernel:
-            raise NotImplementedError(f"{name}: gaussian_kernel=False (a uniform window) is not built here")
-        sig = tuple(sigma) if isinstance(sigma, (tuple, list)) else (sigma, sigma)
-        if len(sig) != 2 or any(isinstance(s, bool) or not isinstance(s, numbers.Real) or float(s) != 1.5 for s in sig):
-            raise NotImplementedError(f"{name}: sigma={sigma!r} is not built here; only 1.5 is")
-        ks = tuple(kernel_size) if isinstance(kernel_size, (tuple, list)) else (kernel_size, kernel_size)
-        if len(ks) != 2 or any(isinstance(k, bool) or k != _WIN for k in ks):
-            raise NotImplementedError(f"{name}: kernel_size={kernel_size!r} is not built here; only 11 is")
-        if return_full_image:
-            raise NotImplementedError(f"{name}: return_full_image=True is not built here")
-        if return_contrast_sensitivity:
-            raise NotImplementedError(f"{name}: return_contrast_sensitivity=True is not built here")
-        if data_range is None:
-            raise NotImplementedError(f"{name}: data_range=None (inferred from the inputs) is not built here; pass a number")
-        if isinstance(data_range, (tuple, list)):
-            raise NotImplementedError(f"{name}: data_range as a (min, max) tuple (clamping the inputs) is not built here")
-        self.data_range = _positive_float(name, "data_range", data_range)
-        self.k1 = _positive_float(name, "k1", k1)
-        self.k2 = _positive_float(name, "k2", k2)
-        self.reduction = _check_reduction(name, reduction)
-        self.c1 = (self.k1 * self.data_range) ** 2
-        self.c2 = (self.k2 * self.data_range) ** 2
-        if not (0 < float(C.c_float(self.c1).value) < math.inf and 0 < float(C.c_float(self.c2).value) < math.inf):
-            raise ValueError(f"{name}: (k * data_range)^2 leaves the fp32 range")
+    def _init_state(self, reduction):
+        self.reduction = _check_reduction(type(self).__name__, reduction)
         self._st = _RunningState()
 
-    # ---- running state
     def reset(self):
         self._st = _RunningState()
-
-    def update(self, preds, target):
-        _check_pair("StructuralSimilarityIndexMeasure", preds, target)
-        per, _ = self._run(preds, target)
-        self._accumulate(per)
 
     def compute(self):
         st = self._st
         if not st.updated:
-            raise RuntimeError("StructuralSimilarityIndexMeasure.compute() called before update()")
+            raise RuntimeError(f"{type(self).__name__}.compute() called before update()")
         if self.reduction == "none":
             return torch.cat(st.values)
         out = torch.empty(1, dtype=torch.float32, device=st.buf.device)
@@ -251,16 +226,6 @@ class StructuralSimilarityIndexMeasure(nn.Module):
         check(_lib.lib().dsr_metric_compute(_ptr(st.buf), mode, 0, 1.0, 1.0, _ptr(out), _stream()))
         return out.reshape(())
 
-    def forward(self, preds, target):
-        _check_pair("StructuralSimilarityIndexMeasure", preds, target)
-        if torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad):
-            per, tot = _SSIMFunction.apply(self, preds, target)
-        else:
-            per, tot = self._run(preds, target)
-        self._accumulate(per.detach())
-        return per if self.reduction == "none" else tot.reshape(())
-
-    # ---- the device path
     def _total_scale(self, n):
         return 1.0 / n if self.reduction == "elementwise_mean" else 1.0
 
@@ -270,23 +235,6 @@ class StructuralSimilarityIndexMeasure(nn.Module):
         if self.reduction == "none":
             st.values.append(per.clone())
         st.updated = True
-
-    def _run(self, preds, target, a=None, b=None):
-        """(per_image [N], total [1] = the reduction's scale * sum) of fp32 copies a, b of the inputs."""
-        n, c, h, w = preds.shape
-        a = _f32(preds) if a is None else a
-        b = _f32(target) if b is None else b
-        lib = _lib.lib()
-        blocks = lib.dsr_ssim_img_blocks(n, c, h, w)
-        if blocks <= 0:
-            raise RuntimeError(f"StructuralSimilarityIndexMeasure: {tuple(preds.shape)} needs too many window tiles")
-        dev = a.device
-        partial = torch.empty(blocks, dtype=torch.float32, device=dev)
-        per = torch.empty(n, dtype=torch.float32, device=dev)
-        tot = torch.empty(1, dtype=torch.float32, device=dev)
-        check(lib.dsr_ssim_img_f32(_ptr(a), _ptr(b), n, c, h, w, self.c1, self.c2, _ptr(partial), _ptr(per), _ptr(tot),
-                                   self._total_scale(n), 0, _stream()))
-        return per, tot
 
     def _upstream(self, gper, gtot, n, dev):
         """fp32 [n]: d loss / d per_image[i] = gper[i] + total_scale * gtot, formed on the device."""
@@ -305,6 +253,86 @@ class StructuralSimilarityIndexMeasure(nn.Module):
             check(lib.dsr_pw_axpby_f32(_ptr(gper), _ptr(g), 1.0, 1.0, None, _ptr(both), n, _stream()))
             return both
         return g
+
+
+def _check_window(name, gaussian_kernel, sigma, kernel_size):
+    """The one window both SSIM modules are built for: Gaussian, 11 x 11, sigma 1.5."""
+    if not gaussian_kernel:
+        raise NotImplementedError(f"{name}: gaussian_kernel=False (a uniform window) is not built here")
+    sig = tuple(sigma) if isinstance(sigma, (tuple, list)) else (sigma, sigma)
+    if len(sig) != 2 or any(isinstance(s, bool) or not isinstance(s, numbers.Real) or float(s) != 1.5 for s in sig):
+        raise NotImplementedError(f"{name}: sigma={sigma!r} is not built here; only 1.5 is")
+    ks = tuple(kernel_size) if isinstance(kernel_size, (tuple, list)) else (kernel_size, kernel_size)
+    if len(ks) != 2 or any(isinstance(k, bool) or k != _WIN for k in ks):
+        raise NotImplementedError(f"{name}: kernel_size={kernel_size!r} is not built here; only 11 is")
+
+
+def _check_constants(name, data_range, k1, k2):
+    """(data_range, k1, k2, c1, c2) with c = (k * data_range)^2 inside the fp32 range."""
+    if data_range is None:
+        raise NotImplementedError(f"{name}: data_range=None (inferred from the inputs) is not built here; pass a number")
+    if isinstance(data_range, (tuple, list)):
+        raise NotImplementedError(f"{name}: data_range as a (min, max) tuple (clamping the inputs) is not built here")
+    data_range = _positive_float(name, "data_range", data_range)
+    k1 = _positive_float(name, "k1", k1)
+    k2 = _positive_float(name, "k2", k2)
+    c1, c2 = (k1 * data_range) ** 2, (k2 * data_range) ** 2
+    if not (0 < float(C.c_float(c1).value) < math.inf and 0 < float(C.c_float(c2).value) < math.inf):
+        raise ValueError(f"{name}: (k * data_range)^2 leaves the fp32 range")
+    return data_range, k1, k2, c1, c2
+
+
+class StructuralSimilarityIndexMeasure(_PerImageMetric):
+    """torchmetrics ``StructuralSimilarityIndexMeasure`` on the HIP path, for what the reference uses: the Gaussian 11x11 window
+    with sigma 1.5 and a positive ``data_range`` (the reference passes 1.0).  ``reduction``: 'elementwise_mean' (0-dim),
+    'sum' (0-dim) or 'none' / None ([N], one value per image).
+
+    ``forward`` is differentiable with respect to either input or both when grad mode is on and an input requires a gradient:
+    ``1 - ssim(x, y)`` is a loss term.  ``update`` never is."""
+
+    def __init__(self, gaussian_kernel=True, sigma=1.5, kernel_size=11, reduction="elementwise_mean", data_range=1.0,
+                 k1=0.01, k2=0.03, return_full_image=False, return_contrast_sensitivity=False):
+        super().__init__()
+        name = "StructuralSimilarityIndexMeasure"
+        _check_window(name, gaussian_kernel, sigma, kernel_size)
+        if return_full_image:
+            raise NotImplementedError(f"{name}: return_full_image=True is not built here")
+        if return_contrast_sensitivity:
+            raise NotImplementedError(f"{name}: return_contrast_sensitivity=True is not built here")
+        self.data_range, self.k1, self.k2, self.c1, self.c2 = _check_constants(name, data_range, k1, k2)
+        self._init_state(reduction)
+
+    def update(self, preds, target):
+        _check_pair("StructuralSimilarityIndexMeasure", preds, target)
+        per, _ = self._run(preds, target)
+        self._accumulate(per)
+
+    def forward(self, preds, target):
+        _check_pair("StructuralSimilarityIndexMeasure", preds, target)
+        if torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad):
+            per, tot = _SSIMFunction.apply(self, preds, target)
+        else:
+            per, tot = self._run(preds, target)
+        self._accumulate(per.detach())
+        return per if self.reduction == "none" else tot.reshape(())
+
+    # ---- the device path
+    def _run(self, preds, target, a=None, b=None):
+        """(per_image [N], total [1] = the reduction's scale * sum) of fp32 copies a, b of the inputs."""
+        n, c, h, w = preds.shape
+        a = _f32(preds) if a is None else a
+        b = _f32(target) if b is None else b
+        lib = _lib.lib()
+        blocks = lib.dsr_ssim_img_blocks(n, c, h, w)
+        if blocks <= 0:
+            raise RuntimeError(f"StructuralSimilarityIndexMeasure: {tuple(preds.shape)} needs too many window tiles")
+        dev = a.device
+        partial = torch.empty(blocks, dtype=torch.float32, device=dev)
+        per = torch.empty(n, dtype=torch.float32, device=dev)
+        tot = torch.empty(1, dtype=torch.float32, device=dev)
+        check(lib.dsr_ssim_img_f32(_ptr(a), _ptr(b), n, c, h, w, self.c1, self.c2, _ptr(partial), _ptr(per), _ptr(tot),
+                                   self._total_scale(n), 0, _stream()))
+        return per, tot
 
 
 class _SSIMFunction(torch.autograd.Function):
@@ -335,5 +363,151 @@ class _SSIMFunction(torch.autograd.Function):
         return None, out[0], out[1]
 
 
+_DEFAULT_BETAS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+_MAX_SCALES = 8
+_NORMALIZE = {None: 0, "relu": 1, "simple": 2}
+
+
+class MultiScaleStructuralSimilarityIndexMeasure(_PerImageMetric):
+    """torchmetrics ``MultiScaleStructuralSimilarityIndexMeasure`` on the HIP path (restated, PARITY UNPINNED: see the module
+    docstring for the definition), for the Gaussian 11x11 window with sigma 1.5 and a positive ``data_range``.
+
+    ``betas``: 1 to 8 positive finite exponents, one per scale.  Inputs are [N, C, H, W] with H, W >= 11 * 2^(len(betas) - 1)
+    (176 for the default five scales, the bound torchmetrics applies).  ``normalize``: 'relu', 'simple' or None.  ``reduction``
+    as for SSIM.  ``last_scales`` holds the [L, N] normalised per-scale values of the latest call (device, fp32).
+
+    ``forward`` is differentiable like SSIM's; ``alpha * (1 - ms_ssim(x, y)) + (1 - alpha) * L1`` is steps.gen_msssim_step.
+    The one deliberate difference from torch autograd of the same formula: where 'relu' clamps a per-scale value to 0 the
+    image's value is 0 and its gradient is defined as 0 (autograd gives NaN there, 0 * inf).  With ``normalize=None`` a negative
+    per-scale mean is the caller's risk, as in torchmetrics: NaN propagates."""
+
+    def __init__(self, gaussian_kernel=True, kernel_size=11, sigma=1.5, reduction="elementwise_mean", data_range=1.0,
+                 k1=0.01, k2=0.03, betas=_DEFAULT_BETAS, normalize="relu"):
+        super().__init__()
+        name = "MultiScaleStructuralSimilarityIndexMeasure"
+        _check_window(name, gaussian_kernel, sigma, kernel_size)
+        self.data_range, self.k1, self.k2, self.c1, self.c2 = _check_constants(name, data_range, k1, k2)
+        if not isinstance(betas, (tuple, list)) or not 1 <= len(betas) <= _MAX_SCALES:
+            raise ValueError(f"{name}: betas must be a tuple or list of 1 to {_MAX_SCALES} numbers, got {betas!r}")
+        self.betas = tuple(_positive_float(name, "each of betas", b) for b in betas)
+        if any(not (0 < float(C.c_float(b).value) < math.inf) for b in self.betas):
+            raise ValueError(f"{name}: betas leave the fp32 range: {betas!r}")
+        if isinstance(normalize, bool) or normalize not in _NORMALIZE:
+            raise ValueError(f"{name}: normalize must be 'relu', 'simple' or None, got {normalize!r}")
+        self.normalize = normalize
+        self.min_size = _WIN << (len(self.betas) - 1)
+        self.last_scales = None
+        self._init_state(reduction)
+
+    def update(self, preds, target):
+        self._check(preds, target)
+        per, _ = self._run(_f32(preds), _f32(target))
+        self._accumulate(per)
+
+    def forward(self, preds, target):
+        self._check(preds, target)
+        if torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad):
+            per, tot = _MSSSIMFunction.apply(self, preds, target)
+        else:
+            per, tot = self._run(_f32(preds), _f32(target))
+        self._accumulate(per.detach())
+        return per if self.reduction == "none" else tot.reshape(())
+
+    # ---- the device path
+    def _check(self, preds, target):
+        """As _check_pair, with the pyramid's size rule in front of the device check: every refusal precedes any launch."""
+        name = "MultiScaleStructuralSimilarityIndexMeasure"
+        if torch.is_tensor(preds) and torch.is_tensor(target) and preds.dim() == 4 and preds.shape == target.shape:
+            h, w = preds.shape[2:]
+            if min(h, w) >= _WIN and min(h, w) < self.min_size:
+                raise ValueError(f"{name}: images of {h}x{w} are smaller than {self.min_size}x{self.min_size}, which "
+                                 f"{len(self.betas)} scales need (11 * 2^(scales - 1))")
+        return _check_pair(name, preds, target)
+
+    def _levels(self, shape):
+        n, c, h, w = shape
+        return [(h >> s, w >> s) for s in range(len(self.betas))]
+
+    def _run(self, a, b, keep=False):
+        """(per_image [N], total [1]) of the fp32 contiguous pair a, b; with `keep` also what the backward needs: the pooled
+        levels of both images (lists of [N, C, h, w] views, level 0 = a, b) and the [L, N] factors d per_image / d scale mean."""
+        n, c, h, w = a.shape
+        L = len(self.betas)
+        lib = _lib.lib()
+        st = _stream()
+        dev = a.device
+        blocks = lib.dsr_ssim_cs_img_blocks(n, c, h, w)
+        if blocks <= 0:
+            raise RuntimeError(f"MultiScaleStructuralSimilarityIndexMeasure: {tuple(a.shape)} needs too many window tiles")
+        levels = self._levels(a.shape)
+        pyr = int(lib.dsr_msssim_pyramid_floats(n, c, h, w, L))
+        pa = torch.empty(max(pyr, 1), dtype=torch.float32, device=dev)
+        pb = torch.empty(max(pyr, 1), dtype=torch.float32, device=dev)
+        la, lb, off = [a], [b], 0
+        for hs, ws in levels[1:]:
+            cnt = n * c * hs * ws
+            la.append(pa[off:off + cnt].view(n, c, hs, ws))
+            lb.append(pb[off:off + cnt].view(n, c, hs, ws))
+            off += cnt
+        partial = torch.empty(2 * blocks, dtype=torch.float32, device=dev)       # scale 0 has the most blocks
+        raw = torch.empty(L, n, dtype=torch.float32, device=dev)
+        for s, (hs, ws) in enumerate(levels):
+            last = s == L - 1
+            check(lib.dsr_ssim_cs_img_f32(_ptr(la[s]), _ptr(lb[s]), n, c, hs, ws, self.c1, self.c2, _ptr(partial),
+                                          _ptr(raw[s]) if last else None, None if last else _ptr(raw[s]), st))
+            if not last:
+                check(lib.dsr_avgpool2_pair_f32(_ptr(la[s]), _ptr(lb[s]), _ptr(la[s + 1]), _ptr(lb[s + 1]), n * c, hs, ws, st))
+        vals = torch.empty(L, n, dtype=torch.float32, device=dev)
+        per = torch.empty(n, dtype=torch.float32, device=dev)
+        tot = torch.empty(1, dtype=torch.float32, device=dev)
+        factors = torch.empty(L, n, dtype=torch.float32, device=dev) if keep else None
+        check(lib.dsr_msssim_combine(_ptr(raw), n, L, (C.c_float * L)(*self.betas), _NORMALIZE[self.normalize], _ptr(vals), _ptr(per), _ptr(tot),
+                                     self._total_scale(n), _ptr(factors), st))
+        self.last_scales = vals
+        if keep:
+            return per, tot, la, lb, factors
+        return per, tot
+
+
+class _MSSSIMFunction(torch.autograd.Function):
+    """(per_image [N], total [1]) of MultiScaleStructuralSimilarityIndexMeasure._run; the backward is one dsr_msssim_bwd_f32
+    per scale from the coarsest to the finest, each adding the coarser gradient through the pool in its epilogue."""
+
+    @staticmethod
+    def forward(ctx, mod, preds, target):
+        a, b = _f32(preds), _f32(target)
+        per, tot, la, lb, factors = mod._run(a, b, keep=True)
+        ctx.mod, ctx.la, ctx.lb, ctx.factors = mod, la, lb, factors
+        ctx.dtypes = (preds.dtype, target.dtype)
+        ctx.set_materialize_grads(False)
+        return per, tot
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gper, gtot):
+        want1, want2 = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if not (want1 or want2) or (gper is None and gtot is None):
+            return None, None, None
+        mod, la, lb, factors = ctx.mod, ctx.la, ctx.lb, ctx.factors
+        n, c = la[0].shape[:2]
+        L = len(la)
+        lib = _lib.lib()
+        st = _stream()
+        g = mod._upstream(gper, gtot, n, la[0].device)
+        g1 = g2 = None
+        for s in range(L - 1, -1, -1):
+            hs, ws = la[s].shape[2:]
+            last = s == L - 1
+            n1 = torch.empty_like(la[s]) if want1 else None
+            n2 = torch.empty_like(lb[s]) if want2 else None
+            check(lib.dsr_msssim_bwd_f32(_ptr(la[s]), _ptr(lb[s]), n, c, hs, ws, mod.c1, mod.c2, _ptr(g),
+                                         _ptr(factors[s]) if last else None, None if last else _ptr(factors[s]),
+                                         _ptr(g1), _ptr(g2), _ptr(n1), _ptr(n2), st))
+            g1, g2 = n1, n2
+        out = [o if o is None or o.dtype == dt else o.to(dt) for o, dt in zip((g1, g2), ctx.dtypes)]
+        return None, out[0], out[1]
+
+
 PSNR = PeakSignalNoiseRatio
 SSIM = StructuralSimilarityIndexMeasure
+MS_SSIM = MultiScaleStructuralSimilarityIndexMeasure

@@ -2,6 +2,7 @@
 
 gen_l1_step : BASELINE config 2 (generator-only x4, L1, Adam) -- defined by SURVEY.md 8(d).
 gen_lpips_step : the same step with the perceptual fine-tuning loss l1_weight * L1 + lpips_weight * LPIPS(fake, hr).
+gen_msssim_step : the same step with the structural loss alpha * (1 - MS-SSIM(fake, hr)) + (1 - alpha) * L1.
 gan_step    : train_GAN.py:38-71 (do_epoch): D step, then G step with the detached adversarial term.
 dip_step    : DIP.py:47-95 closure + utils/DIP.py:33-40 Adam iteration.
 """
@@ -47,6 +48,23 @@ def gen_lpips_step(gen, opt, lpips, lr_patches, hr_patches, l1_weight=1.0, lpips
     opt.zero_grad()
     _backward_and_step(loss, opt, scaler)
     return l1.detach(), lp.detach(), fake.detach()
+
+
+def gen_msssim_step(gen, opt, msssim, lr_patches, hr_patches, alpha=0.84, *, scaler=None):
+    """The structural loss of Zhao, Gallo, Frosio, Kautz 2017: loss = alpha * (1 - MS-SSIM(fake, hr)) + (1 - alpha) * L1.
+
+    `msssim`: a metrics.MultiScaleStructuralSimilarityIndexMeasure with reduction 'elementwise_mean' or 'sum' whose data_range
+    spans the images (2.0 for a tanh generator and scale_images targets in [-1, 1]); the patches must be at least its min_size
+    on a side (176 for the default five scales).  Only `fake` requires a gradient, so each scale's backward writes one image's
+    gradient.  Returns the two unweighted terms (1 - MS-SSIM, L1) and `fake` as device tensors (no host sync here); usable
+    inside GraphedStep.  `scaler`: an optim.DynamicLossScaler around the summed loss."""
+    fake = gen(lr_patches)
+    l1 = F.l1_loss(fake, hr_patches)
+    dis = F.one_minus(msssim(fake, hr_patches))
+    loss = F.add_losses(F.scale_loss(dis, float(alpha)), F.scale_loss(l1, 1.0 - float(alpha)))
+    opt.zero_grad()
+    _backward_and_step(loss, opt, scaler)
+    return dis.detach(), l1.detach(), fake.detach()
 
 
 _side_streams = {}

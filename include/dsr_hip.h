@@ -430,6 +430,40 @@ int dsr_metric_accumulate(const float* per_image, int N, double* state, dsr_stre
 int dsr_metric_compute(const double* state, int mode, int infer_range, float data_range, float log_scale, float* out,
                        dsr_stream_t s);
 
+/* Multi-scale SSIM (torchmetrics MultiScaleStructuralSimilarityIndexMeasure restated; metrics.py).  Per scale s < L the pair
+ * of images gives per-image means of SSIM and of its contrast-structure term cs = (2 cov + c2) / (var1 + var2 + c2) over the
+ * same window positions as dsr_ssim_img_f32; between scales both images are halved by a 2x2 mean (floor: an odd last row or
+ * column is dropped); out[n] = prod_s v_s[n]^betas[s] with v = (cs_0 .. cs_{L-2}, ssim_{L-1}) after `normalize`.
+ * 1 <= L <= DSR_MSSSIM_MAX_SCALES, and H >> (L-1), W >> (L-1) >= 11: H, W >= dsr_msssim_min_size(L) = 11 << (L-1) (0: bad L).
+ * dsr_ssim_cs_img_f32: sim[N], cs[N] (either nullable, not both) = the two per-image means; partial: 8-byte aligned scratch of
+ * 2 * dsr_ssim_cs_img_blocks(N, C, H, W) floats.  Two launches (tiles, then a one-block fold in a fixed order).
+ * dsr_avgpool2_pair_f32: in1, in2 [planes][H][W] -> out1, out2 [planes][H/2][W/2], one launch.
+ * dsr_msssim_pyramid_floats: the floats of one image's levels 1 .. L-1, [N][C][H >> s][W >> s] each, level 1 first (0: bad sizes).
+ * dsr_msssim_combine: raw [L][N] (device; row s = the cs means of scale s, row L-1 the SSIM means), betas[L] (HOST, positive
+ * and finite), normalize 0 none / 1 relu (max(raw, 0)) / 2 simple ((raw + 1) / 2) -> vals [L][N] (nullable) the normalised
+ * values, per_image[N] (nullable), total[0] (nullable) = total_scale * sum_n per_image[n], factors [L][N] (nullable) =
+ * d per_image[n] / d raw[s][n] = betas[s] per_image[n] / vals[s][n] (halved under simple).  Under relu a clamped value gives
+ * per_image[n] = 0 and all of that image's factors 0.  One launch.
+ * dsr_msssim_bwd_f32: one scale of the backward.  g[N] = upstream of per_image; w_sim[N], w_cs[N] (either nullable, not both) =
+ * this scale's factors for the SSIM / cs mean; coarse1 / coarse2 (nullable) [N][C][H/2][W/2] = the gradient that arrived at
+ * the pooled images.  grad1 / grad2 (either nullable, not both; a coarse gradient needs its grad) =
+ * g (w_sim d sim + w_cs d cs) / d img + 0.25 coarse[y/2][x/2] inside the pooled extent.  One launch of
+ * dsr_msssim_bwd_blocks(N, C, H, W) blocks; calling it from scale L-1 down to 0 is the whole backward. */
+#define DSR_MSSSIM_MAX_SCALES 8
+int dsr_msssim_min_size(int L);
+size_t dsr_msssim_pyramid_floats(int N, int C, int H, int W, int L);
+int dsr_ssim_cs_img_blocks(int N, int C, int H, int W);
+int dsr_ssim_cs_img_f32(const float* img1, const float* img2, int N, int C, int H, int W, float c1, float c2, float* partial,
+                        float* sim, float* cs, dsr_stream_t s);
+int dsr_avgpool2_pair_f32(const float* in1, const float* in2, float* out1, float* out2, int planes, int H, int W,
+                          dsr_stream_t s);
+int dsr_msssim_combine(const float* raw, int N, int L, const float* betas, int normalize, float* vals, float* per_image,
+                       float* total, float total_scale, float* factors, dsr_stream_t s);
+int dsr_msssim_bwd_blocks(int N, int C, int H, int W);
+int dsr_msssim_bwd_f32(const float* img1, const float* img2, int N, int C, int H, int W, float c1, float c2, const float* g,
+                       const float* w_sim, const float* w_cs, const float* coarse1, const float* coarse2, float* grad1,
+                       float* grad2, dsr_stream_t s);
+
 /* LPIPS with the AlexNet trunk (torchmetrics LearnedPerceptualImagePatchSimilarity(net_type='alex') at train_GAN.py:32,112,
  * eval_GAN.py:32,49, DIP.py:75,185; csrc/lpips.hip).  The five convolutions are dsr_conv_fwd calls; these are the rest.
  * dsr_lpips_tap_sizes: hw[2k], hw[2k+1] = height, width of tap k (relu1..relu5) for an H x W image; DSR_E_ARG if the trunk
