@@ -49,6 +49,10 @@ SIGNATURES = {
     "dsr_scale_images_f32": (_I, [_P, _Z, _I, _P]),
     "dsr_patch_batch_u8": (_I, [_I, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                 C.POINTER(C.c_int), _I, _I, _I, _P, _P]),
+    "dsr_patch_batch_u8_d4": (_I, [_I, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                   C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _I, _P, _P]),
+    "dsr_d4_expand_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "dsr_d4_mean_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "dsr_conv_fwd_affine_supported": (_I, [_DESC]),
     "dsr_conv_first_bwd_supported": (_I, [_DESC, _I]),
     "dsr_conv_first_bwd_workspace": (_Z, [_DESC]),

@@ -5,7 +5,8 @@
         training patches) runs as HIP kernels on device-resident uint8 images.  Items come back as device tensors.
   PatchBank   what the reference's DataLoader + GANDIV2KDataset amount to for a training step, restructured for the device: the
         whole (pre-shrunk) image set lives in HBM as uint8 and ``sample(batch)`` cuts and converts a batch of LR / HR patch
-        pairs in two kernel launches -- the step is fed at its own rate instead of the host's.
+        pairs in two kernel launches -- the step is fed at its own rate instead of the host's; ``augment=True`` flips /
+        turns each pair by a random element of D4 in the same launches.
 
 The reference scales by 255 twice (ToTensor at :59-60, then scale_images :152,155): ``reference_scaling=True`` (default)
 reproduces that, bit for bit; ``False`` gives the [0,1] / [-1,1] ranges its comments describe (SURVEY.md 8f row 1 asks for
@@ -28,11 +29,27 @@ def _device(device):
     return torch.device(device if device is not None else "cuda:0")
 
 
-def patch_batch(images, tops, lefts, ph, pw, mode):
-    """fp32 [B,3,ph,pw] batch of patches, patch b cut from uint8 [H,W,3] device image images[b] at (tops[b], lefts[b])."""
+def _check_transforms(transforms, n, ph, pw):
+    """The D4 codes of `n` ph x pw patches as ints: 0..7 each, and a quarter turn (odd code) only for a square patch."""
+    codes = [int(k) for k in transforms]
+    if len(codes) != n:
+        raise ValueError(f"transforms: {len(codes)} codes for {n} patches")
+    for k in codes:
+        if not 0 <= k <= 7:
+            raise ValueError(f"transforms: code {k} is not in 0..7")
+        if k % 2 and ph != pw:
+            raise ValueError(f"transforms: code {k} turns a {ph}x{pw} patch by a quarter; only 0, 2, 4, 6 keep its shape")
+    return codes
+
+
+def patch_batch(images, tops, lefts, ph, pw, mode, transforms=None):
+    """fp32 [B,3,ph,pw] batch of patches, patch b cut from uint8 [H,W,3] device image images[b] at (tops[b], lefts[b]).
+    ``transforms``: one D4 code per patch (0..7: k % 4 quarter turns of the patch, mirrored left-right first when k >= 4, as
+    ``torch.rot90(torch.flip(x, [-1]) if k >= 4 else x, k % 4, [-2, -1])``), applied in the same launch."""
     n = len(images)
     if not (n == len(tops) == len(lefts)) or n == 0:
         raise ValueError("patch_batch: images, tops and lefts must be equally long and non-empty")
+    codes = None if transforms is None else _check_transforms(transforms, n, ph, pw)
     for im in images:
         if not (torch.is_tensor(im) and im.is_cuda and im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3
                 and im.is_contiguous()):
@@ -40,8 +57,12 @@ def patch_batch(images, tops, lefts, ph, pw, mode):
     out = torch.empty((n, 3, ph, pw), dtype=torch.float32, device=images[0].device)
     ptrs = (C.c_void_p * n)(*[im.data_ptr() for im in images])
     ints = lambda v: (C.c_int * n)(*[int(q) for q in v])
-    check(_lib.lib().dsr_patch_batch_u8(n, ptrs, ints([im.shape[0] for im in images]), ints([im.shape[1] for im in images]),
-                                        ints(tops), ints(lefts), ph, pw, mode, _ptr(out), _stream()))
+    heights, widths = ints([im.shape[0] for im in images]), ints([im.shape[1] for im in images])
+    if codes is None:
+        check(_lib.lib().dsr_patch_batch_u8(n, ptrs, heights, widths, ints(tops), ints(lefts), ph, pw, mode, _ptr(out), _stream()))
+    else:
+        check(_lib.lib().dsr_patch_batch_u8_d4(n, ptrs, heights, widths, ints(tops), ints(lefts), ints(codes), ph, pw, mode,
+                                               _ptr(out), _stream()))
     return out
 
 
@@ -163,9 +184,13 @@ class PatchBank:
     """A (pre-shrunk, optionally degraded) image set resident in HBM as uint8, and batches of training patches cut from it on
     the device: ``sample(batch)`` = `batch` draws of (image index, patch position) + two launches of dsr_patch_batch_u8.
 
-    pairs: iterable of (LR uint8 [h,w,3], HR uint8 [h*s, w*s, 3]) device tensors (e.g. from `_shrink_pair` + degradations)."""
+    pairs: iterable of (LR uint8 [h,w,3], HR uint8 [h*s, w*s, 3]) device tensors (e.g. from `_shrink_pair` + degradations).
+    augment: every sample is flipped / turned by one of the eight D4 codes (`patch_batch`), the same for its LR and its HR
+        patch, in the launches that cut them (dsr_patch_batch_u8_d4).  The codes are drawn AFTER all indices and positions, so
+        a seeded bank crops the same patches with and without augmentation; a non-square patch only gets the four codes that
+        keep its shape."""
 
-    def __init__(self, pairs, scale_factor, LR_patch_size, reference_scaling=True, rng=None):
+    def __init__(self, pairs, scale_factor, LR_patch_size, reference_scaling=True, rng=None, augment=False):
         self.lr = [p[0].contiguous() for p in pairs]
         self.hr = [p[1].contiguous() for p in pairs]
         if not self.lr:
@@ -176,16 +201,25 @@ class PatchBank:
         self.scale, self.patch = scale_factor, tuple(LR_patch_size)
         self.modes = (PATCH_LR_REF, PATCH_HR_REF) if reference_scaling else (PATCH_UNIT, PATCH_HR_UNIT)
         self.rng = np.random if rng is None else rng
+        self.augment = bool(augment)
 
-    def sample(self, batch, indices=None):
-        """(LR [B,3,ph,pw], HR [B,3,ph*s,pw*s]) fp32 device batches; image b is `indices[b]` (default: uniform draws)."""
+    def sample(self, batch, indices=None, transforms=None):
+        """(LR [B,3,ph,pw], HR [B,3,ph*s,pw*s]) fp32 device batches; image b is `indices[b]` (default: uniform draws).
+        ``transforms``: explicit D4 codes, one per sample, instead of the draw (also without ``augment``)."""
+        pw, ph = self.patch
+        if transforms is not None:
+            transforms = _check_transforms(transforms, batch if indices is None else len(indices), ph, pw)
         if indices is None:
             indices = [int(self.rng.randint(0, len(self.lr))) for _ in range(batch)]
-        pw, ph = self.patch
         tops, lefts, htops, hlefts = [], [], [], []
         for i in indices:
             t, l, ht, hl = train_patch_coords(self.lr[i].shape[0], self.lr[i].shape[1], self.patch, self.scale, self.rng)
             tops.append(t), lefts.append(l), htops.append(ht), hlefts.append(hl)
-        lr = patch_batch([self.lr[i] for i in indices], tops, lefts, ph, pw, self.modes[0])
-        hr = patch_batch([self.hr[i] for i in indices], htops, hlefts, ph * self.scale, pw * self.scale, self.modes[1])
+        if transforms is None and self.augment:
+            if ph == pw:
+                transforms = [int(self.rng.randint(0, 8)) for _ in indices]
+            else:
+                transforms = [2 * int(self.rng.randint(0, 4)) for _ in indices]
+        lr = patch_batch([self.lr[i] for i in indices], tops, lefts, ph, pw, self.modes[0], transforms)
+        hr = patch_batch([self.hr[i] for i in indices], htops, hlefts, ph * self.scale, pw * self.scale, self.modes[1], transforms)
         return lr, hr

@@ -91,19 +91,20 @@ def to_uint8_image(img):
 
 
 def evaluate_generator(gen, pairs, tile=None, out_dir=None, data_range=None, dtype=torch.float16, to_unit=None,
-                       with_ssim=True, lpips_model=None):
+                       with_ssim=True, lpips_model=None, self_ensemble=False):
     """eval_GAN.py:21-69 for an iterable of (LR [1,3,h,w], HR [1,3,H,W], name) on the device.
 
     Returns {'avg_psnr': ..., 'psnr': {name: value}, 'avg_ssim': ..., 'ssim': {name: value}}, and with ``lpips_model`` (an
     ``lpips.LPIPS``; eval_GAN.py:32,49) also 'avg_lpips' (the reference's key, :66) and 'lpips': {name: value}; its numbers
     are the trained metric's only when the model was given the AlexNet and head weights.  ``out_dir`` (optional) receives <out_dir>/images/<name>.png like
     save_image (utils/common.py:20-33); ``to_unit`` maps the network's output range to [0,1] for the PNG (default:
-    identity, as in the reference)."""
+    identity, as in the reference).  ``self_ensemble`` (True, or a sequence of D4 codes) scores the geometric self-ensemble
+    of ``infer.super_resolve`` instead of the single forward."""
     per, ssims, lps = OrderedDict(), OrderedDict(), OrderedDict()
     for lr_image, hr_image, name in pairs:
         if isinstance(name, (list, tuple)):
             name = name[0]                                  # DataLoader collation of a batch of one (eval_GAN.py:40)
-        resolved = infer.super_resolve(gen, lr_image, tile=tile, dtype=dtype)
+        resolved = infer.super_resolve(gen, lr_image, tile=tile, dtype=dtype, self_ensemble=self_ensemble)
         per[name] = psnr(resolved, hr_image, data_range)
         if with_ssim:
             ssims[name] = ssim(resolved, hr_image, 1.0)          # SSIM(data_range=1.) as at eval_GAN.py:31

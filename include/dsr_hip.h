@@ -536,6 +536,24 @@ int dsr_scale_images_f32(float* x, size_t n, int mode, dsr_stream_t s);
 int dsr_patch_batch_u8(int count, const unsigned char* const* images, const int* heights, const int* widths, const int* tops,
                        const int* lefts, int ph, int pw, int mode, float* out, dsr_stream_t s);
 
+/* ------------------------------------------------------------------ flips and quarter turns (d4.hip)
+ * The eight elements of the dihedral group D4 acting on [..., H, W] images.  Code k in 0..7, r = k % 4, m = k >= 4:
+ *   T_k(x) = rot90(flip(x, W) if m else x, r)        (torch.rot90 / torch.flip; H x W for even r, W x H for odd r)
+ * as a gather T_k(x)[i][j] = x[a][b]:  r = 0: (i, j)   1: (j, W-1-i)   2: (H-1-i, W-1-j)   3: (H-1-j, i);  if m, b = W-1-b
+ * (H, W: the source's sizes).  Training augmentation (one code per patch) and geometric self-ensemble at inference. */
+/* dsr_patch_batch_u8 with one code per patch (HOST table xforms[count]): patch b, scaled by `mode` as there, is stored as
+ * T_{xforms[b]} of itself in out [count][3][ph][pw].  A code with odd r needs ph == pw. */
+int dsr_patch_batch_u8_d4(int count, const unsigned char* const* images, const int* heights, const int* widths, const int* tops,
+                          const int* lefts, const int* xforms, int ph, int pw, int mode, float* out, dsr_stream_t s);
+/* src [planes][h][w] fp32 -> T_k(src) for every k set in the 8-bit mask, one launch: the codes with even r to dst_even
+ * [n_even][planes][h][w], those with odd r to dst_odd [n_odd][planes][w][h], each in ascending k.  A destination may be NULL
+ * only when the mask holds none of its codes. */
+int dsr_d4_expand_f32(const float* src, int planes, int h, int w, int mask, float* dst_even, float* dst_odd, dsr_stream_t s);
+/* The inverse and the mean, one launch: src_even [n_even][planes][H][W] and src_odd [n_odd][planes][W][H] laid out as
+ * dsr_d4_expand_f32 writes them; dst [planes][H][W] = (sum over the k of mask, ASCENDING, of T_k^-1(src_k)) * (1.0f / count),
+ * summed in fp32 in exactly that order (the first term is taken as it is): the result is defined bit for bit. */
+int dsr_d4_mean_f32(const float* src_even, const float* src_odd, int planes, int H, int W, int mask, float* dst, dsr_stream_t s);
+
 /* ------------------------------------------------------------------ L-BFGS (lbfgs.hip)
  * torch.optim.LBFGS with line_search_fn=None (utils/DIP.py:24-31) in the vector-free form (Chen, Wang & Zhou, NIPS 2014):
  * the two-loop recursion runs on the Gram matrix of the basis {s_i, y_i, g} in fp64; the vectors are read by two streaming
