@@ -180,6 +180,10 @@ SIGNATURES = {
     "dsr_lbfgs_dots": (_I, [_P, _Z, _P, _I, _Z, _I, _P]),
     "dsr_lbfgs_scalar": (_I, [_P, _Z, _I, _Z, _I, _P, _I, _P, C.c_double, _I, _I, C.c_double, C.c_double, _P]),
     "dsr_lbfgs_combine": (_I, [_I, C.POINTER(C.c_void_p), C.POINTER(_Z), _P, _Z, _P, _I, _Z, _P]),
+    "dsr_ema_update_multi": (_I, [_I, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(_Z), C.POINTER(C.c_ubyte), _F, _I,
+                                  _P, _P, _P]),
+    "dsr_ema_tick": (_I, [_P, _P, _P]),
+    "dsr_ema_swap_multi": (_I, [_I, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(_Z), _P]),
 }
 
 _lib = None

@@ -91,7 +91,7 @@ def to_uint8_image(img):
 
 
 def evaluate_generator(gen, pairs, tile=None, out_dir=None, data_range=None, dtype=torch.float16, to_unit=None,
-                       with_ssim=True, lpips_model=None, self_ensemble=False):
+                       with_ssim=True, lpips_model=None, self_ensemble=False, ema=None):
     """eval_GAN.py:21-69 for an iterable of (LR [1,3,h,w], HR [1,3,H,W], name) on the device.
 
     Returns {'avg_psnr': ..., 'psnr': {name: value}, 'avg_ssim': ..., 'ssim': {name: value}}, and with ``lpips_model`` (an
@@ -99,7 +99,15 @@ def evaluate_generator(gen, pairs, tile=None, out_dir=None, data_range=None, dty
     are the trained metric's only when the model was given the AlexNet and head weights.  ``out_dir`` (optional) receives <out_dir>/images/<name>.png like
     save_image (utils/common.py:20-33); ``to_unit`` maps the network's output range to [0,1] for the PNG (default:
     identity, as in the reference).  ``self_ensemble`` (True, or a sequence of D4 codes) scores the geometric self-ensemble
-    of ``infer.super_resolve`` instead of the single forward."""
+    of ``infer.super_resolve`` instead of the single forward.  ``ema`` (an ``optim.WeightEMA`` over ``gen``) scores the
+    averaged weights: they are swapped into ``gen`` for the loop and out again afterwards, also when the loop raises."""
+    if ema is not None:
+        if ema.module is not gen:
+            raise ValueError("evaluate_generator: `ema` averages another module than `gen`")
+        with ema.average_parameters():
+            return evaluate_generator(gen, pairs, tile=tile, out_dir=out_dir, data_range=data_range, dtype=dtype,
+                                      to_unit=to_unit, with_ssim=with_ssim, lpips_model=lpips_model,
+                                      self_ensemble=self_ensemble)
     per, ssims, lps = OrderedDict(), OrderedDict(), OrderedDict()
     for lr_image, hr_image, name in pairs:
         if isinstance(name, (list, tuple)):

@@ -1,14 +1,17 @@
 """Adam with torch.optim.Adam's default semantics (train_GAN.py:35-36, utils/DIP.py:34) as one fused
 HIP kernel per tensor; the step counter lives on the device so a whole train step can be captured
 in a HIP graph.  L-BFGS with torch.optim.LBFGS's semantics (utils/DIP.py:24-31) as four HIP passes
-per closure call, its whole state on the device."""
+per closure call, its whole state on the device.  WeightEMA: torch.optim.swa_utils.AveragedModel's exponential
+moving average of a model's weights, one multi-tensor HIP launch per 64 tensors, its counter on the device."""
+import contextlib
 import ctypes as C
 import math
+from collections import OrderedDict
 
 import torch
 
 from . import _lib
-from .functional import _ptr, _stream, bump, check, mark_shadow_current, repack_cached, shadow_for_update
+from .functional import _need_gpu, _ptr, _stream, bump, check, mark_shadow_current, repack_cached, shadow_for_update
 
 
 class FusedAdam:
@@ -275,6 +278,7 @@ class DynamicLossScaler:
         self._growth_factor, self._backoff_factor = float(growth_factor), float(backoff_factor)
         self._growth_interval = int(growth_interval)
         self._scale = self._growth_tracker = self._found_inf = self._stats = None
+        self._checked = False        # host side: step() has raised or left the overflow flag and update() has not cleared it yet
 
     def _state(self, device):
         """(scale, found_inf) device tensors, created on first use."""
@@ -313,6 +317,7 @@ class DynamicLossScaler:
         check(_lib.lib().dsr_amp_check(k, (C.c_void_p * k)(*[None if g is None else g.data_ptr() for g in grads]),
                                        (C.c_size_t * k)(*[0 if g is None else g.numel() for g in grads]), _ptr(found),
                                        _stream()))
+        self._checked = True
         return optimizer.step(scaler=self)
 
     def update(self):
@@ -323,6 +328,7 @@ class DynamicLossScaler:
         check(_lib.lib().dsr_amp_update(_ptr(self._scale), _ptr(self._growth_tracker), _ptr(self._found_inf),
                                         self._growth_factor, self._backoff_factor, self._growth_interval,
                                         _ptr(self._stats), _stream()))
+        self._checked = False
 
     def get_scale(self):
         """The current scale as a host float (synchronises)."""
@@ -367,6 +373,224 @@ class DynamicLossScaler:
         if self._scale is not None:
             self._scale.fill_(self._init_scale)
             self._growth_tracker.fill_(self._init_growth_tracker)
+
+
+class WeightEMA:
+    """Exponential moving average of a module's weights on the device -- the copy of a GAN generator that gets evaluated and
+    shipped (ESRGAN, Real-ESRGAN, SwinIR, BasicSR: ``ema_decay = 0.999``) -- as csrc/ema.hip runs it: one launch per 64 tensors
+    plus a one-thread counter launch, whatever the number of averaged steps.
+
+        ema = WeightEMA(gen, decay=0.999)
+        ... opt.step(); ema.update()                                    # or: scaler.step(opt); ema.update(scaler); scaler.update()
+        with ema.average_parameters(): evaluate(gen)                    # the averaged weights swapped in, and out again
+        torch.save(ema.module_state_dict(), path)                       # loads into a fresh module of the same class
+
+    ``warmup=False`` is ``AveragedModel(module, multi_avg_fn=get_ema_multi_avg_fn(decay), use_buffers=use_buffers)``: the
+    first update copies the weights, later ones move the average by ``1 - decay`` of the difference.  ``warmup=True`` is the
+    rule of timm and torch-ema: update number k (from 1) uses ``min(decay, (1 + k) / (10 + k))``, and there is no copy step:
+    the average starts as the copy of the weights taken here, at construction.
+
+    ``use_buffers=False``: every buffer is copied from the module at each update, as torch does (BatchNorm's running statistics
+    are moving averages already).  ``use_buffers=True``: floating-point buffers are averaged like parameters; integer buffers
+    (``num_batches_tracked``) are COPIED -- a deliberate departure from torch, which truncates ``b_ema * decay + b * (1 -
+    decay)`` to an integer and so leaves such a counter behind the model's for good.
+
+    The count of averaged steps is ``n_averaged``, an int32 device tensor [1]; which of copy and lerp an update performs is
+    decided inside the kernel, so ``update()`` reads nothing on the host, issues the same launches on every call and is
+    captured by steps.GraphedStep with the rest of a step (warm-up and capture calls count as updates, as they do for Adam).
+
+    Skipped steps: ``update(scaler)`` with the optim.DynamicLossScaler that drove the optimizer reads the scaler's overflow
+    word on the device; after a step the scaler skipped nothing moves, ``n_averaged`` included.  (torch's AveragedModel beside a
+    GradScaler knows nothing of the skip and averages the unchanged weights once more.)  The word is cleared by
+    ``scaler.update()``, so the order is ``scaler.step(opt); ema.update(scaler); scaler.update()``; anything else raises.
+
+    ``swap()`` / ``copy_to()`` / ``restore()`` rewrite live tensors through their raw pointers and then do what FusedAdam does
+    after its own launches: every rewritten tensor's version is advanced (functional.bump), so the packed 16-bit conv weight
+    images are re-packed here (functional.repack_cached), an eval-mode BatchNorm's kept affine map is formed again, and the bf16
+    shadow of a dense-head matrix is cast again at its next use.
+
+    Parameters must be contiguous fp32 (what FusedAdam trains); buffers contiguous with a byte size that is a multiple of four."""
+
+    def __init__(self, module, decay=0.999, warmup=False, use_buffers=False):
+        self.module = module
+        self.decay, self.warmup, self.use_buffers = self._checked_decay(decay), bool(warmup), bool(use_buffers)
+        self._slots = []             # (name, owner, key, is_buffer): the live tensor is looked up at every call (.to() replaces buffers)
+        seen = set()
+        for is_buffer, table in ((False, "_parameters"), (True, "_buffers")):
+            for prefix, owner in module.named_modules():
+                for key, t in getattr(owner, table).items():
+                    if t is None or id(t) in seen:
+                        continue
+                    seen.add(id(t))
+                    self._slots.append(((prefix + "." if prefix else "") + key, owner, key, is_buffer))
+        if not any(not s[3] for s in self._slots):
+            raise ValueError("WeightEMA got a module without parameters")
+        live = self._live()
+        for (name, _, _, is_buffer), t in zip(self._slots, live):
+            if not is_buffer and (t.dtype != torch.float32 or not t.is_contiguous()):
+                raise TypeError(f"WeightEMA takes contiguous fp32 parameters; {name} is {t.dtype}, contiguous={t.is_contiguous()}")
+            if is_buffer and (not t.is_contiguous() or t.numel() * t.element_size() % 4):
+                raise TypeError(f"WeightEMA takes contiguous buffers of a multiple of 4 bytes; {name} is {t.dtype} "
+                                f"{tuple(t.shape)}, contiguous={t.is_contiguous()}")
+            if is_buffer and self.use_buffers and t.is_floating_point() and t.dtype != torch.float32:
+                raise TypeError(f"WeightEMA(use_buffers=True) averages fp32 buffers; {name} is {t.dtype}")
+        self._shadow = [t.detach().clone(memory_format=torch.contiguous_format) for t in live]
+        self.n_averaged = torch.zeros(1, dtype=torch.int32, device=live[0].device)
+        self._backup = None
+
+    @staticmethod
+    def _checked_decay(decay):
+        if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= decay <= 1.0:     # (NaN fails too)
+            raise ValueError(f"Invalid decay value {decay!r} provided. Please provide a value in [0,1] range.")   # torch's words
+        return float(decay)
+
+    # ------------------------------------------------------------------ tables
+    def _live(self):
+        return [getattr(owner, "_buffers" if is_buffer else "_parameters")[key] for _, owner, key, is_buffer in self._slots]
+
+    def _copied(self, i):
+        """Is slot i copied from the module (not averaged)?"""
+        return self._slots[i][3] and not (self.use_buffers and self._shadow[i].is_floating_point())
+
+    def _on_device(self, live):
+        """The tensors of an operation that runs on the HIP path: on the GPU, the state beside them."""
+        _need_gpu(live[0])
+        dev = live[0].device
+        for (name, _, _, _), t, sh in zip(self._slots, live, self._shadow):
+            if t.device != dev or t.shape != sh.shape or t.dtype != sh.dtype or not t.is_contiguous():
+                raise RuntimeError(f"WeightEMA: {name} is now {t.dtype} {tuple(t.shape)} on {t.device}, contiguous="
+                                   f"{t.is_contiguous()}; the average holds {sh.dtype} {tuple(sh.shape)} for {dev}")
+        if self.n_averaged.device != dev:          # the module was moved after construction: the state follows it
+            self._shadow = [sh.to(dev) for sh in self._shadow]
+            self.n_averaged = self.n_averaged.to(dev)
+            if self._backup is not None:
+                self._backup = [b.to(dev) for b in self._backup]
+
+    @staticmethod
+    def _tables(dst, src):
+        """HOST tables of the C ABI over 32-bit words (a copy or a swap moves bits, so an int64 counter is two words each)."""
+        k = len(dst)
+        return (k, (C.c_void_p * k)(*[t.data_ptr() for t in dst]), (C.c_void_p * k)(*[t.data_ptr() for t in src]),
+                (C.c_size_t * k)(*[t.numel() * t.element_size() // 4 for t in dst]))
+
+    def _rewritten(self, module, tensors):
+        for t in tensors:
+            bump(t)
+        repack_cached(list(module.parameters()))
+
+    def _copy_exact(self, dst, src):
+        """dst[i] <- src[i], bit for bit (the update launch with every tensor flagged `copy`)."""
+        k, d, s_, n = self._tables(dst, src)
+        check(_lib.lib().dsr_ema_update_multi(k, d, s_, n, (C.c_ubyte * k)(*([1] * k)), 0.0, 0, _ptr(self.n_averaged), None,
+                                              _stream()))
+
+    # ------------------------------------------------------------------ the step
+    def update(self, scaler=None):
+        """One averaging step, after ``opt.step()``.  ``scaler``: the optim.DynamicLossScaler whose ``step(opt)`` has just run
+        and whose ``update()`` has not (see the class docstring)."""
+        live = self._live()
+        self._on_device(live)
+        found = None
+        if scaler is not None and scaler.enabled:
+            if not scaler._checked:
+                raise RuntimeError("WeightEMA.update(scaler): the scaler's overflow flag of this step is gone -- the order is "
+                                   "scaler.step(opt); ema.update(scaler); scaler.update()")
+            found = scaler._state(live[0].device)[1]
+        lib, st = _lib.lib(), _stream()
+        k, sh, p, n = self._tables(self._shadow, live)
+        flags = (C.c_ubyte * k)(*[1 if self._copied(i) else 0 for i in range(k)])
+        check(lib.dsr_ema_update_multi(k, sh, p, n, flags, self.decay, 1 if self.warmup else 0, _ptr(self.n_averaged),
+                                       _ptr(found), st))
+        check(lib.dsr_ema_tick(_ptr(self.n_averaged), _ptr(found), st))
+
+    # ------------------------------------------------------------------ the averaged weights in a live module
+    def swap(self):
+        """Exchange the module's tensors with the average, bit for bit; a second call undoes the first."""
+        live = self._live()
+        self._on_device(live)
+        k, a, b, n = self._tables(live, self._shadow)
+        check(_lib.lib().dsr_ema_swap_multi(k, a, b, n, _stream()))
+        self._rewritten(self.module, live)
+
+    @contextlib.contextmanager
+    def average_parameters(self):
+        """``with ema.average_parameters():`` -- the module holds the averaged weights (and the average's buffers) inside the
+        block and its own again afterwards, also when the block raises."""
+        self.swap()
+        try:
+            yield self
+        finally:
+            self.swap()
+
+    def copy_to(self, module=None):
+        """Write the average into ``module`` (same tensor names, shapes and dtypes, on the GPU).  Default: the EMA's own module,
+        whose tensors are kept aside first so that ``restore()`` can bring them back."""
+        own = module is None or module is self.module
+        if own:
+            live = self._live()
+            self._on_device(live)
+            self._backup = [t.detach().clone() for t in live]
+            self._copy_exact(live, self._shadow)
+            self._rewritten(self.module, live)
+            return
+        theirs = dict(module.named_parameters())
+        theirs.update(dict(module.named_buffers()))
+        dst = []
+        for (name, _, _, _), sh in zip(self._slots, self._shadow):
+            t = theirs.get(name)
+            if t is None or t.shape != sh.shape or t.dtype != sh.dtype or not t.is_contiguous():
+                raise RuntimeError(f"WeightEMA.copy_to: the target has no contiguous {sh.dtype} {tuple(sh.shape)} tensor {name}")
+            _need_gpu(t)
+            dst.append(t)
+        self._on_device(self._live())
+        self._copy_exact(dst, self._shadow)
+        self._rewritten(module, dst)
+
+    def restore(self):
+        """Undo one ``copy_to()`` onto the EMA's own module."""
+        if self._backup is None:
+            raise RuntimeError("WeightEMA.restore() without a copy_to() onto the EMA's own module before it")
+        live = self._live()
+        self._on_device(live)
+        self._copy_exact(live, self._backup)
+        self._backup = None
+        self._rewritten(self.module, live)
+
+    # ------------------------------------------------------------------ checkpoints
+    def module_state_dict(self):
+        """The averaged weights under the module's own ``state_dict()`` keys, order and dtypes (copies): what
+        ``module.load_state_dict`` and evaluate.save_model's file format take."""
+        mine = {id(t): sh for t, sh in zip(self._live(), self._shadow)}
+        out = OrderedDict()
+        for key, t in self.module.state_dict(keep_vars=True).items():
+            sh = mine.get(id(t))
+            out[key] = (t if sh is None else sh).detach().clone()
+        return out
+
+    def state_dict(self):
+        """``shadow`` (name -> tensor, parameters then buffers), ``n_averaged`` (host int: one read), ``decay``, ``warmup``,
+        ``use_buffers``."""
+        return {"shadow": OrderedDict((s[0], sh.detach().clone()) for s, sh in zip(self._slots, self._shadow)),
+                "n_averaged": int(self.n_averaged.item()), "decay": self.decay, "warmup": self.warmup,
+                "use_buffers": self.use_buffers}
+
+    def load_state_dict(self, state_dict):
+        shadow = state_dict["shadow"]
+        names = [s[0] for s in self._slots]
+        if list(shadow.keys()) != names:
+            odd = sorted(set(shadow.keys()) ^ set(names))
+            raise RuntimeError(f"WeightEMA.load_state_dict: tensor names differ from the module's: {odd or 'order'}")
+        decay = self._checked_decay(state_dict["decay"])
+        for name, sh in zip(names, self._shadow):
+            src = shadow[name]
+            if src.shape != sh.shape or src.dtype != sh.dtype:
+                raise RuntimeError(f"WeightEMA.load_state_dict: {name} is {src.dtype} {tuple(src.shape)}, expected "
+                                   f"{sh.dtype} {tuple(sh.shape)}")
+        with torch.no_grad():
+            for name, sh in zip(names, self._shadow):
+                sh.copy_(shadow[name])
+            self.n_averaged.fill_(int(state_dict["n_averaged"]))
+        self.decay, self.warmup, self.use_buffers = decay, bool(state_dict["warmup"]), bool(state_dict["use_buffers"])
 
 
 class FusedLBFGS:

@@ -13,27 +13,34 @@ import torch
 from . import functional as F
 
 
-def _backward_and_step(loss, opt, scaler):
-    """loss.backward(); opt.step() -- under an optim.DynamicLossScaler: scaled loss, checked and predicated step, update."""
+def _backward_and_step(loss, opt, scaler, ema=None):
+    """loss.backward(); opt.step() -- under an optim.DynamicLossScaler: scaled loss, checked and predicated step, update.
+    `ema` (an optim.WeightEMA): averaged right after the optimizer's step, while the scaler's overflow flag of this step is
+    still up -- a skipped step leaves the average alone too."""
     with F.batched_wgrad():              # e.g. the 35 3x3 weight gradients of the generator: one grouped launch at the end
         (loss if scaler is None else scaler.scale(loss)).backward()
     if scaler is None:
         opt.step()
+        if ema is not None:
+            ema.update()
     else:
         scaler.step(opt)
+        if ema is not None:
+            ema.update(scaler)
         scaler.update()
 
 
-def gen_l1_step(gen, opt, lr_patches, hr_patches, *, scaler=None):
-    """`scaler`: an optim.DynamicLossScaler for a generator with fp16 storage (the default bf16 needs none)."""
+def gen_l1_step(gen, opt, lr_patches, hr_patches, *, scaler=None, ema=None):
+    """`scaler`: an optim.DynamicLossScaler for a generator with fp16 storage (the default bf16 needs none).  `ema`: an
+    optim.WeightEMA over the generator, updated after the optimizer's step (here and in the recipes below)."""
     fake = gen(lr_patches)
     loss = F.l1_loss(fake, hr_patches)
     opt.zero_grad()
-    _backward_and_step(loss, opt, scaler)
+    _backward_and_step(loss, opt, scaler, ema)
     return loss.detach(), fake.detach()
 
 
-def gen_lpips_step(gen, opt, lpips, lr_patches, hr_patches, l1_weight=1.0, lpips_weight=0.1, *, scaler=None):
+def gen_lpips_step(gen, opt, lpips, lr_patches, hr_patches, l1_weight=1.0, lpips_weight=0.1, *, scaler=None, ema=None):
     """Perceptual fine-tuning of a PSNR-trained generator: loss = l1_weight * L1 + lpips_weight * LPIPS(fake, hr).
 
     `lpips`: an lpips.LPIPS with normalize=False (the generator ends in tanh and scale_images targets live in [-1, 1]); only
@@ -46,11 +53,11 @@ def gen_lpips_step(gen, opt, lpips, lr_patches, hr_patches, l1_weight=1.0, lpips
     lp = lpips(fake, hr_patches)
     loss = F.add_losses(F.scale_loss(l1, float(l1_weight)), F.scale_loss(lp, float(lpips_weight)))
     opt.zero_grad()
-    _backward_and_step(loss, opt, scaler)
+    _backward_and_step(loss, opt, scaler, ema)
     return l1.detach(), lp.detach(), fake.detach()
 
 
-def gen_msssim_step(gen, opt, msssim, lr_patches, hr_patches, alpha=0.84, *, scaler=None):
+def gen_msssim_step(gen, opt, msssim, lr_patches, hr_patches, alpha=0.84, *, scaler=None, ema=None):
     """The structural loss of Zhao, Gallo, Frosio, Kautz 2017: loss = alpha * (1 - MS-SSIM(fake, hr)) + (1 - alpha) * L1.
 
     `msssim`: a metrics.MultiScaleStructuralSimilarityIndexMeasure with reduction 'elementwise_mean' or 'sum' whose data_range
@@ -63,7 +70,7 @@ def gen_msssim_step(gen, opt, msssim, lr_patches, hr_patches, alpha=0.84, *, sca
     dis = F.one_minus(msssim(fake, hr_patches))
     loss = F.add_losses(F.scale_loss(dis, float(alpha)), F.scale_loss(l1, 1.0 - float(alpha)))
     opt.zero_grad()
-    _backward_and_step(loss, opt, scaler)
+    _backward_and_step(loss, opt, scaler, ema)
     return dis.detach(), l1.detach(), fake.detach()
 
 
@@ -89,7 +96,7 @@ def _mark(label, stream):
 
 
 def gan_step(gen, disc, perceptual, opt_g, opt_d, lr_patches, hr_patches, sync_g=None, sync_d=None, overlap=True,
-             batch_wgrad=None):
+             batch_wgrad=None, ema=None):
     """train_GAN.py:38-71.  Returns (loss_D, loss_G, fake) as device tensors (no host sync here).
 
     Once `fake` exists the reference's two halves are independent: the D step (:44-53) reads only `fake.detach()`,
@@ -97,7 +104,8 @@ def gan_step(gen, disc, perceptual, opt_g, opt_d, lr_patches, hr_patches, sync_g
     DETACHED generator output (:58), so it contributes a number to loss_G (:59) and nothing to loss_G.backward()
     (:63).  With `overlap` the D step (+ the no_grad D pass that feeds that number) runs on a second HIP stream
     while VGG forward/backward, the generator backward and its Adam run on the main one: the HBM-bound BatchNorm /
-    Adam passes of one half execute under the MFMA-bound convolutions of the other.  The arithmetic is unchanged."""
+    Adam passes of one half execute under the MFMA-bound convolutions of the other.  The arithmetic is unchanged.
+    `ema`: an optim.WeightEMA over the generator, updated after opt_g.step() on the main stream."""
     # train_GAN.py:46 and :56 evaluate gen(lr_patches) twice with the same weights and batch statistics -- the
     # two outputs are bit-identical and only the BatchNorm running statistics notice the second call.  One forward
     # (with the autograd graph the G step needs) + a double running-stat update is exactly equivalent.
@@ -167,6 +175,8 @@ def gan_step(gen, disc, perceptual, opt_g, opt_d, lr_patches, hr_patches, sync_g
     if sync_g is not None:
         sync_g()
     opt_g.step()                                                 # :64
+    if ema is not None:
+        ema.update()
     _mark("main: G Adam done", main)
     if overlap:
         main.wait_stream(side)                                   # D half done before anything later on `main`

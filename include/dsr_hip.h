@@ -575,6 +575,29 @@ int dsr_lbfgs_scalar(void* ws, size_t ws_bytes, int history, size_t n, int count
 int dsr_lbfgs_combine(int count, float* const* params, const size_t* numel, void* ws, size_t ws_bytes, float* vecs,
                       int history, size_t n, dsr_stream_t s);
 
+/* ------------------------------------------------------------------ exponential moving average of a model's weights
+ * (optim.WeightEMA).  torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn, with nothing read on the host: the
+ * count of averaged steps is a device word and "copy or lerp" is decided inside the kernel, so an update is the same launch
+ * sequence on every call and replays from a HIP graph.  Order within a step: after the Adam launches, every
+ * dsr_ema_update_multi launch, then ONE dsr_ema_tick; under a dynamic loss scale, before dsr_amp_update clears found_inf.
+ * dsr_ema_update_multi: shadow[i] <- shadow[i] + w * (p[i] - shadow[i]) over `count` fp32 tensors (HOST tables of device
+ * pointers and element counts, read before the call returns; 64 tensors per launch; an entry with n[i] == 0, or with both
+ * pointers NULL, is skipped; views 4 / 8 / 12 bytes off a 16-byte boundary are fine).  w comes from n_averaged[0] (int32,
+ * only read here):
+ *   mode 0 (DSR_EMA_TORCH):  n_averaged == 0: shadow <- p, an exact copy; otherwise w = 1 - decay
+ *   mode 1 (DSR_EMA_WARMUP): k = n_averaged + 1, w = 1 - min(decay, (1 + k) / (10 + k)); no copy step
+ * copy (nullable HOST array): copy[i] != 0 -> tensor i is copied exactly whatever n_averaged is (buffers that follow the
+ * model).  found_inf (nullable; the dynamic loss scaler's fp32 word): != 0 -> no write at all.  Plain vector stores, no
+ * atomics: the same bits on every run.  0 <= decay <= 1.
+ * dsr_ema_tick: n_averaged[0] += 1 unless found_inf[0] != 0 (one thread; the only writer of that word).
+ * dsr_ema_swap_multi: a[i] <-> b[i], bit for bit, same tables (a[i] == b[i] is a no-op; other overlaps are undefined). */
+#define DSR_EMA_TORCH 0
+#define DSR_EMA_WARMUP 1
+int dsr_ema_update_multi(int count, float* const* shadow, const float* const* p, const size_t* n, const unsigned char* copy,
+                         float decay, int mode, const int* n_averaged, const float* found_inf, dsr_stream_t s);
+int dsr_ema_tick(int* n_averaged, const float* found_inf, dsr_stream_t s);
+int dsr_ema_swap_multi(int count, float* const* a, float* const* b, const size_t* n, dsr_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
