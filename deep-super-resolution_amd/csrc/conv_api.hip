@@ -330,19 +330,24 @@ extern "C" int dsr_conv_fwd(const dsr_conv_desc* d, const void* x, const void* w
   }
 }
 
-// ---- reflect-padding adjoint: dx[i][j] = sum of dxp over the padded coordinates that mirror onto (i,j)
+// ---- reflect-padding adjoint: dx[i][j] = sum of dxp over the padded coordinates that mirror onto (i,j).  dxp is the fp32
+// NCHW [N][C][H+2p][W+2p] gradient of the padded input (real channels only), so that dx is rounded to 16 bits exactly once:
+// a 16-bit dxp made the two outermost rows and columns the rounded sum of rounded terms (tests/test_gpu_conv_exact.py).
 template <int DT>
-__global__ void reflect_fold_kernel(const unsigned short* __restrict__ dxp, unsigned short* __restrict__ dx, int N,
+__global__ void reflect_fold_kernel(const float* __restrict__ dxp, unsigned short* __restrict__ dx, int N, int C,
                                     int H, int W, int Cp, int p) {
   size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int cpr = Cp / 8;
   size_t total = (size_t)N * H * W * cpr;
   if (idx >= total) return;
-  int ch = (int)(idx % cpr);
-  size_t pix = idx / cpr;
-  int j = (int)(pix % W);
-  int i = (int)((pix / W) % H);
-  int n = (int)(pix / ((size_t)W * H));
+  // neighbouring lanes take neighbouring columns of one channel group: each fp32 plane is read in contiguous runs
+  int j = (int)(idx % W);
+  size_t t = idx / W;
+  int ch = (int)(t % cpr);
+  t /= cpr;
+  int i = (int)(t % H);
+  int n = (int)(t / H);
+  size_t pix = ((size_t)n * H + i) * W + j;
   const int HP = H + 2 * p, WP = W + 2 * p;
   int ys[3], xs[3], ny = 0, nx = 0;
   ys[ny++] = i + p;
@@ -356,10 +361,11 @@ __global__ void reflect_fold_kernel(const unsigned short* __restrict__ dxp, unsi
   for (int k = 0; k < 8; ++k) acc[k] = 0.f;
   for (int a = 0; a < ny; ++a)
     for (int b = 0; b < nx; ++b) {
-      float f[8];
-      unpack8<DT>(*reinterpret_cast<const U4*>(dxp + ((size_t)(n * HP + ys[a]) * WP + xs[b]) * Cp + ch * 8), f);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) acc[k] += f[k];
+      for (int k = 0; k < 8; ++k) {
+        const int c = ch * 8 + k;      // pad channels stay zero
+        if (c < C) acc[k] += dxp[(((size_t)n * C + c) * HP + ys[a]) * WP + xs[b]];
+      }
     }
   *reinterpret_cast<U4*>(dx + pix * Cp + ch * 8) = pack8<DT>(acc);
 }
@@ -393,11 +399,12 @@ static void launch_c64_dgrad(const dsr_conv_desc* d, const void* dy, const void*
 extern "C" size_t dsr_conv_dgrad_workspace(const dsr_conv_desc* d) {
   if (check_desc(d)) return 0;
   if (d->pad_mode == DSR_PAD_ZERO || d->pad == 0) return 0;
-  return (size_t)d->N * (d->H + 2 * d->pad) * (d->W + 2 * d->pad) * r8(d->Cin) * 2;
+  return (size_t)d->N * (d->H + 2 * d->pad) * (d->W + 2 * d->pad) * d->Cin * sizeof(float);   // fp32 NCHW, real channels
 }
 
 // the gather kernel's arguments of output-parity class (ph, pw) of an input gradient; false if the class is empty.  With
-// reflect padding the gradient is first taken w.r.t. the PADDED input (a pad = 0 problem into the workspace), then folded.
+// reflect padding the gradient is first taken w.r.t. the PADDED input (a pad = 0 problem into the workspace, stored as fp32
+// NCHW so that nothing is rounded before the fold), then folded.
 static bool dgrad_gemm_args(const dsr_conv_desc* d, int ph, int pw, const void* dy, const void* w, void* target,
                             const void* mask_x, int mask_act, float mask_slope, ConvGemmArgs& a) {
   int OH, OW;
@@ -433,6 +440,10 @@ static bool dgrad_gemm_args(const dsr_conv_desc* d, int ph, int pw, const void* 
   a.mask_x = mask_x;
   a.mask_act = mask_act;
   a.mask_slope = mask_slope;
+  if (folded) {
+    a.out_f32 = (float*)target;
+    a.flags = DSR_F_OUT_NCHW_F32;
+  }
   int nt = 0;
   for (int kh = 0; kh < d->KH; ++kh) {
     if ((ph + pad - kh) % st != 0) continue;
@@ -559,11 +570,11 @@ static int conv_dgrad_impl(const dsr_conv_desc* d, const void* dy, const void* w
     size_t total = (size_t)d->N * d->H * d->W * (r8(d->Cin) / 8);
     dim3 grid((unsigned)((total + 255) / 256)), block(256);
     if (d->dtype == DSR_BF16)
-      hipLaunchKernelGGL((reflect_fold_kernel<DSR_DTYPE_BF16>), grid, block, 0, s, (const unsigned short*)workspace,
-                         (unsigned short*)dx, d->N, d->H, d->W, r8(d->Cin), d->pad);
+      hipLaunchKernelGGL((reflect_fold_kernel<DSR_DTYPE_BF16>), grid, block, 0, s, (const float*)workspace,
+                         (unsigned short*)dx, d->N, d->Cin, d->H, d->W, r8(d->Cin), d->pad);
     else
-      hipLaunchKernelGGL((reflect_fold_kernel<DSR_DTYPE_F16>), grid, block, 0, s, (const unsigned short*)workspace,
-                         (unsigned short*)dx, d->N, d->H, d->W, r8(d->Cin), d->pad);
+      hipLaunchKernelGGL((reflect_fold_kernel<DSR_DTYPE_F16>), grid, block, 0, s, (const float*)workspace,
+                         (unsigned short*)dx, d->N, d->Cin, d->H, d->W, r8(d->Cin), d->pad);
   }
   return dsr_launch_status("dsr_conv_dgrad");
 }

@@ -420,7 +420,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, BM * BN >= 224 * 256 ? 2 : (WGM * W
     // acc[i][k][j] = out[row = wm*WM + 16i + r16][col = wn*WN + 16k + 4g + j].  A lane therefore owns 4 consecutive
     // channels of one pixel: one packed 8-byte LDS write per 4 values (the pixel-major layout needs four 2-byte ones).
     if (nchw) {
-      // fp32 NCHW store straight from the accumulators (last layers: Cout <= 16, so this is a small tensor)
+      // fp32 NCHW store straight from the accumulators (last layers with Cout <= 16; the gradient of a reflect-padded input)
   #pragma unroll
       for (int k = 0; k < TN; ++k) {
   #pragma unroll
@@ -513,7 +513,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, BM * BN >= 224 * 256 ? 2 : (WGM * W
       run_epilogue([&](float v) { return act_apply(a.act, v, slope); });
   } else {
     if (nchw) {
-      // fp32 NCHW store straight from the accumulators (last layers: Cout <= 16, so this is a small tensor)
+      // fp32 NCHW store straight from the accumulators (last layers with Cout <= 16; the gradient of a reflect-padded input)
   #pragma unroll
       for (int k = 0; k < TN; ++k) {
         const int col = n0 + wn * WN + 16 * k + r16;
@@ -791,7 +791,9 @@ GemmTile dsr_conv_gemm_plan(const ConvGemmArgs& a) {
     return r224 * 7 < r256 * 8 ? GemmTile::T224x256 : GemmTile::T256x256;
   }
   const int bm64 = env_int("DSR_CONV_BM64", 1);
-  if (bm64 != 0 && dma_fast && a.NB % 128 == 0 && plain && (bm64 == 2 || ((M + 127) / 128) * (a.NB / 128) < 256))
+  // (the fp32 NCHW store is the same accumulator walk on every tile: the reflect-padded input gradient keeps this tile)
+  const bool plain64 = !(a.flags & (DSR_F_STATS | DSR_F_PIXSHUF));
+  if (bm64 != 0 && dma_fast && a.NB % 128 == 0 && plain64 && (bm64 == 2 || ((M + 127) / 128) * (a.NB / 128) < 256))
     return GemmTile::T64x128;
   return GemmTile::T128x128;
 }

@@ -85,7 +85,8 @@ int dsr_conv_pack_weight_multi(int dtype, int count, const float* const* w, void
 int dsr_conv_fwd(const dsr_conv_desc* d, const void* x, const void* w_fwd, const dsr_epilogue* e, void* y,
                  dsr_stream_t s);
 /* dx = conv_transpose(dy, w) : autograd of nn.Conv2d w.r.t. its input.
- * workspace: dsr_conv_dgrad_workspace(d) bytes (non-zero only for reflect padding). */
+ * workspace: dsr_conv_dgrad_workspace(d) bytes (non-zero only for reflect padding: the fp32 gradient of the padded input,
+ * folded onto dx with one rounding). */
 size_t dsr_conv_dgrad_workspace(const dsr_conv_desc* d);
 int dsr_conv_dgrad(const dsr_conv_desc* d, const void* dy, const void* w_dgrad, void* dx, void* workspace,
                    size_t ws_bytes, dsr_stream_t s);
