@@ -91,7 +91,7 @@ def to_uint8_image(img):
 
 
 def evaluate_generator(gen, pairs, tile=None, out_dir=None, data_range=None, dtype=torch.float16, to_unit=None,
-                       with_ssim=True, lpips_model=None, self_ensemble=False, ema=None):
+                       with_ssim=True, lpips_model=None, self_ensemble=False, ema=None, y_channel=False, shave=None):
     """eval_GAN.py:21-69 for an iterable of (LR [1,3,h,w], HR [1,3,H,W], name) on the device.
 
     Returns {'avg_psnr': ..., 'psnr': {name: value}, 'avg_ssim': ..., 'ssim': {name: value}}, and with ``lpips_model`` (an
@@ -100,15 +100,24 @@ def evaluate_generator(gen, pairs, tile=None, out_dir=None, data_range=None, dty
     save_image (utils/common.py:20-33); ``to_unit`` maps the network's output range to [0,1] for the PNG (default:
     identity, as in the reference).  ``self_ensemble`` (True, or a sequence of D4 codes) scores the geometric self-ensemble
     of ``infer.super_resolve`` instead of the single forward.  ``ema`` (an ``optim.WeightEMA`` over ``gen``) scores the
-    averaged weights: they are swapped into ``gen`` for the loop and out again afterwards, also when the loop raises."""
+    averaged weights: they are swapped into ``gen`` for the loop and out again afterwards, also when the loop raises.
+
+    ``y_channel=True`` adds the numbers of the published super-resolution tables next to the ones above, which stay as they
+    are: 'avg_psnr_y', 'psnr_y' and (with ``with_ssim``) 'avg_ssim_y', 'ssim_y' -- PSNR and SSIM of the BT.601 luma of the
+    8-bit-quantised output against that of the target, ``shave`` pixels cut from each border (``metrics.PSNR_Y`` /
+    ``metrics.SSIM_Y``; the images are taken to be in [0, 1]).  ``shave=None`` is the scale factor, HR height // LR height.
+    That path reads nothing on the host inside the loop: the per-image values stay on the device and cross once at the end."""
     if ema is not None:
         if ema.module is not gen:
             raise ValueError("evaluate_generator: `ema` averages another module than `gen`")
         with ema.average_parameters():
             return evaluate_generator(gen, pairs, tile=tile, out_dir=out_dir, data_range=data_range, dtype=dtype,
                                       to_unit=to_unit, with_ssim=with_ssim, lpips_model=lpips_model,
-                                      self_ensemble=self_ensemble)
+                                      self_ensemble=self_ensemble, y_channel=y_channel, shave=shave)
+    if shave is not None and (isinstance(shave, bool) or not isinstance(shave, int) or shave < 0):
+        raise ValueError(f"evaluate_generator: shave must be None or a non-negative integer, got {shave!r}")
     per, ssims, lps = OrderedDict(), OrderedDict(), OrderedDict()
+    y_names, y_psnr, y_ssim = [], [], []                    # device tensors, one [1] per image
     for lr_image, hr_image, name in pairs:
         if isinstance(name, (list, tuple)):
             name = name[0]                                  # DataLoader collation of a batch of one (eval_GAN.py:40)
@@ -118,6 +127,13 @@ def evaluate_generator(gen, pairs, tile=None, out_dir=None, data_range=None, dty
             ssims[name] = ssim(resolved, hr_image, 1.0)          # SSIM(data_range=1.) as at eval_GAN.py:31
         if lpips_model is not None:
             lps[name] = lpips(resolved, hr_image, lpips_model)   # eval_GAN.py:49
+        if y_channel:
+            from . import metrics
+            border = hr_image.shape[2] // lr_image.shape[2] if shave is None else shave
+            p_y, s_y = metrics.luma_psnr_ssim(resolved, hr_image, shave=border, quantize=True, with_ssim=with_ssim)
+            y_names.append(name)
+            y_psnr.append(p_y)
+            y_ssim.append(s_y)
         if out_dir is not None:
             from PIL import Image
             img_dir = os.path.join(out_dir, "images")
@@ -129,4 +145,10 @@ def evaluate_generator(gen, pairs, tile=None, out_dir=None, data_range=None, dty
         out.update(avg_ssim=sum(ssims.values()) / max(len(ssims), 1), ssim=ssims)
     if lpips_model is not None:
         out.update(avg_lpips=sum(lps.values()) / max(len(lps), 1), lpips=lps)
+    if y_channel:
+        cols = [y_psnr, y_ssim] if with_ssim else [y_psnr]
+        host = torch.stack([torch.cat(c) for c in cols]).double().cpu().tolist() if y_names else [[] for _ in cols]
+        for key, vals in zip(("psnr_y", "ssim_y"), host):
+            out["avg_" + key] = sum(vals) / max(len(vals), 1)
+            out[key] = OrderedDict(zip(y_names, vals))
     return out

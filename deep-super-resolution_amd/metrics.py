@@ -35,6 +35,19 @@ as SSIM, the per-image means of ``cs = (2 cov + c2) / (var_a + var_b + c2)`` and
   dsr_msssim_combine      normalised values, powers, product, the reduction's total and d out / d (per-scale mean), one launch;
   dsr_msssim_bwd_f32      one scale of the backward: each image carries a weight for its SSIM mean and one for its cs mean, and
                           the epilogue adds the coarser scale's gradient spread back through the pool -- L launches, coarse to fine.
+
+``LumaPeakSignalNoiseRatio`` (``PSNR_Y``), ``LumaStructuralSimilarityIndexMeasure`` (``SSIM_Y``) and ``rgb_to_y`` are the
+evaluation protocol of the published super-resolution tables (SRGAN, ESRGAN, EDSR, ...; basicsr's ``calculate_psnr`` /
+``calculate_ssim`` with ``test_y_channel=True`` and MATLAB's ``rgb2ycbcr``) -- PARITY UNPINNED as well, neither is installed
+here: the output is quantised to 8 bits, ``shave`` pixels are cut from each border, RGB becomes the BT.601 luma
+``Y = (16 + 65.481 r + 128.553 g + 24.966 b) / 255``, and PSNR / SSIM are taken per image on that one plane, then averaged.
+Device work (csrc/luma.hip), reading fp32 / fp16 / bf16 [N,3,H,W] as they are:
+  dsr_luma_sse_stats       one pass over both images: per-block sums of dY^2 over the cropped region, dY formed from the
+                           channel differences (exact integers / 255 when quantised), nothing of image size written;
+  dsr_luma_pair            both cropped luma planes in one launch (they feed dsr_ssim_img_f32 with C = 1), optionally with the
+                           same partial sums: one read of each frame for both metrics;
+  dsr_rgb_to_y             one tensor's plane;
+  dsr_luma_psnr_finalize   per-image 10 log10(count / SSE_n), the reduction's total and the running state.
 """
 import ctypes as C
 import math
@@ -508,6 +521,202 @@ class _MSSSIMFunction(torch.autograd.Function):
         return None, out[0], out[1]
 
 
+# ============================================================================= Y-channel PSNR / SSIM with a border shave
+_LUMA_DTYPES = {torch.bfloat16: _lib.BF16, torch.float16: _lib.F16, torch.float32: _lib.F32}
+
+
+def _check_shave(name, shave):
+    if isinstance(shave, bool) or not isinstance(shave, numbers.Integral) or shave < 0:
+        raise ValueError(f"{name}: shave must be a non-negative integer, got {shave!r}")
+    return int(shave)
+
+
+def _check_rgb(name, x, shave, min_side):
+    """x: a floating-point [N, 3, H, W] tensor whose shaved region is at least min_side x min_side, on the device.
+    Returns (N, H, W)."""
+    if not torch.is_tensor(x) or x.dim() != 4:
+        raise ValueError(f"{name}: expected [N, 3, H, W] tensors, got "
+                         f"{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+    n, c, h, w = x.shape
+    if c != 3:
+        raise ValueError(f"{name}: the luma is defined for RGB, got {c} channels in {tuple(x.shape)}")
+    if n < 1:
+        raise ValueError(f"{name}: empty batch {tuple(x.shape)}")
+    if not x.is_floating_point():
+        raise ValueError(f"{name}: expected floating-point inputs, got {x.dtype}")
+    if h - 2 * shave < min_side or w - 2 * shave < min_side:
+        raise ValueError(f"{name}: shave={shave} leaves {max(h - 2 * shave, 0)}x{max(w - 2 * shave, 0)} of a {h}x{w} image; "
+                         f"at least {min_side}x{min_side} is needed")
+    return n, h, w
+
+
+def _check_rgb_pair(name, preds, target, shave, min_side):
+    for t in (preds, target):
+        if not torch.is_tensor(t) or t.dim() != 4:
+            raise ValueError(f"{name}: expected two [N, 3, H, W] tensors, got "
+                             f"{tuple(preds.shape) if torch.is_tensor(preds) else type(preds).__name__} and "
+                             f"{tuple(target.shape) if torch.is_tensor(target) else type(target).__name__}")
+    if preds.shape != target.shape:
+        raise ValueError(f"{name}: the two inputs must have one shape, got {tuple(preds.shape)} and {tuple(target.shape)}")
+    n, h, w = _check_rgb(name, preds, shave, min_side)
+    _check_rgb(name, target, shave, min_side)
+    if not (preds.is_cuda and target.is_cuda):
+        raise RuntimeError("deep-super-resolution_amd: tensors must live on the MI355X (cuda device); "
+                           "there is no CPU implementation of this path")
+    return n, h, w
+
+
+def _luma_in(t):
+    """(dtype code, tensor) as the luma kernels read it: fp32 / fp16 / bf16 as they are, any other float type as fp32."""
+    t = t.detach()
+    if t.dtype not in _LUMA_DTYPES:
+        t = t.float()
+    return _LUMA_DTYPES[t.dtype], t.contiguous()
+
+
+def rgb_to_y(x, shave=0, quantize=False):
+    """fp32 [N, 1, H - 2 shave, W - 2 shave]: the BT.601 luma ``(16 + 65.481 r + 128.553 g + 24.966 b) / 255`` of MATLAB's
+    ``rgb2ycbcr`` in unit scale (white 235/255, black 16/255) of an [N, 3, H, W] tensor in fp32, fp16 or bf16, with ``shave``
+    pixels cut from each border; ``quantize`` first rounds each channel to its 8-bit code, ``round(clamp(x, 0, 1) * 255) /
+    255``.  Not differentiable.  PARITY UNPINNED (see the module docstring)."""
+    shave = _check_shave("rgb_to_y", shave)
+    n, h, w = _check_rgb("rgb_to_y", x, shave, 1)
+    if not x.is_cuda:
+        raise RuntimeError("deep-super-resolution_amd: tensors must live on the MI355X (cuda device); "
+                           "there is no CPU implementation of this path")
+    dt, xx = _luma_in(x)
+    y = torch.empty(n, 1, h - 2 * shave, w - 2 * shave, dtype=torch.float32, device=x.device)
+    check(_lib.lib().dsr_rgb_to_y(dt, _ptr(xx), n, 3, h, w, shave, int(bool(quantize)), _ptr(y), _stream()))
+    return y
+
+
+def _luma_stats(name, preds, target, shave, quantize, planes):
+    """One pass over both images: (partial sums of dY^2, the two cropped luma planes or None)."""
+    n, _, h, w = preds.shape
+    lib = _lib.lib()
+    dev = preds.device
+    blocks = lib.dsr_luma_blocks(n, h, w, shave)
+    if blocks <= 0:
+        raise RuntimeError(f"{name}: {tuple(preds.shape)} is too large for one launch")
+    dp, p = _luma_in(preds)
+    dt, t = _luma_in(target)
+    sse = torch.empty(blocks, dtype=torch.float32, device=dev)
+    if not planes:
+        check(lib.dsr_luma_sse_stats(dp, _ptr(p), dt, _ptr(t), n, 3, h, w, shave, int(quantize), _ptr(sse), _stream()))
+        return sse, None, None
+    yp = torch.empty(n, 1, h - 2 * shave, w - 2 * shave, dtype=torch.float32, device=dev)
+    yt = torch.empty_like(yp)
+    check(lib.dsr_luma_pair(dp, _ptr(p), dt, _ptr(t), n, 3, h, w, shave, int(quantize), _ptr(yp), _ptr(yt),
+                            _ptr(sse) if planes == "both" else None, _stream()))
+    return (sse if planes == "both" else None), yp, yt
+
+
+def _luma_psnr(sse, n, h, w, shave, scale, state, dev, want_total=True):
+    """(per_image [N], total [1] or None) from the partial sums; `state` (float64 [4] or None) takes the batch."""
+    per = torch.empty(n, dtype=torch.float32, device=dev)
+    tot = torch.empty(1, dtype=torch.float32, device=dev) if want_total else None
+    check(_lib.lib().dsr_luma_psnr_finalize(_ptr(sse), n, h, w, shave, _ptr(per), _ptr(tot), scale, _ptr(state), _stream()))
+    return per, tot
+
+
+_SSIM_C1, _SSIM_C2 = 0.01 ** 2, 0.03 ** 2
+
+
+def _luma_ssim(yp, yt, scale, want_total=True):
+    """(per_image [N], total [1] or None): dsr_ssim_img_f32 on the two luma planes (C = 1, data_range 1)."""
+    n, _, h, w = yp.shape
+    lib = _lib.lib()
+    blocks = lib.dsr_ssim_img_blocks(n, 1, h, w)
+    if blocks <= 0:
+        raise RuntimeError(f"LumaStructuralSimilarityIndexMeasure: {tuple(yp.shape)} needs too many window tiles")
+    dev = yp.device
+    partial = torch.empty(blocks, dtype=torch.float32, device=dev)
+    per = torch.empty(n, dtype=torch.float32, device=dev)
+    tot = torch.empty(1, dtype=torch.float32, device=dev) if want_total else None
+    check(lib.dsr_ssim_img_f32(_ptr(yp), _ptr(yt), n, 1, h, w, _SSIM_C1, _SSIM_C2, _ptr(partial), _ptr(per), _ptr(tot), scale, 0,
+                               _stream()))
+    return per, tot
+
+
+def luma_psnr_ssim(preds, target, shave=0, quantize=True, with_ssim=True):
+    """(PSNR-Y [N], SSIM-Y [N] or None) per image, fp32 on the device, from ONE read of the two frames: the luma-pair launch
+    writes both cropped planes and the squared-error partials, then the PSNR fold and the SSIM tile + fold launches (4 launches;
+    2 without SSIM).  Nothing is read on the host.  The loop of ``evaluate.evaluate_generator(y_channel=True)``."""
+    name = "luma_psnr_ssim"
+    shave = _check_shave(name, shave)
+    n, h, w = _check_rgb_pair(name, preds, target, shave, _WIN if with_ssim else 1)
+    sse, yp, yt = _luma_stats(name, preds, target, shave, bool(quantize), "both" if with_ssim else None)
+    psnr, _ = _luma_psnr(sse, n, h, w, shave, 1.0, None, preds.device, want_total=False)
+    if not with_ssim:
+        return psnr, None
+    ssim, _ = _luma_ssim(yp, yt, 1.0, want_total=False)
+    return psnr, ssim
+
+
+class _LumaMetric(_PerImageMetric):
+    """Options, input checks and the forward / update pair shared by the two Y-channel metrics."""
+    _min_side = 1
+
+    def __init__(self, shave=0, quantize=True, reduction="elementwise_mean"):
+        super().__init__()
+        self.shave = _check_shave(type(self).__name__, shave)
+        self.quantize = bool(quantize)
+        self._init_state(reduction)
+
+    def update(self, preds, target):
+        self._batch(preds, target)
+
+    def forward(self, preds, target):
+        per, tot = self._batch(preds, target)
+        return per if self.reduction == "none" else tot.reshape(())
+
+    def _check(self, preds, target):
+        return _check_rgb_pair(type(self).__name__, preds, target, self.shave, self._min_side)
+
+
+class LumaPeakSignalNoiseRatio(_LumaMetric):
+    """PSNR on the luma plane, the way super-resolution tables report it (basicsr ``calculate_psnr(crop_border=shave,
+    test_y_channel=True)`` on the 8-bit output) -- PARITY UNPINNED: basicsr and MATLAB are not installed here, this restates
+    their documented behaviour.  Per image, ``10 log10(1 / mean(dY^2))`` over rows and columns ``[shave, size - shave)`` with
+    ``dY = (65.481 dr + 128.553 dg + 24.966 db) / 255`` and ``d. = q(preds.) - q(target.)``, ``q`` = the 8-bit quantisation
+    ``round(clamp(x, 0, 1) * 255) / 255`` when ``quantize`` (default) else the identity; ``+inf`` for identical images.
+
+    Reduced per image first (the SR convention, not torchmetrics' pooled batch MSE), then ``reduction``: 'elementwise_mean'
+    (0-dim), 'sum' (0-dim) or 'none' / None ([N]).  ``forward`` / ``update`` / ``compute`` / ``reset`` and the float64 device
+    state are those of the other per-image metrics here; inputs are [N, 3, H, W] in fp32, fp16 or bf16 (read as they are).
+    Nothing is read on the host, so a call can be captured in a HIP graph.  Not differentiable."""
+
+    def _batch(self, preds, target):
+        n, h, w = self._check(preds, target)
+        sse, _, _ = _luma_stats(type(self).__name__, preds, target, self.shave, self.quantize, None)
+        st = self._st
+        per, tot = _luma_psnr(sse, n, h, w, self.shave, self._total_scale(n), st.get(preds.device), preds.device)
+        if self.reduction == "none":
+            st.values.append(per.clone())
+        st.updated = True
+        return per, tot
+
+
+class LumaStructuralSimilarityIndexMeasure(_LumaMetric):
+    """SSIM on the luma plane, the way super-resolution tables report it (basicsr ``calculate_ssim(crop_border=shave,
+    test_y_channel=True)``) -- PARITY UNPINNED: basicsr and MATLAB are not installed here, this restates their documented
+    behaviour.  Both images become ``Y = (16 + 65.481 r + 128.553 g + 24.966 b) / 255`` of their 8-bit quantisation (when
+    ``quantize``, the default) over rows and columns ``[shave, size - shave)``; the per-image value is the SSIM of
+    ``StructuralSimilarityIndexMeasure`` (Gaussian 11x11, sigma 1.5, K1 0.01, K2 0.03, data_range 1) of that one plane, which
+    must be at least 11x11.  ``reduction``, the running state, dtypes and graph capture as for ``LumaPeakSignalNoiseRatio``.
+    Not differentiable."""
+    _min_side = _WIN
+
+    def _batch(self, preds, target):
+        self._check(preds, target)
+        _, yp, yt = _luma_stats(type(self).__name__, preds, target, self.shave, self.quantize, "planes")
+        per, tot = _luma_ssim(yp, yt, self._total_scale(preds.shape[0]))
+        self._accumulate(per)
+        return per, tot
+
+
 PSNR = PeakSignalNoiseRatio
 SSIM = StructuralSimilarityIndexMeasure
 MS_SSIM = MultiScaleStructuralSimilarityIndexMeasure
+PSNR_Y = LumaPeakSignalNoiseRatio
+SSIM_Y = LumaStructuralSimilarityIndexMeasure

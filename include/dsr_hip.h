@@ -599,6 +599,32 @@ int dsr_ema_update_multi(int count, float* const* shadow, const float* const* p,
 int dsr_ema_tick(int* n_averaged, const float* found_inf, dsr_stream_t s);
 int dsr_ema_swap_multi(int count, float* const* a, float* const* b, const size_t* n, dsr_stream_t s);
 
+/* ------------------------------------------------------------------ Y-channel PSNR / SSIM with a border shave (luma.hip)
+ * The evaluation protocol of the published super-resolution tables (metrics.LumaPeakSignalNoiseRatio,
+ * metrics.LumaStructuralSimilarityIndexMeasure, metrics.rgb_to_y; PARITY UNPINNED: restated from the documented behaviour of
+ * MATLAB's rgb2ycbcr and basicsr).  Images are [N][3][H][W] of dtype DSR_BF16, DSR_F16 or DSR_F32, read as they are and
+ * computed in fp32:
+ *   q(x) = rintf(fminf(fmaxf(x, 0), 1) * 255.0f) / 255 if quantize, else x;   Y = (16 + 65.481 r + 128.553 g + 24.966 b) / 255;
+ *   region: rows [shave, H - shave), columns [shave, W - shave), h x w = (H - 2 shave) x (W - 2 shave) >= 1 x 1.
+ * dsr_luma_blocks: the number of partial sums of one launch (N images, consecutive blocks per image; 0: bad sizes).
+ * dsr_luma_sse_stats: partial_sse[dsr_luma_blocks()] = per-block sums of dY^2 over the region, dY = (65.481 dr + 128.553 dg +
+ *   24.966 db) / 255 with d. = q(preds.) - q(target.) (the difference is taken per channel, before the weights).
+ * dsr_luma_pair: y_preds, y_target [N][1][h][w] fp32 = Y of the region of both images in one launch (h, w >= 11: they feed
+ *   dsr_ssim_img_f32 with C = 1), and, if partial_sse is not NULL, the same partial sums in the same pass.
+ * dsr_rgb_to_y: y [N][1][h][w] fp32 of one tensor.
+ * dsr_luma_psnr_finalize: per_image[n] = 10 log10(h w / SSE_n) (+inf for SSE_n == 0), the partials of an image folded in a
+ *   fixed order in double; value[0] = value_scale * sum_n per_image[n]; state (dsr_metric_accumulate's float64 pair): state[0]
+ *   += sum_n per_image[n], state[1] += N.  per_image, value, state: each nullable, not all three.  No atomics anywhere. */
+#define DSR_F32 2
+int dsr_luma_blocks(int N, int H, int W, int shave);
+int dsr_luma_sse_stats(int dtype_preds, const void* preds, int dtype_target, const void* target, int N, int C, int H, int W,
+                       int shave, int quantize, float* partial_sse, dsr_stream_t s);
+int dsr_luma_pair(int dtype_preds, const void* preds, int dtype_target, const void* target, int N, int C, int H, int W, int shave,
+                  int quantize, float* y_preds, float* y_target, float* partial_sse, dsr_stream_t s);
+int dsr_rgb_to_y(int dtype, const void* x, int N, int C, int H, int W, int shave, int quantize, float* y, dsr_stream_t s);
+int dsr_luma_psnr_finalize(const float* partial_sse, int N, int H, int W, int shave, float* per_image, float* value,
+                           float value_scale, double* state, dsr_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
