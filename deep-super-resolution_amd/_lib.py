@@ -15,6 +15,7 @@ BF16, F16 = 0, 1
 F32 = 2                  # the luma entry points (csrc/luma.hip) also read fp32 images
 ACT_NONE, ACT_LEAKY, ACT_PRELU, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_ELU = range(7)
 PAD_ZERO, PAD_REFLECT, PAD_REPLICATE = range(3)
+FEAT_L1, FEAT_MSE = 0, 1  # modes of the feature-loss taps (csrc/featloss.hip)
 
 
 class ConvDesc(C.Structure):
@@ -190,6 +191,13 @@ SIGNATURES = {
     "dsr_luma_pair": (_I, [_I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dsr_rgb_to_y": (_I, [_I, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "dsr_luma_psnr_finalize": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _P, _P]),
+    "dsr_featloss_blocks": (_I, [_Z]),
+    "dsr_featloss_tap_fwd": (_I, [_I, _P, _P, _P, _Z, _I, _I, _P, _P]),
+    "dsr_featloss_fold": (_I, [_P, _I, _F, _P, _P]),
+    "dsr_featloss_tap_bwd": (_I, [_I, _P, _P, _P, _P, _F, _I, _I, _P, _Z, _I, _P]),
+    "dsr_featloss_relu": (_I, [_I, _P, _P, _Z, _I, _P]),
+    "dsr_featloss_combine": (_I, [_I, C.POINTER(C.c_void_p), C.POINTER(_F), _P, _P]),
+    "dsr_featloss_combine_bwd": (_I, [_I, C.POINTER(_F), _P, _P, _P]),
 }
 
 _lib = None
@@ -203,7 +211,8 @@ _NO_LAUNCH = ("dsr_last_error", "dsr_abi_version", "dsr_conv_dgrad_ps_supported"
               "dsr_pw_reduce_blocks", "dsr_linear_fwd_workspace", "dsr_ssim_blocks", "dsr_lpips_tap_sizes", "dsr_lpips_distance_blocks",
               "dsr_ssim_img_blocks", "dsr_psnr_blocks", "dsr_lbfgs_workspace", "dsr_lbfgs_vector_floats", "dsr_clip_sumsq_partials",
               "dsr_linear_factor_gram_workspace", "dsr_linear_factor_gram_dots", "dsr_downsample_dense_wgrad_workspace",
-              "dsr_msssim_min_size", "dsr_msssim_pyramid_floats", "dsr_ssim_cs_img_blocks", "dsr_msssim_bwd_blocks", "dsr_luma_blocks")
+              "dsr_msssim_min_size", "dsr_msssim_pyramid_floats", "dsr_ssim_cs_img_blocks", "dsr_msssim_bwd_blocks", "dsr_luma_blocks",
+              "dsr_featloss_blocks")
 
 
 class _Lib:

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import (ACT_ELU, ACT_LEAKY, ACT_NONE, ACT_PRELU, ACT_RELU, ACT_SIGMOID, ACT_TANH, BF16, F16,  # noqa: F401
-                   PAD_REFLECT, PAD_REPLICATE, PAD_ZERO, ConvDesc, Epilogue, check)
+                   FEAT_L1, FEAT_MSE, PAD_REFLECT, PAD_REPLICATE, PAD_ZERO, ConvDesc, Epilogue, check)
 
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
@@ -620,7 +620,7 @@ class ConvAct(torch.autograd.Function):
             db = dprelu = None
         elif ctx.act == ACT_NONE and not ctx.ps:
             dy = dout
-            db = _colsum(dy, cout) if ctx.has_bias else None
+            db = _colsum(dy, cout) if (ctx.has_bias and ctx.needs_input_grad[2]) else None   # (a frozen trunk's bias: no pass)
             dprelu = None
         else:
             dy = torch.empty((n, oh, ow, cyp), dtype=x.dtype, device=x.device)
@@ -1053,6 +1053,98 @@ class ScaleLossDevice(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         return axpby(g.reshape(1), None, 1.0, 0.0, ctx.scale).reshape(()), None
+
+
+# ----------------------------------------------------------------------------- feature-space loss taps
+class FeatureTap(torch.autograd.Function):
+    """One tap of a feature-space loss on the 16-bit NHWC map where it lives (csrc/featloss.hip).
+
+    forward(f, t, mode, want_relu, c=None) -> (x_next, value): value = mean |f - t| (mode FEAT_L1) or mean (f - t)^2
+    (FEAT_MSE) over the N * c * H * W real elements (c defaults to the padded channel count; pad channels are zero in both
+    maps), a 1-element fp32 tensor.  want_relu: f is a PRE-activation map -- x_next is a new tensor max(f, 0), written by the
+    same pass, for the next layer; otherwise x_next is f itself and nothing is written.  Whatever consumes the map next must
+    consume x_next: the tap is then f's only consumer in the graph and its backward, ONE launch with one rounding per element,
+    adds the gradient arriving through x_next (times the ReLU mask when want_relu) to the tap's own term.  Either incoming
+    gradient may be None (the deepest tap has no next layer).  t gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, f, t, mode, want_relu, c=None):
+        _need_gpu(f)
+        if mode not in (FEAT_L1, FEAT_MSE):
+            raise ValueError(f"FeatureTap: mode {mode!r} is neither FEAT_L1 nor FEAT_MSE")
+        if f.dim() != 4 or f.shape != t.shape or f.dtype != t.dtype:
+            raise RuntimeError(f"FeatureTap: maps differ: {tuple(f.shape)} {f.dtype} vs {tuple(t.shape)} {t.dtype}")
+        f, t = f.contiguous(), t.contiguous()
+        n, h, w, cp = f.shape
+        p = n * h * w
+        count = p * (cp if c is None else int(c))
+        lib = _lib.lib()
+        blocks = lib.dsr_featloss_blocks(p)
+        part = torch.empty(max(blocks, 1), dtype=torch.float32, device=f.device)
+        x_next = torch.empty_like(f) if want_relu else None
+        check(lib.dsr_featloss_tap_fwd(_dt(f), _ptr(f), _ptr(t), _ptr(x_next), p, cp, mode, _ptr(part), _stream()))
+        value = torch.empty(1, dtype=torch.float32, device=f.device)
+        check(lib.dsr_featloss_fold(_ptr(part), blocks, float(count), _ptr(value), _stream()))
+        ctx.mode, ctx.masked, ctx.coef, ctx.pc = mode, bool(want_relu), 1.0 / count, (p, cp)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(f, t)
+        return (x_next if want_relu else f), value
+
+    @staticmethod
+    def backward(ctx, d_next, g_value):
+        f, t = ctx.saved_tensors
+        if not ctx.needs_input_grad[0] or (d_next is None and g_value is None):
+            return None, None, None, None, None
+        if g_value is None:
+            if not ctx.masked:
+                return d_next, None, None, None, None
+            g_value = torch.zeros(1, dtype=torch.float32, device=f.device)     # only the mask is left to apply
+        g = g_value.reshape(1).contiguous().float()
+        if d_next is not None:
+            d_next = d_next.contiguous()
+        p, cp = ctx.pc
+        df = torch.empty_like(f)
+        check(_lib.lib().dsr_featloss_tap_bwd(_dt(f), _ptr(f), _ptr(t), _ptr(d_next), _ptr(g), ctx.coef, ctx.mode,
+                                              int(ctx.masked), _ptr(df), p, cp, _stream()))
+        return df, None, None, None, None
+
+
+class WeightedSum(torch.autograd.Function):
+    """sum_k w_k * v_k over one-element device scalars with host weights, one launch each way (dsr_featloss_combine): the
+    weighted sum of a multi-tap loss without a chain of scale_loss / add_losses launches.  forward(weights, *values)."""
+
+    @staticmethod
+    def forward(ctx, weights, *values):
+        k = len(values)
+        vals = [v.reshape(1).contiguous().float() for v in values]
+        out = torch.empty(1, dtype=torch.float32, device=vals[0].device)
+        ctx.w = (C.c_float * k)(*[float(w) for w in weights])
+        check(_lib.lib().dsr_featloss_combine(k, (C.c_void_p * k)(*[v.data_ptr() for v in vals]), ctx.w, _ptr(out), _stream()))
+        ctx.shapes = [tuple(v.shape) for v in values]
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        k = len(ctx.shapes)
+        g = g.reshape(1).contiguous().float()
+        gout = torch.empty(k, dtype=torch.float32, device=g.device)
+        check(_lib.lib().dsr_featloss_combine_bwd(k, ctx.w, _ptr(g), _ptr(gout), _stream()))
+        return (None,) + tuple(gout[i:i + 1].reshape(s) for i, s in enumerate(ctx.shapes))
+
+
+def weighted_sum(values, weights):
+    if len(values) != len(weights) or not values:
+        raise ValueError("weighted_sum: one weight per value, at least one")
+    return WeightedSum.apply(tuple(float(w) for w in weights), *values)
+
+
+def relu16(x):
+    """max(x, 0) on a 16-bit NHWC map, no gradient (the target's trunk behind a pre-activation tap): dsr_featloss_relu."""
+    x = x.detach().contiguous()
+    n, h, w, cp = x.shape
+    out = torch.empty_like(x)
+    check(_lib.lib().dsr_featloss_relu(_dt(x), _ptr(x), _ptr(out), n * h * w, cp, _stream()))
+    return out
 
 
 _ambient_scale = None    # the open ambient_loss_scale context's device scalar (per process, like _wgrad_batch)

@@ -3,6 +3,7 @@
 gen_l1_step : BASELINE config 2 (generator-only x4, L1, Adam) -- defined by SURVEY.md 8(d).
 gen_lpips_step : the same step with the perceptual fine-tuning loss l1_weight * L1 + lpips_weight * LPIPS(fake, hr).
 gen_msssim_step : the same step with the structural loss alpha * (1 - MS-SSIM(fake, hr)) + (1 - alpha) * L1.
+gen_perceptual_step : the same step with the content loss l1_weight * L1 + VggFeatureLoss(fake, hr) (ESRGAN / Real-ESRGAN).
 gan_step    : train_GAN.py:38-71 (do_epoch): D step, then G step with the detached adversarial term.
 dip_step    : DIP.py:47-95 closure + utils/DIP.py:33-40 Adam iteration.
 """
@@ -72,6 +73,24 @@ def gen_msssim_step(gen, opt, msssim, lr_patches, hr_patches, alpha=0.84, *, sca
     opt.zero_grad()
     _backward_and_step(loss, opt, scaler, ema)
     return dis.detach(), l1.detach(), fake.detach()
+
+
+def gen_perceptual_step(gen, opt, vggfeat, lr_patches, hr_patches, l1_weight=1.0, *, scaler=None, ema=None):
+    """The pixel + content loss of the ESRGAN / Real-ESRGAN recipes (without the adversarial term):
+    loss = l1_weight * L1 + vggfeat(fake, hr).
+
+    `vggfeat`: a perceptual.VggFeatureLoss; its layer weights and perceptual_weight are the content term's whole weighting.
+    Build it with range_norm=True for a tanh generator and scale_images targets in [-1, 1].  Only `fake` requires a gradient.
+    Returns the unweighted L1 term, the (weighted) content term and `fake` as device tensors (no host sync here); usable
+    inside GraphedStep.  `scaler`: an optim.DynamicLossScaler around the summed loss (needed for compute_dtype=float16: the
+    feature loss keeps no gradient scale of its own)."""
+    fake = gen(lr_patches)
+    l1 = F.l1_loss(fake, hr_patches)
+    pc = vggfeat(fake, hr_patches)
+    loss = F.add_losses(F.scale_loss(l1, float(l1_weight)), pc)
+    opt.zero_grad()
+    _backward_and_step(loss, opt, scaler, ema)
+    return l1.detach(), pc.detach(), fake.detach()
 
 
 _side_streams = {}
@@ -160,7 +179,8 @@ def gan_step(gen, disc, perceptual, opt_g, opt_d, lr_patches, hr_patches, sync_g
     # --- generator (main stream)
     if hr_feat is not None:
         main.wait_event(hr_feat_ready)   # only the target features are needed here, not the D half queued behind them
-        hr_feat.record_stream(main)
+        for feat in (hr_feat if isinstance(hr_feat, (tuple, list)) else (hr_feat,)):     # (a multi-tap content loss: a tuple)
+            feat.record_stream(main)
     content = perceptual.content(fake, hr_patches, hr_feat)      # the only term of :59 with a gradient path
     opt_g.zero_grad()                                            # :62
     _mark("main: VGG content loss forward done", main)

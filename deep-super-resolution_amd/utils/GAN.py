@@ -194,9 +194,11 @@ def get_loss_D(real_output, fake_output, bce_loss=None):
 
 
 class PerceptualLoss(nn.Module):
-    def __init__(self, vgg_state_dict=None, resize_to=256, crop=224):
+    def __init__(self, vgg_state_dict=None, resize_to=256, crop=224, vgg_loss=None):
+        """vgg_loss: a module to use as the content term instead of the built-in Vgg19Loss (e.g. a
+        perceptual.VggFeatureLoss); it needs ``__call__(image1, image2, features2)`` and ``target_features(image)``."""
         super(PerceptualLoss, self).__init__()
-        self.vgg_loss = Vgg19Loss(vgg_state_dict, resize_to, crop)
+        self.vgg_loss = vgg_loss if vgg_loss is not None else Vgg19Loss(vgg_state_dict, resize_to, crop)
 
     def content(self, fake_output_G, HR_images, hr_features=None):
         return self.vgg_loss(fake_output_G, HR_images, hr_features)   # :119

@@ -625,6 +625,38 @@ int dsr_rgb_to_y(int dtype, const void* x, int N, int C, int H, int W, int shave
 int dsr_luma_psnr_finalize(const float* partial_sse, int N, int H, int W, int shave, float* per_image, float* value,
                            float value_scale, double* state, dsr_stream_t s);
 
+/* ------------------------------------------------------------------ feature-space loss taps (featloss.hip)
+ * The content term of SRGAN / ESRGAN / Real-ESRGAN (perceptual.VggFeatureLoss, functional.FeatureTap): a distance between two
+ * feature maps of a frozen trunk, taken on the 16-bit NHWC maps where they live.  f (generated image) and t (target) are
+ * [P][Cp], P = N H W pixels, Cp = round_up(C, 8) with zero pad channels in BOTH maps (they then contribute nothing), dtype
+ * DSR_BF16 or DSR_F16, 16-byte aligned.  mode: DSR_FEAT_L1 or DSR_FEAT_MSE.
+ * dsr_featloss_blocks: the number of fp32 partials of one tap (the grid of dsr_pw_reduce_blocks(P); 0 for P == 0).
+ * dsr_featloss_tap_fwd: partial[b] = block b's sum of |f - t| (L1) or (f - t)^2 (MSE), accumulated in fp32 from the 16-bit
+ *   values; relu_out (nullable, [P][Cp]): max(f, 0) written in the same pass -- a tap BEFORE the activation feeds the next
+ *   layer without a second read of the map.  Plain stores, no atomics: two calls on the same inputs give the same bits.
+ * dsr_featloss_fold: value[0] = (float)(sum of the partials, in a fixed order, in double) / count; count = N C H W, the number
+ *   of REAL elements, gives the unweighted mean.
+ * dsr_featloss_tap_bwd: one launch and one rounding per element,
+ *     df = (dnext ? dnext * m : 0) + g[0] * coef * d,
+ *   d = sign(f - t) with sign(0) = 0 (L1) or 2 (f - t) (MSE); m = (f > 0) if masked (the forward wrote relu_out: the ReLU's
+ *   backward rides here) else 1; dnext: the nullable 16-bit gradient arriving from the next layer; g: the device fp32 upstream
+ *   gradient of this tap's mean; coef: a host float, 1 / (N C H W) times any scale the caller folds in.
+ * dsr_featloss_relu: out = max(x, 0) on a map (the target's trunk behind a pre-activation tap).
+ * dsr_featloss_combine: out[0] = sum_k weights[k] * values[k][0] over n <= 32 one-element device scalars (HOST tables, read
+ *   before the call returns); dsr_featloss_combine_bwd: gout[k] = g[0] * weights[k], k < n.
+ * A null required pointer, Cp % 8 != 0, P == 0 or an unknown mode returns DSR_E_ARG before anything is launched. */
+#define DSR_FEAT_L1 0
+#define DSR_FEAT_MSE 1
+int dsr_featloss_blocks(size_t P);
+int dsr_featloss_tap_fwd(int dtype, const void* f, const void* t, void* relu_out, size_t P, int Cp, int mode, float* partial,
+                         dsr_stream_t s);
+int dsr_featloss_fold(const float* partial, int blocks, float count, float* value, dsr_stream_t s);
+int dsr_featloss_tap_bwd(int dtype, const void* f, const void* t, const void* dnext, const float* g, float coef, int mode,
+                         int masked, void* df, size_t P, int Cp, dsr_stream_t s);
+int dsr_featloss_relu(int dtype, const void* x, void* out, size_t P, int Cp, dsr_stream_t s);
+int dsr_featloss_combine(int n, const float* const* values, const float* weights, float* out, dsr_stream_t s);
+int dsr_featloss_combine_bwd(int n, const float* weights, const float* g, float* gout, dsr_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,231 @@
+"""CPU: the multi-layer VGG feature loss (perceptual.VggFeatureLoss) without a device -- the fp32 yardstick
+tests/vggfeat_ref.py against hand values and against oracle.vgg, the constructor's refusals, and the argument checks of the
+entry points of csrc/featloss.hip through the built library (every refusal precedes any launch)."""
+import ctypes
+import importlib
+import math
+
+import pytest
+import torch
+
+import vggfeat_ref
+from oracle import filler, vgg
+
+PKG = "deep-super-resolution_amd"
+E_ARG = -1
+
+
+def P(sub):
+    return importlib.import_module(PKG + "." + sub)
+
+
+@pytest.fixture(scope="module")
+def so():
+    return P("_build").build()
+
+
+# ----------------------------------------------------------------------------- the yardstick against hand values
+def _toy():
+    """Two convolutions with two live channels: conv1_1 channel 0 = x_r - 0.5, channel 1 = -x_r; conv1_2 channel 0 = 2 * relu1_1
+    channel 0.  Image 1 holds (1, 0.25, 0, 2) in its red plane, image 2 is zero."""
+    sd = {"0.weight": torch.zeros(64, 3, 3, 3), "0.bias": torch.zeros(64),
+          "2.weight": torch.zeros(64, 64, 3, 3), "2.bias": torch.zeros(64)}
+    sd["0.weight"][0, 0, 1, 1] = 1.0
+    sd["0.bias"][0] = -0.5
+    sd["0.weight"][1, 0, 1, 1] = -1.0
+    sd["2.weight"][0, 0, 1, 1] = 2.0
+    a = torch.zeros(1, 3, 2, 2)
+    a[0, 0] = torch.tensor([[1.0, 0.25], [0.0, 2.0]])
+    return sd, a, torch.zeros(1, 3, 2, 2)
+
+
+def test_yardstick_hand_values_pre_and_post_activation():
+    sd, a, b = _toy()
+    kw = dict(use_input_norm=False, range_norm=False)
+    n = 64 * 4                                                     # N C H W elements of a tap
+    # conv1_1: channel 0 is (0.5, -0.25, -0.5, 1.5) against -0.5: |d| = (1, 0.25, 0, 2); channel 1 is -x against 0: the same
+    t = vggfeat_ref.ref_terms(sd, a, b, {"conv1_1": 1.0, "relu1_1": 1.0, "conv1_2": 1.0}, "l1", **kw)
+    assert float(t["conv1_1"]) == pytest.approx(6.5 / n, rel=1e-6)
+    # relu1_1: channel 0 is (0.5, 0, 0, 1.5) against 0, channel 1 vanishes: the activation changes the term
+    assert float(t["relu1_1"]) == pytest.approx(2.0 / n, rel=1e-6)
+    assert float(t["conv1_2"]) == pytest.approx(4.0 / n, rel=1e-6)   # 2 * (0.5, 0, 0, 1.5)
+    t2 = vggfeat_ref.ref_terms(sd, a, b, {"conv1_2": 1.0}, "mse", **kw)
+    assert float(t2["conv1_2"]) == pytest.approx(10.0 / n, rel=1e-6)
+    assert float(vggfeat_ref.ref_terms(sd, a, b, {"conv1_2": 1.0}, "l2", **kw)["conv1_2"]) == float(t2["conv1_2"])
+    loss = vggfeat_ref.ref_loss(sd, a, b, {"conv1_1": 0.5, "conv1_2": 2.0}, "l1", **kw)
+    assert float(loss) == pytest.approx((0.5 * 6.5 + 2.0 * 4.0) / n, rel=1e-6)
+    # range_norm maps [-1, 1] to [0, 1] first: image 2a - 1 against 2b - 1 gives the same terms
+    t3 = vggfeat_ref.ref_terms(sd, 2 * a - 1, 2 * b - 1, {"conv1_1": 1.0}, "l1", use_input_norm=False, range_norm=True)
+    assert float(t3["conv1_1"]) == pytest.approx(6.5 / n, rel=1e-6)
+    # the ImageNet normalisation: the red plane becomes (x - 0.485) / 0.229
+    t4 = vggfeat_ref.ref_terms(sd, a, b, {"conv1_1": 1.0}, "l1", use_input_norm=True)
+    assert float(t4["conv1_1"]) == pytest.approx(6.5 / 0.229 / n, rel=1e-5)
+
+
+def test_layer_names_of_yardstick_and_module_agree():
+    table = vggfeat_ref.layer_table()
+    assert len(table) == 32
+    assert table["conv1_1"] == (0, False) and table["relu1_2"] == (2, True) and table["conv2_2"] == (7, False)
+    assert table["conv3_4"] == (16, False) and table["conv4_4"] == (25, False) and table["relu5_4"] == (34, True)
+    assert sorted({i for i, _ in table.values()}) == vgg.CONV_INDEX
+    pc = P("perceptual")
+    for name, (idx, post) in table.items():
+        ordinal, is_post = pc.parse_layer(name)
+        assert vgg.CONV_INDEX[ordinal] == idx and is_post == post, name
+    with pytest.raises(ValueError):
+        vggfeat_ref.taps({}, torch.zeros(1, 3, 2, 2), ["conv1_3"])
+
+
+def test_yardstick_equals_oracle_vgg_loss_for_the_reference_choice():
+    """{'relu5_4': 1}, 'mse', resize 32 / crop 28 is utils/GAN.py's content loss: the same fp32 torch ops as oracle.vgg."""
+    sd = P("utils.GAN")._standin_vgg_state()
+    a = filler.tensor("vggfeat:host_a", (2, 3, 40, 48))
+    b = filler.tensor("vggfeat:host_b", (2, 3, 40, 48))
+    want = float(vgg.vgg_loss(sd, a, b, 32, 28))
+    got = float(vggfeat_ref.ref_loss(sd, a, b, {"relu5_4": 1.0}, "mse", True, False, 32, 28))
+    assert want > 0 and abs(got - want) <= 1e-6 * want, (got, want)
+
+
+# ----------------------------------------------------------------------------- the module's refusals (no device needed)
+def test_import_and_construction_need_no_gpu():
+    pc = P("perceptual")
+    m = pc.VggFeatureLoss()
+    assert m.layer_names == ("conv5_4",) and m.depth == 16 and m.mode == P("_lib").FEAT_L1
+    keys = list(m.state_dict().keys())
+    assert keys[0] == "net.0.0.weight" and keys[-1] == "net.0.34.bias" and len(keys) == 32
+    assert not any(p.requires_grad for p in m.parameters())
+    ref = P("utils.GAN").Vgg19Loss()
+    for k, v in ref.state_dict().items():
+        assert torch.equal(v, m.state_dict()[k]), k
+    m5 = pc.VggFeatureLoss({"conv5_4": 1, "conv1_2": .1, "conv3_4": 1, "relu2_2": 0.0, "conv2_2": .1}, "l2", range_norm=True)
+    assert m5.layer_names == ("conv1_2", "conv2_2", "relu2_2", "conv3_4", "conv5_4") and m5.mode == P("_lib").FEAT_MSE
+    assert pc.VggFeatureLoss({"conv2_2": 1}).depth == 4
+    # range_norm and the ImageNet statistics fold into one affine map: ((x + 1) / 2 - m) / s = (x - (2 m - 1)) / (2 s)
+    assert m5.mean == pytest.approx((2 * 0.485 - 1, 2 * 0.456 - 1, 2 * 0.406 - 1)) and m5.std == pytest.approx((0.458, 0.448, 0.45))
+    assert pc.VggFeatureLoss(use_input_norm=False).mean == (0.0, 0.0, 0.0)
+
+
+@pytest.mark.parametrize("bad", ["conv6_1", "conv1_3", "relu3_5", "conv0_1", "pool1", "conv5_4 ", "Conv5_4", "relu5", 7])
+def test_unknown_layer_names_are_refused_by_name(bad):
+    with pytest.raises(ValueError, match="unknown layer") as e:
+        P("perceptual").VggFeatureLoss({bad: 1.0})
+    assert repr(bad) in str(e.value)
+
+
+def test_constructor_refusals():
+    V = P("perceptual").VggFeatureLoss
+    for w in (-0.1, math.nan, math.inf, "x", None):
+        with pytest.raises(ValueError, match="conv5_4"):
+            V({"conv5_4": w})
+    with pytest.raises(ValueError, match="at least one"):
+        V({"conv5_4": 0.0, "conv1_2": 0})
+    with pytest.raises(ValueError, match="empty"):
+        V({})
+    for crit in ("huber", "L1", None, 1):
+        with pytest.raises(ValueError, match="criterion"):
+            V(criterion=crit)
+    with pytest.raises(ValueError, match="perceptual_weight"):
+        V(perceptual_weight=-1.0)
+    with pytest.raises(ValueError, match="resize_to and crop"):
+        V(resize_to=48)
+    with pytest.raises(ValueError, match="resize_to and crop"):
+        V(crop=40)
+    with pytest.raises(ValueError, match="compute_dtype"):
+        V(compute_dtype=torch.float32)
+
+
+def test_sizes_the_pools_cannot_take_raise_before_any_launch():
+    """At its own size the trunk refuses an odd map in front of a pool that runs -- on the host, before a table or a tensor
+    reaches the device (so this needs none)."""
+    V = P("perceptual").VggFeatureLoss
+    z = torch.zeros(1, 3, 30, 32)                        # 30 -> 15: odd in front of the second pool
+    with pytest.raises(ValueError, match="odd"):
+        V({"conv3_1": 1.0})(z, z)
+    with pytest.raises(ValueError, match="odd"):
+        V({"conv3_1": 1.0}).target_features(z)
+    with pytest.raises(ValueError, match="odd"):
+        V({"conv2_1": 1.0})(torch.zeros(1, 3, 33, 32), torch.zeros(1, 3, 33, 32))
+    V({"conv2_2": 1.0})._check_size(30, 32)              # the second pool does not run behind conv2_2
+    V({"conv1_2": 1.0})._check_size(33, 31)              # ... nor the first behind conv1_2
+    V({"conv5_4": 1.0})._check_size(48, 32)
+    with pytest.raises(ValueError, match="odd"):
+        V({"conv5_4": 1.0})._check_size(48, 40)          # 40 -> 20 -> 10 -> 5
+    with pytest.raises(ValueError, match=r"\[N, 3, H, W\]"):
+        V()(torch.zeros(1, 1, 32, 32), torch.zeros(1, 1, 32, 32))
+
+
+def test_target_that_requires_grad_is_refused():
+    V = P("perceptual").VggFeatureLoss
+    a = torch.zeros(1, 3, 32, 32)
+    with pytest.raises(ValueError, match="image2"):
+        V()(a, a.clone().requires_grad_(True))
+
+
+def test_perceptual_loss_takes_a_supplied_content_module():
+    G, pc = P("utils.GAN"), P("perceptual")
+    m = pc.VggFeatureLoss({"conv5_4": 1.0})
+    assert G.PerceptualLoss(vgg_loss=m).vgg_loss is m
+    assert isinstance(G.PerceptualLoss(resize_to=32, crop=28).vgg_loss, G.Vgg19Loss)
+
+
+# ----------------------------------------------------------------------------- the C entries refuse bad arguments on the host
+def test_abi_version_is_still_7(so):
+    L = P("_lib")
+    assert L.ABI_VERSION == 7 and L.lib().dsr_abi_version() == 7
+    assert (L.FEAT_L1, L.FEAT_MSE) == (0, 1)
+
+
+def test_bad_arguments_return_e_arg_without_a_launch(so):
+    L = P("_lib")
+    lib = L.lib()
+    N, st = None, None
+    one = ctypes.c_void_p(4096)          # a non-null, aligned "pointer" that is never dereferenced: validation fails first
+    odd = ctypes.c_void_p(4100)          # ... and one that is not 16-byte aligned
+    calls = [
+        lambda: lib.dsr_featloss_tap_fwd(L.BF16, N, one, N, 64, 64, 0, one, st),           # f
+        lambda: lib.dsr_featloss_tap_fwd(L.BF16, one, N, N, 64, 64, 0, one, st),           # t
+        lambda: lib.dsr_featloss_tap_fwd(L.BF16, one, one, N, 64, 64, 0, N, st),           # partial
+        lambda: lib.dsr_featloss_tap_fwd(L.BF16, one, one, N, 64, 60, 0, one, st),         # Cp % 8
+        lambda: lib.dsr_featloss_tap_fwd(L.BF16, one, one, N, 64, 0, 0, one, st),          # Cp == 0
+        lambda: lib.dsr_featloss_tap_fwd(L.BF16, one, one, N, 0, 64, 0, one, st),          # P == 0
+        lambda: lib.dsr_featloss_tap_fwd(L.BF16, one, one, N, 64, 64, 2, one, st),         # mode
+        lambda: lib.dsr_featloss_tap_fwd(L.BF16, one, one, N, 64, 64, -1, one, st),
+        lambda: lib.dsr_featloss_tap_fwd(2, one, one, N, 64, 64, 0, one, st),              # dtype
+        lambda: lib.dsr_featloss_tap_fwd(L.BF16, odd, one, N, 64, 64, 0, one, st),         # alignment
+        lambda: lib.dsr_featloss_tap_fwd(L.BF16, one, one, odd, 64, 64, 0, one, st),
+        lambda: lib.dsr_featloss_fold(N, 4, 64.0, one, st),
+        lambda: lib.dsr_featloss_fold(one, 4, 64.0, N, st),
+        lambda: lib.dsr_featloss_fold(one, 0, 64.0, one, st),
+        lambda: lib.dsr_featloss_fold(one, 4, 0.0, one, st),
+        lambda: lib.dsr_featloss_tap_bwd(L.BF16, N, one, N, one, 1.0, 0, 0, one, 64, 64, st),     # f
+        lambda: lib.dsr_featloss_tap_bwd(L.BF16, one, N, N, one, 1.0, 0, 0, one, 64, 64, st),     # t
+        lambda: lib.dsr_featloss_tap_bwd(L.BF16, one, one, N, N, 1.0, 0, 0, one, 64, 64, st),     # g
+        lambda: lib.dsr_featloss_tap_bwd(L.BF16, one, one, N, one, 1.0, 0, 0, N, 64, 64, st),     # df
+        lambda: lib.dsr_featloss_tap_bwd(L.BF16, one, one, one, one, 1.0, 0, 1, one, 64, 12, st), # Cp % 8
+        lambda: lib.dsr_featloss_tap_bwd(L.BF16, one, one, one, one, 1.0, 0, 1, one, 0, 64, st),  # P == 0
+        lambda: lib.dsr_featloss_tap_bwd(L.BF16, one, one, one, one, 1.0, 5, 1, one, 64, 64, st), # mode
+        lambda: lib.dsr_featloss_tap_bwd(7, one, one, one, one, 1.0, 0, 1, one, 64, 64, st),      # dtype
+        lambda: lib.dsr_featloss_tap_bwd(L.BF16, one, one, odd, one, 1.0, 0, 1, one, 64, 64, st), # alignment
+        lambda: lib.dsr_featloss_relu(L.BF16, N, one, 64, 64, st),
+        lambda: lib.dsr_featloss_relu(L.BF16, one, N, 64, 64, st),
+        lambda: lib.dsr_featloss_relu(L.BF16, one, one, 0, 64, st),
+        lambda: lib.dsr_featloss_relu(L.BF16, one, one, 64, 7, st),
+        lambda: lib.dsr_featloss_combine(1, N, (ctypes.c_float * 1)(1.0), one, st),
+        lambda: lib.dsr_featloss_combine(1, (ctypes.c_void_p * 1)(4096), (ctypes.c_float * 1)(1.0), N, st),
+        lambda: lib.dsr_featloss_combine(1, (ctypes.c_void_p * 1)(4096), N, one, st),
+        lambda: lib.dsr_featloss_combine(1, (ctypes.c_void_p * 1)(None), (ctypes.c_float * 1)(1.0), one, st),
+        lambda: lib.dsr_featloss_combine(0, (ctypes.c_void_p * 1)(4096), (ctypes.c_float * 1)(1.0), one, st),
+        lambda: lib.dsr_featloss_combine(33, (ctypes.c_void_p * 33)(*[4096] * 33), (ctypes.c_float * 33)(), one, st),
+        lambda: lib.dsr_featloss_combine_bwd(1, (ctypes.c_float * 1)(1.0), N, one, st),
+        lambda: lib.dsr_featloss_combine_bwd(1, (ctypes.c_float * 1)(1.0), one, N, st),
+        lambda: lib.dsr_featloss_combine_bwd(1, N, one, one, st),
+        lambda: lib.dsr_featloss_combine_bwd(0, (ctypes.c_float * 1)(1.0), one, one, st),
+    ]
+    for i, call in enumerate(calls):
+        assert call() == E_ARG, i
+        assert b"featloss" in lib.dsr_last_error(), i
+    # the grid of one tap is that of the other pointwise reductions
+    rpb = ctypes.c_int()
+    assert lib.dsr_featloss_blocks(0) == 0
+    for p in (1, 70, 4551, 32 * 128 * 128):
+        assert lib.dsr_featloss_blocks(p) == lib.dsr_pw_reduce_blocks(p, ctypes.byref(rpb)) >= 1
