@@ -53,6 +53,9 @@ SIGNATURES = {
                                 C.POINTER(C.c_int), _I, _I, _I, _P, _P]),
     "dsr_patch_batch_u8_d4": (_I, [_I, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _I, _P, _P]),
+    "dsr_degrade_batch_u8": (_I, [_I, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                  C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P]),
+    "dsr_degrade_image_u8": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "dsr_d4_expand_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "dsr_d4_mean_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "dsr_conv_fwd_affine_supported": (_I, [_DESC]),

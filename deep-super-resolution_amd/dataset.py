@@ -6,7 +6,8 @@
   PatchBank   what the reference's DataLoader + GANDIV2KDataset amount to for a training step, restructured for the device: the
         whole (pre-shrunk) image set lives in HBM as uint8 and ``sample(batch)`` cuts and converts a batch of LR / HR patch
         pairs in two kernel launches -- the step is fed at its own rate instead of the host's; ``augment=True`` flips /
-        turns each pair by a random element of D4 in the same launches.
+        turns each pair by a random element of D4 in the same launches; ``degradation=BlindDegradation(...)`` makes the LR
+        patch from the HR image with a fresh blur kernel and noise level per sample (csrc/degrade.hip).
 
 The reference scales by 255 twice (ToTensor at :59-60, then scale_images :152,155): ``reference_scaling=True`` (default)
 reproduces that, bit for bit; ``False`` gives the [0,1] / [-1,1] ranges its comments describe (SURVEY.md 8f row 1 asks for
@@ -23,6 +24,7 @@ from .functional import _ptr, _stream, check
 from .utils import degradation
 
 PATCH_UNIT, PATCH_LR_REF, PATCH_HR_REF, PATCH_HR_UNIT = range(4)
+BlindDegradation = degradation.BlindDegradation
 
 
 def _device(device):
@@ -188,38 +190,94 @@ class PatchBank:
     augment: every sample is flipped / turned by one of the eight D4 codes (`patch_batch`), the same for its LR and its HR
         patch, in the launches that cut them (dsr_patch_batch_u8_d4).  The codes are drawn AFTER all indices and positions, so
         a seeded bank crops the same patches with and without augmentation; a non-square patch only gets the four codes that
-        keep its shape."""
+        keep its shape.
+    degradation: a `BlindDegradation`.  The LR patch is then cut from the HR image by dsr_degrade_batch_u8 with a fresh blur
+        kernel (and noise level) per sample: ``LR = quant(clip((HR (*) k)[offset::s, offset::s] + sigma * z))``.  The LR image
+        of a pair only supplies the size of the LR grid and may be None (the grid is then HR // s); the HR patch comes from
+        the same launch as without it.  The kernels and noise levels are drawn AFTER the indices, positions and D4 codes (a
+        seeded bank crops the same patches, with the same codes, with and without `degradation`): the kernels by
+        ``degradation.random_kernels`` (four uniform draws per sample), then, only if the noise range is not (0, 0), `batch`
+        uniform noise levels.  The noise itself is ``torch.randn`` on the device (`generator`).  ``last_kernels`` /
+        ``last_noise_std`` hold the device tensors of the values used, e.g. as targets of a kernel estimator."""
 
-    def __init__(self, pairs, scale_factor, LR_patch_size, reference_scaling=True, rng=None, augment=False):
-        self.lr = [p[0].contiguous() for p in pairs]
-        self.hr = [p[1].contiguous() for p in pairs]
-        if not self.lr:
+    def __init__(self, pairs, scale_factor, LR_patch_size, reference_scaling=True, rng=None, augment=False, degradation=None,
+                 generator=None):
+        pairs = list(pairs)
+        if not pairs:
             raise ValueError("PatchBank needs at least one image pair")
-        for a, b in zip(self.lr, self.hr):
-            if b.shape[0] < a.shape[0] * scale_factor or b.shape[1] < a.shape[1] * scale_factor:
+        if degradation is not None:
+            degradation.validate(scale_factor)
+        elif any(p[0] is None for p in pairs):
+            raise ValueError("a pair without an LR image needs a `degradation` that makes one")
+        self.lr = [None if p[0] is None else p[0].contiguous() for p in pairs]
+        self.hr = [p[1].contiguous() for p in pairs]
+        # (h, w) of each LR grid: what the patch positions are drawn in
+        self.grid = [(b.shape[0] // scale_factor, b.shape[1] // scale_factor) if a is None else (a.shape[0], a.shape[1])
+                     for a, b in zip(self.lr, self.hr)]
+        for (h, w), b in zip(self.grid, self.hr):
+            if b.shape[0] < h * scale_factor or b.shape[1] < w * scale_factor:
                 raise ValueError("an HR image is smaller than scale_factor x its LR image")
         self.scale, self.patch = scale_factor, tuple(LR_patch_size)
         self.modes = (PATCH_LR_REF, PATCH_HR_REF) if reference_scaling else (PATCH_UNIT, PATCH_HR_UNIT)
         self.rng = np.random if rng is None else rng
         self.augment = bool(augment)
+        self.degradation, self.generator = degradation, generator
+        self.last_kernels = self.last_noise_std = None
 
-    def sample(self, batch, indices=None, transforms=None):
+    def sample(self, batch, indices=None, transforms=None, kernels=None, noise_std=None):
         """(LR [B,3,ph,pw], HR [B,3,ph*s,pw*s]) fp32 device batches; image b is `indices[b]` (default: uniform draws).
-        ``transforms``: explicit D4 codes, one per sample, instead of the draw (also without ``augment``)."""
+        ``transforms``: explicit D4 codes, one per sample, instead of the draw (also without ``augment``).
+        ``kernels`` (fp32 [B, ks, ks], numpy or tensor) / ``noise_std`` ([B], 0..255 units): explicit blur kernels / noise
+        levels instead of the draws of a bank with a ``degradation``."""
         pw, ph = self.patch
+        n = batch if indices is None else len(indices)
         if transforms is not None:
-            transforms = _check_transforms(transforms, batch if indices is None else len(indices), ph, pw)
+            transforms = _check_transforms(transforms, n, ph, pw)
+        deg = self.degradation
+        if deg is None and (kernels is not None or noise_std is not None):
+            raise ValueError("kernels / noise_std need a bank with a `degradation`")
+        if kernels is not None:
+            shape = tuple(kernels.shape)
+            if len(shape) != 3 or shape[0] != n or shape[1] != shape[2] or shape[1] % 2 == 0 or shape[1] > degradation.KERNEL_SIZE_MAX:
+                raise ValueError(f"kernels: {shape} is not [{n}, ks, ks] with an odd ks <= {degradation.KERNEL_SIZE_MAX}")
+        if noise_std is not None:
+            noise_std = np.asarray(noise_std.cpu() if torch.is_tensor(noise_std) else noise_std, dtype=np.float32).reshape(-1)
+            if noise_std.shape[0] != n or bool((noise_std < 0).any()):
+                raise ValueError(f"noise_std: {n} non-negative levels expected")
         if indices is None:
-            indices = [int(self.rng.randint(0, len(self.lr))) for _ in range(batch)]
+            indices = [int(self.rng.randint(0, len(self.hr))) for _ in range(batch)]
         tops, lefts, htops, hlefts = [], [], [], []
         for i in indices:
-            t, l, ht, hl = train_patch_coords(self.lr[i].shape[0], self.lr[i].shape[1], self.patch, self.scale, self.rng)
+            t, l, ht, hl = train_patch_coords(self.grid[i][0], self.grid[i][1], self.patch, self.scale, self.rng)
             tops.append(t), lefts.append(l), htops.append(ht), hlefts.append(hl)
         if transforms is None and self.augment:
             if ph == pw:
                 transforms = [int(self.rng.randint(0, 8)) for _ in indices]
             else:
                 transforms = [2 * int(self.rng.randint(0, 4)) for _ in indices]
-        lr = patch_batch([self.lr[i] for i in indices], tops, lefts, ph, pw, self.modes[0], transforms)
+        if deg is None:
+            lr = patch_batch([self.lr[i] for i in indices], tops, lefts, ph, pw, self.modes[0], transforms)
+        else:
+            lr = self._degraded(deg, indices, tops, lefts, transforms, kernels, noise_std)
         hr = patch_batch([self.hr[i] for i in indices], htops, hlefts, ph * self.scale, pw * self.scale, self.modes[1], transforms)
         return lr, hr
+
+    def _degraded(self, deg, indices, tops, lefts, transforms, kernels, noise_std):
+        pw, ph = self.patch
+        n = len(indices)
+        dev = self.hr[0].device
+        if kernels is None:
+            kernels = degradation.random_kernels(n, deg.kernel_size, deg.sigma, deg.iso_prob, self.rng)
+        if noise_std is None and deg.noise_std[1] > 0:
+            noise_std = np.asarray(self.rng.uniform(deg.noise_std[0], deg.noise_std[1], n), dtype=np.float32)
+        if isinstance(kernels, np.ndarray):
+            kernels = torch.from_numpy(np.ascontiguousarray(kernels, dtype=np.float32))
+        self.last_kernels = kernels.to(device=dev, dtype=torch.float32).contiguous()            # one transfer
+        z = None
+        self.last_noise_std = None
+        if noise_std is not None:
+            self.last_noise_std = torch.from_numpy(noise_std).to(dev)                           # one transfer
+            z = torch.randn((n, 3, ph, pw), dtype=torch.float32, device=dev, generator=self.generator)
+        return degradation.degrade_batch([self.hr[i] for i in indices], tops, lefts, ph, pw, self.scale, self.last_kernels,
+                                         offset=deg.offset, noise=z, noise_std=self.last_noise_std, quantise=deg.quantise,
+                                         mode=self.modes[0], transforms=transforms)

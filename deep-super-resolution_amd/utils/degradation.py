@@ -8,6 +8,11 @@ Bit-exactness: ``downsample`` reproduces Pillow's 8-bit bicubic resampler (fixed
 libImaging/Resample.c's precompute_coeffs, the two passes run in csrc/data.hip); the noise functions draw from numpy's global
 generator in the reference's order by default (``rng="numpy"``: same pixels as the reference for the same seed) or on the
 device (``rng="device"``: torch's generator, for throughput).
+
+Beyond the reference, the blind degradation of SRMD / IKC / KernelGAN / BSRGAN (csrc/degrade.hip):
+``LR = quant(clip((HR (*) k)[offset::s, offset::s] + sigma * z))`` with a blur kernel per sample -- ``gaussian_kernel`` and
+``random_kernels`` make the kernels on the host, ``blur_downsample`` degrades a whole image to uint8 and ``degrade_batch``
+cuts a batch of degraded LR patches straight out of HR images (``dataset.PatchBank(degradation=...)`` is built on it).
 """
 import ctypes as C
 import math
@@ -148,3 +153,139 @@ def add_salt_pepper_noise(image, s=0.01, p=0.01, rng="numpy"):
     out = torch.empty_like(img)
     check(_lib.lib().dsr_salt_pepper_u8(_ptr(img), _ptr(salt), _ptr(pepper), _ptr(out), h, w, c, _stream()))
     return restore(out)
+
+
+# ------------------------------------------------------------------ blind degradation (csrc/degrade.hip)
+KERNEL_SIZE_MAX = 21
+
+
+def gaussian_kernel(size, sigma_x, sigma_y=None, theta=0.0):
+    """fp32 [size, size] bivariate Gaussian with covariance R diag(sigma_x^2, sigma_y^2) R^T (R: rotation by `theta`),
+    evaluated in float64 at (x, y) = (j - r, i - r), r = size // 2, normalised to sum 1 and rounded to fp32 once.
+    ``sigma_y=None``: isotropic."""
+    size = int(size)
+    if size < 1 or size % 2 == 0:
+        raise ValueError(f"gaussian_kernel: size {size} is not a positive odd number")
+    sigma_y = sigma_x if sigma_y is None else sigma_y
+    if not (sigma_x > 0 and sigma_y > 0):
+        raise ValueError("gaussian_kernel: sigmas must be positive")
+    r = size // 2
+    y, x = np.meshgrid(np.arange(size, dtype=np.float64) - r, np.arange(size, dtype=np.float64) - r, indexing="ij")
+    c, sn = math.cos(theta), math.sin(theta)
+    u, v = c * x + sn * y, -sn * x + c * y                          # R^T (x, y): the coordinates along the two axes
+    k = np.exp(-0.5 * (u * u / (float(sigma_x) ** 2) + v * v / (float(sigma_y) ** 2)))
+    return (k / k.sum()).astype(np.float32)
+
+
+def random_kernels(n, size=21, sigma=(0.2, 3.0), iso_prob=0.5, rng=None):
+    """fp32 [n, size, size] random Gaussian blur kernels on the host.  Per sample, in this order, four ``rng.uniform`` draws:
+    u in [0, 1) (isotropic iff u < iso_prob), sigma_x and sigma_y in [sigma[0], sigma[1]), theta in [-pi, pi).  All four are
+    always drawn; an isotropic sample uses sigma_x alone.  `rng` defaults to numpy's global generator."""
+    rng = np.random if rng is None else rng
+    lo, hi = float(sigma[0]), float(sigma[1])
+    if not 0 < lo <= hi:
+        raise ValueError(f"random_kernels: sigma range ({lo}, {hi}) is not 0 < low <= high")
+    out = np.empty((n, size, size), dtype=np.float32)
+    for b in range(n):
+        iso = float(rng.uniform(0.0, 1.0)) < iso_prob
+        sx = float(rng.uniform(lo, hi))
+        sy = float(rng.uniform(lo, hi))
+        theta = float(rng.uniform(-math.pi, math.pi))
+        out[b] = gaussian_kernel(size, sx) if iso else gaussian_kernel(size, sx, sy, theta)
+    return out
+
+
+def _device_kernels(kernels, n, device):
+    """-> contiguous fp32 [n, ks, ks] on `device` (one upload when the kernels come from the host)"""
+    k = torch.from_numpy(np.ascontiguousarray(kernels, dtype=np.float32)) if isinstance(kernels, np.ndarray) else kernels
+    if not torch.is_tensor(k) or k.dtype != torch.float32 or k.dim() != 3 or k.shape[0] != n or k.shape[1] != k.shape[2]:
+        raise ValueError(f"kernels must be fp32 [{n}, ks, ks]")
+    ks = int(k.shape[1])
+    if ks % 2 == 0 or ks > KERNEL_SIZE_MAX:
+        raise ValueError(f"kernel size {ks} is not an odd number in 1..{KERNEL_SIZE_MAX}")
+    return k.to(device).contiguous(), ks
+
+
+def blur_downsample(image, kernel, factor, offset=0, noise_std=0.0, generator=None):
+    """uint8 [H, W, 3] -> uint8 [h, w, 3], h = ceil((H - offset) / factor): the image blurred with `kernel` (fp32 [ks, ks],
+    reflected borders), sampled at ``[offset::factor, offset::factor]``, plus ``noise_std`` (0..255 units) times a standard
+    normal drawn on the device (only when noise_std > 0; `generator`: a torch.Generator), clipped and rounded half to even.
+    The image may be a device tensor, a numpy array or a PIL image and comes back in that type."""
+    img, restore = _to_device(image)
+    if img.shape[2] != 3:
+        raise TypeError("blur_downsample: an RGB image [H, W, 3] is expected")
+    k, ks = _device_kernels(kernel[None] if getattr(kernel, "ndim", 0) == 2 else kernel, 1, img.device)
+    H, W = int(img.shape[0]), int(img.shape[1])
+    factor, offset = int(factor), int(offset)
+    if factor < 1 or not 0 <= offset < factor:
+        raise ValueError(f"blur_downsample: factor {factor}, offset {offset}")
+    h, w = (H - offset + factor - 1) // factor, (W - offset + factor - 1) // factor
+    z = std = None
+    if noise_std > 0:
+        z = torch.randn((3, h, w), dtype=torch.float32, device=img.device, generator=generator)
+        std = torch.full((1,), float(noise_std), dtype=torch.float32, device=img.device)
+    out = torch.empty((h, w, 3), dtype=torch.uint8, device=img.device)
+    check(_lib.lib().dsr_degrade_image_u8(_ptr(img), H, W, factor, offset, _ptr(k), ks, None if z is None else _ptr(z),
+                                          None if std is None else _ptr(std), _ptr(out), _stream()))
+    return restore(out)
+
+
+def degrade_batch(images, tops, lefts, ph, pw, scale, kernels, offset=0, noise=None, noise_std=None, quantise=True, mode=0,
+                  transforms=None):
+    """fp32 [B, 3, ph, pw] batch of degraded LR patches, patch b cut from the uint8 [H, W, 3] HR device image images[b] at the
+    LR position (tops[b], lefts[b]): the counterpart of ``dataset.patch_batch`` (same `mode` and `transforms`), one launch of
+    dsr_degrade_batch_u8.  kernels: fp32 [B, ks, ks] (device tensor, or numpy: uploaded once); noise: device fp32 [B, 3, ph, pw]
+    standard-normal draws with noise_std: fp32 [B] in 0..255 units (device tensor or a sequence), both or neither."""
+    from ..dataset import _check_transforms
+    n = len(images)
+    if not (n == len(tops) == len(lefts)) or n == 0:
+        raise ValueError("degrade_batch: images, tops and lefts must be equally long and non-empty")
+    codes = None if transforms is None else _check_transforms(transforms, n, ph, pw)
+    if (noise is None) != (noise_std is None):
+        raise ValueError("degrade_batch: noise and noise_std go together")
+    for im in images:
+        if not (torch.is_tensor(im) and im.is_cuda and im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3
+                and im.is_contiguous()):
+            raise TypeError("degrade_batch: images must be contiguous uint8 [H, W, 3] tensors on the device")
+    dev = images[0].device
+    k, ks = _device_kernels(kernels, n, dev)
+    if noise is not None:
+        if not (torch.is_tensor(noise) and noise.dtype == torch.float32 and tuple(noise.shape) == (n, 3, ph, pw)):
+            raise ValueError(f"degrade_batch: noise must be fp32 [{n}, 3, {ph}, {pw}]")
+        noise = noise.to(dev).contiguous()
+        if not torch.is_tensor(noise_std):
+            noise_std = torch.tensor([float(v) for v in noise_std], dtype=torch.float32)
+        if noise_std.dtype != torch.float32 or tuple(noise_std.shape) != (n,):
+            raise ValueError(f"degrade_batch: noise_std must be fp32 [{n}]")
+        noise_std = noise_std.to(dev).contiguous()
+    out = torch.empty((n, 3, ph, pw), dtype=torch.float32, device=dev)
+    ptrs = (C.c_void_p * n)(*[im.data_ptr() for im in images])
+    ints = lambda v: (C.c_int * n)(*[int(q) for q in v])
+    check(_lib.lib().dsr_degrade_batch_u8(n, ptrs, ints([im.shape[0] for im in images]), ints([im.shape[1] for im in images]),
+                                          ints(tops), ints(lefts), None if codes is None else ints(codes), ph, pw, int(scale),
+                                          int(offset), _ptr(k), ks, None if noise is None else _ptr(noise),
+                                          None if noise is None else _ptr(noise_std), int(bool(quantise)), int(mode), _ptr(out),
+                                          _stream()))
+    return out
+
+
+class BlindDegradation:
+    """What ``dataset.PatchBank(degradation=...)`` draws per sample: a Gaussian blur kernel of `kernel_size` as
+    ``random_kernels(sigma=, iso_prob=)`` and a noise level, uniform in `noise_std` = (low, high) in 0..255 units (no noise
+    when high is 0); `quantise`: round the LR patch to whole grey levels; `offset`: the sampling phase in 0..scale-1."""
+
+    def __init__(self, kernel_size=21, sigma=(0.2, 3.0), iso_prob=0.5, noise_std=(0.0, 0.0), quantise=True, offset=0):
+        self.kernel_size, self.sigma, self.iso_prob = int(kernel_size), (float(sigma[0]), float(sigma[1])), float(iso_prob)
+        self.noise_std, self.quantise, self.offset = (float(noise_std[0]), float(noise_std[1])), bool(quantise), int(offset)
+
+    def validate(self, scale):
+        if self.kernel_size < 1 or self.kernel_size % 2 == 0 or self.kernel_size > KERNEL_SIZE_MAX:
+            raise ValueError(f"BlindDegradation: kernel_size {self.kernel_size} is not an odd number in 1..{KERNEL_SIZE_MAX}")
+        if not 0 < self.sigma[0] <= self.sigma[1]:
+            raise ValueError(f"BlindDegradation: sigma range {self.sigma} is not 0 < low <= high")
+        if not 0.0 <= self.iso_prob <= 1.0:
+            raise ValueError(f"BlindDegradation: iso_prob {self.iso_prob}")
+        if not 0.0 <= self.noise_std[0] <= self.noise_std[1]:
+            raise ValueError(f"BlindDegradation: noise_std range {self.noise_std} is not 0 <= low <= high")
+        if not 0 <= self.offset < scale:
+            raise ValueError(f"BlindDegradation: offset {self.offset} is not in 0..{scale - 1}")

@@ -555,6 +555,28 @@ int dsr_d4_expand_f32(const float* src, int planes, int h, int w, int mask, floa
  * summed in fp32 in exactly that order (the first term is taken as it is): the result is defined bit for bit. */
 int dsr_d4_mean_f32(const float* src_even, const float* src_odd, int planes, int H, int W, int mask, float* dst, dsr_stream_t s);
 
+/* ------------------------------------------------------------------ blind degradation (degrade.hip)
+ * LR = quant(clip((HR (*) k) sampled every `scale`-th pixel + sigma * z)) on uint8 [H][W][3] device images, a blur kernel and
+ * a noise level per sample.  LR pixel (Y, X) of the LR grid, channel c, r = ks / 2, taps in row-major order:
+ *   acc = 0;  for i, for j:  acc = fmaf(k[i][j], (float)HR[refl(s*Y + offset + i - r, H)][refl(s*X + offset + j - r, W)][c], acc)
+ *   if noise:  acc = fmaf(noise_std[b], z[b][c][y][x], acc)        (z at the OUTPUT position, after the D4 code)
+ *   acc = min(max(acc, 0), 255);  if quantise: acc = rintf(acc)    (half to even)
+ *   v = acc / 255.0f, then the scaling `mode` selects, as dsr_patch_batch_u8
+ * refl: reflection at the borders of the whole image without repeating the edge (-1 -> 1, H -> H - 2).  offset = 0 samples
+ * blurred[0::s, 0::s].  Both entry points run the same code: a patch equals that region of the whole image bit for bit. */
+/* dsr_patch_batch_u8_d4 cutting LR patches out of HR images: HOST tables as there, tops / lefts in LR pixels, xforms NULL for
+ * no D4 codes; kernels: device fp32 [count][ks][ks], ks odd in 1..21 and ks / 2 < min(H, W); scale in 1..8, offset in
+ * 0..scale-1; noise: device fp32 [count][3][ph][pw] standard-normal draws or NULL, noise_std: device fp32 [count] in 0..255
+ * units (given exactly when noise is); out: fp32 [count][3][ph][pw].  The centre scale * (top + ph - 1) + offset of the last
+ * row (column) of a patch has to lie inside its image. */
+int dsr_degrade_batch_u8(int count, const unsigned char* const* images, const int* heights, const int* widths, const int* tops,
+                         const int* lefts, const int* xforms, int ph, int pw, int scale, int offset, const float* kernels, int ks,
+                         const float* noise, const float* noise_std, int quantise, int mode, float* out, dsr_stream_t s);
+/* One image, one kernel [ks][ks]: out uint8 [h][w][3], h = (H - offset + scale - 1) / scale and w likewise, always clipped and
+ * rounded; noise: device fp32 [3][h][w] or NULL, noise_std: device fp32 [1] */
+int dsr_degrade_image_u8(const unsigned char* image, int H, int W, int scale, int offset, const float* kernel, int ks,
+                         const float* noise, const float* noise_std, unsigned char* out, dsr_stream_t s);
+
 /* ------------------------------------------------------------------ L-BFGS (lbfgs.hip)
  * torch.optim.LBFGS with line_search_fn=None (utils/DIP.py:24-31) in the vector-free form (Chen, Wang & Zhou, NIPS 2014):
  * the two-loop recursion runs on the Gram matrix of the basis {s_i, y_i, g} in fp64; the vectors are read by two streaming
