@@ -416,22 +416,46 @@ __global__ void bn_eval_affine_kernel(const float* __restrict__ gamma, const flo
   if (rstd_out) rstd_out[c] = rstd;
 }
 
-// channel statistics of a plain NHWC tensor (used where BN does not follow a conv: DIP's BN after Concat)
+// channel statistics of a plain NHWC tensor (used where BN does not follow a conv: DIP's BN after Concat).
+// Such inputs (post-activation, concatenated features) can have channels whose mean is large against their spread, and the
+// finalize forms the variance as E[y^2] - mean^2: a chain of fp32 additions of y^2 then leaves (mean / sigma)^2 times its own
+// relative error in the variance.  So next to the raw sums the block accumulates about K[c] = the mean of its first four (two,
+// one) rows -- sum (y - K), sum (y - K)^2, small numbers -- and, for a channel whose mean^2 exceeds 64 times its variance in this
+// block (below that the raw chain loses at most 6 of fp32's 24 bits: far under a 16-bit ulp), the partial row is formed from those (sum y = S1 + n K, sum y^2 = S2 + 2 K S1 + n K^2, in double, rounded to fp32 once:
+// the error left is that one rounding).  Every other channel stores the raw sums, which are the better conditioned there (a
+// shift taken from a few pixels may lie further from the mean than zero does).  Same rows, same ABI.
 template <int DT>
 __global__ __launch_bounds__(256) void channel_stats_kernel(const unsigned short* __restrict__ x, size_t P, int Cp,
                                                             int rows_per_block, float* __restrict__ partial) {
-  __shared__ float red[256 * 16];
+  __shared__ float red[256 * 32];            // per thread: sum y, sum y^2, sum (y - K), sum (y - K)^2 of its 8 channels
+  __shared__ float shift_k[2048];            // K per channel (Cp <= 2048), written by the block's first thread row
   const int cpr = Cp / 8;
   const int tid = threadIdx.x;
   const int rpi = 256 / cpr;                 // rows per iteration
   const int ch = tid % cpr, rr = tid / cpr;
-  float s1[8], s2[8];
+  float s1[8], s2[8], t1[8], t2[8];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) s1[k] = s2[k] = 0.f;
+  for (int k = 0; k < 8; ++k) s1[k] = s2[k] = t1[k] = t2[k] = 0.f;
   size_t p0 = (size_t)blockIdx.x * rows_per_block;
   size_t p1 = p0 + rows_per_block;
   if (p1 > P) p1 = P;
-  if (rr < rpi) {
+  if (rr < rpi && p0 < p1) {
+    float kk[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) kk[k] = 0.f;
+    const int nk = p1 - p0 >= 4 ? 4 : (p1 - p0 >= 2 ? 2 : 1);      // a power of two: K of integer data stays dyadic, its sums exact
+    for (int i = 0; i < nk; ++i) {
+      float f[8];
+      unpack8<DT>(*reinterpret_cast<const U4*>(x + (p0 + i) * Cp + ch * 8), f);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) kk[k] += f[k];
+    }
+    const float inv = 1.f / (float)nk;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      kk[k] *= inv;
+      if (rr == 0) shift_k[ch * 8 + k] = kk[k];
+    }
     for (size_t p = p0 + rr; p < p1; p += rpi) {
       U4 v = *reinterpret_cast<const U4*>(x + p * Cp + ch * 8);
       float f[8];
@@ -440,21 +464,41 @@ __global__ __launch_bounds__(256) void channel_stats_kernel(const unsigned short
       for (int k = 0; k < 8; ++k) {
         s1[k] += f[k];
         s2[k] += f[k] * f[k];
+        const float d = f[k] - kk[k];
+        t1[k] += d;
+        t2[k] += d * d;
       }
     }
   }
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    red[tid * 16 + k] = s1[k];
-    red[tid * 16 + 8 + k] = s2[k];
+    red[tid * 32 + k] = s1[k];
+    red[tid * 32 + 8 + k] = s2[k];
+    red[tid * 32 + 16 + k] = t1[k];
+    red[tid * 32 + 24 + k] = t2[k];
   }
   __syncthreads();
-  for (int c = tid; c < 2 * Cp; c += 256) {
-    int which = c / Cp, cc = c % Cp;
-    int chn = cc / 8, k = cc % 8;
-    float s = 0.f;
-    for (int r = 0; r < rpi; ++r) s += red[(r * cpr + chn) * 16 + which * 8 + k];
-    partial[((size_t)blockIdx.x * 2 + which) * Cp + cc] = s;
+  const double n = p0 < p1 ? (double)(p1 - p0) : 0.0;
+  for (int c = tid; c < Cp; c += 256) {
+    int chn = c / 8, k = c % 8;
+    float r1 = 0.f, r2 = 0.f, a = 0.f, b = 0.f;
+    for (int r = 0; r < rpi; ++r) {
+      const float* q = red + (r * cpr + chn) * 32 + k;
+      r1 += q[0];
+      r2 += q[8];
+      a += q[16];
+      b += q[24];
+    }
+    if (n > 0.0) {
+      const double K = (double)shift_k[c];
+      const double mean = K + (double)a / n, m2 = (double)b - (double)a * (double)a / n;      // n * variance of the block
+      if (n * mean * mean > 64.0 * m2) {
+        r1 = (float)((double)a + n * K);
+        r2 = (float)((double)b + 2.0 * K * (double)a + n * K * K);
+      }
+    }
+    partial[((size_t)blockIdx.x * 2 + 0) * Cp + c] = r1;
+    partial[((size_t)blockIdx.x * 2 + 1) * Cp + c] = r2;
   }
 }
 
@@ -486,6 +530,31 @@ __device__ __forceinline__ void st16(unsigned short* p, const U4& v) {
 }
 #define DSR_PW_NT_BYTES (192ull << 20)   // operand tensors of at least this size use the nontemporal path
 
+// tanh of the run-time instantiations, and act'(z) of the two BatchNorm backward kernels.  act_apply's tanh(v) = 2 sigmoid(2v) - 1
+// is accurate in ABSOLUTE terms (~1e-7), which next to zero is more than an ulp of the 16-bit result (|v| < 1e-4: the difference
+// cancels); and 1 - o^2 / o (1 - o) taken from the output cancel where it saturates (the gradient of a pixel at |z| = 5 came out
+// with a relative error of 1e-3).  Both are formed from exp(-|.|) here, which is accurate in RELATIVE terms at either end.  The
+// compile-time activations (none / ReLU / LeakyReLU / PReLU) fold to what they were.  ELU keeps act_apply's __expf(v) - 1 (the same
+// absolute accuracy next to zero, inside an ulp of the 16-bit result on the sweep's data): whole DIP nets run through it, and
+// their fp16 trajectories are pinned by golden tests.
+__device__ __forceinline__ float pw_act_apply(int act, float v, float slope) {
+  if (act == DSR_ACT_TANH) {
+    const float em = expm1f(-2.f * fabsf(v));            // in (-1, 0]: tanh |v| = -em / (2 + em)
+    return copysignf(__fdividef(-em, 2.f + em), v);
+  }
+  return act_apply(act, v, slope);
+}
+__device__ __forceinline__ float pw_act_grad(int act, float z, float slope) {
+  if (act == DSR_ACT_TANH || act == DSR_ACT_SIGMOID) {
+    const float e = expf(-(act == DSR_ACT_TANH ? 2.f : 1.f) * fabsf(z));      // in (0, 1]
+    const float r = __fdividef(1.f, 1.f + e);
+    const float s = e * r * r;                           // sigmoid'(t) = e^-|t| / (1 + e^-|t|)^2;  tanh'(z) = 4 sigmoid'(2z)
+    return act == DSR_ACT_TANH ? 4.f * s : s;
+  }
+  const bool lin = act == DSR_ACT_LEAKY || act == DSR_ACT_PRELU;
+  return act_grad_from_out(act, lin ? z : act_apply(act, z, slope), slope);
+}
+
 // ACTC (this and the three kernels below): the activation as a compile-time constant (-1: the run-time `act`).  With the run-time
 // value every element went through act_apply's / act_grad_from_out's chain of scalar compares and branches (114-589 s_cbranch
 // per kernel): the launchers pick the instantiation for None / LeakyReLU / PReLU / ReLU.
@@ -516,7 +585,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const unsigned short* _
     if (residual) unpack8<DT>(vr, r);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      float v = act_apply(act, f[k] * sc[k] + sh[k], slope);
+      float v = pw_act_apply(act, f[k] * sc[k] + sh[k], slope);
       if (residual) v += r[k];
       f[k] = v;
     }
@@ -586,8 +655,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_reduce_kernel(
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const float z = f[k] * csc[k] + csh[k];
-      const float o = act_apply(act, z, slope);
-      const float gg = d[k] * act_grad_from_out(act, (act == DSR_ACT_LEAKY || act == DSR_ACT_PRELU) ? z : o, slope);
+      const float gg = d[k] * pw_act_grad(act, z, slope);
       sg[k] += gg;
       sgx[k] += gg * f[k];
       if constexpr (WITH_P)
@@ -713,7 +781,6 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(
 #pragma unroll
     for (int k = 0; k < 8; ++k) cb[k] = cc[k] = 0.f;
   }
-  const bool lin = act == DSR_ACT_LEAKY || act == DSR_ACT_PRELU;
   auto apply = [&](const U4& vd, const U4& vy) {
     float d[8], f[8];
     unpack8<DT>(vd, d);
@@ -721,7 +788,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const float z = f[k] * sc[k] + sh[k];
-      const float gg = d[k] * act_grad_from_out(act, lin ? z : act_apply(act, z, slope), slope);
+      const float gg = d[k] * pw_act_grad(act, z, slope);
       f[k] = sc[k] * gg + cb[k] * f[k] + cc[k];
     }
     return pack8<DT>(f);
