@@ -56,6 +56,9 @@ SIGNATURES = {
     "dsr_degrade_batch_u8": (_I, [_I, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                   C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P]),
     "dsr_degrade_image_u8": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
+    "dsr_jpeg_workspace": (_Z, [_I, _I, _I, _I]),
+    "dsr_jpeg_u8": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
+    "dsr_jpeg_batch_f32": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _P, _P]),
     "dsr_d4_expand_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "dsr_d4_mean_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "dsr_conv_fwd_affine_supported": (_I, [_DESC]),
@@ -215,7 +218,7 @@ _NO_LAUNCH = ("dsr_last_error", "dsr_abi_version", "dsr_conv_dgrad_ps_supported"
               "dsr_ssim_img_blocks", "dsr_psnr_blocks", "dsr_lbfgs_workspace", "dsr_lbfgs_vector_floats", "dsr_clip_sumsq_partials",
               "dsr_linear_factor_gram_workspace", "dsr_linear_factor_gram_dots", "dsr_downsample_dense_wgrad_workspace",
               "dsr_msssim_min_size", "dsr_msssim_pyramid_floats", "dsr_ssim_cs_img_blocks", "dsr_msssim_bwd_blocks", "dsr_luma_blocks",
-              "dsr_featloss_blocks")
+              "dsr_featloss_blocks", "dsr_jpeg_workspace")
 
 
 class _Lib:

@@ -7,7 +7,8 @@
         whole (pre-shrunk) image set lives in HBM as uint8 and ``sample(batch)`` cuts and converts a batch of LR / HR patch
         pairs in two kernel launches -- the step is fed at its own rate instead of the host's; ``augment=True`` flips /
         turns each pair by a random element of D4 in the same launches; ``degradation=BlindDegradation(...)`` makes the LR
-        patch from the HR image with a fresh blur kernel and noise level per sample (csrc/degrade.hip).
+        patch from the HR image with a fresh blur kernel and noise level per sample (csrc/degrade.hip) and, with a
+        ``jpeg_quality`` range, a JPEG round trip at a quality per sample after it (csrc/jpeg.hip).
 
 The reference scales by 255 twice (ToTensor at :59-60, then scale_images :152,155): ``reference_scaling=True`` (default)
 reproduces that, bit for bit; ``False`` gives the [0,1] / [-1,1] ranges its comments describe (SURVEY.md 8f row 1 asks for
@@ -198,7 +199,12 @@ class PatchBank:
         seeded bank crops the same patches, with the same codes, with and without `degradation`): the kernels by
         ``degradation.random_kernels`` (four uniform draws per sample), then, only if the noise range is not (0, 0), `batch`
         uniform noise levels.  The noise itself is ``torch.randn`` on the device (`generator`).  ``last_kernels`` /
-        ``last_noise_std`` hold the device tensors of the values used, e.g. as targets of a kernel estimator."""
+        ``last_noise_std`` hold the device tensors of the values used, e.g. as targets of a kernel estimator.
+        With ``degradation.jpeg_quality = (low, high)`` the degraded patch finishes with a JPEG round trip (BSRGAN,
+        Real-ESRGAN): it is cut in PATCH_UNIT scaling and rounded to whole grey levels whatever `quantise` says, passed
+        through ``degradation.jpeg_batch`` at a quality per sample and leaves in the bank's LR scaling.  The patch is the
+        image: the 8x8 grid starts at its corner, after the D4 code.  The qualities are drawn LAST, `batch` draws of
+        ``rng.randint(low, high + 1)``, and only with a range; ``last_jpeg_quality`` is the int32 device tensor used."""
 
     def __init__(self, pairs, scale_factor, LR_patch_size, reference_scaling=True, rng=None, augment=False, degradation=None,
                  generator=None):
@@ -222,13 +228,14 @@ class PatchBank:
         self.rng = np.random if rng is None else rng
         self.augment = bool(augment)
         self.degradation, self.generator = degradation, generator
-        self.last_kernels = self.last_noise_std = None
+        self.last_kernels = self.last_noise_std = self.last_jpeg_quality = None
 
-    def sample(self, batch, indices=None, transforms=None, kernels=None, noise_std=None):
+    def sample(self, batch, indices=None, transforms=None, kernels=None, noise_std=None, jpeg_quality=None):
         """(LR [B,3,ph,pw], HR [B,3,ph*s,pw*s]) fp32 device batches; image b is `indices[b]` (default: uniform draws).
         ``transforms``: explicit D4 codes, one per sample, instead of the draw (also without ``augment``).
         ``kernels`` (fp32 [B, ks, ks], numpy or tensor) / ``noise_std`` ([B], 0..255 units): explicit blur kernels / noise
-        levels instead of the draws of a bank with a ``degradation``."""
+        levels instead of the draws of a bank with a ``degradation``; ``jpeg_quality`` ([B] integers in 1..100): explicit
+        JPEG qualities instead of the draws of a degradation with a ``jpeg_quality`` range."""
         pw, ph = self.patch
         n = batch if indices is None else len(indices)
         if transforms is not None:
@@ -244,6 +251,13 @@ class PatchBank:
             noise_std = np.asarray(noise_std.cpu() if torch.is_tensor(noise_std) else noise_std, dtype=np.float32).reshape(-1)
             if noise_std.shape[0] != n or bool((noise_std < 0).any()):
                 raise ValueError(f"noise_std: {n} non-negative levels expected")
+        if jpeg_quality is not None:
+            if deg is None or deg.jpeg_quality is None:
+                raise ValueError("jpeg_quality needs a bank whose `degradation` has a jpeg_quality range")
+            jpeg_quality = [int(q) if degradation._is_int(q) else q
+                            for q in (jpeg_quality.tolist() if hasattr(jpeg_quality, "tolist") else jpeg_quality)]
+            if len(jpeg_quality) != n or not all(degradation._is_int(q) and 1 <= q <= 100 for q in jpeg_quality):
+                raise ValueError(f"jpeg_quality: {n} integers in 1..100 expected")
         if indices is None:
             indices = [int(self.rng.randint(0, len(self.hr))) for _ in range(batch)]
         tops, lefts, htops, hlefts = [], [], [], []
@@ -258,11 +272,11 @@ class PatchBank:
         if deg is None:
             lr = patch_batch([self.lr[i] for i in indices], tops, lefts, ph, pw, self.modes[0], transforms)
         else:
-            lr = self._degraded(deg, indices, tops, lefts, transforms, kernels, noise_std)
+            lr = self._degraded(deg, indices, tops, lefts, transforms, kernels, noise_std, jpeg_quality)
         hr = patch_batch([self.hr[i] for i in indices], htops, hlefts, ph * self.scale, pw * self.scale, self.modes[1], transforms)
         return lr, hr
 
-    def _degraded(self, deg, indices, tops, lefts, transforms, kernels, noise_std):
+    def _degraded(self, deg, indices, tops, lefts, transforms, kernels, noise_std, jpeg_quality=None):
         pw, ph = self.patch
         n = len(indices)
         dev = self.hr[0].device
@@ -278,6 +292,15 @@ class PatchBank:
         if noise_std is not None:
             self.last_noise_std = torch.from_numpy(noise_std).to(dev)                           # one transfer
             z = torch.randn((n, 3, ph, pw), dtype=torch.float32, device=dev, generator=self.generator)
-        return degradation.degrade_batch([self.hr[i] for i in indices], tops, lefts, ph, pw, self.scale, self.last_kernels,
-                                         offset=deg.offset, noise=z, noise_std=self.last_noise_std, quantise=deg.quantise,
-                                         mode=self.modes[0], transforms=transforms)
+        self.last_jpeg_quality = None
+        if deg.jpeg_quality is None:
+            return degradation.degrade_batch([self.hr[i] for i in indices], tops, lefts, ph, pw, self.scale, self.last_kernels,
+                                             offset=deg.offset, noise=z, noise_std=self.last_noise_std, quantise=deg.quantise,
+                                             mode=self.modes[0], transforms=transforms)
+        if jpeg_quality is None:
+            jpeg_quality = [int(self.rng.randint(deg.jpeg_quality[0], deg.jpeg_quality[1] + 1)) for _ in range(n)]
+        self.last_jpeg_quality = torch.tensor(jpeg_quality, dtype=torch.int32).to(dev)           # one transfer
+        lr = degradation.degrade_batch([self.hr[i] for i in indices], tops, lefts, ph, pw, self.scale, self.last_kernels,
+                                       offset=deg.offset, noise=z, noise_std=self.last_noise_std, quantise=True,
+                                       mode=PATCH_UNIT, transforms=transforms)
+        return degradation.jpeg_batch(lr, self.last_jpeg_quality, deg.jpeg_subsampling, self.modes[0])

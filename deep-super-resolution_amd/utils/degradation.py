@@ -13,6 +13,8 @@ Beyond the reference, the blind degradation of SRMD / IKC / KernelGAN / BSRGAN (
 ``LR = quant(clip((HR (*) k)[offset::s, offset::s] + sigma * z))`` with a blur kernel per sample -- ``gaussian_kernel`` and
 ``random_kernels`` make the kernels on the host, ``blur_downsample`` degrades a whole image to uint8 and ``degrade_batch``
 cuts a batch of degraded LR patches straight out of HR images (``dataset.PatchBank(degradation=...)`` is built on it).
+The last stage of the BSRGAN / Real-ESRGAN recipe is a JPEG round trip at a random quality (csrc/jpeg.hip): ``jpeg_compress``
+on uint8 images and ``jpeg_batch`` on fp32 patch batches, equal to Pillow's encoder and decoder bit for bit.
 """
 import ctypes as C
 import math
@@ -269,14 +271,114 @@ def degrade_batch(images, tops, lefts, ph, pw, scale, kernels, offset=0, noise=N
     return out
 
 
+# ------------------------------------------------------------------ JPEG round trip (csrc/jpeg.hip)
+def _subsampling(subsampling):
+    """"4:4:4" / 0 -> 0, "4:2:0" / 2 -> 2 (Pillow's numbers); anything else is refused"""
+    if isinstance(subsampling, str):
+        if subsampling in ("4:4:4", "4:2:0"):
+            return 0 if subsampling == "4:4:4" else 2
+    elif not isinstance(subsampling, bool) and subsampling in (0, 2):
+        return int(subsampling)
+    raise ValueError(f"subsampling {subsampling!r} is not '4:4:4' / 0 or '4:2:0' / 2")
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _device_qualities(quality, n, device):
+    """-> int32 [n] on `device`.  An int (for every sample), a sequence, numpy array or host tensor of n integers: checked to
+    lie in 1..100 and uploaded once.  An int32 device tensor [n] is used as it is, with no host read (the kernels clamp)."""
+    if torch.is_tensor(quality) and quality.is_cuda:
+        if quality.dtype != torch.int32 or tuple(quality.shape) != (n,):
+            raise ValueError(f"quality: a device tensor must be int32 [{n}], got {quality.dtype} {tuple(quality.shape)}")
+        return quality.to(device).contiguous()
+    if torch.is_tensor(quality):
+        if quality.dtype.is_floating_point or quality.dtype == torch.bool:
+            raise ValueError(f"quality: integers are expected, got {quality.dtype}")
+        quality = quality.reshape(-1).tolist()
+    elif isinstance(quality, np.ndarray):
+        if not np.issubdtype(quality.dtype, np.integer):
+            raise ValueError(f"quality: integers are expected, got {quality.dtype}")
+        quality = quality.reshape(-1).tolist()
+    elif _is_int(quality):
+        quality = [quality] * n
+    else:
+        try:
+            quality = list(quality)
+        except TypeError:
+            raise ValueError(f"quality {quality!r} is neither an integer nor a sequence of integers") from None
+    if len(quality) != n:
+        raise ValueError(f"quality: {len(quality)} values for {n} images")
+    for q in quality:
+        if not _is_int(q) or not 1 <= q <= 100:
+            raise ValueError(f"quality {q!r} is not an integer in 1..100")
+    return torch.tensor([int(q) for q in quality], dtype=torch.int32).to(device)
+
+
+def _jpeg_workspace(lib, n, h, w, ss, device):
+    size = lib.dsr_jpeg_workspace(n, h, w, ss)
+    return None if size == 0 else torch.empty((size,), dtype=torch.uint8, device=device)
+
+
+def jpeg_compress(image, quality=75, subsampling="4:2:0"):
+    """What ``PIL.Image.save(f, 'JPEG', quality=quality, subsampling=...)`` followed by ``Image.open(f)`` does to a uint8 RGB
+    image, bit for bit, on the device (dsr_jpeg_u8; no bitstream is made).  image: [H, W, 3] as a device tensor, a numpy
+    array or a PIL image, returned in that type; or a device tensor [B, H, W, 3] with one quality for all or one per image
+    (a sequence, or an int32 device tensor, which is not read back).  subsampling: "4:4:4" / 0 or "4:2:0" / 2."""
+    ss = _subsampling(subsampling)
+    if torch.is_tensor(image) and image.dim() == 4:
+        _need_gpu(image)
+        if image.dtype != torch.uint8:
+            raise TypeError(f"image tensor must be uint8, got {image.dtype}")
+        img, restore = image.contiguous(), (lambda t: t)
+    else:
+        img, restore = _to_device(image)
+        img = img[None]
+    if img.shape[3] != 3 or img.shape[0] == 0 or img.shape[1] == 0 or img.shape[2] == 0:
+        raise TypeError(f"jpeg_compress: RGB images [H, W, 3] or [B, H, W, 3] are expected, got {tuple(image.shape)}")
+    n, h, w = int(img.shape[0]), int(img.shape[1]), int(img.shape[2])
+    q = _device_qualities(quality, n, img.device)
+    lib = _lib.lib()
+    ws = _jpeg_workspace(lib, n, h, w, ss, img.device)
+    out = torch.empty_like(img)
+    check(lib.dsr_jpeg_u8(_ptr(img), _ptr(out), n, h, w, _ptr(q), ss, None if ws is None else _ptr(ws), _stream()))
+    return restore(out if torch.is_tensor(image) and image.dim() == 4 else out[0])
+
+
+def jpeg_batch(x, quality, subsampling="4:2:0", mode=0):
+    """fp32 [B, 3, h, w] device batch in PATCH_UNIT scaling ([0, 1]) -> the batch after a JPEG round trip of its grey levels
+    ``rint(clip(255 x, 0, 255))``, scaled by `mode` as ``dataset.patch_batch`` scales (dsr_jpeg_batch_f32; a new tensor).
+    quality: as ``jpeg_compress``.  Every image is its own JPEG: the 8x8 grid starts at its corner."""
+    ss = _subsampling(subsampling)
+    if not (torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3 and x.numel() > 0):
+        raise TypeError("jpeg_batch: an fp32 [B, 3, h, w] tensor is expected")
+    _need_gpu(x)
+    if not _is_int(mode) or not 0 <= mode <= 3:
+        raise ValueError(f"jpeg_batch: mode {mode!r} is not one of the four patch scalings 0..3")
+    x = x.contiguous()
+    n, h, w = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    q = _device_qualities(quality, n, x.device)
+    lib = _lib.lib()
+    ws = _jpeg_workspace(lib, n, h, w, ss, x.device)
+    out = torch.empty_like(x)
+    check(lib.dsr_jpeg_batch_f32(_ptr(x), _ptr(out), n, h, w, _ptr(q), ss, int(mode), None if ws is None else _ptr(ws), _stream()))
+    return out
+
+
 class BlindDegradation:
     """What ``dataset.PatchBank(degradation=...)`` draws per sample: a Gaussian blur kernel of `kernel_size` as
     ``random_kernels(sigma=, iso_prob=)`` and a noise level, uniform in `noise_std` = (low, high) in 0..255 units (no noise
-    when high is 0); `quantise`: round the LR patch to whole grey levels; `offset`: the sampling phase in 0..scale-1."""
+    when high is 0); `quantise`: round the LR patch to whole grey levels; `offset`: the sampling phase in 0..scale-1.
+    `jpeg_quality` = (low, high), integers in 1..100, both included: the degraded patch then goes through a JPEG round trip
+    (``jpeg_batch``, chroma `jpeg_subsampling`) at a quality drawn per sample; None: no JPEG stage."""
 
-    def __init__(self, kernel_size=21, sigma=(0.2, 3.0), iso_prob=0.5, noise_std=(0.0, 0.0), quantise=True, offset=0):
+    def __init__(self, kernel_size=21, sigma=(0.2, 3.0), iso_prob=0.5, noise_std=(0.0, 0.0), quantise=True, offset=0,
+                 jpeg_quality=None, jpeg_subsampling="4:2:0"):
         self.kernel_size, self.sigma, self.iso_prob = int(kernel_size), (float(sigma[0]), float(sigma[1])), float(iso_prob)
         self.noise_std, self.quantise, self.offset = (float(noise_std[0]), float(noise_std[1])), bool(quantise), int(offset)
+        self.jpeg_quality = None if jpeg_quality is None else tuple(jpeg_quality)
+        self.jpeg_subsampling = jpeg_subsampling
 
     def validate(self, scale):
         if self.kernel_size < 1 or self.kernel_size % 2 == 0 or self.kernel_size > KERNEL_SIZE_MAX:
@@ -289,3 +391,8 @@ class BlindDegradation:
             raise ValueError(f"BlindDegradation: noise_std range {self.noise_std} is not 0 <= low <= high")
         if not 0 <= self.offset < scale:
             raise ValueError(f"BlindDegradation: offset {self.offset} is not in 0..{scale - 1}")
+        if self.jpeg_quality is not None:
+            q = self.jpeg_quality
+            if len(q) != 2 or not all(_is_int(v) for v in q) or not 1 <= q[0] <= q[1] <= 100:
+                raise ValueError(f"BlindDegradation: jpeg_quality {q} is not (low, high) with integers 1 <= low <= high <= 100")
+        _subsampling(self.jpeg_subsampling)

@@ -577,6 +577,48 @@ int dsr_degrade_batch_u8(int count, const unsigned char* const* images, const in
 int dsr_degrade_image_u8(const unsigned char* image, int H, int W, int scale, int offset, const float* kernel, int ks,
                          const float* noise, const float* noise_std, unsigned char* out, dsr_stream_t s);
 
+/* ------------------------------------------------------------------ JPEG round trip (jpeg.hip)
+ * Baseline JPEG compression and decompression of RGB images at a quality per sample, uint8 in, uint8 out, no bitstream (the
+ * entropy coder is lossless): the last stage of the BSRGAN / Real-ESRGAN degradation.  With libjpeg's default "islow" DCT
+ * the codec is integer arithmetic throughout, and this is its definition here (equal to Pillow's
+ * save(..., 'JPEG', quality=q, subsampling=0|2) + open; tests/jpeg_ref.py restates it in numpy).  All values are integers,
+ * >> is an arithmetic shift, DS(x, n) = (x + (1 << (n-1))) >> n, F(x) = int(x * 65536 + 0.5).
+ *  1. Pad on the right and bottom by edge replication to multiples of 8 (4:4:4) or 16 (4:2:0).
+ *  2. Y  = ( F(.299) R + F(.587) G + F(.114) B + 32768) >> 16
+ *     Cb = (-F(.16874) R - F(.33126) G + F(.5) B + (128 << 16) + 32767) >> 16
+ *     Cr = ( F(.5) R - F(.41869) G - F(.08131) B + (128 << 16) + 32767) >> 16
+ *  3. 4:2:0 only: each chroma plane becomes (a + b + c + d + bias) >> 2 over the 2x2 cells of the padded plane, bias = 1 in
+ *     even output columns and 2 in odd ones; then every chroma row at or below ceil(H/2) is replaced by row ceil(H/2) - 1
+ *     (the bottom padding repeats the last DOWNSAMPLED row, not the last image row).
+ *  4. s = 5000 / q for q < 50, else 200 - 2 q;  t = clip((base * s + 50) / 100, 1, 255) with the two Annex-K base tables
+ *     (luminance for Y, chrominance for Cb and Cr); q in 1..100.
+ *  5. Per 8x8 block, jfdctint on sample - 128: rows, then columns, CONST_BITS = 13, PASS1_BITS = 2, constants 2446, 3196,
+ *     4433, 6270, 7373, 9633, 12299, 15137, 16069, 16819, 20995, 25172; pass 1 descales by 11 with the DC and index-4
+ *     terms << 2, pass 2 by 15 with those terms DS(., 2): 8 times the DCT.
+ *  6. d = t << 3;  k = (|c| + (d >> 1)) / d with the sign of c;  dequantised: k * t.
+ *  7. jidctint: columns (descale 11), then rows (descale 18); + 128, clipped to 0..255.
+ *  8. 4:2:0 only: chroma is upsampled to 2 ceil(H/2) x 2 ceil(W/2) from the ceil(H/2) x ceil(W/2) real samples alone.
+ *     ceil(W/2) > 2: libjpeg's triangle filter -- cs = 3 * this row + the nearer neighbour row (the row above for the upper
+ *     output row, the row below for the lower one, replicated at the edges); out[2i] = (3 cs[i] + cs[i-1] + 8) >> 4,
+ *     out[2i+1] = (3 cs[i] + cs[i+1] + 7) >> 4, the first column (4 cs[0] + 8) >> 4, the last (4 cs[last] + 7) >> 4.
+ *     ceil(W/2) <= 2: every sample is repeated 2x2.
+ *  9. cb = Cb - 128, cr = Cr - 128;  R = Y + ((F(1.402) cr + 32768) >> 16),  B = Y + ((F(1.772) cb + 32768) >> 16),
+ *     G = Y + ((-F(.34414) cb + 32768 - F(.71414) cr) >> 16), each clipped to 0..255; cropped to H x W.
+ * 32-bit integers hold every intermediate.  Nothing is allocated, read back or waited for: the calls can be captured into a
+ * graph.  quality: DEVICE int32 [count], 1..100 (the kernels clamp a value outside; they derive the tables themselves);
+ * subsampling: 0 (4:4:4, one launch) or 2 (4:2:0, two launches), Pillow's numbers; count in 1..65535, H and W in 1..65536. */
+/* bytes of workspace of the two calls below: 0 for 4:4:4 (workspace may then be NULL) and for arguments they refuse; for
+ * 4:2:0 the decoded Y, Cb and Cr planes of every image.  A pure host query. */
+size_t dsr_jpeg_workspace(int count, int H, int W, int subsampling);
+/* in, out: uint8 [count][H][W][3]; out must not be in; workspace: 16-byte aligned device memory of dsr_jpeg_workspace bytes */
+int dsr_jpeg_u8(const unsigned char* in, unsigned char* out, int count, int H, int W, const int* quality, int subsampling,
+                void* workspace, dsr_stream_t s);
+/* The patch batches of the data path: in fp32 [count][3][h][w] in DSR_PATCH_UNIT scaling, read as the grey level
+ * (int)rintf(min(max(255 * v, 0), 255)); out, same shape, not in: the decoded level as a float, / 255.0f, then the scaling
+ * `mode` selects, as dsr_patch_batch_u8 */
+int dsr_jpeg_batch_f32(const float* in, float* out, int count, int h, int w, const int* quality, int subsampling, int mode,
+                       void* workspace, dsr_stream_t s);
+
 /* ------------------------------------------------------------------ L-BFGS (lbfgs.hip)
  * torch.optim.LBFGS with line_search_fn=None (utils/DIP.py:24-31) in the vector-free form (Chen, Wang & Zhou, NIPS 2014):
  * the two-loop recursion runs on the Gram matrix of the basis {s_i, y_i, g} in fp64; the vectors are read by two streaming

@@ -1,0 +1,272 @@
+"""CPU: the JPEG yardstick (tests/jpeg_ref.py) against Pillow's own encoder and decoder, bit for bit; the validation of
+BlindDegradation(jpeg_quality=...) and of PatchBank's JPEG arguments with their draw order; the new symbols of
+include/dsr_hip.h, their binding and their host-side argument checks.  Nothing is launched."""
+import ctypes
+import importlib
+import io
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import jpeg_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = "deep-super-resolution_amd"
+DSR_E_ARG = -1
+QUALITIES = (1, 10, 50, 75, 95, 100)
+SIZES = [(h, w) for h in range(1, 19) for w in range(1, 19)] + [(33, 50), (48, 64)]
+
+
+def P(sub):
+    return importlib.import_module(PKG + "." + sub)
+
+
+@pytest.fixture(scope="module")
+def so():
+    return P("_build").build()
+
+
+def pictures(h, w, rng):
+    """noise, a smooth ramp, a 1-px checkerboard and saturated random 0 / 255"""
+    yy, xx = np.mgrid[0:h, 0:w]
+    ramp = np.stack([(255 * xx) // max(w - 1, 1), (255 * yy) // max(h - 1, 1), (255 * (xx + yy)) // max(h + w - 2, 1)], axis=-1)
+    board = np.repeat((((yy + xx) % 2) * 255)[..., None], 3, axis=-1)
+    return {"noise": rng.randint(0, 256, (h, w, 3)).astype(np.uint8), "ramp": ramp.astype(np.uint8),
+            "checkerboard": board.astype(np.uint8), "saturated": (rng.randint(0, 2, (h, w, 3)) * 255).astype(np.uint8)}
+
+
+# ------------------------------------------------------------------ the yardstick is Pillow
+@pytest.mark.parametrize("subsampling", [0, 2])
+def test_yardstick_equals_pillow_bit_for_bit(subsampling):
+    Image = pytest.importorskip("PIL.Image")
+    features = pytest.importorskip("PIL.features")
+    if not features.check("jpg"):
+        pytest.skip("this Pillow has no JPEG codec")
+    rng = np.random.RandomState(7)
+    bad = []
+    for h, w in SIZES:
+        for name, img in pictures(h, w, rng).items():
+            for q in QUALITIES:
+                f = io.BytesIO()
+                Image.fromarray(img).save(f, "JPEG", quality=q, subsampling=subsampling)
+                f.seek(0)
+                want = np.array(Image.open(f).convert("RGB"))
+                if not np.array_equal(jpeg_ref.jpeg_roundtrip(img, q, subsampling), want):
+                    bad.append((h, w, name, q))
+    assert not bad, bad[:20]
+
+
+def test_yardstick_tables_and_scalings():
+    assert np.array_equal(jpeg_ref.quant_table(jpeg_ref.LUMA, 50), jpeg_ref.LUMA)               # s = 100
+    assert np.array_equal(jpeg_ref.quant_table(jpeg_ref.CHROMA, 100), np.ones((8, 8), dtype=np.int64))
+    assert jpeg_ref.quant_table(jpeg_ref.LUMA, 1).max() == 255 and jpeg_ref.quant_table(jpeg_ref.LUMA, 1)[0, 0] == 255
+    assert jpeg_ref.quant_table(jpeg_ref.LUMA, 75)[0, :3].tolist() == [8, 6, 5]                 # (16, 11, 10) * 50 + 50) // 100
+    grey = np.full((9, 11, 3), 77, dtype=np.uint8)                     # Y = 77, Cb = Cr = 128; t = 1 keeps the DC term as it is
+    for ss in (0, 2):
+        assert np.array_equal(jpeg_ref.jpeg_roundtrip(grey, 100, ss), grey)
+    x = np.array([[[[0.0, 0.5, 1.0, 1.5, -0.2, 0.3]]] * 3], dtype=np.float32)
+    assert jpeg_ref.levels_f32(x)[0, 0, :, 0].tolist() == [0, 128, 255, 255, 0, 76]             # 127.5 -> 128: half to even
+    u = np.arange(6, dtype=np.uint8).reshape(1, 2, 3)
+    f = np.float32
+    assert jpeg_ref.scale_f32(u, jpeg_ref.LR_REF)[:, 0, 0].tolist() == [float(f(v) / f(255) / f(255)) for v in (0, 1, 2)]
+    assert jpeg_ref.scale_f32(u, jpeg_ref.HR_UNIT)[:, 0, 1].tolist() == [float(f(v) / f(255) * f(2) - f(1)) for v in (3, 4, 5)]
+
+
+# ------------------------------------------------------------------ BlindDegradation
+def test_blind_degradation_jpeg_arguments():
+    DS = P("dataset")
+    BD = DS.BlindDegradation
+    plain = BD()
+    assert plain.jpeg_quality is None and plain.jpeg_subsampling == "4:2:0"
+    assert (plain.kernel_size, plain.sigma, plain.iso_prob, plain.noise_std, plain.quantise, plain.offset) == \
+        (21, (0.2, 3.0), 0.5, (0.0, 0.0), True, 0)                                              # the defaults of before
+    plain.validate(4)
+    for ok in [BD(jpeg_quality=(30, 95)), BD(jpeg_quality=[1, 100], jpeg_subsampling="4:4:4"), BD(jpeg_quality=(75, 75), jpeg_subsampling=0),
+               BD(jpeg_quality=(np.int64(5), 9), jpeg_subsampling=2), BD(jpeg_subsampling="4:4:4")]:
+        ok.validate(4)
+    for bad in [dict(jpeg_quality=(0, 50)), dict(jpeg_quality=(50, 101)), dict(jpeg_quality=(60, 40)), dict(jpeg_quality=(30.5, 90)),
+                dict(jpeg_quality=(30.0, 90.0)), dict(jpeg_quality=(30,)), dict(jpeg_quality=(30, 60, 90)), dict(jpeg_quality=(True, 90)),
+                dict(jpeg_quality=(30, 90), jpeg_subsampling="4:2:2"), dict(jpeg_quality=(30, 90), jpeg_subsampling=1),
+                dict(jpeg_subsampling="420"), dict(jpeg_subsampling=None), dict(jpeg_subsampling=True), dict(jpeg_subsampling=2.5)]:
+        with pytest.raises(ValueError):
+            BD(**bad).validate(4)
+    D = P("utils.degradation")
+    assert [D._subsampling(v) for v in ("4:4:4", 0, "4:2:0", 2)] == [0, 0, 2, 2]
+
+
+def test_qualities_are_checked_on_the_host():
+    D = P("utils.degradation")
+    cpu = torch.device("cpu")
+    assert D._device_qualities(75, 3, cpu).tolist() == [75, 75, 75]
+    assert D._device_qualities([1, 100], 2, cpu).dtype == torch.int32
+    assert D._device_qualities(np.array([5, 6]), 2, cpu).tolist() == [5, 6]
+    assert D._device_qualities(torch.tensor([7, 8, 9]), 3, cpu).tolist() == [7, 8, 9]
+    for bad, n in [(0, 1), (101, 1), (-5, 1), (75.0, 1), ("75", 1), (None, 1), (True, 1), ([50, 0], 2), ([50], 2), ([50, 60, 70], 2),
+                   (np.array([50.0, 60.0]), 2), (torch.tensor([0.5, 0.7]), 2), (torch.tensor([50, 200]), 2)]:
+        with pytest.raises(ValueError):
+            D._device_qualities(bad, n, cpu)
+    x = torch.zeros((2, 3, 8, 8))
+    for call in [lambda: D.jpeg_batch(x, 75, subsampling="4:1:1"), lambda: D.jpeg_compress(torch.zeros((8, 8, 3), dtype=torch.uint8), 75, 1)]:
+        with pytest.raises(ValueError):
+            call()
+    for call in [lambda: D.jpeg_batch(x.double(), 75), lambda: D.jpeg_batch(x[:, :2], 75), lambda: D.jpeg_batch(x[0], 75)]:
+        with pytest.raises(TypeError):
+            call()
+
+
+# ------------------------------------------------------------------ PatchBank
+class RecordingRng:
+    """a RandomState that writes down every draw asked of it"""
+
+    def __init__(self, seed):
+        self.rs = np.random.RandomState(seed)
+        self.calls = []
+
+    def randint(self, *a, **k):
+        v = self.rs.randint(*a, **k)
+        self.calls.append(("randint", a, v))
+        return v
+
+    def uniform(self, *a, **k):
+        v = self.rs.uniform(*a, **k)
+        self.calls.append(("uniform", a, v))
+        return v
+
+
+def host_pairs():
+    rng = np.random.RandomState(11)
+    u8 = lambda h, w: torch.from_numpy(rng.randint(0, 256, (h, w, 3), dtype=np.uint8))
+    return [(u8(24, 40), u8(96, 160)), (None, u8(112, 130))]
+
+
+def test_patch_bank_refuses_bad_jpeg_arguments_before_any_draw():
+    DS = P("dataset")
+    pairs = host_pairs()
+    rng = np.random.RandomState(5)
+    state = rng.get_state()[1].copy()
+    BD = DS.BlindDegradation
+    for spec in [BD(jpeg_quality=(0, 10)), BD(jpeg_quality=(90, 30)), BD(jpeg_quality=(30, 90), jpeg_subsampling="4:2:2")]:
+        with pytest.raises(ValueError):
+            DS.PatchBank(pairs, 4, (8, 8), rng=rng, degradation=spec)
+    bank = DS.PatchBank(pairs, 4, (8, 8), rng=rng, degradation=BD(kernel_size=7, jpeg_quality=(30, 90)))
+    assert bank.last_jpeg_quality is None
+    for q in ([50, 60], [50, 60, 0], [50, 60, 101], [50, 60, 70.5], [50, 60, 70, 80], torch.tensor([0.5, 0.6, 0.7])):
+        with pytest.raises(ValueError):
+            bank.sample(3, jpeg_quality=q)
+    for other in (DS.PatchBank(pairs[:1], 4, (8, 8), rng=rng), DS.PatchBank(pairs, 4, (8, 8), rng=rng, degradation=BD(kernel_size=7))):
+        with pytest.raises(ValueError):
+            other.sample(3, jpeg_quality=[50, 60, 70])                 # no JPEG stage to apply them in
+    assert np.array_equal(rng.get_state()[1], state)                   # every one refused before any draw
+
+
+@pytest.mark.parametrize("reference_scaling", [True, False])
+def test_patch_bank_draws_the_qualities_last(monkeypatch, reference_scaling):
+    """Through a recording rng, with the launches replaced by recorders (host tensors): the draws of a bank with a JPEG range
+    are those of the bank without it followed by `batch` randint(low, high + 1); the patch is degraded in PATCH_UNIT scaling,
+    quantised, and jpeg_batch applies the bank's LR scaling."""
+    DS = P("dataset")
+    D = P("utils.degradation")
+    pairs = host_pairs()
+    launches = []
+    monkeypatch.setattr(DS, "patch_batch", lambda *a, **k: launches.append(("patch", a, k)))
+    monkeypatch.setattr(D, "degrade_batch", lambda *a, **k: launches.append(("degrade", a, k)) or "degraded")
+    monkeypatch.setattr(D, "jpeg_batch", lambda *a, **k: launches.append(("jpeg", a, k)) or "compressed")
+    batch, seed = 6, 23
+    spec = dict(kernel_size=5, noise_std=(1.0, 9.0), quantise=False, offset=1)
+    r0, r1 = RecordingRng(seed), RecordingRng(seed)
+    b0 = DS.PatchBank(pairs, 4, (8, 8), rng=r0, augment=True, reference_scaling=reference_scaling, degradation=DS.BlindDegradation(**spec))
+    lr0, _ = b0.sample(batch)
+    before, launches[:] = list(launches), []
+    b1 = DS.PatchBank(pairs, 4, (8, 8), rng=r1, augment=True, reference_scaling=reference_scaling,
+                      degradation=DS.BlindDegradation(jpeg_quality=(30, 95), jpeg_subsampling="4:4:4", **spec))
+    lr1, _ = b1.sample(batch)
+    n0 = len(r0.calls)
+    assert [(c[0], c[1]) for c in r1.calls[:n0]] == [(c[0], c[1]) for c in r0.calls]
+    assert all(np.array_equal(a[2], b[2]) for a, b in zip(r0.calls, r1.calls))
+    assert [(c[0], c[1]) for c in r1.calls[n0:]] == [("randint", (30, 96))] * batch
+    drawn = [int(c[2]) for c in r1.calls[n0:]]
+    assert b1.last_jpeg_quality.dtype == torch.int32 and b1.last_jpeg_quality.tolist() == drawn and b0.last_jpeg_quality is None
+    assert torch.equal(b0.last_kernels, b1.last_kernels) and torch.equal(b0.last_noise_std, b1.last_noise_std)
+    lr_mode = DS.PATCH_LR_REF if reference_scaling else DS.PATCH_UNIT
+    assert [l[0] for l in before] == ["degrade", "patch"] and [l[0] for l in launches] == ["degrade", "jpeg", "patch"]
+    assert lr0 == "degraded" and lr1 == "compressed"
+    k0, k1 = before[0][2], launches[0][2]
+    assert before[0][1][1:6] == launches[0][1][1:6]                    # tops, lefts, ph, pw, scale
+    assert k0["quantise"] is False and k0["mode"] == lr_mode and k1["quantise"] is True and k1["mode"] == DS.PATCH_UNIT
+    assert k0["transforms"] == k1["transforms"] and k0["offset"] == k1["offset"] == 1
+    assert launches[1][1][0] == "degraded" and launches[1][1][1] is b1.last_jpeg_quality and launches[1][1][2:] == ("4:4:4", lr_mode)
+    # explicit qualities replace the draw, and only it
+    r2 = RecordingRng(seed)
+    b2 = DS.PatchBank(pairs, 4, (8, 8), rng=r2, augment=True, reference_scaling=reference_scaling,
+                      degradation=DS.BlindDegradation(jpeg_quality=(30, 95), **spec))
+    b2.sample(batch, jpeg_quality=[10, 20, 30, 40, 50, 100])
+    assert len(r2.calls) == n0 and b2.last_jpeg_quality.tolist() == [10, 20, 30, 40, 50, 100]
+    b2.sample(batch, jpeg_quality=np.array([1, 2, 3, 4, 5, 6]))
+    assert b2.last_jpeg_quality.tolist() == [1, 2, 3, 4, 5, 6]
+
+
+# ------------------------------------------------------------------ header, binding, host-side checks
+def declared():
+    src = open(os.path.join(ROOT, "include", "dsr_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    out = {}
+    for m in re.finditer(r"\b(?:int|size_t|const char\*)\s+(dsr_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S):
+        args = m.group(2).strip()
+        out[m.group(1)] = 0 if args in ("", "void") else args.count(",") + 1
+    return out
+
+
+def test_symbols_declared_bound_and_exported(so):
+    L = P("_lib")
+    decl = declared()
+    for name, nargs in (("dsr_jpeg_workspace", 4), ("dsr_jpeg_u8", 9), ("dsr_jpeg_batch_f32", 10)):
+        assert decl.get(name) == nargs and len(L.SIGNATURES[name][1]) == nargs, name
+        assert hasattr(ctypes.CDLL(so), name)
+        assert (name in L._NO_LAUNCH) == (name == "dsr_jpeg_workspace"), name
+    assert L.ABI_VERSION == 7 and L.lib().dsr_abi_version() == 7
+    assert "jpeg.hip" in P("_build").SOURCES
+    header = open(os.path.join(ROOT, "include", "dsr_hip.h")).read()
+    for word in ("jfdctint", "jidctint", "25172", "F(.33126)", "F(1.772)", "ceil(H/2) - 1"):                # the definition is there
+        assert word in header, word
+
+
+def test_workspace_query(so):
+    W = P("_lib").lib().dsr_jpeg_workspace
+    assert W(1, 16, 16, 0) == 0 and W(7, 100, 100, 0) == 0             # 4:4:4 needs none
+    assert W(1, 16, 16, 2) == 16 * 16 + 2 * 8 * 8
+    assert W(1, 1, 1, 2) == 64 + 2 * 64
+    assert W(3, 18, 24, 2) == 3 * (24 * 24 + 2 * 16 * 16)              # luma 18 -> 24 rows; chroma 9 x 12 -> 16 x 16
+    assert W(2, 17, 33, 2) == 2 * (24 * 40 + 2 * 16 * 24)
+    for bad in [(0, 8, 8, 2), (1, 0, 8, 2), (1, 8, -1, 2), (1, 8, 8, 1), (1, 8, 8, 3), (70000, 8, 8, 2), (1, 70000, 8, 2)]:
+        assert W(*bad) == 0, bad
+
+
+def test_bad_arguments_return_codes_not_crashes(so):
+    """Both entry points validate on the host and return DSR_E_ARG before anything is launched (no GPU needed)."""
+    lib = P("_lib").lib()
+    N, st = None, None
+    a, b, q, ws = ctypes.c_void_p(256), ctypes.c_void_p(512), ctypes.c_void_p(1024), ctypes.c_void_p(2048)
+    odd = ctypes.c_void_p(2056)                                        # 8-byte, not 16-byte aligned
+    U, F = lib.dsr_jpeg_u8, lib.dsr_jpeg_batch_f32
+    # valid calls, argument by argument: U(a, b, 1, 8, 8, q, 2, ws, st) and F(a, b, 1, 8, 8, q, 2, 0, ws, st)
+    calls = [
+        lambda: U(N, b, 1, 8, 8, q, 0, N, st), lambda: U(a, N, 1, 8, 8, q, 0, N, st), lambda: U(a, b, 1, 8, 8, N, 0, N, st),   # null pointers
+        lambda: U(a, a, 1, 8, 8, q, 0, N, st),                                                                             # out is in
+        lambda: U(a, b, 0, 8, 8, q, 0, N, st), lambda: U(a, b, -1, 8, 8, q, 0, N, st), lambda: U(a, b, 65536, 8, 8, q, 0, N, st),
+        lambda: U(a, b, 1, 0, 8, q, 0, N, st), lambda: U(a, b, 1, 8, 0, q, 0, N, st), lambda: U(a, b, 1, 65537, 8, q, 0, N, st),
+        lambda: U(a, b, 1, 8, -3, q, 0, N, st),
+        lambda: U(a, b, 1, 8, 8, q, 1, ws, st), lambda: U(a, b, 1, 8, 8, q, 3, ws, st), lambda: U(a, b, 1, 8, 8, q, -1, ws, st),   # subsampling
+        lambda: U(a, b, 1, 8, 8, q, 2, N, st), lambda: U(a, b, 1, 8, 8, q, 2, odd, st),                                     # workspace
+        lambda: F(N, b, 1, 8, 8, q, 0, 0, N, st), lambda: F(a, N, 1, 8, 8, q, 0, 0, N, st), lambda: F(a, b, 1, 8, 8, N, 0, 0, N, st),
+        lambda: F(a, a, 1, 8, 8, q, 0, 0, N, st),
+        lambda: F(a, b, 0, 8, 8, q, 0, 0, N, st), lambda: F(a, b, 1, 0, 8, q, 0, 0, N, st), lambda: F(a, b, 1, 8, 0, q, 0, 0, N, st),
+        lambda: F(a, b, 1, 8, 8, q, 1, 0, ws, st), lambda: F(a, b, 1, 8, 8, q, 2, 0, N, st), lambda: F(a, b, 1, 8, 8, q, 2, 0, odd, st),
+        lambda: F(a, b, 1, 8, 8, q, 0, 4, N, st), lambda: F(a, b, 1, 8, 8, q, 0, -1, N, st), lambda: F(a, b, 1, 8, 8, q, 2, 4, ws, st),   # mode
+    ]
+    for i, call in enumerate(calls):
+        rc = call()
+        assert rc == DSR_E_ARG, f"call #{i} returned {rc}"
+        assert lib.dsr_last_error(), i
