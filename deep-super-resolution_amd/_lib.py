@@ -272,3 +272,13 @@ def check(rc):
     if rc != 0:
         raise RuntimeError("dsr_hip: " + lib().dsr_last_error().decode())
     return rc
+
+
+def ptr_table(tensors):
+    """HOST table of device pointers for the multi-tensor entry points, one per tensor; None becomes a NULL entry."""
+    return (C.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def size_table(values):
+    """HOST table of size_t (element counts) for the multi-tensor entry points."""
+    return (C.c_size_t * len(values))(*values)

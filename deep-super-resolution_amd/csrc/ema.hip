@@ -3,38 +3,31 @@
 // Reference semantics: torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn(decay) (first update copies, later
 // ones lerp with 1 - decay), and the warm-up rule of timm / torch-ema, decay_k = min(decay, (1 + k) / (10 + k)).
 //
-// Streaming kernels, two reads and one write per element (swap: two and two).  The layout is amp_check_kernel's
-// (pointwise.hip): up to 64 tensors per launch behind a block-to-tensor table, the 16-byte aligned body of a tensor cut
-// into chunks of DSR_EMA_CHUNK elements, one block each, 16-byte vector accesses in the body; the tensor's first block
-// also does the scalar head (a view may start 4, 8 or 12 bytes off a 16-byte boundary) and the tail.  Alignment is taken
-// from the first operand; when the second one sits at another offset from a 16-byte boundary the body of that tensor runs
-// on 4-byte accesses instead.  Every element is written by exactly one thread with a plain store: no atomics, the same
-// bits on every run.  The averaged-step counter is only read here; ema_tick_kernel, one thread, launched on the same
-// stream after every update launch of a step, is its only writer.
+// Streaming kernels, two reads and one write per element (swap: two and two).  The layout is multi_tensor.h's: up to 64
+// tensors per launch, each an aligned span in chunks of DSR_EMA_CHUNK elements with 16-byte vector accesses in the body.
+// Alignment is taken from the first operand; when the second one sits at another offset from a 16-byte boundary that
+// tensor is cut into plain chunks from element 0 and runs on 4-byte accesses instead (DSR_EMA_VEC, decided per tensor).
+// Every element is written by exactly one thread with a plain store: no atomics, the same bits on every run.  The
+// averaged-step counter is only read here; ema_tick_kernel, one thread, launched on the same stream after every update
+// launch of a step, is its only writer.
 #include <math.h>
 
 #include "dsr_common.h"
 #include "dsr_kernels.h"
+#include "multi_tensor.h"
 #include "../../include/dsr_hip.h"
 
-#define DSR_EMA_GROUP 64
 #define DSR_EMA_CHUNK 4096   // body elements per block: 4 16-byte vectors per thread
 #define DSR_EMA_COPY 1       // flags: exact copy whatever the counter says
 #define DSR_EMA_VEC 2        // flags: both operands share their offset from a 16-byte boundary
 struct EmaGroup {
-  float* a[DSR_EMA_GROUP];         // update: the shadow (written); swap: one side
-  float* b[DSR_EMA_GROUP];         // update: the parameter (read only); swap: the other side
-  size_t n[DSR_EMA_GROUP];
-  unsigned first_block[DSR_EMA_GROUP + 1];
-  unsigned char flags[DSR_EMA_GROUP];
-  int count;
+  float* a[DSR_MT_MAX];            // update: the shadow (written); swap: one side
+  float* b[DSR_MT_MAX];            // update: the parameter (read only); swap: the other side
+  size_t n[DSR_MT_MAX];
+  unsigned char flags[DSR_MT_MAX];
+  MtTable tb;
 };
 static_assert(sizeof(EmaGroup) <= 4096, "kernel arguments are limited to 4 KB");
-
-static __host__ __device__ inline size_t ema_head(const void* a, size_t n) {
-  const size_t h = ((16 - ((size_t)(uintptr_t)a & 15)) & 15) / 4;
-  return h < n ? h : n;
-}
 
 // s + w * (p - s) on raw bits; w == 1 with COPY set never reaches the arithmetic, so a copy keeps NaN payloads and -0
 __device__ __forceinline__ unsigned ema_mix(unsigned s, unsigned p, float w, bool copy) {
@@ -45,24 +38,28 @@ __device__ __forceinline__ unsigned ema_mix(unsigned s, unsigned p, float w, boo
 // SWAP = false: a <- mix(a, b); SWAP = true: a <-> b
 template <bool SWAP>
 __device__ __forceinline__ void ema_chunk(const EmaGroup& g, float w, bool copy_all) {
-  int t = 0;
-  while (t + 1 < g.count && blockIdx.x >= g.first_block[t + 1]) ++t;      // wave-uniform scan of <= 64 entries
-  const unsigned blk = blockIdx.x - g.first_block[t];
+  unsigned blk;
+  const int t = mt_locate(g.tb, blk);
   unsigned* __restrict__ a = reinterpret_cast<unsigned*>(g.a[t]);
   unsigned* __restrict__ b = reinterpret_cast<unsigned*>(g.b[t]);
   const size_t n = g.n[t];
   const bool copy = copy_all || (g.flags[t] & DSR_EMA_COPY);
   const bool vec = g.flags[t] & DSR_EMA_VEC;
-  const size_t head = vec ? ema_head(a, n) : 0;
-  const size_t nvec = vec ? (n - head) / 4 : 0;
-  const size_t body = vec ? nvec * 4 : n;        // elements handled in chunks, as vectors or one by one
-  const size_t e0 = (size_t)blk * DSR_EMA_CHUNK;
-  const size_t e1 = e0 + DSR_EMA_CHUNK < body ? e0 + DSR_EMA_CHUNK : body;
+  auto one = [&](size_t i) {                       // one element on 4-byte accesses
+    const unsigned x = a[i], y = b[i];
+    if constexpr (SWAP) {
+      a[i] = y;
+      b[i] = x;
+    } else {
+      a[i] = ema_mix(x, y, w, copy);
+    }
+  };
   if (vec) {
-    U4* __restrict__ av = reinterpret_cast<U4*>(a + head);
-    U4* __restrict__ bv = reinterpret_cast<U4*>(b + head);
+    const MtSpan sp = mt_span(a, n, blk, DSR_EMA_CHUNK);
+    U4* __restrict__ av = reinterpret_cast<U4*>(a + sp.head);
+    U4* __restrict__ bv = reinterpret_cast<U4*>(b + sp.head);
 #pragma unroll 4
-    for (size_t i = e0 / 4 + threadIdx.x; i < e1 / 4; i += 256) {
+    for (size_t i = sp.v0 + threadIdx.x; i < sp.v1; i += 256) {
       const U4 x = av[i], y = bv[i];
       if constexpr (SWAP) {
         av[i] = y;
@@ -76,32 +73,17 @@ __device__ __forceinline__ void ema_chunk(const EmaGroup& g, float w, bool copy_
         av[i] = r;
       }
     }
+    if (blk == 0) {                               // at most 3 head elements on threads 0..2, 3 tail elements on 64..66
+      size_t i = n;
+      if (threadIdx.x < sp.head) i = threadIdx.x;
+      else if (threadIdx.x >= 64 && sp.tail0 + (threadIdx.x - 64) < n) i = sp.tail0 + (threadIdx.x - 64);
+      if (i < n) one(i);
+    }
   } else {
+    const size_t e0 = (size_t)blk * DSR_EMA_CHUNK;
+    const size_t e1 = e0 + DSR_EMA_CHUNK < n ? e0 + DSR_EMA_CHUNK : n;
 #pragma unroll 4
-    for (size_t i = e0 + threadIdx.x; i < e1; i += 256) {
-      const unsigned x = a[i], y = b[i];
-      if constexpr (SWAP) {
-        a[i] = y;
-        b[i] = x;
-      } else {
-        a[i] = ema_mix(x, y, w, copy);
-      }
-    }
-  }
-  if (blk == 0 && vec) {                          // at most 3 head and 3 tail elements
-    const size_t tail0 = head + body;
-    size_t i = n;
-    if (threadIdx.x < head) i = threadIdx.x;
-    else if (threadIdx.x >= 64 && tail0 + (threadIdx.x - 64) < n) i = tail0 + (threadIdx.x - 64);
-    if (i < n) {
-      const unsigned x = a[i], y = b[i];
-      if constexpr (SWAP) {
-        a[i] = y;
-        b[i] = x;
-      } else {
-        a[i] = ema_mix(x, y, w, copy);
-      }
-    }
+    for (size_t i = e0 + threadIdx.x; i < e1; i += 256) one(i);
   }
 }
 
@@ -122,7 +104,8 @@ __global__ void ema_tick_kernel(int* n_averaged, const float* found_inf) {
   if (!found_inf || found_inf[0] == 0.f) n_averaged[0] += 1;
 }
 
-// every entry is checked before the first launch; 0: fine, < 0: dsr_fail's code
+// every entry is checked before the first launch; 0: fine, < 0: dsr_fail's code.  A tensor holds fewer than 2^42 elements
+// (2^30 blocks of DSR_EMA_CHUNK).
 static int ema_check_tables(const char* what, int count, float* const* a, const float* const* b, const size_t* n) {
   if (count < 0) return dsr_fail(DSR_E_ARG, "%s: count %d is negative", what, count);
   if (count && (!a || !b || !n)) return dsr_fail(DSR_E_ARG, "%s: null table", what);
@@ -139,34 +122,17 @@ static int ema_check_tables(const char* what, int count, float* const* a, const 
 template <class Launch>
 static int ema_for_groups(int count, float* const* a, const float* const* b, const size_t* n, const unsigned char* copy,
                            Launch launch) {
-  EmaGroup g;
-  g.count = 0;
-  size_t blocks = 0;
-  int launches = 0;
-  auto flush = [&]() {
-    if (!g.count) return;
-    g.first_block[g.count] = (unsigned)blocks;
-    launch(g, (unsigned)blocks);
-    ++launches;
-    g.count = 0;
-    blocks = 0;
-  };
-  for (int i = 0; i < count; ++i) {
-    if (!n[i] || !a[i] || a[i] == b[i]) continue;          // (a tensor against itself: nothing to do)
-    const bool vec = (((uintptr_t)a[i] ^ (uintptr_t)b[i]) & 15) == 0;
-    const size_t body = vec ? (n[i] - ema_head(a[i], n[i])) / 4 * 4 : n[i];
-    const size_t nb = body ? (body + DSR_EMA_CHUNK - 1) / DSR_EMA_CHUNK : 1;      // (a block for head / tail alone)
-    if (g.count == DSR_EMA_GROUP || blocks + nb > 0x7fffffffull) flush();
-    g.a[g.count] = a[i];
-    g.b[g.count] = const_cast<float*>(b[i]);
-    g.n[g.count] = n[i];
-    g.flags[g.count] = (unsigned char)((copy && copy[i] ? DSR_EMA_COPY : 0) | (vec ? DSR_EMA_VEC : 0));
-    g.first_block[g.count] = (unsigned)blocks;
-    blocks += nb;
-    ++g.count;
-  }
-  flush();
-  return launches;
+  auto vec = [&](int i) { return (((uintptr_t)a[i] ^ (uintptr_t)b[i]) & 15) == 0; };
+  return mt_for_groups<EmaGroup>(
+      count, DSR_MT_MAX, [&](int i) { return !n[i] || !a[i] || a[i] == b[i]; },         // (a tensor against itself: nothing to do)
+      [&](int i) { return vec(i) ? mt_span_blocks(a[i], n[i], DSR_EMA_CHUNK) : mt_blocks(n[i], DSR_EMA_CHUNK); },
+      [&](EmaGroup& g, int j, int i) {
+        g.a[j] = a[i];
+        g.b[j] = const_cast<float*>(b[i]);
+        g.n[j] = n[i];
+        g.flags[j] = (unsigned char)((copy && copy[i] ? DSR_EMA_COPY : 0) | (vec(i) ? DSR_EMA_VEC : 0));
+      },
+      launch);
 }
 
 extern "C" int dsr_ema_update_multi(int count, float* const* shadow, const float* const* p, const size_t* n,

@@ -18,9 +18,9 @@
 // results are bitwise deterministic.
 #include "dsr_common.h"
 #include "dsr_kernels.h"
+#include "multi_tensor.h"
 #include "../../include/dsr_hip.h"
 
-#define LB_GROUP 64              // tensors per gather / combine launch
 #define LB_GATHER_CHUNK 4096     // elements per gather block
 #define LB_COMBINE_CHUNK 1024    // elements per combine block (4 per thread)
 #define LB_DOT_E 8               // elements per thread of the dot pass (multiple of 4)
@@ -83,14 +83,13 @@ __device__ __forceinline__ unsigned lb_wave_max(unsigned v) {
   return v;
 }
 
-// a table of up to 64 tensors of one flat vector; blocks of a tensor are consecutive (dsr_pw_adam_multi's scheme)
+// up to 64 tensors of one flat vector per gather / combine launch (multi_tensor.h)
 struct LbGroup {
-  float* ptr[LB_GROUP];
-  size_t off[LB_GROUP];
-  size_t n[LB_GROUP];
-  unsigned first_block[LB_GROUP + 1];
-  int count;
-  unsigned block_base, total_blocks;
+  float* ptr[DSR_MT_MAX];
+  size_t off[DSR_MT_MAX];              // the tensor's offset in the flat vector
+  size_t n[DSR_MT_MAX];
+  MtTable tb;
+  unsigned block_base, total_blocks;   // blocks of the launches before this one; blocks of the whole table
 };
 static_assert(sizeof(LbGroup) <= 4096, "kernel arguments are limited to 4 KB");
 
@@ -101,9 +100,9 @@ __global__ __launch_bounds__(256) void lbfgs_gather_kernel(const LbGroup a, Lbfg
                                                            unsigned* __restrict__ gmax) {
   __shared__ double ss[4];
   __shared__ unsigned sx[4];
-  int t = 0;
-  while (t + 1 < a.count && blockIdx.x >= a.first_block[t + 1]) ++t;      // wave-uniform scan of <= 64 entries
-  const size_t base = (size_t)(blockIdx.x - a.first_block[t]) * LB_GATHER_CHUNK;
+  unsigned blk;
+  const int t = mt_locate(a.tb, blk);
+  const size_t base = (size_t)blk * LB_GATHER_CHUNK;
   const size_t nt = a.n[t];
   const float* __restrict__ gr = a.ptr[t];
   const int gprev = hdr->gprev, slot = hdr->free_slot;
@@ -430,9 +429,9 @@ __global__ __launch_bounds__(256) void lbfgs_combine_kernel(const LbGroup a, Lbf
                                                             const double* __restrict__ coef, float* __restrict__ vecs,
                                                             size_t n_pad, unsigned* __restrict__ cmax) {
   __shared__ unsigned sx[4];
-  int t = 0;
-  while (t + 1 < a.count && blockIdx.x >= a.first_block[t + 1]) ++t;
-  const size_t base = (size_t)(blockIdx.x - a.first_block[t]) * LB_COMBINE_CHUNK;
+  unsigned blk;
+  const int t = mt_locate(a.tb, blk);
+  const size_t base = (size_t)blk * LB_COMBINE_CHUNK;
   const size_t nt = a.n[t], off = a.off[t];
   const int mode = hdr->mode;
   unsigned mx = 0;
@@ -492,7 +491,7 @@ static unsigned lb_blocks(const char* what, int count, const void* const* ptrs, 
       return 0;
     }
     tot += numel[i];
-    blocks += (numel[i] + chunk - 1) / chunk;
+    blocks += mt_blocks(numel[i], chunk);
   }
   if (tot != n) {
     dsr_fail(DSR_E_ARG, "%s: tensor sizes add up to %zu, not n = %zu", what, tot, n);
@@ -505,24 +504,21 @@ template <typename K>
 static void lb_launch_groups(int count, const void* const* ptrs, const size_t* numel, size_t chunk, unsigned total, K launch) {
   size_t off = 0;
   unsigned block_base = 0;
-  for (int i0 = 0; i0 < count; i0 += LB_GROUP) {
-    LbGroup g;
-    g.count = count - i0 < LB_GROUP ? count - i0 : LB_GROUP;
-    unsigned blocks = 0;
-    for (int j = 0; j < g.count; ++j) {
-      g.ptr[j] = const_cast<float*>(static_cast<const float*>(ptrs[i0 + j]));
-      g.off[j] = off;
-      g.n[j] = numel[i0 + j];
-      g.first_block[j] = blocks;
-      blocks += (unsigned)((numel[i0 + j] + chunk - 1) / chunk);
-      off += numel[i0 + j];
-    }
-    g.first_block[g.count] = blocks;
-    g.block_base = block_base;
-    g.total_blocks = total;
-    launch(g, blocks);
-    block_base += blocks;
-  }
+  mt_for_groups<LbGroup>(
+      count, DSR_MT_MAX, [](int) { return false; },                        // fixed slices (lb_blocks refused empty tensors)
+      [&](int i) { return mt_blocks(numel[i], chunk); },
+      [&](LbGroup& g, int j, int i) {
+        g.ptr[j] = const_cast<float*>(static_cast<const float*>(ptrs[i]));
+        g.off[j] = off;
+        g.n[j] = numel[i];
+        off += numel[i];
+      },
+      [&](LbGroup& g, unsigned blocks) {
+        g.block_base = block_base;
+        g.total_blocks = total;
+        launch(g, blocks);
+        block_base += blocks;
+      });
 }
 
 extern "C" int dsr_lbfgs_gather(int count, const float* const* grads, const size_t* numel, void* ws, size_t ws_bytes,

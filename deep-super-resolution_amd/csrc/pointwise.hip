@@ -14,6 +14,7 @@
 
 #include "dsr_common.h"
 #include "dsr_kernels.h"
+#include "multi_tensor.h"
 #include "../../include/dsr_hip.h"
 
 // ------------------------------------------------------------------ layout conversion
@@ -75,24 +76,24 @@ __global__ void pack_weight_kernel(const float* __restrict__ w, unsigned short* 
 }
 
 // All conv weights of an optimiser re-packed in one launch per 48 tensors (after Adam rewrote them): the per-layer
-// launches above are 45 x ~8 us per step for a few MB of data.
+// launches above are 45 x ~8 us per step for a few MB of data.  multi_tensor.h's scheme, 256 padded elements per block.
 #define DSR_PACK_GROUP 48
 struct PackGroup {
   const float* w[DSR_PACK_GROUP];
   unsigned short* wf[DSR_PACK_GROUP];
   unsigned short* wd[DSR_PACK_GROUP];
   int cout[DSR_PACK_GROUP], cin[DSR_PACK_GROUP], taps[DSR_PACK_GROUP];
-  unsigned first_block[DSR_PACK_GROUP + 1];
-  int count;
+  MtTable tb;
 };
+static_assert(sizeof(PackGroup) <= 4096 && DSR_PACK_GROUP <= DSR_MT_MAX, "kernel arguments are limited to 4 KB");
 template <int DT>
 __global__ __launch_bounds__(256) void pack_weight_multi_kernel(const PackGroup a) {
-  int t = 0;
-  while (t + 1 < a.count && blockIdx.x >= a.first_block[t + 1]) ++t;      // block-uniform scan
+  unsigned blk;
+  const int t = mt_locate(a.tb, blk);
   const int Cout = a.cout[t], Cin = a.cin[t], T = a.taps[t];
   const int CoutP = (Cout + 7) & ~7, CinP = (Cin + 7) & ~7;
   const float* __restrict__ w = a.w[t];
-  const size_t idx = (size_t)(blockIdx.x - a.first_block[t]) * 256 + threadIdx.x;
+  const size_t idx = (size_t)blk * 256 + threadIdx.x;
   const size_t nf = (size_t)T * CoutP * CinP;                              // both images have T * CoutP * CinP elements
   if (idx >= nf) return;
   {
@@ -111,28 +112,23 @@ __global__ __launch_bounds__(256) void pack_weight_multi_kernel(const PackGroup 
 extern "C" int dsr_conv_pack_weight_multi(int dtype, int count, const float* const* w, void* const* wf, void* const* wd,
                                           const int* cout, const int* cin, const int* taps, hipStream_t st) {
   if (count < 0 || (count && (!w || !wf || !wd || !cout || !cin || !taps))) return dsr_fail(DSR_E_ARG, "pack_weight_multi: null table");
-  for (int i0 = 0; i0 < count; i0 += DSR_PACK_GROUP) {
-    PackGroup g;
-    g.count = count - i0 < DSR_PACK_GROUP ? count - i0 : DSR_PACK_GROUP;
-    unsigned blocks = 0;
-    for (int j = 0; j < g.count; ++j) {
-      g.w[j] = w[i0 + j];
-      g.wf[j] = (unsigned short*)wf[i0 + j];
-      g.wd[j] = (unsigned short*)wd[i0 + j];
-      g.cout[j] = cout[i0 + j];
-      g.cin[j] = cin[i0 + j];
-      g.taps[j] = taps[i0 + j];
-      g.first_block[j] = blocks;
-      const size_t n = (size_t)taps[i0 + j] * ((cout[i0 + j] + 7) & ~7) * ((cin[i0 + j] + 7) & ~7);
-      blocks += (unsigned)((n + 255) / 256);
-    }
-    g.first_block[g.count] = blocks;
-    if (!blocks) continue;
-    if (dtype == DSR_BF16)
-      hipLaunchKernelGGL((pack_weight_multi_kernel<DSR_DTYPE_BF16>), dim3(blocks), dim3(256), 0, st, g);
-    else
-      hipLaunchKernelGGL((pack_weight_multi_kernel<DSR_DTYPE_F16>), dim3(blocks), dim3(256), 0, st, g);
-  }
+  mt_for_groups<PackGroup>(
+      count, DSR_PACK_GROUP, [](int) { return false; },                    // fixed slices: an empty weight keeps its slot
+      [&](int i) { return mt_blocks((size_t)taps[i] * ((cout[i] + 7) & ~7) * ((cin[i] + 7) & ~7), 256); },
+      [&](PackGroup& g, int j, int i) {
+        g.w[j] = w[i];
+        g.wf[j] = (unsigned short*)wf[i];
+        g.wd[j] = (unsigned short*)wd[i];
+        g.cout[j] = cout[i];
+        g.cin[j] = cin[i];
+        g.taps[j] = taps[i];
+      },
+      [&](const PackGroup& g, unsigned blocks) {
+        if (dtype == DSR_BF16)
+          hipLaunchKernelGGL((pack_weight_multi_kernel<DSR_DTYPE_BF16>), dim3(blocks), dim3(256), 0, st, g);
+        else
+          hipLaunchKernelGGL((pack_weight_multi_kernel<DSR_DTYPE_F16>), dim3(blocks), dim3(256), 0, st, g);
+      });
   return dsr_launch_status("dsr_conv_pack_weight_multi");
 }
 
@@ -1168,43 +1164,33 @@ __global__ void incr_unless_kernel(int* step, const float* found_inf) {
 
 // ------------------------------------------------------------------ dynamic loss scale (optim.DynamicLossScaler)
 // State: scale (fp32, a power of two), growth_tracker (int32), found_inf (fp32 0 / 1), all on the device.
-// amp_check_kernel: one streaming read of up to 64 fp32 gradient tensors.  A tensor's 16-byte aligned body is cut into
-// chunks of DSR_AMP_CHUNK elements, one block each; the tensor's first block also reads the scalar head (a view may start
-// 4, 8 or 12 bytes off a 16-byte boundary) and tail.  Inf and NaN are the values whose exponent bits are all ones.  Every
-// writer stores the same 1, so the store needs neither an atomic nor an order; 0 is never written here.
-#define DSR_AMP_GROUP 64
+// amp_check_kernel: one streaming read of up to 64 fp32 gradient tensors, each an aligned span of multi_tensor.h in chunks
+// of DSR_AMP_CHUNK elements.  Inf and NaN are the values whose exponent bits are all ones.  Every writer stores the same 1,
+// so the store needs neither an atomic nor an order; 0 is never written here.
 #define DSR_AMP_CHUNK 8192   // elements per block: 8 16-byte vectors per thread
 struct AmpGroup {
-  const float* g[DSR_AMP_GROUP];
-  size_t n[DSR_AMP_GROUP];
-  unsigned first_block[DSR_AMP_GROUP + 1];
-  int count;
+  const float* g[DSR_MT_MAX];
+  size_t n[DSR_MT_MAX];
+  MtTable tb;
 };
 static_assert(sizeof(AmpGroup) <= 4096, "kernel arguments are limited to 4 KB");
 __device__ __forceinline__ bool amp_nonfinite(unsigned bits) { return (bits & 0x7f800000u) == 0x7f800000u; }
-static __host__ __device__ inline size_t amp_head(const float* g, size_t n) {
-  const size_t h = ((16 - ((size_t)(uintptr_t)g & 15)) & 15) / 4;
-  return h < n ? h : n;
-}
 __global__ __launch_bounds__(256) void amp_check_kernel(const AmpGroup a, float* __restrict__ found_inf) {
-  int t = 0;
-  while (t + 1 < a.count && blockIdx.x >= a.first_block[t + 1]) ++t;      // wave-uniform scan of <= 64 entries
-  const unsigned blk = blockIdx.x - a.first_block[t];
+  unsigned blk;
+  const int t = mt_locate(a.tb, blk);
   const unsigned* __restrict__ g = reinterpret_cast<const unsigned*>(a.g[t]);
-  const size_t n = a.n[t], head = amp_head(a.g[t], n), nvec = (n - head) / 4;
-  const U4* __restrict__ body = reinterpret_cast<const U4*>(g + head);
-  const size_t v0 = (size_t)blk * (DSR_AMP_CHUNK / 4);
-  const size_t v1 = v0 + DSR_AMP_CHUNK / 4 < nvec ? v0 + DSR_AMP_CHUNK / 4 : nvec;
+  const size_t n = a.n[t];
+  const MtSpan sp = mt_span(g, n, blk, DSR_AMP_CHUNK);
+  const U4* __restrict__ body = reinterpret_cast<const U4*>(g + sp.head);
   bool bad = false;
 #pragma unroll 4
-  for (size_t i = v0 + threadIdx.x; i < v1; i += 256) {
+  for (size_t i = sp.v0 + threadIdx.x; i < sp.v1; i += 256) {
     const U4 x = __builtin_nontemporal_load(body + i);
     bad |= amp_nonfinite(x.x) | amp_nonfinite(x.y) | amp_nonfinite(x.z) | amp_nonfinite(x.w);
   }
   if (blk == 0) {
-    const size_t tail0 = head + nvec * 4;
-    if (threadIdx.x < head) bad |= amp_nonfinite(g[threadIdx.x]);
-    if (tail0 + threadIdx.x < n) bad |= amp_nonfinite(g[tail0 + threadIdx.x]);
+    if (threadIdx.x < sp.head) bad |= amp_nonfinite(g[threadIdx.x]);
+    if (sp.tail0 + threadIdx.x < n) bad |= amp_nonfinite(g[sp.tail0 + threadIdx.x]);
   }
   if (__ballot(bad) != 0 && (threadIdx.x & 63) == 0) found_inf[0] = 1.f;
 }
@@ -1233,27 +1219,24 @@ __global__ void amp_update_kernel(float* scale, int* growth_tracker, float* foun
 // ------------------------------------------------------------------ gradient-norm clipping (optim.FusedAdam(max_grad_norm=c))
 // torch.nn.utils.clip_grad_norm_(params, c, norm_type=2) with nothing read on the host and no gradient rewritten: one
 // streaming read forms the sum of squares, dsr_clip_finalize turns it into the coefficient, the _hyper Adam kernels apply it.
-// clip_sumsq_kernel: amp_check_kernel's layout (<= 64 tensors per launch, DSR_AMP_CHUNK elements of a tensor's 16-byte
-// aligned body per block, scalar head and tail in the tensor's first block).  A thread squares and adds at most 32 body
-// elements (8 vectors x 4) and 2 head / tail elements in fp32, in a fixed order; from there on everything is fp64 (butterfly
-// over the wave, the four wave sums in order), and the block stores ONE fp32 partial at its own index: no atomics, the same
-// bits on every run.
+// clip_sumsq_kernel: amp_check_kernel's group struct and chunk (aligned spans of multi_tensor.h).  A thread squares and adds
+// at most 32 body elements (8 vectors x 4) and 2 head / tail elements in fp32, in a fixed order; from there on everything is
+// fp64 (butterfly over the wave, the four wave sums in order), and the block stores ONE fp32 partial at its own index: no
+// atomics, the same bits on every run.
 __global__ __launch_bounds__(256) void clip_sumsq_kernel(const AmpGroup a, float* __restrict__ partial) {
   typedef __attribute__((ext_vector_type(4))) float F4;
   __shared__ double red[4];
-  int t = 0;
-  while (t + 1 < a.count && blockIdx.x >= a.first_block[t + 1]) ++t;      // wave-uniform scan of <= 64 entries
-  const unsigned blk = blockIdx.x - a.first_block[t];
+  unsigned blk;
+  const int t = mt_locate(a.tb, blk);
   const float* __restrict__ g = a.g[t];
-  const size_t n = a.n[t], head = amp_head(a.g[t], n), nvec = (n - head) / 4;
-  const F4* __restrict__ body = reinterpret_cast<const F4*>(g + head);
-  const size_t v0 = (size_t)blk * (DSR_AMP_CHUNK / 4);
-  const size_t v1 = v0 + DSR_AMP_CHUNK / 4 < nvec ? v0 + DSR_AMP_CHUNK / 4 : nvec;
+  const size_t n = a.n[t];
+  const MtSpan sp = mt_span(g, n, blk, DSR_AMP_CHUNK);
+  const F4* __restrict__ body = reinterpret_cast<const F4*>(g + sp.head);
   float s = 0.f;
   {
 #pragma clang fp contract(off)
 #pragma unroll 4
-    for (size_t i = v0 + threadIdx.x; i < v1; i += 256) {
+    for (size_t i = sp.v0 + threadIdx.x; i < sp.v1; i += 256) {
       const F4 x = __builtin_nontemporal_load(body + i);
       s += x.x * x.x;
       s += x.y * x.y;
@@ -1261,9 +1244,8 @@ __global__ __launch_bounds__(256) void clip_sumsq_kernel(const AmpGroup a, float
       s += x.w * x.w;
     }
     if (blk == 0) {
-      const size_t tail0 = head + nvec * 4;
-      if (threadIdx.x < head) s += g[threadIdx.x] * g[threadIdx.x];
-      if (tail0 + threadIdx.x < n) s += g[tail0 + threadIdx.x] * g[tail0 + threadIdx.x];
+      if (threadIdx.x < sp.head) s += g[threadIdx.x] * g[threadIdx.x];
+      if (sp.tail0 + threadIdx.x < n) s += g[sp.tail0 + threadIdx.x] * g[sp.tail0 + threadIdx.x];
     }
   }
   double d = (double)s;
@@ -1590,23 +1572,23 @@ extern "C" int dsr_pw_adam_amp(float* p, const float* g, float* m, float* v, siz
                      (unsigned short*)shadow_bf16, scale, found_inf);
   return dsr_launch_status("dsr_pw_adam_amp");
 }
-// ---- multi-tensor Adam: the generator and discriminator hold ~100 small tensors each; one launch per 64 of them.
-#define DSR_ADAM_GROUP 64
+// ---- multi-tensor Adam: the generator and discriminator hold ~100 small tensors each; one launch per 64 of them
+// (multi_tensor.h).  Element indices are 32-bit here, so a tensor holds at most 2^32 - 1 - DSR_ADAM_CHUNK elements.
 #define DSR_ADAM_CHUNK 4096   // elements per block
 struct AdamGroup {
-  float* p[DSR_ADAM_GROUP];
-  const float* g[DSR_ADAM_GROUP];
-  float* m[DSR_ADAM_GROUP];
-  float* v[DSR_ADAM_GROUP];
-  unsigned n[DSR_ADAM_GROUP];
-  unsigned first_block[DSR_ADAM_GROUP + 1];
-  int count;
+  float* p[DSR_MT_MAX];
+  const float* g[DSR_MT_MAX];
+  float* m[DSR_MT_MAX];
+  float* v[DSR_MT_MAX];
+  unsigned n[DSR_MT_MAX];
+  MtTable tb;
 };
+static_assert(sizeof(AdamGroup) <= 4096, "kernel arguments are limited to 4 KB");
 // this block's chunk of its tensor (shared by adam_multi_kernel and adam_multi_hyper_kernel)
 __device__ __forceinline__ void adam_multi_chunk(const AdamGroup& a, const AdamCoef& co) {
-  int t = 0;
-  while (t + 1 < a.count && blockIdx.x >= a.first_block[t + 1]) ++t;      // wave-uniform scan of <= 64 entries
-  const unsigned base = (blockIdx.x - a.first_block[t]) * DSR_ADAM_CHUNK;
+  unsigned blk;
+  const int t = mt_locate(a.tb, blk);
+  const unsigned base = blk * DSR_ADAM_CHUNK;
   const unsigned n = a.n[t];
   float* __restrict__ p = a.p[t];
   const float* __restrict__ g = a.g[t];
@@ -1645,28 +1627,26 @@ static int adam_multi_launch(const char* what, int count, float* const* p, const
                              float* const* v, const size_t* n, float lr, float b1, float b2, float eps, const int* step,
                              float grad_scale, const float* loss_scale, const float* found_inf, hipStream_t st,
                              const float* hyper = nullptr) {
-  for (int i0 = 0; i0 < count; i0 += DSR_ADAM_GROUP) {
-    AdamGroup a;
-    a.count = count - i0 < DSR_ADAM_GROUP ? count - i0 : DSR_ADAM_GROUP;
-    unsigned blocks = 0;
-    for (int j = 0; j < a.count; ++j) {
-      if (n[i0 + j] > 0xFFFFFFFFull - DSR_ADAM_CHUNK) return dsr_fail(DSR_E_UNSUPPORTED, "adam_multi: tensor too large");
-      a.p[j] = p[i0 + j];
-      a.g[j] = g[i0 + j];
-      a.m[j] = m[i0 + j];
-      a.v[j] = v[i0 + j];
-      a.n[j] = (unsigned)n[i0 + j];
-      a.first_block[j] = blocks;
-      blocks += (unsigned)((n[i0 + j] + DSR_ADAM_CHUNK - 1) / DSR_ADAM_CHUNK);
-    }
-    a.first_block[a.count] = blocks;
-    if (blocks && hyper)
-      hipLaunchKernelGGL(adam_multi_hyper_kernel, dim3(blocks), dim3(256), 0, st, a, hyper, b1, b2, eps, step, grad_scale,
-                         loss_scale, found_inf);
-    else if (blocks)
-      hipLaunchKernelGGL(adam_multi_kernel<AMP>, dim3(blocks), dim3(256), 0, st, a, lr, b1, b2, eps, step, grad_scale,
-                         loss_scale, found_inf);
-  }
+  for (int i = 0; i < count; ++i)          // every entry is checked before the first launch
+    if (n[i] > 0xFFFFFFFFull - DSR_ADAM_CHUNK) return dsr_fail(DSR_E_UNSUPPORTED, "adam_multi: tensor too large");
+  mt_for_groups<AdamGroup>(
+      count, DSR_MT_MAX, [](int) { return false; },                        // fixed slices: an empty tensor keeps its slot
+      [&](int i) { return mt_blocks(n[i], DSR_ADAM_CHUNK); },
+      [&](AdamGroup& a, int j, int i) {
+        a.p[j] = p[i];
+        a.g[j] = g[i];
+        a.m[j] = m[i];
+        a.v[j] = v[i];
+        a.n[j] = (unsigned)n[i];
+      },
+      [&](const AdamGroup& a, unsigned blocks) {
+        if (hyper)
+          hipLaunchKernelGGL(adam_multi_hyper_kernel, dim3(blocks), dim3(256), 0, st, a, hyper, b1, b2, eps, step,
+                             grad_scale, loss_scale, found_inf);
+        else
+          hipLaunchKernelGGL(adam_multi_kernel<AMP>, dim3(blocks), dim3(256), 0, st, a, lr, b1, b2, eps, step, grad_scale,
+                             loss_scale, found_inf);
+      });
   return dsr_launch_status(what);
 }
 extern "C" int dsr_pw_adam_multi(int count, float* const* p, const float* const* g, float* const* m, float* const* v,
@@ -1695,33 +1675,31 @@ extern "C" int dsr_pw_incr_unless(int* step, const float* found_inf, hipStream_t
   hipLaunchKernelGGL(incr_unless_kernel, dim3(1), dim3(1), 0, st, step, found_inf);
   return dsr_launch_status("dsr_pw_incr_unless");
 }
+// The gradient tables of dsr_amp_check and dsr_clip_sumsq*: NULL = no gradient, skipped; any other entry holds 0 < n < 2^43
+// elements (2^30 blocks of DSR_AMP_CHUNK) at a 4-byte aligned address.  Returns the first entry that does not, or -1.
+static int amp_bad_entry(int count, const float* const* grads, const size_t* numel) {
+  for (int i = 0; i < count; ++i)
+    if (grads[i] && !(numel[i] > 0 && numel[i] < ((size_t)1 << 43) && ((uintptr_t)grads[i] & 3) == 0)) return i;
+  return -1;
+}
+template <class Launch>
+static void amp_for_groups(int count, const float* const* grads, const size_t* numel, Launch launch) {
+  mt_for_groups<AmpGroup>(
+      count, DSR_MT_MAX, [&](int i) { return !grads[i]; },
+      [&](int i) { return mt_span_blocks(grads[i], numel[i], DSR_AMP_CHUNK); },
+      [&](AmpGroup& a, int j, int i) {
+        a.g[j] = grads[i];
+        a.n[j] = numel[i];
+      },
+      launch);
+}
 extern "C" int dsr_amp_check(int count, const float* const* grads, const size_t* numel, float* found_inf, hipStream_t st) {
   DSR_REQUIRE(count > 0 && grads && numel && found_inf, "amp_check: null pointer or no tensors");
-  for (int i = 0; i < count; ++i)      // NULL = no gradient, skipped; a launch holds < 2^31 blocks of DSR_AMP_CHUNK elements
-    DSR_REQUIRE(!grads[i] || (numel[i] > 0 && numel[i] < ((size_t)1 << 43) && ((uintptr_t)grads[i] & 3) == 0),
-                "amp_check: tensor %d is empty, too large or not 4-byte aligned", i);
-  AmpGroup a;
-  a.count = 0;
-  size_t blocks = 0;
-  auto flush = [&]() {
-    if (!a.count) return;
-    a.first_block[a.count] = (unsigned)blocks;
-    hipLaunchKernelGGL(amp_check_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, found_inf);
-    a.count = 0;
-    blocks = 0;
-  };
-  for (int i = 0; i < count; ++i) {
-    if (!grads[i]) continue;
-    const size_t nvec = (numel[i] - amp_head(grads[i], numel[i])) / 4;
-    const size_t nb = nvec ? (nvec + DSR_AMP_CHUNK / 4 - 1) / (DSR_AMP_CHUNK / 4) : 1;
-    if (a.count == DSR_AMP_GROUP || blocks + nb > 0x7fffffffull) flush();
-    a.g[a.count] = grads[i];
-    a.n[a.count] = numel[i];
-    a.first_block[a.count] = (unsigned)blocks;
-    blocks += nb;
-    ++a.count;
-  }
-  flush();
+  const int bad = amp_bad_entry(count, grads, numel);
+  DSR_REQUIRE(bad < 0, "amp_check: tensor %d is empty, too large or not 4-byte aligned", bad);
+  amp_for_groups(count, grads, numel, [&](const AmpGroup& a, unsigned blocks) {
+    hipLaunchKernelGGL(amp_check_kernel, dim3(blocks), dim3(256), 0, st, a, found_inf);
+  });
   return dsr_launch_status("dsr_amp_check");
 }
 static bool amp_pow2(float x) {
@@ -1740,56 +1718,28 @@ extern "C" int dsr_amp_update(float* scale, int* growth_tracker, float* found_in
 }
 
 // ------------------------------------------------------------------ clipping + device hyper-parameters: C ABI
-static bool clip_tables_ok(int count, const float* const* grads, const size_t* numel) {
-  if (count <= 0 || !grads || !numel) return false;
-  for (int i = 0; i < count; ++i)
-    if (grads[i] && !(numel[i] > 0 && numel[i] < ((size_t)1 << 43) && ((uintptr_t)grads[i] & 3) == 0)) return false;
-  return true;
-}
-static size_t clip_tensor_blocks(const float* g, size_t n) {
-  const size_t nvec = (n - amp_head(g, n)) / 4;
-  return nvec ? (nvec + DSR_AMP_CHUNK / 4 - 1) / (DSR_AMP_CHUNK / 4) : 1;
-}
 extern "C" size_t dsr_clip_sumsq_partials(int count, const float* const* grads, const size_t* numel) {
-  if (!clip_tables_ok(count, grads, numel)) return 0;
+  if (count <= 0 || !grads || !numel || amp_bad_entry(count, grads, numel) >= 0) return 0;
   size_t blocks = 0;
   for (int i = 0; i < count; ++i)
-    if (grads[i]) blocks += clip_tensor_blocks(grads[i], numel[i]);
+    if (grads[i]) blocks += mt_span_blocks(grads[i], numel[i], DSR_AMP_CHUNK);
   return blocks;
 }
 extern "C" int dsr_clip_sumsq(int count, const float* const* grads, const size_t* numel, float* partials, size_t n_partials,
                               hipStream_t st) {
   DSR_REQUIRE(count > 0 && grads && numel && partials, "clip_sumsq: null pointer or no tensors");
   DSR_REQUIRE(((uintptr_t)partials & 3) == 0, "clip_sumsq: partials not 4-byte aligned");
-  for (int i = 0; i < count; ++i)      // NULL = no gradient, skipped
-    DSR_REQUIRE(!grads[i] || (numel[i] > 0 && numel[i] < ((size_t)1 << 43) && ((uintptr_t)grads[i] & 3) == 0),
-                "clip_sumsq: tensor %d is empty, too large or not 4-byte aligned", i);
+  const int bad = amp_bad_entry(count, grads, numel);
+  DSR_REQUIRE(bad < 0, "clip_sumsq: tensor %d is empty, too large or not 4-byte aligned", bad);
   const size_t need = dsr_clip_sumsq_partials(count, grads, numel);
   if (need == 0) return dsr_fail(DSR_E_ARG, "clip_sumsq: every table entry is NULL");
   if (n_partials < need || need > 0x7fffffffull)
     return dsr_fail(DSR_E_WORKSPACE, "clip_sumsq: %zu partials needed, %zu given", need, n_partials);
-  AmpGroup a;
-  a.count = 0;
-  size_t blocks = 0, base = 0;
-  auto flush = [&]() {
-    if (!a.count) return;
-    a.first_block[a.count] = (unsigned)blocks;
-    hipLaunchKernelGGL(clip_sumsq_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, partials + base);
+  size_t base = 0;                         // partials are indexed by running block number across launches
+  amp_for_groups(count, grads, numel, [&](const AmpGroup& a, unsigned blocks) {
+    hipLaunchKernelGGL(clip_sumsq_kernel, dim3(blocks), dim3(256), 0, st, a, partials + base);
     base += blocks;
-    a.count = 0;
-    blocks = 0;
-  };
-  for (int i = 0; i < count; ++i) {
-    if (!grads[i]) continue;
-    const size_t nb = clip_tensor_blocks(grads[i], numel[i]);
-    if (a.count == DSR_AMP_GROUP || blocks + nb > 0x7fffffffull) flush();
-    a.g[a.count] = grads[i];
-    a.n[a.count] = numel[i];
-    a.first_block[a.count] = (unsigned)blocks;
-    blocks += nb;
-    ++a.count;
-  }
-  flush();
+  });
   return dsr_launch_status("dsr_clip_sumsq");
 }
 extern "C" int dsr_clip_finalize(const float* partials, int n_partials, const double* gram_partials, int n_gram,

@@ -138,11 +138,10 @@ def repack_cached(params):
     lib = _lib.lib()
     for dtype, items in by_dtype.items():
         k = len(items)
-        arr = lambda vals: (C.c_void_p * k)(*vals)
         ints = lambda vals: (C.c_int * k)(*vals)
         check(lib.dsr_conv_pack_weight_multi(
-            BF16 if dtype == torch.bfloat16 else F16, k, arr([p.data_ptr() for _, p, _ in items]),
-            arr([h[1].data_ptr() for _, _, h in items]), arr([h[2].data_ptr() for _, _, h in items]),
+            BF16 if dtype == torch.bfloat16 else F16, k, _lib.ptr_table([p for _, p, _ in items]),
+            _lib.ptr_table([h[1] for _, _, h in items]), _lib.ptr_table([h[2] for _, _, h in items]),
             ints([p.shape[0] for _, p, _ in items]), ints([p.shape[1] for _, p, _ in items]),
             ints([p.shape[2] * p.shape[3] for _, p, _ in items]), _stream()))
         for key, p, hit in items:

@@ -11,6 +11,7 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
+from ._lib import ptr_table, size_table
 from .functional import _need_gpu, _ptr, _stream, bump, check, mark_shadow_current, repack_cached, shadow_for_update
 
 
@@ -115,8 +116,7 @@ class FusedAdam:
             grads = [g for g in list(grads) + keep if g.numel()]
             if grads:
                 k = len(grads)
-                ptrs = (C.c_void_p * k)(*[g.data_ptr() for g in grads])
-                ns = (C.c_size_t * k)(*[g.numel() for g in grads])
+                ptrs, ns = ptr_table(grads), size_table([g.numel() for g in grads])
                 npart = lib.dsr_clip_sumsq_partials(k, ptrs, ns)
                 parts = self._buffer("_partials", 4 * npart)
                 check(lib.dsr_clip_sumsq(k, ptrs, ns, _ptr(parts), npart, st))
@@ -220,8 +220,8 @@ class FusedAdam:
                 run()
         if small:                            # every small tensor in one launch per 64 (dsr_pw_adam_multi)
             k = len(small)
-            arr = [(C.c_void_p * k)(*[t[i].data_ptr() for t in small]) for i in range(4)]
-            ns = (C.c_size_t * k)(*[t[0].numel() for t in small])
+            arr = [ptr_table([t[i] for t in small]) for i in range(4)]
+            ns = size_table([t[0].numel() for t in small])
             if hyper:
                 check(lib.dsr_pw_adam_multi_hyper(k, arr[0], arr[1], arr[2], arr[3], ns, hp, b1, b2, self.eps,
                                                   _ptr(self.step_t), self.grad_scale, _ptr(scale), _ptr(found), st))
@@ -314,9 +314,8 @@ class DynamicLossScaler:
             grads.append(g if g is not None and g.numel() else None)
         _, found = self._state(optimizer.step_t.device)
         k = len(grads)
-        check(_lib.lib().dsr_amp_check(k, (C.c_void_p * k)(*[None if g is None else g.data_ptr() for g in grads]),
-                                       (C.c_size_t * k)(*[0 if g is None else g.numel() for g in grads]), _ptr(found),
-                                       _stream()))
+        check(_lib.lib().dsr_amp_check(k, ptr_table(grads), size_table([0 if g is None else g.numel() for g in grads]),
+                                       _ptr(found), _stream()))
         self._checked = True
         return optimizer.step(scaler=self)
 
@@ -470,8 +469,7 @@ class WeightEMA:
     def _tables(dst, src):
         """HOST tables of the C ABI over 32-bit words (a copy or a swap moves bits, so an int64 counter is two words each)."""
         k = len(dst)
-        return (k, (C.c_void_p * k)(*[t.data_ptr() for t in dst]), (C.c_void_p * k)(*[t.data_ptr() for t in src]),
-                (C.c_size_t * k)(*[t.numel() * t.element_size() // 4 for t in dst]))
+        return k, ptr_table(dst), ptr_table(src), size_table([t.numel() * t.element_size() // 4 for t in dst])
 
     def _rewritten(self, module, tensors):
         for t in tensors:
@@ -638,7 +636,7 @@ class FusedLBFGS:
         self._ws = torch.zeros(self._ws_bytes, dtype=torch.uint8, device=dev)
         self._vecs = torch.zeros(nvec, dtype=torch.float32, device=dev)
         self._stop = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._numel = (C.c_size_t * k)(*[p.numel() for p in self._flat])
+        self._numel = size_table([p.numel() for p in self._flat])
 
     def zero_grad(self, set_to_none=True):
         for p in self.params:
@@ -663,26 +661,21 @@ class FusedLBFGS:
         lib = _lib.lib()
         st = _stream()
         k, h, n = len(self._flat), self.history_size, self.n
-        keep, grads = [], []
+        grads = []
         for p in self._flat:
             g = p.grad
-            if g is None:
-                grads.append(None)
-                continue
-            if g.is_sparse:
+            if g is not None and g.is_sparse:
                 g = g.to_dense()
-            if g.dtype != torch.float32 or not g.is_contiguous():
+            if g is not None and (g.dtype != torch.float32 or not g.is_contiguous()):
                 g = g.float().contiguous()
-            keep.append(g)
-            grads.append(g.data_ptr())
+            grads.append(g)
         lv = self._loss_scalar(loss)
         ws, vecs = _ptr(self._ws), _ptr(self._vecs)
-        check(lib.dsr_lbfgs_gather(k, (C.c_void_p * k)(*grads), self._numel, ws, self._ws_bytes, vecs, h, n, st))
+        check(lib.dsr_lbfgs_gather(k, ptr_table(grads), self._numel, ws, self._ws_bytes, vecs, h, n, st))
         check(lib.dsr_lbfgs_dots(ws, self._ws_bytes, vecs, h, n, k, st))
         check(lib.dsr_lbfgs_scalar(ws, self._ws_bytes, h, n, k, _ptr(lv), 1 if first else 0, _ptr(self._stop), self.lr,
                                    self.max_iter, self.max_eval, self.tolerance_grad, self.tolerance_change, st))
-        check(lib.dsr_lbfgs_combine(k, (C.c_void_p * k)(*[p.data_ptr() for p in self._flat]), self._numel, ws,
-                                    self._ws_bytes, vecs, h, n, st))
+        check(lib.dsr_lbfgs_combine(k, ptr_table(self._flat), self._numel, ws, self._ws_bytes, vecs, h, n, st))
         for p in self._flat:
             bump(p)
         repack_cached(self.params)

@@ -358,6 +358,39 @@ def test_adam_multi_tensor_matches_per_tensor(dev):
         assert rel_err(a[i].detach().cpu(), r[i].detach()) < 1e-6, i
 
 
+def test_repack_cached_crosses_the_group_of_48(dev):
+    """functional.repack_cached over 50 cached conv weights (dsr_conv_pack_weight_multi takes 48 per launch, so two launches,
+    the second with two tensors): Cout, Cin ragged in 1..20 (most no multiple of 8), 1, 9 and 81 taps mixed, packed in bf16
+    through the cached per-tensor path, three of them in f16 as well, then rewritten in place.  pack_weight_kernel as
+    dsr_conv_pack_weight calls it and pack_weight_multi_kernel write the same two layouts for every shape -- forward
+    [T][r8(Cout)][r8(Cin)], dgrad [T][r8(Cin)][r8(Cout)], zero padded, one rounding of the fp32 value -- so both images of
+    every tensor must equal, bit for bit, a fresh per-tensor pack of the new values."""
+    F, L = P("functional"), P("_lib")
+    lib = L.lib()
+    shapes = [(1 + (7 * i) % 20, 1 + (11 * i) % 20, (1, 3, 9)[i % 3]) for i in range(50)]
+    ws = [filler.tensor(f"rp:w{i}", (co, ci, k, k)).to(dev) for i, (co, ci, k) in enumerate(shapes)]
+    f16 = (0, 23, 49)
+
+    def desc(w, dtype):
+        co, ci, k, _ = w.shape
+        return L.ConvDesc(L.BF16 if dtype == torch.bfloat16 else L.F16, 1, 16, 16, ci, co, k, k, 1, k // 2, L.PAD_ZERO)
+
+    def dtypes(i):
+        return (torch.bfloat16, torch.float16) if i in f16 else (torch.bfloat16,)
+
+    cached = {(i, dt): F.packed_weights(w, desc(w, dt), dt) for i, w in enumerate(ws) for dt in dtypes(i)}
+    for i, w in enumerate(ws):
+        w.copy_(filler.tensor(f"rp:v{i}", tuple(w.shape)).to(dev))
+    F.repack_cached(ws)
+    for (i, dt), (wf, wd) in cached.items():
+        w, d = ws[i], desc(ws[i], dt)
+        again = F.packed_weights(w, d, dt)                         # marked current: the same two tensors, no new pack
+        assert again[0] is wf and again[1] is wd, (i, dt)
+        ff, fd = torch.empty_like(wf), torch.empty_like(wd)
+        F.check(lib.dsr_conv_pack_weight(L.C.byref(d), F._ptr(w), F._ptr(ff), F._ptr(fd), F._stream()))
+        assert torch.equal(wf, ff) and torch.equal(wd, fd), (i, dt, shapes[i])
+
+
 def test_adam_keeps_the_dense_shadow_current(dev):
     """The bf16 image of the dense head's matrix (functional.shadow16) is rewritten by the Adam launch itself and must
     be recognised as current afterwards: no second cast pass per step, and never a stale image."""

@@ -119,6 +119,20 @@ def test_fused_lbfgs_quadratic_vs_torch(dev, history):
     assert r["err"] <= 2 * r["floor"]
 
 
+def test_fused_lbfgs_table_crosses_64_tensors(dev):
+    """The quadratic of the test above at history 5, n = 5000 in 70 tensors + one whose gradient stays None: 68 ragged small
+    ones (1 + 7 i mod 13 elements), one of 4097 (one element past a gather chunk of 4096, four combine chunks of 1024 and one
+    element) and the remaining 437 -- gather and combine take 64 tensors per launch, so each is two launches, the second
+    with a running block base and a tensor of several blocks.  Same bar as above.  Measured on an MI355X: fused 3.008e-4
+    against torch's fp32 floor 3.028e-4 (ratio 0.994)."""
+    small = [1 + (7 * i) % 13 for i in range(68)]
+    splits = small + [4097, 5000 - 4097 - sum(small)]
+    assert len(splits) == 70 and splits[-1] > 0
+    r = compare(quadratic(), splits, dev, unused=3, lr=1, max_iter=30, history_size=5, tolerance_grad=-1, tolerance_change=-1)
+    assert r["cf"] == r["c32"] == r["c64"]
+    assert r["err"] <= 2 * r["floor"]
+
+
 def test_fused_lbfgs_rosenbrock_vs_torch(dev):
     """Extended Rosenbrock, 1000 elements split 1 / 499 / 500, lr 0.1, 30 iterations from (-1.2, 1, ...).  Measured on an
     MI355X: fused 3.418e-6 against torch's fp32 floor 3.241e-6 (ratio 1.054)."""
