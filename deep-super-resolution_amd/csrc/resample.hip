@@ -9,6 +9,9 @@
 #include "dsr_kernels.h"
 
 // ------------------------------------------------------------------ MaxPool 2x2 / stride 2 (floor)
+// torch's rule (ATen max_pool2d): scan the window in the order (0,0),(0,1),(1,0),(1,1) and replace the running maximum when
+// v > m or v is NaN.  A NaN therefore propagates (an overflowed fp16 conv output is not hidden from a loss scaler), the
+// last NaN of a window owns it, and among finite / infinite values the FIRST maximum does.
 template <int DT>
 __global__ void maxpool2_fwd_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ y, int N, int H,
                                     int W, int Cp) {
@@ -29,12 +32,14 @@ __global__ void maxpool2_fwd_kernel(const unsigned short* __restrict__ x, unsign
       float f[8];
       unpack8<DT>(*reinterpret_cast<const U4*>(x + ((size_t)(n * H + 2 * oy + i) * W + 2 * ox + j) * Cp + ch * 8), f);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) m[k] = f[k] > m[k] ? f[k] : m[k];
+      for (int k = 0; k < 8; ++k) m[k] = (f[k] > m[k] || f[k] != f[k]) ? f[k] : m[k];
     }
   *reinterpret_cast<U4*>(y + pix * Cp + ch * 8) = pack8<DT>(m);
 }
 
-// dx at (y,x) = dy of its window iff (y,x) is the FIRST maximum of the window in scan order (ATen's choice)
+// dx at (y,x) = dy of its window iff (y,x) is the element the forward's scan ends on: the last NaN of the window if it
+// holds one, otherwise the FIRST maximum in scan order (ATen's choice in both cases); every other element, and a trailing
+// odd row / column, gets 0.  dy is routed, never multiplied: an Inf or NaN in dy reaches exactly one input.
 template <int DT>
 __global__ void maxpool2_bwd_kernel(const unsigned short* __restrict__ x, const unsigned short* __restrict__ dy,
                                     unsigned short* __restrict__ dx, int N, int H, int W, int Cp, int relu_mask) {
@@ -65,11 +70,12 @@ __global__ void maxpool2_bwd_kernel(const unsigned short* __restrict__ x, const 
       float m = v[0][k];
 #pragma unroll
       for (int q = 1; q < 4; ++q)
-        if (v[q][k] > m) {
+        if (v[q][k] > m || v[q][k] != v[q][k]) {
           m = v[q][k];
           arg = q;
         }
-      // relu_mask: x is a ReLU output and its backward rides along: the routed gradient survives where the maximum is > 0
+      // relu_mask: x is assumed to be a ReLU output (finite or +Inf, never negative, never NaN) and the ReLU's backward rides
+      // along: the routed gradient survives where the maximum is > 0 (a NaN maximum, which a ReLU cannot produce, gives 0)
       g[k] = (arg == me && (!relu_mask || m > 0.f)) ? d[k] : 0.f;
     }
   }
@@ -495,8 +501,9 @@ extern "C" int dsr_box_copy(const void* src, void* dst, int N, int BH, int BW, i
 extern "C" int dsr_downsample_fwd(const float* x, const float* kern, float* y, int NC, int H, int W, int k, int f,
                                   int p, dsr_stream_t st) {
   DSR_REQUIRE(x && kern && y && NC > 0 && H > 0 && W > 0 && k > 0 && f > 0 && p >= 0, "downsample_fwd: null pointer or bad shape");
+  // (tested on the extents, not on OH: C's division truncates, so (H + 2p - k) / f + 1 is 1 for -f < H + 2p - k < 0)
+  if (H + 2 * p < k || W + 2 * p < k) return dsr_fail(DSR_E_ARG, "downsample: empty output");
   int OH = (H + 2 * p - k) / f + 1, OW = (W + 2 * p - k) / f + 1;
-  if (OH < 1 || OW < 1) return dsr_fail(DSR_E_ARG, "downsample: empty output");
   size_t total = (size_t)NC * OH * OW;
   hipLaunchKernelGGL(downsample_fwd_kernel, dim3(nb(total)), dim3(256), 0, st, x, kern, y, NC, H, W, OH, OW, k, f, p);
   return dsr_launch_status("dsr_downsample_fwd");

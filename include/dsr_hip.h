@@ -339,11 +339,13 @@ int dsr_dense2_bwd(int dtype, const float* dout, const float* out, const float* 
                    int Bp, float slope, float* dw2, float* db2, float* db1, void* dy16, void* dyT16, dsr_stream_t s);
 
 /* ------------------------------------------------------------------ resampling / data movement (resample.hip) */
-/* nn.MaxPool2d(2,2) of the VGG19 trunk (utils/GAN.py:24,29,38,47); backward routes to the first maximum */
+/* nn.MaxPool2d(2,2) of the VGG19 trunk (utils/GAN.py:24,29,38,47) and of DIP's downsample_mode='max'.  torch's rule: the window is
+ * scanned (0,0),(0,1),(1,0),(1,1) and the running maximum replaced when v > m or v is NaN -- a NaN propagates; the backward
+ * routes dy to the last NaN of the window if it holds one, otherwise to the first maximum */
 int dsr_maxpool2_fwd(int dtype, const void* x, void* y, int N, int H, int W, int Cp, dsr_stream_t s);
 int dsr_maxpool2_bwd(int dtype, const void* x, const void* dy, void* dx, int N, int H, int W, int Cp, dsr_stream_t s);
 /* the same with the backward of the ReLU that produced x folded in (conv + ReLU + MaxPool of the VGG trunk, utils/GAN.py:24-47):
- * dx = routed dy where the window maximum is > 0 */
+ * dx = routed dy where the window maximum is > 0.  x must be a ReLU output: no NaN, nothing negative */
 int dsr_maxpool2_relu_bwd(int dtype, const void* x, const void* dy, void* dx, int N, int H, int W, int Cp, dsr_stream_t s);
 /* nn.AvgPool2d(2,2) after a stride-1 conv: downsample_mode='avg' of models/DIP/utils.py:86-94 (floor mode);
  * H, W are the INPUT size of the pool.  downsample_mode='max' uses dsr_maxpool2_* above. */

@@ -16,12 +16,11 @@ import pytest
 import torch
 
 import pointwise_ref as R
+from canaries import Canaries
 
 pytestmark = pytest.mark.gpu
 
 PKG = "deep-super-resolution_amd"
-SENTINEL = 7777.0
-MARGIN = 512          # elements on each side of an output
 EPS, MOMENTUM = 1e-5, 0.1
 U24 = 2.0 ** -24      # half an fp32 ulp, relative: the error of one fp32 rounding
 
@@ -39,31 +38,6 @@ def dev():
 
 
 DT = [pytest.param(R.BF16, id="bf16"), pytest.param(R.F16, id="f16")]
-
-
-class Canaries:
-    """Outputs allocated inside sentinel-filled buffers; check() asserts that nothing outside an output was written."""
-
-    def __init__(self, dev):
-        self.dev, self.bufs = dev, []
-
-    def alloc(self, shape, dtype, what):
-        numel = 1
-        for s in shape:
-            numel *= int(s)
-        flat = torch.full((numel + 2 * MARGIN,), SENTINEL, dtype=dtype, device=self.dev)
-        self.bufs.append((flat, numel, what))
-        return flat[MARGIN:MARGIN + numel].view(*shape)
-
-    def check(self):
-        torch.cuda.synchronize()
-        for flat, numel, what in self.bufs:
-            lo, hi = flat[:MARGIN], flat[MARGIN + numel:]
-            assert bool((lo == lo[0]).all()) and bool((hi == lo[0]).all()) and bool(lo[0] == flat.new_tensor(SENTINEL)), \
-                f"store outside {what}"
-
-    def untouched(self, view):
-        return bool((view == view.new_tensor(SENTINEL)).all())
 
 
 def ptr(t):
