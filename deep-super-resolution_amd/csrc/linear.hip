@@ -817,6 +817,7 @@ __global__ void dense2_bwd_kernel(const float* __restrict__ dout, const float* _
 extern "C" int dsr_cast16(int dtype, const float* src, void* dst, size_t n, dsr_stream_t st) {
   DSR_REQUIRE(src && dst && DSR_DTYPE_OK(dtype) && n > 0, "cast16: null pointer or empty");
   if (n % 8) return dsr_fail(DSR_E_ARG, "cast16: element count %zu not a multiple of 8", n);
+  DSR_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 15) == 0, "cast16: src and dst must be 16-byte aligned");
   size_t n8 = n / 8;
   unsigned blocks = (unsigned)((n8 + 255) / 256);
   if (blocks > 8192) blocks = 8192;
@@ -973,6 +974,9 @@ extern "C" int dsr_linear_wgrad_adam(int dtype, const void* dyT16_all, const voi
   if (Bp != 32 && Bp != 64) return dsr_fail(DSR_E_UNSUPPORTED, "linear_wgrad_adam: padded batch must be 32 or 64");
   if (R < 1) return dsr_fail(DSR_E_ARG, "linear_wgrad_adam: R < 1");
   if (K % 64) return dsr_fail(DSR_E_UNSUPPORTED, "linear_wgrad_adam: K %% 64 (use dsr_linear_wgrad + dsr_pw_adam)");
+  DSR_REQUIRE((((uintptr_t)dyT16_all | (uintptr_t)xT16_all | (uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) == 0 &&
+                  ((uintptr_t)shadow_bf16 & 7) == 0 && ((uintptr_t)step & 3) == 0,
+              "linear_wgrad_adam: misaligned pointer");
   const char* e = getenv("DSR_WGRAD_ADAM_KPB");      // tuning switch: 256-wide k groups per block
   const int kpb = e ? atoi(e) : 1;          // (1: 2.71 ms stand-alone and 0.1-0.15 ms per config-3 step better than 2; 4 worse)
   if (kpb < 1) return dsr_fail(DSR_E_ARG, "linear_wgrad_adam: DSR_WGRAD_ADAM_KPB < 1");
@@ -1004,7 +1008,7 @@ extern "C" int dsr_linear_wgrad_adam(int dtype, const void* dyT16_all, const voi
 
 extern "C" int dsr_dense2_fwd(const float* h, const float* w2, const float* b2, int B, int K1, float* out,
                               dsr_stream_t st) {
-  DSR_REQUIRE(h && w2 && out && B > 0 && K1 > 0, "dense2_fwd: null pointer or bad shape");
+  DSR_REQUIRE(h && w2 && b2 && out && B > 0 && K1 > 0, "dense2_fwd: null pointer or bad shape");
   hipLaunchKernelGGL(dense2_fwd_kernel, dim3(B), dim3(256), 0, st, h, w2, b2, K1, out);
   return dsr_launch_status("dsr_dense2_fwd");
 }

@@ -293,7 +293,8 @@ int dsr_pw_adam_multi_hyper(int count, float* const* p, const float* const* g, f
 
 /* ------------------------------------------------------------------ discriminator dense head (linear.hip)
  * models/GAN/discriminator.py:37-45,65-72: flatten(C,H,W) -> Linear(K,O) -> LeakyReLU(0.2) -> Linear(O,1) -> Sigmoid */
-/* 16-bit shadow copy of an fp32 tensor (n % 8 == 0) */
+/* 16-bit shadow copy of an fp32 tensor (n % 8 == 0; src and dst 16-byte aligned: the kernel moves 16-byte vectors, a
+ * misaligned pointer is DSR_E_ARG) */
 int dsr_cast16(int dtype, const float* src, void* dst, size_t n, dsr_stream_t s);
 /* mode 0: flat[b][c*HW+p] = act[b][p][c];  1: flatT[c*HW+p][b] (Bp columns, zero padded);  2: act <- flat */
 int dsr_flatten(int dtype, const void* src, void* dst, int B, int HW, int C, int Cp, int Bp, int mode, dsr_stream_t s);
@@ -312,6 +313,8 @@ int dsr_linear_wgrad_gathered(int dtype, const void* dyT16_all, const void* xT16
                               int R, float scale, dsr_stream_t s);
 /* the same contraction with torch.optim.Adam's update applied to p / m / v (and p's bf16 shadow) in the epilogue: the
  * gradient is never written (R = 1, scale = 1: bit-identical to dsr_linear_wgrad followed by dsr_pw_adam); K % 64 == 0.
+ * p / m / v and the two factor tables are accessed 16 bytes at a time and the shadow 8: they must be aligned to that
+ * (step to 4), in this form and in the _hyper one; a misaligned pointer is DSR_E_ARG.
  * Replaces loss.backward() writing dense1.weight.grad + optimizer.step() reading it (train_GAN.py:52-53 on
  * discriminator.py:54). */
 int dsr_linear_wgrad_adam(int dtype, const void* dyT16_all, const void* xT16_all, int Bp, int O, size_t K, int R, float scale,
@@ -332,7 +335,7 @@ int dsr_linear_wgrad_adam_hyper(int dtype, const void* dyT16_all, const void* xT
                                 float scale, float* p, float* m, float* v, void* shadow_bf16, const int* step,
                                 const float* hyper, float b1, float b2, float eps, float grad_scale, const float* loss_scale,
                                 const float* found_inf, dsr_stream_t s);
-/* out[b] = sigmoid(h[b][:] . w2 + b2) */
+/* out[b] = sigmoid(h[b][:] . w2 + b2[0]);  b2 is required (a one-element device tensor): NULL is DSR_E_ARG */
 int dsr_dense2_fwd(const float* h, const float* w2, const float* b2, int B, int K1, float* out, dsr_stream_t s);
 /* backward of the fp32 tail; also emits the 16-bit dy / dy^T operands of the two dense1 GEMMs */
 int dsr_dense2_bwd(int dtype, const float* dout, const float* out, const float* h, const float* w2, int B, int K1,

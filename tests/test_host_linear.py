@@ -1,0 +1,412 @@
+"""CPU: the dense-head sweep's references, regime conditions, launcher branches, Adam floor and argument checks (linear_ref.py).
+
+Nothing here launches a kernel.  Each float64 reference is checked against the torch op it restates (F.linear + leaky_relu under
+float64 autograd, x.view(N, -1) of an NCHW tensor, sigmoid(F.linear) under autograd, the Frobenius norm); every regime-A case is
+shown to stay below 2^24 by sum |a||b| and to round-trip through both storage types; regime B's exact ties are counted; the case
+table is shown to reach every instantiation and branch the launchers of csrc/linear.hip can take, with the thresholds read from
+that file as text and the plans from the workspace queries; the torch-fp32 floor of the Adam bar and the distance of two wrong
+variants from it are shown; and every entry point's argument checks return an error before any launch."""
+import ctypes as C
+import importlib
+import os
+import re
+
+import pytest
+import torch
+import torch.nn.functional as TF
+
+import clip_ref
+import linear_ref as R
+
+PKG = "deep-super-resolution_amd"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F64 = torch.float64
+E_ARG, E_WORKSPACE, E_UNSUPPORTED = -1, -3, -4
+
+
+@pytest.fixture(scope="module")
+def lib():
+    importlib.import_module(PKG + "._build").build()
+    return importlib.import_module(PKG + "._lib").lib()
+
+
+def _flat_src():
+    return re.sub(r"\s+", "", open(os.path.join(ROOT, PKG, "csrc", "linear.hip")).read())
+
+
+# ----------------------------------------------------------------------------- the references are the torch ops they restate
+@pytest.mark.parametrize("slope", [0.0, 0.25, 0.2])
+def test_linear_references_equal_float64_autograd(slope):
+    g = R.gen(1)
+    B, O, K, Bp = 5, 24, 40, 32
+    x = torch.randn(B, K, generator=g, dtype=F64, requires_grad=True)
+    w = torch.randn(O, K, generator=g, dtype=F64, requires_grad=True)
+    bias, dy = torch.randn(O, generator=g, dtype=F64), torch.randn(B, O, generator=g, dtype=F64)
+    pre = TF.linear(x, w, bias)
+    s32 = R.f32(slope)
+    y = pre if slope == 0.0 else TF.leaky_relu(pre, s32)
+    act = R.ACT_NONE if slope == 0.0 else R.ACT_LEAKY
+    ref = R.linear_fwd(x.detach(), w.detach(), bias, act, slope)
+    # the reference rounds the LeakyReLU product to fp32 once (the kernel's one fp32 multiply); nothing else differs
+    tol = 2.0 ** -24 * y.detach().abs() if slope else 1e-12
+    assert bool(((ref - y.detach()).abs() <= tol + 1e-12).all())
+    assert float((R.linear_fwd(x.detach(), w.detach(), None, R.ACT_NONE, 0.0) - TF.linear(x, w).detach()).abs().max()) <= 1e-12
+    TF.linear(x, w).backward(dy)
+    assert float((R.linear_dgrad(dy, w.detach()) - x.grad).abs().max()) <= 1e-12
+    dyT, xT = torch.zeros(1, O, Bp, dtype=F64), torch.zeros(1, K, Bp, dtype=F64)
+    dyT[0, :, :B], xT[0, :, :B] = dy.t(), x.detach().t()
+    assert float((R.linear_wgrad(dyT, xT) - w.grad.to(torch.float32).to(F64)).abs().max()) <= 1e-12
+    # gathered: the sum over R pairs, times the scale
+    two = R.linear_wgrad(torch.cat([dyT, 2 * dyT]), torch.cat([xT, xT]), 0.5)
+    assert float((two - (1.5 * w.grad).to(torch.float32).to(F64)).abs().max()) <= 1e-6 * float(w.grad.abs().max())
+
+
+def test_integer_cases_equal_float64_linear():
+    """On the integer tables the reference and float64 F.linear agree exactly (LeakyReLU 0.25 included)."""
+    for B, O, K in ((17, 8, 72), (33, 257, 264)):
+        for impulse in (False, True):
+            x, w, bias = R.fwd_case(B, O, K, impulse)
+            assert torch.equal(R.linear_fwd(x, w, bias, R.ACT_LEAKY, 0.25), TF.leaky_relu(TF.linear(x, w, bias), 0.25) + 0.0)
+            if impulse:                                          # the impulse names the element: out[b][o] = w[o][k_b]
+                kb = x.argmax(1)
+                assert torch.equal(R.linear_fwd(x, w, None, R.ACT_NONE, 0.0), w[:, kb].t())
+
+
+def test_flatten_references_are_the_nchw_view():
+    B, HW, C, Cp, Bp = 3, 6, 5, 8, 32
+    nchw = torch.arange(B * C * HW, dtype=torch.int16).reshape(B, C, HW) + 1
+    act = torch.full((B, HW, Cp), -7, dtype=torch.int16)
+    act[:, :, :C] = nchw.permute(0, 2, 1)
+    flat = nchw.reshape(B, -1)                                    # x.view(N, -1) of the NCHW tensor (discriminator.py:65)
+    assert torch.equal(R.flatten0(act, C), flat)
+    f1 = R.flatten1(act, C, Bp)
+    assert torch.equal(f1[:, :B], flat.t()) and not bool(f1[:, B:].any())
+    back = R.flatten2(flat, C, HW, Cp)
+    assert torch.equal(back[:, :, :C], act[:, :, :C]) and not bool(back[:, :, C:].any())
+    c = R.counter((64, 200, 128))
+    assert int((c.flatten()[1:] == c.flatten()[:-1]).sum()) == 0 and int((c[:, 1:] == c[:, :-1]).sum()) == 0
+
+
+def test_dense2_references_equal_float64_autograd():
+    g = R.gen(2)
+    B, K1, Bp, slope = 5, 33, 32, 0.25
+    z = torch.randn(B, K1, generator=g, dtype=F64)
+    z = torch.where(z.abs() < 0.05, torch.ones_like(z), z).requires_grad_(True)          # away from 0
+    w2 = torch.randn(K1, generator=g, dtype=F64, requires_grad=True)
+    b2 = torch.randn(1, generator=g, dtype=F64, requires_grad=True)
+    dout = torch.randn(B, generator=g, dtype=F64)
+    h = TF.leaky_relu(z, slope)
+    out = torch.sigmoid(TF.linear(h, w2[None], b2))[:, 0]
+    assert float((torch.sigmoid(R.dense2_fwd_sum(h.detach(), w2.detach(), float(b2.detach()))) - out.detach()).abs().max()) <= 1e-12
+    out.backward(dout)
+    ref = R.dense2_bwd(dout, out.detach(), h.detach(), w2.detach(), Bp, slope)
+    for got, want in ((ref["dw2"], w2.grad), (ref["db2"], b2.grad), (ref["dy"], z.grad), (ref["db1"], z.grad.sum(0)),
+                      (ref["dyT"][:, :B], z.grad.t())):
+        assert float((got - want).abs().max()) <= 1e-12
+    assert not bool(ref["dyT"][:, B:].any())
+    # the convention at h == 0 (dsr_common.h act_grad_from_out, pointwise_ref.py): derivative 1, for +0 and -0; torch: slope
+    z0 = torch.tensor([[0.0, -0.0, 1.0, -1.0]], dtype=F64, requires_grad=True)
+    TF.leaky_relu(z0, slope).sum().backward()
+    ours = R.dense2_bwd(torch.ones(1, dtype=F64), torch.full((1,), 0.5, dtype=F64), z0.detach(), torch.full((4,), 4.0, dtype=F64), 32, slope)
+    assert ours["dy"][0].tolist() == [1.0, 1.0, 1.0, slope] and z0.grad[0].tolist() == [slope, slope, 1.0, slope]
+
+
+def test_gram_identity_is_the_frobenius_norm():
+    for Bp, Rr, O, K, _ in R.gram_cases()[::5]:
+        dyT, xT = R.wgrad_case(Bp, O, K, Rr)
+        n2 = R.gram_norm2(dyT, xT)
+        assert R.gram_identity(dyT, xT) == float(n2)
+        fro = float(torch.linalg.norm(torch.einsum("rob,rkb->ok", dyT, xT))) ** 2
+        assert abs(fro - n2) <= 1e-12 * n2
+
+
+# ----------------------------------------------------------------------------- regime A is exact, regime B is rounded once
+def _bound(a, b, n):
+    """sum |a||b| over n terms is at most max|a| max|b| n."""
+    return float(a.abs().max()) * float(b.abs().max()) * n
+
+
+def test_regime_a_is_exact_and_representable():
+    for K in R.FWD_K:
+        for B, O in R.fwd_shapes(K):
+            x, w, bias = R.fwd_case(B, O, K)
+            assert _bound(x, w, K) + float(bias.abs().max()) < R.EXACT and R.fits16(x) and R.fits16(w), (B, O, K)
+            assert bool((bias.to(torch.float32).to(F64) == bias).all())
+            if K <= 264:
+                xi, wi, _ = R.fwd_case(B, O, K, True)
+                assert float((xi.abs() @ wi.abs().t()).max()) < R.EXACT and R.fits16(xi) and R.fits16(wi)
+                pre = R.linear_pre(x, w) + bias[None, :]
+                assert bool((pre[:, 0] == 0).all()) and (O < 3 or float(pre[0, 2]) == 0.0)        # the planted zeros
+                assert str(float(bias[0])) == "-0.0"
+    for K in R.DG_K:
+        for B, O in R.dgrad_shapes(K):
+            for impulse in (False, True):
+                dy, w = R.dgrad_case(B, O, K, "A", impulse=impulse)
+                assert _bound(dy, w, O) < R.EXACT and R.fits16(dy) and R.fits16(w)
+                assert R.fits16(R.linear_dgrad(dy, w)), (B, O, K, impulse)
+    for Bp in R.WG_BP:
+        for O in R.WG_O:
+            for K in R.WG_K:
+                for Rr in (1, 2, 3, 4):
+                    for impulse in (False, True):
+                        dyT, xT = R.wgrad_case(Bp, O, K, Rr, impulse)
+                        assert _bound(dyT, xT, Rr * Bp) < R.EXACT and R.fits16(dyT) and R.fits16(xT)
+                        assert not bool(dyT[:, :, Bp - 5:].any()) and not bool(xT[:, :, Bp - 5:].any())
+    for Rr, O, K, *_ in R.wa_cases():
+        for Bp in R.WG_BP:
+            dyT, xT = R.wgrad_case(Bp, O, K, Rr)
+            assert 4 * _bound(dyT, xT, Rr * Bp) < R.EXACT and R.fits16(dyT * 4.0)          # the loss_scale = 4 run
+    for Bp, Rr, O, K, _ in R.gram_cases():
+        dyT, xT = R.wgrad_case(Bp, O, K, Rr)
+        gx, gy = _bound(xT, xT, K), _bound(dyT, dyT, O)
+        assert gx < R.EXACT and gy < R.EXACT and gx * gy * (Rr * Bp) ** 2 < 2.0 ** 53
+    for B in R.D2B_B:
+        for K1 in R.D2B_K1:
+            for regime in "AB":
+                dout, out, h, w2 = R.dense2_bwd_case(B, K1, regime)
+                ref = R.dense2_bwd(dout, out, h, w2, 64, R.D2_SLOPE)
+                for name in ("dw2", "db2", "db1", "dy"):                         # every term a multiple of 1/64 below 2^24
+                    t = ref[name] * 64.0
+                    assert bool((t == t.round()).all())
+                # dh = dout {3, 4} w2 {1, 4} / 64 with at most dout 4 w2 4 / 64 per term: B terms stay below 2^24 / 64
+                assert float(dout.abs().max()) * float(w2.abs().max()) * 16 * B < R.EXACT
+                if B * K1 >= 8:                                                  # both signed zeros are in h
+                    assert bool(((h == 0) & (1.0 / h < 0)).any()) and bool(((h == 0) & (1.0 / h > 0)).any())
+                if regime == "A":
+                    assert R.fits16(ref["dy"])
+    for B in R.D2F_B:
+        for K1 in R.D2F_K1:
+            h, w2, b2, tgt = R.dense2_fwd_case(B, K1)
+            assert torch.equal(R.dense2_fwd_sum(h, w2, b2), tgt)
+            assert float((h.abs() * w2.abs()[None]).sum(1).max()) + abs(b2) < R.EXACT
+
+
+def test_regime_b_is_rounded_with_ties():
+    """The exact values of regime B are integers (dgrad) or multiples of 1/64 (dense2_bwd) below 2^24: float64 -> fp32 is exact,
+    so the double rounding of to16() is a single one; and the tables hold many exact ties per storage type."""
+    for dtype in (R.BF16, R.F16):
+        ties = rounded = 0
+        for K in R.DG_K + R.DG_WIDE_K[:1]:
+            for B, O in (R.dgrad_shapes(K) if K in R.DG_K else [(16, R.DG_WIDE_O)]):
+                dy, w = R.dgrad_case(B, O, K, "B", dtype)
+                e = R.linear_dgrad(dy, w)
+                assert _bound(dy, w, O) < R.EXACT and R.fits16(dy) and R.fits16(w)
+                assert bool((e.to(torch.float32).to(F64) == e).all()) and bool(R.to16(e, dtype).isfinite().all())
+                ties += R.ties16(e, dtype)
+                rounded += int((R.to16(e, dtype).to(F64) != e).sum())
+        assert ties >= 48 and rounded > ties, (dtype, ties, rounded)
+        ties = 0
+        for B in R.D2B_B:
+            for K1 in R.D2B_K1:
+                e = R.dense2_bwd(*R.dense2_bwd_case(B, K1, "B"), 64, R.D2_SLOPE)["dy"]
+                assert bool((e.to(torch.float32).to(F64) == e).all())
+                ties += R.ties16(e, dtype)
+        assert ties >= 48, (dtype, ties)
+        sp = R.cast_specials().to(F64)
+        assert R.ties16(sp[sp.isfinite()], dtype) >= 2
+    # ties16 itself: 257 (256 | 258) and 2056 (2048 | 2064) are bf16 ties, 2049 is an fp16 tie and merely rounded in bf16
+    t = torch.tensor([257.0, 258.0, 2049.0, 2050.0, 2056.0, 3.0], dtype=F64)
+    assert R.ties16(t, R.BF16) == 2 and R.ties16(t, R.F16) == 1
+
+
+# ----------------------------------------------------------------------------- the table reaches every launcher branch
+def _gram_split(rows, nsub, gy):
+    srows = 32 * nsub
+    per = -(-rows // max(512 // gy, 1))
+    per = -(-per // srows) * srows
+    return -(-rows // per), per
+
+
+def test_case_table_reaches_every_instantiation_and_branch(lib):
+    src = _flat_src()
+    # the thresholds, as the launchers state them
+    for line in ("if(B<=32)LAUNCH_FWD(DSR_DTYPE_BF16,2);elseLAUNCH_FWD(DSR_DTYPE_BF16,4);",
+                 "if(B<=32)LAUNCH_DG(DSR_DTYPE_BF16,2);elseLAUNCH_DG(DSR_DTYPE_BF16,4);",
+                 "constboolwide=ew&&atoi(ew)==256&&K>=256*512;", "if(blocks>8192)blocks=8192;", "#defineDSR_GRAM_MAX_N512",
+                 "g->nsub=512/g->N;if(g->nsub>8)g->nsub=8;", "Cp%64==0&&(mode==1?Bp%8==0:HW%8==0)", "constinttpb=16;",
+                 "longlongmaxs=(longlong)((K+1023)/1024);", "constsize_tkgroups=(K+255)/256;", "for(;z+8<=S;z+=8)"):
+        assert line in src, line
+    assert R.DG_WIDE_MIN_K == 256 * 512 and R.GRAM_MAX_N == 512 and R.CAST_GRID_CAP == 8 * 256 * 8192
+    # MT 2 / 4 (forward, dgrad), a half-filled last fragment; BP 32 / 64
+    for Bs in (R.FWD_B, R.DG_B):
+        assert {R.fwd_mt(B) for B in Bs} == {2, 4} and {32, 33} <= set(Bs) and any(B % 16 for B in Bs)
+    assert set(R.WG_BP) == {32, 64} == {Bp for Bp, _ in R.GRAM_N.values()}
+    # NFW 2 / 4: the switch is taken at and above the threshold only
+    assert [K >= R.DG_WIDE_MIN_K for K in R.DG_WIDE_K] == [False, True, True] and all(K % 8 == 0 for K in R.DG_WIDE_K)
+    assert R.DG_WIDE_K[2] % 256 and max(R.DG_K) < R.DG_WIDE_MIN_K
+    # split counts: 1, below 8, exactly 8 (the reduce's 8-wide loop alone), 9-10 and 33 (with a remainder)
+    S = {}
+    for K in R.FWD_K:
+        for B, O in R.fwd_shapes(K):
+            ws = lib.dsr_linear_fwd_workspace(B, K, O)
+            assert ws % (4 * B * O) == 0
+            S.setdefault(K, set()).add(ws // (4 * B * O))
+    assert all(S[K] == {1} for K in R.FWD_K[:6]) and S[7168] == {7} and S[8192] == {8} and S[9224] <= {9, 10} and S[33000] == {33}
+    assert {K % 128 for K in R.FWD_K} >= {8, 64, 72, 0} and 136 in R.FWD_K              # one tile, half a KT pair, a last tile of 8
+    # wgrad: ragged 32-row k tile, the 512-k block boundary, o blocks of 64 / 256
+    assert {K % 32 for K in R.WG_K} >= {4, 28, 0} and {508, 512, 516} <= set(R.WG_K) and {63, 64, 65, 255, 257} <= set(R.WG_O)
+    # fused Adam: K % 64 == 0, k groups of 256 with 1-3 groups per block and a block whose later groups are past K (the waves' break)
+    assert all(K % 64 == 0 for K in R.WA_K) and {-(-K // 256) for K in R.WA_K} == {1, 2} and any(K % 256 for K in R.WA_K)
+    assert any(-(-K // 256) % int(kpb) for K in R.WA_K for kpb in R.WA_KPB if kpb) and any(O % 64 for O in R.WA_O) and 64 in R.WA_O
+    wa = R.wa_cases()
+    assert {(r, kpb) for r, _, _, _, _, kpb in wa} == {(r, kpb) for r in R.WA_R for kpb in R.WA_KPB}
+    assert {(r, t) for r, _, _, t, _, _ in wa} == {(r, t) for r in R.WA_R for t in R.WA_STEPS}
+    assert {kpb for _, _, K, _, _, kpb in wa if K == 320} == set(R.WA_KPB) and {(o, k) for _, o, k, *_ in wa} == {(o, k) for o in R.WA_O for k in R.WA_K}
+    # Gram: every nsub the plan can choose, CG > 1, and rows below one stage / ragged / over several row chunks
+    nsubs, cgs, chunks = set(), set(), set()
+    for Bp, Rr, O, K, _ in R.gram_cases():
+        N = Bp * Rr
+        nsub, NB = R.gram_nsub(N), N // 16
+        CG = -(-NB // 8)
+        gy = -(-(NB * CG) // 4)
+        (sx, _), (sy, _) = _gram_split(K, nsub, gy), _gram_split(O, nsub, gy)
+        dots = lib.dsr_linear_factor_gram_dots(Bp, Rr)
+        assert dots == N * N // 16
+        assert lib.dsr_linear_factor_gram_workspace(Bp, O, K, Rr) == dots * 8 + (sx + sy) * N * N * 4, (Bp, Rr, O, K)
+        nsubs.add(nsub)
+        cgs.add(CG)
+        chunks |= {sx, sy}
+        assert 32 * nsub * (N // 8) <= 8 * 256                       # a stage fits the loader's 8 vectors per thread
+    assert nsubs == {8, 5, 4, 3, 2, 1} == {R.gram_nsub(N) for N in range(32, 513, 32)} and cgs == {1, 2, 4} and max(chunks) > 1 and 1 in chunks
+    assert any(O < 32 * R.gram_nsub(N) for N in R.GRAM_N for O in R.GRAM_O) and any(K % (32 * R.gram_nsub(N)) for N in R.GRAM_N for K in R.GRAM_K)
+    assert lib.dsr_linear_factor_gram_workspace(32, 8, 64, 17) == 0 and lib.dsr_linear_factor_gram_dots(64, 9) == 0
+    # flatten: both forms, ragged pixel tiles, ragged channel groups
+    tile = {R.takes_tile_form(0, hw, cp, 0) for _, hw, _, cp in R.flatten_shapes()}
+    assert tile == {True, False} and all(not R.takes_tile_form(m, 64, 64, 32, "0") for m in (0, 1, 2))
+    assert any(R.takes_tile_form(0, hw, cp, 0) and hw % 64 for _, hw, _, cp in R.flatten_shapes())
+    assert {b for b, *_ in R.flatten_shapes()} == set(R.FL_B)
+    # dense2 / cast16
+    assert any(Bp not in (32, 64) for Bp in R.D2B_BP) and {127, 128, 129} <= set(R.D2B_K1) and {255, 256, 257} <= set(R.D2F_K1)
+    assert all(n % 8 == 0 for n in R.CAST_N)
+
+
+# ----------------------------------------------------------------------------- the Adam bar: floor and wrong variants
+def test_adam_floor_and_wrong_variants_are_far_apart():
+    """Check 2 of the fused weight-gradient + Adam sweep: the bar is max(1e-6, 4 x floor), floor = torch.optim.Adam in fp32 on
+    the CPU against clip_ref.ClippedAdam in float64 on the same inputs.  A fused launch that lost one 64-wide k tile of the
+    gradient, or that swapped m and v, is at least 100 x the bar away in p."""
+    A = R.ADAM
+    worst = 0.0
+    for Rr, O, K, t, gs, _ in R.wa_cases()[::3]:
+        for Bp in R.WG_BP:
+            dyT, xT = R.wgrad_case(Bp, O, K, Rr)
+            g = R.linear_wgrad(dyT, xT, R.WA_SCALE[Rr])
+            p0, m0, v0 = R.adam_state(O, K)
+
+            def model(grad, swap=False):
+                ref = clip_ref.ClippedAdam([p0.numpy()], lr=A["lr"], betas=(A["b1"], A["b2"]), eps=A["eps"], grad_scale=gs)
+                ref.m[0], ref.v[0], ref.t = (v0 if swap else m0).double().numpy(), (m0.abs() if swap else v0).double().numpy(), t - 1
+                ref.step([grad.numpy()])
+                return ref.p[0], ref.m[0], ref.v[0]
+
+            want = model(g)
+            got = R.adam_torch_fp32(p0, m0, v0, g * gs, t, A["lr"], A["b1"], A["b2"], A["eps"])
+            floors = [R.rel(a, b) for a, b in zip(got, want)]
+            worst = max(worst, *floors)
+            bar = max(1e-6, 4 * floors[0])
+            lost = g.clone()
+            lost[:, K - 64:] = 0.0
+            assert R.rel(model(lost)[0], want[0]) >= 100 * bar, (Rr, O, K, t, Bp)
+            assert R.rel(model(g, swap=True)[0], want[0]) >= 100 * bar, (Rr, O, K, t, Bp)
+    print(f"\ntorch fp32 Adam vs float64 on the sweep's inputs: largest floor {worst:.3e} -> bar {max(1e-6, 4 * worst):.3e}")
+    assert worst < 1e-6                                        # a floor this size keeps the bar at the project's 1e-6
+
+
+def test_sigmoid_bar_on_the_table():
+    sums = torch.cat([R.dense2_fwd_case(B, K1, off)[3] for B in R.D2F_B for K1 in R.D2F_K1 for off in (range(7) if B == 1 else (0,))])
+    assert {0.0, 100.0, -100.0, 200.0, -200.0, 20.0, -20.0} <= set(sums.tolist())
+    d, bar = R.sigmoid_bar(sums[sums.abs() < R.SATURATED])
+    print(f"\ntorch fp32 sigmoid vs float64 on the table's sums: {d:.3f} ulp -> bar {bar:.3f} ulp")
+    assert 2.0 <= bar <= 16.0
+    assert float(R.ulp32(torch.tensor([1.0, 0.75, 0.5], dtype=F64)).sum()) == 2.0 ** -23 + 2 * 2.0 ** -24
+
+
+# ----------------------------------------------------------------------------- argument checks: an error, and no launch
+def test_argument_checks(lib):
+    """Null pointers, B outside 1..64, K % 8, O % 8, Bp not 32 / 64, K % 64, R < 1, short or missing workspace, R Bp > 512 and
+    misaligned pointers return an error code with a message.  Valid-looking pointers are host memory: the checks come before
+    any launch.  Pinned here as well: dsr_linear_wgrad_adam checks the alignment its 16- and 8-byte accesses need,
+    dsr_dense2_fwd rejects a null b2, dsr_cast16 checks the alignment of both pointers."""
+    buf = (C.c_char * 4096)()
+    base = (C.addressof(buf) + 63) & ~63
+    a = C.c_void_p(base)
+    off = lambda n: C.c_void_p(base + n)
+    N, st = None, None
+    BF = R.BF16
+    calls = []
+
+    def each_null(fn, args, slots, code=E_ARG):
+        for i in slots:
+            calls.append((lambda i=i: fn(*[N if j == i else v for j, v in enumerate(args)]), code))
+
+    def vary(fn, args, slot, values, code):
+        for bad in values:
+            calls.append((lambda bad=bad: fn(*[bad if j == slot else v for j, v in enumerate(args)]), code))
+
+    fwd = [BF, a, a, N, 0, 0.0, a, 4, 64, 8, a, 1 << 20, st]
+    each_null(lib.dsr_linear_fwd, fwd, (1, 2, 6))
+    vary(lib.dsr_linear_fwd, fwd, 0, (2, -1), E_ARG)
+    vary(lib.dsr_linear_fwd, fwd, 7, (0, 65, -1), E_UNSUPPORTED)
+    vary(lib.dsr_linear_fwd, fwd, 8, (12, 63), E_ARG)
+    vary(lib.dsr_linear_fwd, fwd, 8, (0,), E_ARG)
+    vary(lib.dsr_linear_fwd, fwd, 9, (0, -8), E_ARG)
+    vary(lib.dsr_linear_fwd, fwd, 10, (N,), E_WORKSPACE)
+    vary(lib.dsr_linear_fwd, fwd, 11, (0, lib.dsr_linear_fwd_workspace(4, 64, 8) - 1), E_WORKSPACE)
+    dg = [BF, a, a, a, 4, 8, 64, st]
+    each_null(lib.dsr_linear_dgrad, dg, (1, 2, 3))
+    vary(lib.dsr_linear_dgrad, dg, 4, (0, 65), E_UNSUPPORTED)
+    vary(lib.dsr_linear_dgrad, dg, 5, (4, 12), E_ARG)
+    vary(lib.dsr_linear_dgrad, dg, 6, (4, 60, 0), E_ARG)
+    wg = [BF, a, a, a, 32, 8, 64, st]
+    each_null(lib.dsr_linear_wgrad, wg, (1, 2, 3))
+    vary(lib.dsr_linear_wgrad, wg, 4, (0, 16, 40, 128), E_UNSUPPORTED)
+    vary(lib.dsr_linear_wgrad, wg, 6, (2, 63), E_ARG)
+    vary(lib.dsr_linear_wgrad, wg, 5, (0,), E_ARG)
+    wgg = [BF, a, a, a, 32, 8, 64, 1, 1.0, st]
+    each_null(lib.dsr_linear_wgrad_gathered, wgg, (1, 2, 3))
+    vary(lib.dsr_linear_wgrad_gathered, wgg, 4, (0, 48), E_UNSUPPORTED)
+    vary(lib.dsr_linear_wgrad_gathered, wgg, 7, (0, -1), E_ARG)
+    wa = [BF, a, a, 32, 8, 64, 1, 1.0, a, a, a, N, a, 1e-3, 0.9, 0.999, 1e-8, 1.0, st]
+    wah = [BF, a, a, 32, 8, 64, 1, 1.0, a, a, a, N, a, a, 0.9, 0.999, 1e-8, 1.0, N, N, st]
+    for fn, args, nulls in ((lib.dsr_linear_wgrad_adam, wa, (1, 2, 8, 9, 10, 12)), (lib.dsr_linear_wgrad_adam_hyper, wah, (1, 2, 8, 9, 10, 12, 13))):
+        each_null(fn, args, nulls)
+        vary(fn, args, 3, (0, 48), E_UNSUPPORTED)
+        vary(fn, args, 5, (32, 72, 100), E_UNSUPPORTED)
+        vary(fn, args, 5, (0,), E_ARG)
+        vary(fn, args, 6, (0, -2), E_ARG)
+        for slot in (1, 2, 8, 9, 10):                                # 16-byte accesses
+            vary(fn, args, slot, (off(4), off(8)), E_ARG)
+        vary(fn, args, 11, (off(2), off(4)), E_ARG)                  # the shadow: 8-byte stores
+        vary(fn, args, 12, (off(2),), E_ARG)
+    vary(lib.dsr_linear_wgrad_adam_hyper, wah, 13, (off(2),), E_ARG)
+    gr = [BF, a, a, 32, 8, 64, 1, 1.0, a, 1 << 22, st]
+    each_null(lib.dsr_linear_factor_gram, gr, (1, 2, 8))
+    vary(lib.dsr_linear_factor_gram, gr, 3, (16, 48), E_UNSUPPORTED)
+    vary(lib.dsr_linear_factor_gram, gr, 6, (0,), E_ARG)
+    vary(lib.dsr_linear_factor_gram, gr, 6, (17,), E_UNSUPPORTED)
+    vary(lib.dsr_linear_factor_gram, gr, 9, (0, lib.dsr_linear_factor_gram_workspace(32, 8, 64, 1) - 1), E_WORKSPACE)
+    vary(lib.dsr_linear_factor_gram, gr, 8, (off(8),), E_ARG)
+    vary(lib.dsr_linear_factor_gram, gr, 7, (float("nan"),), E_ARG)
+    d2f = [a, a, a, 4, 8, a, st]
+    each_null(lib.dsr_dense2_fwd, d2f, (0, 1, 2, 5))                 # slot 2: b2
+    vary(lib.dsr_dense2_fwd, d2f, 3, (0,), E_ARG)
+    vary(lib.dsr_dense2_fwd, d2f, 4, (0,), E_ARG)
+    d2b = [BF, a, a, a, a, 4, 8, 32, 0.25, a, a, a, a, a, st]
+    each_null(lib.dsr_dense2_bwd, d2b, (1, 2, 3, 4, 9, 10, 11, 12, 13))
+    vary(lib.dsr_dense2_bwd, d2b, 7, (3,), E_ARG)                    # Bp < B
+    vary(lib.dsr_dense2_bwd, d2b, 0, (5,), E_ARG)
+    c16 = [BF, a, a, 64, st]
+    each_null(lib.dsr_cast16, c16, (1, 2))
+    vary(lib.dsr_cast16, c16, 3, (0, 12), E_ARG)
+    vary(lib.dsr_cast16, c16, 1, (off(4), off(8)), E_ARG)
+    vary(lib.dsr_cast16, c16, 2, (off(2), off(8)), E_ARG)
+    fl = [BF, a, a, 4, 16, 8, 8, 32, 0, st]
+    each_null(lib.dsr_flatten, fl, (1, 2))
+    vary(lib.dsr_flatten, fl, 6, (12, 4), E_ARG)
+    vary(lib.dsr_flatten, fl, 8, (3, -1), E_ARG)
+    calls.append((lambda: lib.dsr_flatten(BF, a, a, 40, 16, 8, 8, 32, 1, st), E_ARG))      # mode 1: Bp < B
+    assert len(calls) > 120
+    for i, (call, code) in enumerate(calls):
+        rc = call()
+        assert rc == code, f"call #{i} returned {rc}, expected {code}"
+        assert lib.dsr_last_error(), i
