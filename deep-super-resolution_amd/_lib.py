@@ -204,6 +204,8 @@ SIGNATURES = {
     "dsr_featloss_relu": (_I, [_I, _P, _P, _Z, _I, _P]),
     "dsr_featloss_combine": (_I, [_I, C.POINTER(C.c_void_p), C.POINTER(_F), _P, _P]),
     "dsr_featloss_combine_bwd": (_I, [_I, C.POINTER(_F), _P, _P, _P]),
+    "dsr_imresize_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
+    "dsr_imresize_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
 }
 
 _lib = None

@@ -230,6 +230,23 @@ class PatchBank:
         self.degradation, self.generator = degradation, generator
         self.last_kernels = self.last_noise_std = self.last_jpeg_quality = None
 
+    @classmethod
+    def from_hr(cls, hr_images, scale_factor, LR_patch_size, **kw):
+        """A bank built from HR images alone, the way the benchmark LR sets were built: each uint8 [H, W, 3] HR image (device
+        tensor or numpy array) is cropped to a multiple of `scale_factor` (``modcrop``) and its LR image is made once, on the
+        device, by the MATLAB-style ``utils.imresize.imresize(hr, 1 / scale_factor)`` (bicubic, antialiased).  `kw`: the
+        constructor's other arguments."""
+        from .utils.imresize import imresize, modcrop
+        dev = None
+        pairs = []
+        for hr in hr_images:
+            if not torch.is_tensor(hr):
+                hr = torch.from_numpy(np.ascontiguousarray(hr)).to(_device(dev))
+            dev = hr.device
+            hr = modcrop(hr, scale_factor).contiguous()
+            pairs.append((imresize(hr, scale=1.0 / scale_factor), hr))
+        return cls(pairs, scale_factor, LR_patch_size, **kw)
+
     def sample(self, batch, indices=None, transforms=None, kernels=None, noise_std=None, jpeg_quality=None):
         """(LR [B,3,ph,pw], HR [B,3,ph*s,pw*s]) fp32 device batches; image b is `indices[b]` (default: uniform draws).
         ``transforms``: explicit D4 codes, one per sample, instead of the draw (also without ``augment``).

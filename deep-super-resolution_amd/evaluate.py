@@ -90,6 +90,25 @@ def to_uint8_image(img):
     return (img.detach().clamp(0.0, 1.0) * 255.0).round().to(torch.uint8).permute(1, 2, 0).cpu().numpy()
 
 
+def bicubic_pairs(hr_images, scale):
+    """The benchmark protocol's test pairs from HR images alone: each uint8 [H, W, 3] image (device tensor, numpy array or PIL
+    image; or an ``(image, name)`` pair -- the default name is the image's position) is cropped to a multiple of `scale`
+    (``modcrop``) and reduced by the MATLAB-style ``utils.imresize.imresize(hr, 1 / scale)`` to its 8-bit LR image, on the
+    device.  Returns a list of ``(LR [1,3,h,w], HR [1,3,H,W], name)`` fp32 in [0, 1]: what ``evaluate_generator`` takes; with
+    ``y_channel=True`` its 'psnr_y' / 'ssim_y' then follow the published tables end to end on the device (MATLAB's own uint8
+    rounding between the two resampling passes is unpinned, see utils/imresize.py)."""
+    from .dataset import to_tensor
+    from .utils.degradation import _to_device
+    from .utils.imresize import imresize, modcrop
+    out = []
+    for i, item in enumerate(hr_images):
+        image, name = item if isinstance(item, (tuple, list)) else (item, str(i))
+        hr = modcrop(_to_device(image)[0], scale).contiguous()
+        lr = imresize(hr, scale=1.0 / scale)
+        out.append((to_tensor(lr)[None], to_tensor(hr)[None], name))
+    return out
+
+
 def evaluate_generator(gen, pairs, tile=None, out_dir=None, data_range=None, dtype=torch.float16, to_unit=None,
                        with_ssim=True, lpips_model=None, self_ensemble=False, ema=None, y_channel=False, shave=None):
     """eval_GAN.py:21-69 for an iterable of (LR [1,3,h,w], HR [1,3,H,W], name) on the device.

@@ -1656,3 +1656,45 @@ class DownsampleDense(torch.autograd.Function):
             if not need_dw:
                 dw = None
         return dx, dw, db, None, None
+
+
+def imresize_check(rc):
+    """`check` for the imresize entry points: DSR_E_UNSUPPORTED (more than 64 taps on an axis) is a NotImplementedError."""
+    if rc == -4:
+        raise NotImplementedError("dsr_hip: " + _lib.lib().dsr_last_error().decode())
+    return check(rc)
+
+
+def _imresize_launch(src, dst, planes, h, w, oh, ow, idx_h, w_h, taps_h, idx_w, w_w, taps_w):
+    imresize_check(_lib.lib().dsr_imresize_f32(_ptr(src), _ptr(dst), planes, h, w, oh, ow, _ptr(idx_h), _ptr(w_h), taps_h,
+                                               _ptr(idx_w), _ptr(w_w), taps_w, _stream()))
+
+
+class Imresize(torch.autograd.Function):
+    """MATLAB-style separable resampling of fp32 NCHW (csrc/imresize.hip; the tables: utils.imresize.imresize_tables of the
+    H and the W axis).  One launch forward; one launch backward, the same kernel on dy with the transposed tables (a gather:
+    deterministic, no atomics).  Gradient for x only.  Like Downsample it has nothing to do under an ambient loss scale: the
+    scale enters the backward pass at the net's output, after this op, and there is no parameter gradient to scale here.
+    The tables are cached device tensors, so a call reads nothing on the host and allocates its output only."""
+
+    @staticmethod
+    def forward(ctx, x, th, tw):
+        _need_gpu(x)
+        x = x.contiguous().float()
+        n, c, h, w = x.shape
+        if (h, w) != (th.n_in, tw.n_in):
+            raise RuntimeError(f"Imresize: tables for {th.n_in}x{tw.n_in}, input {h}x{w}")
+        y = torch.empty((n, c, th.n_out, tw.n_out), dtype=torch.float32, device=x.device)
+        _imresize_launch(x, y, n * c, h, w, th.n_out, tw.n_out, th.idx, th.w, th.taps, tw.idx, tw.w, tw.taps)
+        ctx.tables = (th, tw)
+        ctx.shape = (n, c, h, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        th, tw = ctx.tables
+        n, c, h, w = ctx.shape
+        dy = dy.contiguous().float()
+        dx = torch.empty((n, c, h, w), dtype=torch.float32, device=dy.device)
+        _imresize_launch(dy, dx, n * c, th.n_out, tw.n_out, h, w, th.t_idx, th.t_w, th.q, tw.t_idx, tw.t_w, tw.q)
+        return dx, None, None

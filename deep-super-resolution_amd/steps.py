@@ -262,6 +262,9 @@ class DipRunner:
         params = list(net.parameters())                          # get_params('net')
         if learn_downsampler:
             # blind super-resolution: the downsampler's weight and bias join the same Adam (and its loss scale / clipping)
+            if not hasattr(downsampler, "set_learnable"):
+                raise TypeError(f"learn_downsampler=True needs a downsampler with trainable filters (utils.downsampler."
+                                f"Downsampler); {type(downsampler).__name__} has no set_learnable()")
             downsampler.set_learnable(True)
             params = params + list(downsampler.parameters())
         self.opt = FusedAdam(params, lr=learning_rate, grad_scale=1.0 / self.loss_scale,

@@ -726,6 +726,24 @@ int dsr_featloss_relu(int dtype, const void* x, void* out, size_t P, int Cp, dsr
 int dsr_featloss_combine(int n, const float* const* values, const float* weights, float* out, dsr_stream_t s);
 int dsr_featloss_combine_bwd(int n, const float* weights, const float* g, float* gout, dsr_stream_t s);
 
+/* ------------------------------------------------------------------ MATLAB-style antialiased resampling (imresize.hip)
+ * y = W_h . x . W_w^T per plane in ONE launch: the H pass runs from global memory into an LDS strip, the W pass out of it; the
+ * intermediate stays fp32 and never reaches HBM.  Per axis the caller passes DEVICE tables built on the host (utils/imresize.py:
+ * float64 arithmetic, one rounding to fp32): idx [out][taps] 0-based source indices, already mirrored, and w [out][taps] fp32;
+ * a padding entry carries weight 0 and a valid index (indices are clamped to the axis before use).  Per output and pass: one
+ * fmaf per tap, in tap order, from 0; no atomics: the result is defined bit for bit.  The backward pass is the same call on dy
+ * with the transposed tables (H, W = dy's size, OH, OW = dx's).
+ * dsr_imresize_f32: x [planes][H][W] -> y [planes][OH][OW], fp32.
+ * dsr_imresize_u8:  x [H][W][C] -> y [OH][OW][C], uint8; computed in fp32 from the bytes with no rounding between the passes,
+ *   stored as min(max(floorf(v + 0.5f), 0), 255).
+ * A null pointer, a size < 1 or planes * max(H W, OH OW) >= 2^31 is DSR_E_ARG; taps_h or taps_w outside 1..64 is
+ * DSR_E_UNSUPPORTED; both before anything is launched.  A tile whose strip does not fit the LDS is computed from global memory
+ * with the same arithmetic (same bits), never truncated. */
+int dsr_imresize_f32(const float* x, float* y, int planes, int H, int W, int OH, int OW, const int* idx_h, const float* w_h,
+                     int taps_h, const int* idx_w, const float* w_w, int taps_w, dsr_stream_t s);
+int dsr_imresize_u8(const unsigned char* x, unsigned char* y, int H, int W, int C, int OH, int OW, const int* idx_h,
+                    const float* w_h, int taps_h, const int* idx_w, const float* w_w, int taps_w, dsr_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
