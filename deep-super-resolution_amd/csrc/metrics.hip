@@ -7,6 +7,10 @@
 //
 // fp32 NCHW in, one partial sum per block out (deterministic two-stage reduction, no atomics).  A block computes a 32x8
 // patch of window centres from a (32+10)x(8+10) tile of both images staged in LDS; 121 taps x 5 moments per thread.
+// Every moment is accumulated the same way -- the product of the two pixels formed once, then one explicit fma per tap -- and
+// the position's value comes from ssim_of_moments: with `r += g * x * y` left to the compiler, hipcc packed some moments into
+// v_pk_fma_f32 and others into v_pk_mul_f32 + v_add_f32, so E[ab] and E[a^2] of IDENTICAL images differed in the last bit and
+// their SSIM was 1 - 1e-6 instead of 1 (the cancellation in the variances amplifies by 1 / (va + vb + c2)).
 #include "dsr_common.h"
 #include "dsr_kernels.h"
 #include "../../include/dsr_hip.h"
@@ -18,6 +22,15 @@
 struct SsimWindow {
   float g[SSIM_K];   // separable 1-D Gaussian, normalised to sum 1
 };
+
+// SSIM of one window position from its raw moments.  No contraction and the products a*b formed once: swapping the images
+// gives the same bits, and identical images give exactly 1 (2 mab == maa + mbb and 2 cab == va + vb then hold exactly).
+__device__ __forceinline__ float ssim_of_moments(float ma, float mb, float saa, float sbb, float sab, float c1, float c2) {
+#pragma clang fp contract(off)
+  const float maa = ma * ma, mbb = mb * mb, mab = ma * mb;
+  const float va = saa - maa, vb = sbb - mbb, cab = sab - mab;
+  return ((2.f * mab + c1) * (2.f * cab + c2)) / ((maa + mbb + c1) * (va + vb + c2));
+}
 
 __global__ __launch_bounds__(256) void ssim_kernel(const float* __restrict__ a, const float* __restrict__ b, int H, int W,
                                                    int tiles_x, int tiles_y, float c1, float c2, SsimWindow win,
@@ -49,21 +62,21 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float* __restrict__ a, 
 #pragma unroll
       for (int dx = 0; dx < SSIM_K; ++dx) {
         const float xa = sa[ly + dy][lx + dx], xb = sb[ly + dy][lx + dx], g = win.g[dx];
-        ra += g * xa;
-        rb += g * xb;
-        raa += g * xa * xa;
-        rbb += g * xb * xb;
-        rab += g * xa * xb;
+        const float paa = xa * xa, pbb = xb * xb, pab = xa * xb;
+        ra = fmaf(g, xa, ra);
+        rb = fmaf(g, xb, rb);
+        raa = fmaf(g, paa, raa);
+        rbb = fmaf(g, pbb, rbb);
+        rab = fmaf(g, pab, rab);
       }
       const float g = win.g[dy];
-      ma += g * ra;
-      mb += g * rb;
-      saa += g * raa;
-      sbb += g * rbb;
-      sab += g * rab;
+      ma = fmaf(g, ra, ma);
+      mb = fmaf(g, rb, mb);
+      saa = fmaf(g, raa, saa);
+      sbb = fmaf(g, rbb, sbb);
+      sab = fmaf(g, rab, sab);
     }
-    const float va = saa - ma * ma, vb = sbb - mb * mb, cab = sab - ma * mb;
-    v = ((2.f * ma * mb + c1) * (2.f * cab + c2)) / ((ma * ma + mb * mb + c1) * (va + vb + c2));
+    v = ssim_of_moments(ma, mb, saa, sbb, sab, c1, c2);
   }
   v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
@@ -119,15 +132,6 @@ static SsimWindow ssim_gauss_window() {
   }
   for (int i = 0; i < SSIM_K; ++i) win.g[i] = (float)(g[i] / s);
   return win;
-}
-
-// SSIM of one window position from its raw moments.  No contraction and the products a*b formed once: swapping the images
-// gives the same bits, and identical images give exactly 1 (2 mab == maa + mbb and 2 cab == va + vb then hold exactly).
-__device__ __forceinline__ float ssim_of_moments(float ma, float mb, float saa, float sbb, float sab, float c1, float c2) {
-#pragma clang fp contract(off)
-  const float maa = ma * ma, mbb = mb * mb, mab = ma * mb;
-  const float va = saa - maa, vb = sbb - mbb, cab = sab - mab;
-  return ((2.f * mab + c1) * (2.f * cab + c2)) / ((maa + mbb + c1) * (va + vb + c2));
 }
 
 // The same position as its two factors: the contrast-structure term cs = (2 cab + c2) / (va + vb + c2) and
