@@ -29,6 +29,15 @@ class Epilogue(C.Structure):
                 ("bn_scale", C.c_void_p), ("bn_shift", C.c_void_p), ("residual", C.c_void_p)]
 
 
+class RdbConv(C.Structure):
+    """dsr_rdb_conv: one prefix convolution over a growth buffer (csrc/conv_rdb.hip)."""
+    _fields_ = [("dtype", C.c_int), ("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int),
+                ("x", C.c_void_p), ("ldx", C.c_int), ("w", C.c_void_p), ("bias", C.c_void_p), ("act", C.c_int),
+                ("slope", C.c_float), ("res1", C.c_void_p), ("ldr1", C.c_int), ("r1_off", C.c_int), ("beta1", C.c_float),
+                ("res2", C.c_void_p), ("ldr2", C.c_int), ("r2_off", C.c_int), ("beta2", C.c_float), ("y", C.c_void_p),
+                ("ldy", C.c_int), ("y_off", C.c_int), ("max_blocks", C.c_int)]
+
+
 _P, _I, _F, _Z, _LL = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_longlong
 _DESC = C.POINTER(ConvDesc)
 
@@ -206,6 +215,9 @@ SIGNATURES = {
     "dsr_featloss_combine_bwd": (_I, [_I, C.POINTER(_F), _P, _P, _P]),
     "dsr_imresize_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
     "dsr_imresize_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
+    "dsr_conv_rdb_supported": (_I, [C.POINTER(RdbConv)]),
+    "dsr_conv_rdb_fwd": (_I, [C.POINTER(RdbConv), _P]),
+    "dsr_scale_add16": (_I, [_I, _P, _F, _P, _P, _Z, _P]),
 }
 
 _lib = None
@@ -220,7 +232,7 @@ _NO_LAUNCH = ("dsr_last_error", "dsr_abi_version", "dsr_conv_dgrad_ps_supported"
               "dsr_ssim_img_blocks", "dsr_psnr_blocks", "dsr_lbfgs_workspace", "dsr_lbfgs_vector_floats", "dsr_clip_sumsq_partials",
               "dsr_linear_factor_gram_workspace", "dsr_linear_factor_gram_dots", "dsr_downsample_dense_wgrad_workspace",
               "dsr_msssim_min_size", "dsr_msssim_pyramid_floats", "dsr_ssim_cs_img_blocks", "dsr_msssim_bwd_blocks", "dsr_luma_blocks",
-              "dsr_featloss_blocks", "dsr_jpeg_workspace")
+              "dsr_featloss_blocks", "dsr_jpeg_workspace", "dsr_conv_rdb_supported")
 
 
 class _Lib:

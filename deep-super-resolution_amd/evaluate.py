@@ -33,8 +33,13 @@ def save_model(model, name, out_dir):
 
 def load_model(model, model_path):
     """utils/common.py:46-60: load a reference-format checkpoint, with or without the ``module.`` key prefix.
-    ``weights_only=True`` (as in the reference): nothing in the file is executed."""
+    ``weights_only=True`` (as in the reference): nothing in the file is executed.  A file that wraps the state dict as
+    ``{'params_ema': ...}`` or ``{'params': ...}`` (BasicSR's format: models/GAN/rrdbnet.py) is unwrapped, the average first."""
     state = torch.load(model_path, map_location="cpu", weights_only=True)
+    for key in ("params_ema", "params"):     # BasicSR's wrapping (ESRGAN / Real-ESRGAN checkpoints); it prefers the average too
+        if isinstance(state.get(key), dict):
+            state = state[key]
+            break
     clean = OrderedDict((k[len("module."):] if k.startswith("module.") else k, v) for k, v in state.items())
     model.load_state_dict(clean)
     return model

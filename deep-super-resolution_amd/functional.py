@@ -1516,6 +1516,166 @@ class ConcatCrop(torch.autograd.Function):
         return grads[0], grads[1], None, None
 
 
+class ConcatChannels(torch.autograd.Function):
+    """torch.cat(tensors, dim=1) on NHWC tensors of one N, H, W: ``ConcatChannels.apply((c0, c1, ...), t0, t1, ...)`` with
+    the real channel count of each input (ConcatCrop for n inputs, without the crop; one dsr_box_copy per input)."""
+
+    @staticmethod
+    def forward(ctx, channels, *tensors):
+        tensors = [t.contiguous() for t in tensors]
+        n, h, w, _ = tensors[0].shape
+        if len(channels) != len(tensors) or any(t.shape[:3] != (n, h, w) or t.dtype != tensors[0].dtype for t in tensors):
+            raise ValueError("ConcatChannels: one channel count per input, inputs of one N, H, W and dtype")
+        total = sum(channels)
+        make = torch.empty if total == r8(total) else torch.zeros        # pad channels are zero
+        out = make((n, h, w, r8(total)), dtype=tensors[0].dtype, device=tensors[0].device)
+        c0 = 0
+        for t, c in zip(tensors, channels):
+            _box_copy(t, out, n, h, w, c, 0, 0, 0, 0, 0, c0)
+            c0 += c
+        ctx.channels, ctx.shapes = tuple(channels), [tuple(t.shape) for t in tensors]
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        dout = dout.contiguous()
+        n, h, w, _ = dout.shape
+        grads, c0 = [], 0
+        for i, (c, shape) in enumerate(zip(ctx.channels, ctx.shapes)):
+            g = None
+            if ctx.needs_input_grad[1 + i]:
+                g = (torch.empty if c == shape[3] else torch.zeros)(shape, dtype=dout.dtype, device=dout.device)
+                _box_copy(dout, g, n, h, w, c, 0, 0, c0, 0, 0, 0)
+            grads.append(g)
+            c0 += c
+        return (None,) + tuple(grads)
+
+
+def scale_add16(a, beta, b=None):
+    """r16(fmaf(a, beta, b)) on two 16-bit tensors of one shape (b=None: r16(a * beta)): dsr_scale_add16."""
+    a = a.contiguous()
+    if b is not None:
+        b = b.contiguous()
+        if b.shape != a.shape or b.dtype != a.dtype:
+            raise ValueError(f"scale_add16: operands of {tuple(a.shape)} {a.dtype} and {tuple(b.shape)} {b.dtype}")
+    if a.numel() % 8:
+        raise ValueError("scale_add16: the element count must be a multiple of 8")
+    out = torch.empty_like(a)
+    check(_lib.lib().dsr_scale_add16(_dt(a), _ptr(a), float(beta), _ptr(b), _ptr(out), a.numel() // 8, _stream()))
+    return out
+
+
+class ScaleAdd(torch.autograd.Function):
+    """a * beta + b on 16-bit NHWC tensors, one rounding (the residual scalings of a dense block on the composed path)."""
+
+    @staticmethod
+    def forward(ctx, a, beta, b):
+        _need_gpu(a)
+        ctx.beta = float(beta)
+        return scale_add16(a, beta, b)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.contiguous()
+        da = scale_add16(g, ctx.beta) if ctx.needs_input_grad[0] else None
+        return da, None, (g if ctx.needs_input_grad[2] else None)
+
+
+# ----------------------------------------------------------------------------- residual dense block on a growth buffer
+def rrdb_fused_enabled():
+    """DSR_RRDB_FUSED (read per call): 0 = the no-grad forward of a dense block also takes the composed launches."""
+    return os.environ.get("DSR_RRDB_FUSED", "1") != "0"
+
+
+def rdb_conv_desc(x, cin, cout, y, y_off, act=ACT_NONE, slope=0.0, res1=None, r1_off=0, beta1=0.0, res2=None, r2_off=0,
+                  beta2=0.0, wf=None, bias=None, max_blocks=0):
+    """The dsr_rdb_conv of one prefix convolution: x [N,H,W,ldx] read in channels [0, cin), y written in [y_off, y_off + cout)."""
+    n, h, w, ldx = x.shape
+    return _lib.RdbConv(_dt(x), n, h, w, cin, cout, x.data_ptr(), ldx, None if wf is None else wf.data_ptr(),
+                        None if bias is None else bias.data_ptr(), act, float(slope),
+                        None if res1 is None else res1.data_ptr(), 0 if res1 is None else res1.shape[3], r1_off, float(beta1),
+                        None if res2 is None else res2.data_ptr(), 0 if res2 is None else res2.shape[3], r2_off, float(beta2),
+                        y.data_ptr(), y.shape[3], y_off, int(max_blocks))
+
+
+def rdb_conv(x, cin, wf, bias, y, y_off, cout, **kw):
+    """One dsr_conv_rdb_fwd launch (see rdb_conv_desc; wf: the packed forward image [9][cout][cin] of packed_weights)."""
+    _need_gpu(x)
+    for t in (x, y, kw.get("res1"), kw.get("res2")):
+        if t is not None and not (t.is_contiguous() and t.dim() == 4 and t.dtype == x.dtype and t.shape[:3] == x.shape[:3]):
+            raise ValueError("rdb_conv: contiguous NHWC tensors of one N, H, W and dtype are expected")
+    d = rdb_conv_desc(x, cin, cout, y, y_off, wf=wf, bias=bias, **kw)
+    if KERNEL_LOG is None:
+        return check(_lib.lib().dsr_conv_rdb_fwd(C.byref(d), _stream()))
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    rc = check(_lib.lib().dsr_conv_rdb_fwd(C.byref(d), _stream()))
+    e1.record()
+    KERNEL_LOG.append(("fwd", (d.N, d.H, d.W, cin, cout, 3, 3, 1, 1), e0, e1, "conv_rdb_kernel"))
+    return rc
+
+
+def rdb_supported(x_shape, dtype, num_feat, num_grow_ch):
+    """Does dsr_conv_rdb_fwd take all five launches of a dense block on [N,H,W,*] growth buffers (and is the switch on)?"""
+    if not rrdb_fused_enabled() or dtype not in (torch.bfloat16, torch.float16):
+        return False
+    n, h, w = x_shape[:3]
+    key = (n, h, w, dtype, num_feat, num_grow_ch)
+    hit = _rdb_supported_cache.get(key)
+    if hit is None:
+        if len(_rdb_supported_cache) > 1024:
+            _rdb_supported_cache.clear()
+        hit = _rdb_supported_cache[key] = _rdb_supported(n, h, w, dtype, num_feat, num_grow_ch)
+    return hit
+
+
+_rdb_supported_cache = {}
+
+
+def _rdb_supported(n, h, w, dtype, num_feat, num_grow_ch):
+    ld = num_feat + 4 * num_grow_ch
+    dt = BF16 if dtype == torch.bfloat16 else F16
+    lib = _lib.lib()
+    for k in range(5):
+        cin = num_feat + k * num_grow_ch
+        cout, ldy, y_off = (num_grow_ch, ld, cin) if k < 4 else (num_feat, ld, 0)
+        d = _lib.RdbConv(dt, n, h, w, cin, cout, None, ld, None, None, ACT_LEAKY if k < 4 else ACT_NONE, 0.2, None, 0, 0, 0.0,
+                         None, 0, 0, 0.0, None, ldy, y_off, 0)
+        if not lib.dsr_conv_rdb_supported(C.byref(d)):
+            return False
+    return True
+
+
+def rdb_forward(buf_in, weights, biases, buf_out, res2=None, slope=0.2, beta=0.2):
+    """One residual dense block on growth buffers, no autograd: five dsr_conv_rdb_fwd launches, no concatenation copy.
+
+    buf_in [N,H,W,F + 4 G] holds the block input in channels [0, F); conv1..4 (LeakyReLU(slope)) append G channels each in
+    place; conv5 writes r16(x5 * beta + x) -- with `res2` r16((x5 * beta + x) * beta + res2[..., :F]) -- into channels
+    [0, F) of buf_out, which may have any pixel stride >= F (the next block's buffer, or a dense [N,H,W,F] tensor).
+    weights / biases: the five fp32 OIHW weights and [Cout] biases (None entries: no bias)."""
+    if not rdb_supported(buf_in.shape, buf_in.dtype, weights[4].shape[0], weights[0].shape[0]):
+        raise RuntimeError("rdb_forward: dsr_conv_rdb_fwd does not take this block (shape, or DSR_RRDB_FUSED=0); "
+                           "the composed path (ConvAct / ConcatChannels / ScaleAdd) does")
+    n, h, w, ld = buf_in.shape
+    nf, gc = weights[4].shape[0], weights[0].shape[0]
+    if ld != nf + 4 * gc or buf_out.data_ptr() == buf_in.data_ptr():
+        raise ValueError("rdb_forward: buf_in must have num_feat + 4 num_grow_ch channels and differ from buf_out")
+    dt = _dt(buf_in)
+    for k in range(5):
+        wk, bk = weights[k], biases[k]
+        cin = nf + k * gc
+        if tuple(wk.shape) != (gc if k < 4 else nf, cin, 3, 3):
+            raise ValueError(f"rdb_forward: conv{k + 1} weight of shape {tuple(wk.shape)}")
+        wf, _ = packed_weights(wk, ConvDesc(dt, n, h, w, cin, wk.shape[0], 3, 3, 1, 1, PAD_ZERO), buf_in.dtype)
+        bk = None if bk is None else bk.detach()
+        if k < 4:
+            rdb_conv(buf_in, cin, wf, bk, buf_in, cin, gc, act=ACT_LEAKY, slope=slope)
+        elif res2 is None:
+            rdb_conv(buf_in, cin, wf, bk, buf_out, 0, nf, res1=buf_in, beta1=beta)
+        else:
+            rdb_conv(buf_in, cin, wf, bk, buf_out, 0, nf, res1=buf_in, beta1=beta, res2=res2, beta2=beta)
+
+
 class BNAct(torch.autograd.Function):
     """act(BatchNorm2d(x)) on a tensor that does not come straight out of a conv (DIP: BN after Concat,
     models/DIP/skip.py:51)."""

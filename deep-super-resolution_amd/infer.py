@@ -5,6 +5,8 @@ receptive field: 4 (9x9 head) + 2*blocks + 1 (3x3 trunk) LR pixels, plus 1, 1/2,
 4/factor for the 9x9 tail -- 40 LR pixels for the 16-block x8 model.  A tile computed with that much
 halo is therefore bit-identical to the same region of the whole-image result; tiling only bounds the activation
 footprint (64 channels at 8x resolution) when images are large.  BASELINE config 5 runs this in fp16.
+A model that carries ``scale`` and ``receptive_halo()`` itself (models/GAN/rrdbnet.py) is tiled by those; one that starts with
+``pixel_unshuffle`` (its ``unshuffle`` factor) needs ``tile`` and ``halo`` to be multiples of that factor.
 
 Geometric self-ensemble (EDSR "+", Lim et al. 2017): the generator runs on the eight flipped / turned copies of the LR
 image, each output is turned back and the eight are averaged.  The copies and the inverse-and-mean are one HIP launch
@@ -18,8 +20,16 @@ from .functional import _ptr, _stream
 
 
 def receptive_halo(gen):
+    own = getattr(gen, "receptive_halo", None)
+    if callable(own):                        # a model that knows its own receptive field (models/GAN/rrdbnet.py)
+        return own()
     blocks = len(gen.residual_blocks)
     return 4 + 2 * blocks + 1 + 2 + 1        # head + trunk + conv2 + shuffle convs/tail (rounded up)
+
+
+def _factor(gen):
+    scale = getattr(gen, "scale", None)
+    return int(scale) if scale is not None else 2 ** len(gen.pixel_shuffle_blocks)
 
 
 def _check_image(x, what):
@@ -58,7 +68,11 @@ def _run(gen, lr, tile, halo):
         return gen(lr)
     n, _, h, w = lr.shape
     halo = receptive_halo(gen) if halo is None else halo
-    f = 2 ** len(gen.pixel_shuffle_blocks)
+    f = _factor(gen)
+    u = int(getattr(gen, "unshuffle", 1))
+    if u > 1 and (tile % u or halo % u):
+        # a model that starts with pixel_unshuffle: every tile must start on its grid
+        raise ValueError(f"super_resolve: tile ({tile}) and halo ({halo}) must be multiples of the model's pixel_unshuffle factor {u}")
     out = torch.empty((n, 3, h * f, w * f), dtype=torch.float32, device=lr.device)
     for y0 in range(0, h, tile):
         for x0 in range(0, w, tile):

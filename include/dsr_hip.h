@@ -744,6 +744,47 @@ int dsr_imresize_f32(const float* x, float* y, int planes, int H, int W, int OH,
 int dsr_imresize_u8(const unsigned char* x, unsigned char* y, int H, int W, int C, int OH, int OW, const int* idx_h,
                     const float* w_h, int taps_h, const int* idx_w, const float* w_w, int taps_w, dsr_stream_t s);
 
+/* ------------------------------------------------------------------ residual dense block on a growth buffer (conv_rdb.hip)
+ * One 3x3 / stride 1 / zero-pad 1 convolution whose input is the channel PREFIX [0, Cin) of an NHWC tensor with pixel stride
+ * ldx >= Cin, and whose Cout in {32, 64} outputs land at channel offset y_off of a tensor with pixel stride ldy -- the same
+ * tensor for conv1..4 of a dense block (the concatenation is then free), another one for conv5:
+ *     v = sum_taps sum_ci x[n, y+dy, x+dx, ci] * w[c, ci, dy, dx] + bias[c]       fp32 accumulation
+ *     v = act(v)                       act: DSR_ACT_NONE, or DSR_ACT_LEAKY with slope > 0 (v >= 0 ? v : v * slope)
+ *     if res1: v = fmaf(v, beta1, res1[n, y, x, r1_off + c]);   if res2: v = fmaf(v, beta2, res2[n, y, x, r2_off + c])
+ *     y[n, y, x, y_off + c] = r16(v)                                               one rounding, to nearest even
+ * w is the packed forward image [9][Cout][Cin] of dsr_conv_pack_weight.  Cin, every stride and every offset are multiples of
+ * 32 channels.  bias, res1 and res2 may be NULL.  Within a launch no byte is both read and written: DSR_E_ARG (before anything
+ * is launched) for a NULL x / w / y, a bad dtype, size, stride or offset, y_off + Cout > ldy (the same for the residuals),
+ * an output range that overlaps the input prefix (y == x and y_off < Cin) or a residual range of the same tensor, a tensor
+ * of 2^31 bytes or more per image or 2^32 bytes or more in total.  max_blocks <= 0: one persistent block per CU; > 0 caps the
+ * grid.  dsr_conv_rdb_supported: non-zero when the shape fields (pointers are not looked at) describe a launch this kernel
+ * takes; 0 for a NULL argument.  (A shape measured slower than the composed form -- dsr_conv_fwd on a concatenated copy --
+ * would be refused here; tools/microbench_rrdb.py found none.) */
+typedef struct {
+  int dtype;               /* DSR_BF16 | DSR_F16 */
+  int N, H, W;
+  int Cin, Cout;
+  const void* x;           /* [N][H][W][ldx], channels [0, Cin) are read */
+  int ldx;
+  const void* w;           /* [9][Cout][Cin] */
+  const float* bias;       /* [Cout] or NULL */
+  int act;
+  float slope;
+  const void* res1;        /* [N][H][W][ldr1] or NULL, channels [r1_off, r1_off + Cout) */
+  int ldr1, r1_off;
+  float beta1;
+  const void* res2;
+  int ldr2, r2_off;
+  float beta2;
+  void* y;                 /* [N][H][W][ldy], channels [y_off, y_off + Cout) are written */
+  int ldy, y_off;
+  int max_blocks;
+} dsr_rdb_conv;
+int dsr_conv_rdb_supported(const dsr_rdb_conv* c);
+int dsr_conv_rdb_fwd(const dsr_rdb_conv* c, dsr_stream_t s);
+/* out = r16(fmaf(a, beta, b)) on nvec 16-byte vectors of 16-bit values; b may be NULL (out = r16(a * beta)); out may be a or b */
+int dsr_scale_add16(int dtype, const void* a, float beta, const void* b, void* out, size_t nvec, dsr_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
