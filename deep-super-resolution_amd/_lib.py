@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "csrc", "libdsr_hip.so")
 
-ABI_VERSION = 7          # bumped whenever a signature in include/dsr_hip.h changes; checked against the loaded library
+ABI_VERSION = 8          # bumped whenever a signature in include/dsr_hip.h changes; checked against the loaded library
 BF16, F16 = 0, 1
 F32 = 2                  # the luma entry points (csrc/luma.hip) also read fp32 images
 ACT_NONE, ACT_LEAKY, ACT_PRELU, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_ELU = range(7)
@@ -36,6 +36,13 @@ class RdbConv(C.Structure):
                 ("slope", C.c_float), ("res1", C.c_void_p), ("ldr1", C.c_int), ("r1_off", C.c_int), ("beta1", C.c_float),
                 ("res2", C.c_void_p), ("ldr2", C.c_int), ("r2_off", C.c_int), ("beta2", C.c_float), ("y", C.c_void_p),
                 ("ldy", C.c_int), ("y_off", C.c_int), ("max_blocks", C.c_int)]
+
+
+class AdamArgs(C.Structure):
+    """dsr_adam_args: where an Adam launch takes its coefficients from (hyper, loss_scale, found_inf: device words, each
+    nullable); one block for dsr_pw_adam, dsr_pw_adam_multi and dsr_linear_wgrad_adam."""
+    _fields_ = [("step", C.c_void_p), ("lr", C.c_float), ("b1", C.c_float), ("b2", C.c_float), ("eps", C.c_float),
+                ("grad_scale", C.c_float), ("hyper", C.c_void_p), ("loss_scale", C.c_void_p), ("found_inf", C.c_void_p)]
 
 
 _P, _I, _F, _Z, _LL = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_longlong
@@ -117,19 +124,14 @@ SIGNATURES = {
     "dsr_pw_axpby_f32": (_I, [_P, _P, _F, _F, _P, _P, _Z, _P]),
     "dsr_pw_diff_loss": (_I, [_P, _P, _P, _Z, _I, _P, _I, _P]),
     "dsr_pw_bce_const": (_I, [_P, _I, _F, _P, _P, _I, _P]),
-    "dsr_pw_adam": (_I, [_P, _P, _P, _P, _Z, _F, _F, _F, _F, _P, _F, _P, _P]),
-    "dsr_pw_adam_multi": (_I, [_I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _P, _F, _P]),
-    "dsr_pw_incr": (_I, [_P, _P]),
+    "dsr_pw_adam": (_I, [_P, _P, _P, _P, _Z, _P, C.POINTER(AdamArgs), _P]),
+    "dsr_pw_adam_multi": (_I, [_I, _P, _P, _P, _P, _P, C.POINTER(AdamArgs), _P]),
+    "dsr_pw_incr": (_I, [_P, _P, _P]),
     "dsr_amp_check": (_I, [_I, C.POINTER(C.c_void_p), C.POINTER(_Z), _P, _P]),
-    "dsr_pw_adam_amp": (_I, [_P, _P, _P, _P, _Z, _F, _F, _F, _F, _P, _P, _P, _P, _P]),
-    "dsr_pw_adam_multi_amp": (_I, [_I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _P, _P, _P, _P]),
-    "dsr_pw_incr_unless": (_I, [_P, _P, _P]),
     "dsr_amp_update": (_I, [_P, _P, _P, _F, _F, _I, _P, _P]),
     "dsr_clip_sumsq_partials": (_Z, [_I, C.POINTER(C.c_void_p), C.POINTER(_Z)]),
     "dsr_clip_sumsq": (_I, [_I, C.POINTER(C.c_void_p), C.POINTER(_Z), _P, _Z, _P]),
     "dsr_clip_finalize": (_I, [_P, _I, _P, _I, _F, _P, _F, _P, _F, _P, _P, _P, _P]),
-    "dsr_pw_adam_hyper": (_I, [_P, _P, _P, _P, _Z, _P, _F, _F, _F, _P, _F, _P, _P, _P, _P]),
-    "dsr_pw_adam_multi_hyper": (_I, [_I, _P, _P, _P, _P, _P, _P, _F, _F, _F, _P, _F, _P, _P, _P]),
     "dsr_cast16": (_I, [_I, _P, _P, _Z, _P]),
     "dsr_flatten": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dsr_linear_fwd_workspace": (_Z, [_I, _Z, _I]),
@@ -137,11 +139,10 @@ SIGNATURES = {
     "dsr_linear_dgrad": (_I, [_I, _P, _P, _P, _I, _I, _Z, _P]),
     "dsr_linear_wgrad": (_I, [_I, _P, _P, _P, _I, _I, _Z, _P]),
     "dsr_linear_wgrad_gathered": (_I, [_I, _P, _P, _P, _I, _I, _Z, _I, _F, _P]),
-    "dsr_linear_wgrad_adam": (_I, [_I, _P, _P, _I, _I, _Z, _I, _F, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _P]),
+    "dsr_linear_wgrad_adam": (_I, [_I, _P, _P, _I, _I, _Z, _I, _F, _P, _P, _P, _P, C.POINTER(AdamArgs), _P]),
     "dsr_linear_factor_gram_workspace": (_Z, [_I, _I, _Z, _I]),
     "dsr_linear_factor_gram_dots": (_I, [_I, _I]),
     "dsr_linear_factor_gram": (_I, [_I, _P, _P, _I, _I, _Z, _I, _F, _P, _Z, _P]),
-    "dsr_linear_wgrad_adam_hyper": (_I, [_I, _P, _P, _I, _I, _Z, _I, _F, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _P, _P, _P]),
     "dsr_dense2_fwd": (_I, [_P, _P, _P, _I, _I, _P, _P]),
     "dsr_dense2_bwd": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
     "dsr_maxpool2_fwd": (_I, [_I, _P, _P, _I, _I, _I, _I, _P]),

@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
+#include "../../include/dsr_hip.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
@@ -179,6 +181,43 @@ __device__ __forceinline__ AdamCoef adam_coef(const int* __restrict__ step, floa
   c.eps = eps;
   c.grad_scale = grad_scale;
   return c;
+}
+// Where the coefficients come from (dsr_adam_args, include/dsr_hip.h).  Every Adam kernel is a template on one bool, "resolved
+// on the device": false takes AdamHost -- the host's lr and grad_scale, no trace of the three device pointers, the registers of
+// the plain kernels -- and true takes the whole block, each pointer nullable.  adam_dispatch() makes the choice, for every
+// entry point: false exactly when hyper, loss_scale and found_inf are all null.
+struct AdamHost {
+  const int* step;
+  float lr, b1, b2, eps, grad_scale;
+};
+template <bool DEV>
+using AdamArgs = std::conditional_t<DEV, dsr_adam_args, AdamHost>;
+// false: the scaler's overflow flag is set and the launch writes nothing
+template <bool DEV>
+__device__ __forceinline__ bool adam_resolve(const AdamArgs<DEV>& a, AdamCoef& co) {
+  float lr = a.lr, gs = a.grad_scale;
+  if constexpr (DEV) {
+    if (a.found_inf != nullptr && a.found_inf[0] != 0.f) return false;
+    if (a.loss_scale != nullptr) gs = 1.f / a.loss_scale[0];      // exact: the scale is a power of two
+    if (a.hyper != nullptr) {
+      lr = a.hyper[0];
+      gs = gs * a.hyper[1];            // ONE fp32 product: a clipping coefficient of exactly 1 leaves the bits
+    }
+  }
+  co = adam_coef(a.step, lr, a.b1, a.b2, a.eps, gs);
+  return true;
+}
+// host: the checks of the block that every entry point makes, and the one place that picks the instantiation
+static inline bool adam_args_ok(const dsr_adam_args* a) {
+  if (!a || ((uintptr_t)a & 3) || !a->step) return false;
+  return (((uintptr_t)a->step | (uintptr_t)a->hyper | (uintptr_t)a->loss_scale | (uintptr_t)a->found_inf) & 3) == 0;
+}
+template <class Launch>
+static inline void adam_dispatch(const dsr_adam_args& a, Launch launch) {
+  if (a.hyper || a.loss_scale || a.found_inf)
+    launch(std::true_type{}, a);
+  else
+    launch(std::false_type{}, AdamHost{a.step, a.lr, a.b1, a.b2, a.eps, a.grad_scale});
 }
 __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, const AdamCoef& c) {
 #pragma clang fp contract(off)

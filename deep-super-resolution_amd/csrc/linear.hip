@@ -471,11 +471,8 @@ struct AdamFused {
   float* m;
   float* v;
   unsigned short* shadow;   // bf16 image of p (the MFMA operand of the next forward), may be null
-  const int* step;
-  float lr, b1, b2, eps, grad_scale;
 };
-// (the tile loop, shared by linear_wgrad_adam_kernel and linear_wgrad_adam_hyper_kernel, which differ only in where the
-// Adam coefficients come from)
+// (the tile loop; linear_wgrad_adam_kernel resolves the Adam coefficients first)
 template <int DT, int BP>
 __device__ __forceinline__ void linear_wgrad_adam_tiles(const unsigned short* __restrict__ dyT,
                                                         const unsigned short* __restrict__ xT, int O, size_t K, int R,
@@ -576,25 +573,14 @@ __device__ __forceinline__ void linear_wgrad_adam_tiles(const unsigned short* __
     }
   }
 }
-template <int DT, int BP>
+template <int DT, int BP, bool DEV>   // DEV: coefficients resolved on the device (dsr_common.h adam_resolve)
 __global__ __launch_bounds__(256, 2) void linear_wgrad_adam_kernel(const unsigned short* __restrict__ dyT,
                                                                    const unsigned short* __restrict__ xT, int O, size_t K,
                                                                    int R, float scale, int kpairs_per_block,
-                                                                   const AdamFused a) {
-  linear_wgrad_adam_tiles<DT, BP>(dyT, xT, O, K, R, scale, kpairs_per_block, a,
-                                  adam_coef(a.step, a.lr, a.b1, a.b2, a.eps, a.grad_scale));
-}
-// Device-resident hyper-parameters (pointwise.hip adam_hyper_kernel): hyper = {lr, clipping coefficient}; loss_scale and
-// found_inf nullable, with the dynamic loss scaler's meaning.
-template <int DT, int BP>
-__global__ __launch_bounds__(256, 2) void linear_wgrad_adam_hyper_kernel(
-    const unsigned short* __restrict__ dyT, const unsigned short* __restrict__ xT, int O, size_t K, int R, float scale,
-    int kpairs_per_block, const AdamFused a, const float* __restrict__ hyper, const float* __restrict__ loss_scale,
-    const float* __restrict__ found_inf) {
-  if (found_inf != nullptr && found_inf[0] != 0.f) return;
-  const float gs = loss_scale != nullptr ? 1.f / loss_scale[0] : a.grad_scale;
-  linear_wgrad_adam_tiles<DT, BP>(dyT, xT, O, K, R, scale, kpairs_per_block, a,
-                                  adam_coef(a.step, hyper[0], a.b1, a.b2, a.eps, gs * hyper[1]));
+                                                                   const AdamFused a, const AdamArgs<DEV> s) {
+  AdamCoef co;
+  if (!adam_resolve<DEV>(s, co)) return;
+  linear_wgrad_adam_tiles<DT, BP>(dyT, xT, O, K, R, scale, kpairs_per_block, a, co);
 }
 
 // ------------------------------------------------------------------ norm of the factored gradient (gradient clipping)
@@ -967,15 +953,16 @@ extern "C" int dsr_linear_wgrad_gathered(int dtype, const void* dyT16_all, const
 }
 
 extern "C" int dsr_linear_wgrad_adam(int dtype, const void* dyT16_all, const void* xT16_all, int Bp, int O, size_t K, int R,
-                                     float scale, float* p, float* m, float* v, void* shadow_bf16, const int* step, float lr,
-                                     float b1, float b2, float eps, float grad_scale, dsr_stream_t st) {
-  DSR_REQUIRE(dyT16_all && xT16_all && p && m && v && step && DSR_DTYPE_OK(dtype) && K > 0 && O > 0,
+                                     float scale, float* p, float* m, float* v, void* shadow_bf16, const dsr_adam_args* args,
+                                     dsr_stream_t st) {
+  DSR_REQUIRE(dyT16_all && xT16_all && p && m && v && DSR_DTYPE_OK(dtype) && K > 0 && O > 0,
               "linear_wgrad_adam: null pointer or bad shape");
+  DSR_REQUIRE(adam_args_ok(args), "linear_wgrad_adam: null or misaligned argument block, step counter or device word");
   if (Bp != 32 && Bp != 64) return dsr_fail(DSR_E_UNSUPPORTED, "linear_wgrad_adam: padded batch must be 32 or 64");
   if (R < 1) return dsr_fail(DSR_E_ARG, "linear_wgrad_adam: R < 1");
   if (K % 64) return dsr_fail(DSR_E_UNSUPPORTED, "linear_wgrad_adam: K %% 64 (use dsr_linear_wgrad + dsr_pw_adam)");
   DSR_REQUIRE((((uintptr_t)dyT16_all | (uintptr_t)xT16_all | (uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) == 0 &&
-                  ((uintptr_t)shadow_bf16 & 7) == 0 && ((uintptr_t)step & 3) == 0,
+                  ((uintptr_t)shadow_bf16 & 7) == 0,
               "linear_wgrad_adam: misaligned pointer");
   const char* e = getenv("DSR_WGRAD_ADAM_KPB");      // tuning switch: 256-wide k groups per block
   const int kpb = e ? atoi(e) : 1;          // (1: 2.71 ms stand-alone and 0.1-0.15 ms per config-3 step better than 2; 4 worse)
@@ -984,25 +971,18 @@ extern "C" int dsr_linear_wgrad_adam(int dtype, const void* dyT16_all, const voi
   dim3 grid((unsigned)((kgroups + kpb - 1) / kpb), (O + 63) / 64), block(256);
   const unsigned short* DYT = (const unsigned short*)dyT16_all;
   const unsigned short* XT = (const unsigned short*)xT16_all;
-  AdamFused a;
-  a.p = p;
-  a.m = m;
-  a.v = v;
-  a.shadow = (unsigned short*)shadow_bf16;
-  a.step = step;
-  a.lr = lr;
-  a.b1 = b1;
-  a.b2 = b2;
-  a.eps = eps;
-  a.grad_scale = grad_scale;
-#define LAUNCH_WGA(DTV, BPV) \
-  hipLaunchKernelGGL((linear_wgrad_adam_kernel<DTV, BPV>), grid, block, 0, st, DYT, XT, O, K, R, scale, kpb, a)
-  if (dtype == DSR_BF16) {
-    if (Bp == 32) LAUNCH_WGA(DSR_DTYPE_BF16, 32); else LAUNCH_WGA(DSR_DTYPE_BF16, 64);
-  } else {
-    if (Bp == 32) LAUNCH_WGA(DSR_DTYPE_F16, 32); else LAUNCH_WGA(DSR_DTYPE_F16, 64);
-  }
+  const AdamFused a{p, m, v, (unsigned short*)shadow_bf16};
+  adam_dispatch(*args, [&](auto dev, const auto& s) {
+#define LAUNCH_WGA(DTV, BPV)                                                                                               \
+  hipLaunchKernelGGL((linear_wgrad_adam_kernel<DTV, BPV, decltype(dev)::value>), grid, block, 0, st, DYT, XT, O, K, R, scale, \
+                     kpb, a, s)
+    if (dtype == DSR_BF16) {
+      if (Bp == 32) LAUNCH_WGA(DSR_DTYPE_BF16, 32); else LAUNCH_WGA(DSR_DTYPE_BF16, 64);
+    } else {
+      if (Bp == 32) LAUNCH_WGA(DSR_DTYPE_F16, 32); else LAUNCH_WGA(DSR_DTYPE_F16, 64);
+    }
 #undef LAUNCH_WGA
+  });
   return dsr_launch_status("dsr_linear_wgrad_adam");
 }
 
@@ -1027,7 +1007,7 @@ extern "C" int dsr_dense2_bwd(int dtype, const float* dout, const float* out, co
   return dsr_launch_status("dsr_dense2_bwd");
 }
 
-// ---- norm of the factored gradient + the device-hyper form of dsr_linear_wgrad_adam
+// ---- norm of the factored gradient
 struct GramPlan {
   int N, nsub, gy;          // Gram size, 32-row sub-stages per stage, grid.y (units of 4 waves)
   int sx, sy;               // row chunks (blocks along x) of the X and the dY table
@@ -1100,48 +1080,4 @@ extern "C" int dsr_linear_factor_gram(int dtype, const void* dyT16_all, const vo
   hipLaunchKernelGGL(factor_gram_dot_kernel, dim3((unsigned)g.dots), dim3(256), 0, st, fx, g.sx, fy, g.sy, g.N * g.N,
                      (double)scale * (double)scale, dots);
   return dsr_launch_status("dsr_linear_factor_gram");
-}
-
-extern "C" int dsr_linear_wgrad_adam_hyper(int dtype, const void* dyT16_all, const void* xT16_all, int Bp, int O, size_t K,
-                                           int R, float scale, float* p, float* m, float* v, void* shadow_bf16,
-                                           const int* step, const float* hyper, float b1, float b2, float eps,
-                                           float grad_scale, const float* loss_scale, const float* found_inf,
-                                           dsr_stream_t st) {
-  DSR_REQUIRE(dyT16_all && xT16_all && p && m && v && step && hyper && DSR_DTYPE_OK(dtype) && K > 0 && O > 0,
-              "linear_wgrad_adam_hyper: null pointer or bad shape");
-  if (Bp != 32 && Bp != 64) return dsr_fail(DSR_E_UNSUPPORTED, "linear_wgrad_adam_hyper: padded batch must be 32 or 64");
-  if (R < 1) return dsr_fail(DSR_E_ARG, "linear_wgrad_adam_hyper: R < 1");
-  if (K % 64) return dsr_fail(DSR_E_UNSUPPORTED, "linear_wgrad_adam_hyper: K %% 64 (use dsr_linear_wgrad + dsr_pw_adam_hyper)");
-  DSR_REQUIRE((((uintptr_t)dyT16_all | (uintptr_t)xT16_all | (uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) == 0 &&
-                  ((uintptr_t)shadow_bf16 & 7) == 0 &&
-                  (((uintptr_t)step | (uintptr_t)hyper | (uintptr_t)loss_scale | (uintptr_t)found_inf) & 3) == 0,
-              "linear_wgrad_adam_hyper: misaligned pointer");
-  const char* e = getenv("DSR_WGRAD_ADAM_KPB");      // the tuning switch of dsr_linear_wgrad_adam
-  const int kpb = e ? atoi(e) : 1;
-  if (kpb < 1) return dsr_fail(DSR_E_ARG, "linear_wgrad_adam_hyper: DSR_WGRAD_ADAM_KPB < 1");
-  const size_t kgroups = (K + 255) / 256;
-  dim3 grid((unsigned)((kgroups + kpb - 1) / kpb), (O + 63) / 64), block(256);
-  const unsigned short* DYT = (const unsigned short*)dyT16_all;
-  const unsigned short* XT = (const unsigned short*)xT16_all;
-  AdamFused a;
-  a.p = p;
-  a.m = m;
-  a.v = v;
-  a.shadow = (unsigned short*)shadow_bf16;
-  a.step = step;
-  a.lr = 0.f;
-  a.b1 = b1;
-  a.b2 = b2;
-  a.eps = eps;
-  a.grad_scale = grad_scale;
-#define LAUNCH_WGAH(DTV, BPV)                                                                                            \
-  hipLaunchKernelGGL((linear_wgrad_adam_hyper_kernel<DTV, BPV>), grid, block, 0, st, DYT, XT, O, K, R, scale, kpb, a, hyper, \
-                     loss_scale, found_inf)
-  if (dtype == DSR_BF16) {
-    if (Bp == 32) LAUNCH_WGAH(DSR_DTYPE_BF16, 32); else LAUNCH_WGAH(DSR_DTYPE_BF16, 64);
-  } else {
-    if (Bp == 32) LAUNCH_WGAH(DSR_DTYPE_F16, 32); else LAUNCH_WGAH(DSR_DTYPE_F16, 64);
-  }
-#undef LAUNCH_WGAH
-  return dsr_launch_status("dsr_linear_wgrad_adam_hyper");
 }

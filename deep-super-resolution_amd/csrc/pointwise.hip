@@ -1059,12 +1059,11 @@ __global__ void bce_const_kernel(const float* __restrict__ p, int n, float targe
 }
 
 // ------------------------------------------------------------------ Adam (torch.optim.Adam defaults, no weight decay)
-// step counter lives on the device so the launch is graph-capturable.
-// AMP (dynamic loss scale, optim.DynamicLossScaler): the same arithmetic, predicated on the device.  found_inf[0] != 0
-// means some gradient of this step is not finite: the kernel returns before it touches p, m, v or the shadow.  Otherwise
-// the gradient multiplier is 1 / loss_scale[0] -- exact, the scale is a power of two -- in place of the host's grad_scale.
-// The streaming loop of the per-tensor launch, shared by adam_kernel and adam_hyper_kernel (which differ only in where the
-// coefficients come from).
+// step counter lives on the device so the launch is graph-capturable.  Where lr and the gradient multiplier come from
+// -- the host, the dynamic loss scaler's words, the hyper block of the clipping pass -- is dsr_adam_args (dsr_common.h
+// adam_resolve); a set found_inf means some gradient of this step is not finite: the kernel returns before it touches p, m,
+// v or the shadow.
+// The streaming loop of the per-tensor launch.
 __device__ __forceinline__ void adam_stream(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                             float* __restrict__ v, size_t n, unsigned short* __restrict__ shadow16,
                                             const AdamCoef& co) {
@@ -1120,46 +1119,16 @@ __device__ __forceinline__ void adam_stream(float* __restrict__ p, const float* 
     if (shadow16) shadow16[i] = f2h<DSR_DTYPE_BF16>(pk);
   }
 }
-template <bool AMP>
+template <bool DEV>   // coefficients resolved on the device (dsr_common.h adam_resolve)
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
-                                                   float b1, float b2, float eps, const int* __restrict__ step,
-                                                   float grad_scale, unsigned short* __restrict__ shadow16,
-                                                   const float* __restrict__ loss_scale,
-                                                   const float* __restrict__ found_inf) {
-  if constexpr (AMP) {
-    if (found_inf[0] != 0.f) return;
-    grad_scale = 1.f / loss_scale[0];
-  }
-  adam_stream(p, g, m, v, n, shadow16, adam_coef(step, lr, b1, b2, eps, grad_scale));
-}
-// Device-resident hyper-parameters (FusedAdam(lr=<tensor>, max_grad_norm=c)): hyper[0] is the learning rate, hyper[1] the
-// clipping coefficient of this step (dsr_clip_finalize writes both).  The gradient multiplier is ONE fp32 product
-// grad_scale * hyper[1], so a coefficient of exactly 1 leaves the bits of the kernels above; loss_scale / found_inf
-// (both nullable) are the dynamic loss scaler's words, with adam_kernel<true>'s meaning.
-__device__ __forceinline__ bool adam_hyper_coef(const float* __restrict__ hyper, float b1, float b2, float eps,
-                                                const int* __restrict__ step, float grad_scale,
-                                                const float* __restrict__ loss_scale,
-                                                const float* __restrict__ found_inf, AdamCoef& co) {
-  if (found_inf != nullptr && found_inf[0] != 0.f) return false;
-  if (loss_scale != nullptr) grad_scale = 1.f / loss_scale[0];
-  co = adam_coef(step, hyper[0], b1, b2, eps, grad_scale * hyper[1]);
-  return true;
-}
-__global__ __launch_bounds__(256) void adam_hyper_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                         float* __restrict__ m, float* __restrict__ v, size_t n,
-                                                         const float* __restrict__ hyper, float b1, float b2, float eps,
-                                                         const int* __restrict__ step, float grad_scale,
-                                                         unsigned short* __restrict__ shadow16,
-                                                         const float* __restrict__ loss_scale,
-                                                         const float* __restrict__ found_inf) {
+                                                   float* __restrict__ m, float* __restrict__ v, size_t n,
+                                                   unsigned short* __restrict__ shadow16, const AdamArgs<DEV> a) {
   AdamCoef co;
-  if (!adam_hyper_coef(hyper, b1, b2, eps, step, grad_scale, loss_scale, found_inf, co)) return;
+  if (!adam_resolve<DEV>(a, co)) return;
   adam_stream(p, g, m, v, n, shadow16, co);
 }
-__global__ void incr_kernel(int* step) { *step += 1; }
-__global__ void incr_unless_kernel(int* step, const float* found_inf) {
-  if (found_inf[0] == 0.f) *step += 1;
+__global__ void incr_kernel(int* step, const float* found_inf) {
+  if (found_inf == nullptr || found_inf[0] == 0.f) *step += 1;
 }
 
 // ------------------------------------------------------------------ dynamic loss scale (optim.DynamicLossScaler)
@@ -1218,7 +1187,7 @@ __global__ void amp_update_kernel(float* scale, int* growth_tracker, float* foun
 
 // ------------------------------------------------------------------ gradient-norm clipping (optim.FusedAdam(max_grad_norm=c))
 // torch.nn.utils.clip_grad_norm_(params, c, norm_type=2) with nothing read on the host and no gradient rewritten: one
-// streaming read forms the sum of squares, dsr_clip_finalize turns it into the coefficient, the _hyper Adam kernels apply it.
+// streaming read forms the sum of squares, dsr_clip_finalize turns it into the coefficient, the Adam kernels apply it (dsr_adam_args.hyper).
 // clip_sumsq_kernel: amp_check_kernel's group struct and chunk (aligned spans of multi_tensor.h).  A thread squares and adds
 // at most 32 body elements (8 vectors x 4) and 2 head / tail elements in fp32, in a fixed order; from there on everything is
 // fp64 (butterfly over the wave, the four wave sums in order), and the block stores ONE fp32 partial at its own index: no
@@ -1553,24 +1522,19 @@ extern "C" int dsr_pw_bce_const(const float* p, int n, float target, float* loss
   hipLaunchKernelGGL(bce_const_kernel, dim3(1), dim3(256), 0, st, p, n, target, loss, grad, accumulate);
   return dsr_launch_status("dsr_pw_bce_const");
 }
-extern "C" int dsr_pw_adam(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps,
-                 const int* step, float grad_scale, void* shadow_bf16, hipStream_t st) {
-  DSR_REQUIRE(p && g && m && v && step && n > 0, "adam: null pointer or empty tensor");
+extern "C" int dsr_pw_adam(float* p, const float* g, float* m, float* v, size_t n, void* shadow_bf16,
+                           const dsr_adam_args* args, hipStream_t st) {
+  DSR_REQUIRE(p && g && m && v && n > 0, "adam: null pointer or empty tensor");
+  DSR_REQUIRE(adam_args_ok(args), "adam: null or misaligned argument block, step counter or device word");
+  DSR_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 3) == 0 && ((uintptr_t)shadow_bf16 & 1) == 0,
+              "adam: misaligned pointer");
   size_t want = (n / 4 + 511) / 512;
   unsigned blocks = (unsigned)(want < 1 ? 1 : (want > 65536 ? 65536 : want));
-  hipLaunchKernelGGL(adam_kernel<false>, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, step, grad_scale,
-                     (unsigned short*)shadow_bf16, (const float*)nullptr, (const float*)nullptr);
+  adam_dispatch(*args, [&](auto dev, const auto& a) {
+    hipLaunchKernelGGL(adam_kernel<decltype(dev)::value>, dim3(blocks), dim3(256), 0, st, p, g, m, v, n,
+                       (unsigned short*)shadow_bf16, a);
+  });
   return dsr_launch_status("dsr_pw_adam");
-}
-extern "C" int dsr_pw_adam_amp(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2,
-                               float eps, const int* step, const float* scale, const float* found_inf, void* shadow_bf16,
-                               hipStream_t st) {
-  DSR_REQUIRE(p && g && m && v && step && scale && found_inf && n > 0, "adam_amp: null pointer or empty tensor");
-  size_t want = (n / 4 + 511) / 512;
-  unsigned blocks = (unsigned)(want < 1 ? 1 : (want > 65536 ? 65536 : want));
-  hipLaunchKernelGGL(adam_kernel<true>, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, step, 1.f,
-                     (unsigned short*)shadow_bf16, scale, found_inf);
-  return dsr_launch_status("dsr_pw_adam_amp");
 }
 // ---- multi-tensor Adam: the generator and discriminator hold ~100 small tensors each; one launch per 64 of them
 // (multi_tensor.h).  Element indices are 32-bit here, so a tensor holds at most 2^32 - 1 - DSR_ADAM_CHUNK elements.
@@ -1584,7 +1548,7 @@ struct AdamGroup {
   MtTable tb;
 };
 static_assert(sizeof(AdamGroup) <= 4096, "kernel arguments are limited to 4 KB");
-// this block's chunk of its tensor (shared by adam_multi_kernel and adam_multi_hyper_kernel)
+// this block's chunk of its tensor
 __device__ __forceinline__ void adam_multi_chunk(const AdamGroup& a, const AdamCoef& co) {
   unsigned blk;
   const int t = mt_locate(a.tb, blk);
@@ -1603,34 +1567,24 @@ __device__ __forceinline__ void adam_multi_chunk(const AdamGroup& a, const AdamC
     p[i] = pk;
   }
 }
-template <bool AMP>
-__global__ __launch_bounds__(256) void adam_multi_kernel(const AdamGroup a, float lr, float b1, float b2, float eps,
-                                                         const int* __restrict__ step, float grad_scale,
-                                                         const float* __restrict__ loss_scale,
-                                                         const float* __restrict__ found_inf) {
-  if constexpr (AMP) {          // see adam_kernel
-    if (found_inf[0] != 0.f) return;
-    grad_scale = 1.f / loss_scale[0];
-  }
-  adam_multi_chunk(a, adam_coef(step, lr, b1, b2, eps, grad_scale));
-}
-__global__ __launch_bounds__(256) void adam_multi_hyper_kernel(const AdamGroup a, const float* __restrict__ hyper, float b1,
-                                                               float b2, float eps, const int* __restrict__ step,
-                                                               float grad_scale, const float* __restrict__ loss_scale,
-                                                               const float* __restrict__ found_inf) {
+template <bool DEV>   // see adam_kernel
+__global__ __launch_bounds__(256) void adam_multi_kernel(const AdamGroup g, const AdamArgs<DEV> a) {
   AdamCoef co;
-  if (!adam_hyper_coef(hyper, b1, b2, eps, step, grad_scale, loss_scale, found_inf, co)) return;
-  adam_multi_chunk(a, co);
+  if (!adam_resolve<DEV>(a, co)) return;
+  adam_multi_chunk(g, co);
 }
-template <bool AMP>
-static int adam_multi_launch(const char* what, int count, float* const* p, const float* const* g, float* const* m,
-                             float* const* v, const size_t* n, float lr, float b1, float b2, float eps, const int* step,
-                             float grad_scale, const float* loss_scale, const float* found_inf, hipStream_t st,
-                             const float* hyper = nullptr) {
-  for (int i = 0; i < count; ++i)          // every entry is checked before the first launch
+extern "C" int dsr_pw_adam_multi(int count, float* const* p, const float* const* g, float* const* m, float* const* v,
+                                 const size_t* n, const dsr_adam_args* args, hipStream_t st) {
+  DSR_REQUIRE(count > 0 && p && g && m && v && n, "adam_multi: null table or no tensors");
+  DSR_REQUIRE(adam_args_ok(args), "adam_multi: null or misaligned argument block, step counter or device word");
+  for (int i = 0; i < count; ++i) {        // every entry is checked before the first launch
+    DSR_REQUIRE(p[i] && g[i] && m[i] && v[i] && n[i] > 0 &&
+                    (((uintptr_t)p[i] | (uintptr_t)g[i] | (uintptr_t)m[i] | (uintptr_t)v[i]) & 3) == 0,
+                "adam_multi: null, empty or misaligned tensor %d", i);
     if (n[i] > 0xFFFFFFFFull - DSR_ADAM_CHUNK) return dsr_fail(DSR_E_UNSUPPORTED, "adam_multi: tensor too large");
+  }
   mt_for_groups<AdamGroup>(
-      count, DSR_MT_MAX, [](int) { return false; },                        // fixed slices: an empty tensor keeps its slot
+      count, DSR_MT_MAX, [](int) { return false; },
       [&](int i) { return mt_blocks(n[i], DSR_ADAM_CHUNK); },
       [&](AdamGroup& a, int j, int i) {
         a.p[j] = p[i];
@@ -1639,41 +1593,17 @@ static int adam_multi_launch(const char* what, int count, float* const* p, const
         a.v[j] = v[i];
         a.n[j] = (unsigned)n[i];
       },
-      [&](const AdamGroup& a, unsigned blocks) {
-        if (hyper)
-          hipLaunchKernelGGL(adam_multi_hyper_kernel, dim3(blocks), dim3(256), 0, st, a, hyper, b1, b2, eps, step,
-                             grad_scale, loss_scale, found_inf);
-        else
-          hipLaunchKernelGGL(adam_multi_kernel<AMP>, dim3(blocks), dim3(256), 0, st, a, lr, b1, b2, eps, step, grad_scale,
-                             loss_scale, found_inf);
+      [&](const AdamGroup& grp, unsigned blocks) {
+        adam_dispatch(*args, [&](auto dev, const auto& a) {
+          hipLaunchKernelGGL(adam_multi_kernel<decltype(dev)::value>, dim3(blocks), dim3(256), 0, st, grp, a);
+        });
       });
-  return dsr_launch_status(what);
+  return dsr_launch_status("dsr_pw_adam_multi");
 }
-extern "C" int dsr_pw_adam_multi(int count, float* const* p, const float* const* g, float* const* m, float* const* v,
-                                 const size_t* n, float lr, float b1, float b2, float eps, const int* step,
-                                 float grad_scale, hipStream_t st) {
-  if (count < 0 || (count && (!p || !g || !m || !v || !n))) return dsr_fail(DSR_E_ARG, "adam_multi: null table");
-  return adam_multi_launch<false>("dsr_pw_adam_multi", count, p, g, m, v, n, lr, b1, b2, eps, step, grad_scale, nullptr,
-                                  nullptr, st);
-}
-extern "C" int dsr_pw_adam_multi_amp(int count, float* const* p, const float* const* g, float* const* m, float* const* v,
-                                     const size_t* n, float lr, float b1, float b2, float eps, const int* step,
-                                     const float* scale, const float* found_inf, hipStream_t st) {
-  DSR_REQUIRE(count > 0 && p && g && m && v && n && step && scale && found_inf, "adam_multi_amp: null pointer or no tensors");
-  for (int i = 0; i < count; ++i)
-    DSR_REQUIRE(p[i] && g[i] && m[i] && v[i] && n[i] > 0, "adam_multi_amp: null or empty tensor %d", i);
-  return adam_multi_launch<true>("dsr_pw_adam_multi_amp", count, p, g, m, v, n, lr, b1, b2, eps, step, 1.f, scale,
-                                 found_inf, st);
-}
-extern "C" int dsr_pw_incr(int* step, hipStream_t st) {
+extern "C" int dsr_pw_incr(int* step, const float* found_inf, hipStream_t st) {
   DSR_REQUIRE(step, "incr: null pointer");
-  hipLaunchKernelGGL(incr_kernel, dim3(1), dim3(1), 0, st, step);
+  hipLaunchKernelGGL(incr_kernel, dim3(1), dim3(1), 0, st, step, found_inf);
   return dsr_launch_status("dsr_pw_incr");
-}
-extern "C" int dsr_pw_incr_unless(int* step, const float* found_inf, hipStream_t st) {
-  DSR_REQUIRE(step && found_inf, "incr_unless: null pointer");
-  hipLaunchKernelGGL(incr_unless_kernel, dim3(1), dim3(1), 0, st, step, found_inf);
-  return dsr_launch_status("dsr_pw_incr_unless");
 }
 // The gradient tables of dsr_amp_check and dsr_clip_sumsq*: NULL = no gradient, skipped; any other entry holds 0 < n < 2^43
 // elements (2^30 blocks of DSR_AMP_CHUNK) at a 4-byte aligned address.  Returns the first entry that does not, or -1.
@@ -1756,30 +1686,4 @@ extern "C" int dsr_clip_finalize(const float* partials, int n_partials, const do
   hipLaunchKernelGGL(clip_finalize_kernel, dim3(1), dim3(256), 0, st, partials, n_partials, gram_partials, n_gram,
                      grad_scale, scale, max_norm, lr_dev, lr_host, grad_norm, clip_coef, hyper);
   return dsr_launch_status("dsr_clip_finalize");
-}
-extern "C" int dsr_pw_adam_hyper(float* p, const float* g, float* m, float* v, size_t n, const float* hyper, float b1,
-                                 float b2, float eps, const int* step, float grad_scale, const float* scale,
-                                 const float* found_inf, void* shadow_bf16, hipStream_t st) {
-  DSR_REQUIRE(p && g && m && v && step && hyper && n > 0, "adam_hyper: null pointer or empty tensor");
-  DSR_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 3) == 0 && ((uintptr_t)shadow_bf16 & 1) == 0 &&
-                  (((uintptr_t)hyper | (uintptr_t)step | (uintptr_t)scale | (uintptr_t)found_inf) & 3) == 0,
-              "adam_hyper: misaligned pointer");
-  size_t want = (n / 4 + 511) / 512;
-  unsigned blocks = (unsigned)(want < 1 ? 1 : (want > 65536 ? 65536 : want));
-  hipLaunchKernelGGL(adam_hyper_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, hyper, b1, b2, eps, step, grad_scale,
-                     (unsigned short*)shadow_bf16, scale, found_inf);
-  return dsr_launch_status("dsr_pw_adam_hyper");
-}
-extern "C" int dsr_pw_adam_multi_hyper(int count, float* const* p, const float* const* g, float* const* m, float* const* v,
-                                       const size_t* n, const float* hyper, float b1, float b2, float eps, const int* step,
-                                       float grad_scale, const float* scale, const float* found_inf, hipStream_t st) {
-  DSR_REQUIRE(count > 0 && p && g && m && v && n && step && hyper, "adam_multi_hyper: null pointer or no tensors");
-  DSR_REQUIRE((((uintptr_t)hyper | (uintptr_t)step | (uintptr_t)scale | (uintptr_t)found_inf) & 3) == 0,
-              "adam_multi_hyper: misaligned pointer");
-  for (int i = 0; i < count; ++i)
-    DSR_REQUIRE(p[i] && g[i] && m[i] && v[i] && n[i] > 0 &&
-                    (((uintptr_t)p[i] | (uintptr_t)g[i] | (uintptr_t)m[i] | (uintptr_t)v[i]) & 3) == 0,
-                "adam_multi_hyper: null, empty or misaligned tensor %d", i);
-  return adam_multi_launch<false>("dsr_pw_adam_multi_hyper", count, p, g, m, v, n, 0.f, b1, b2, eps, step, grad_scale, scale,
-                                  found_inf, st, hyper);
 }

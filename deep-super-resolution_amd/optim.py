@@ -70,7 +70,7 @@ class FusedAdam:
         self.m = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
         self.v = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
         self.step_t = torch.zeros(1, dtype=torch.int32, device=dev)
-        # the device hyper block {lr, clip_coef} the _hyper kernels read; dsr_clip_finalize writes it every step
+        # the device hyper block {lr, clip_coef} the Adam kernels read (dsr_adam_args.hyper); dsr_clip_finalize writes it every step
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
         self.clip_coef = torch.ones(1, dtype=torch.float32, device=dev)
         self._hyper = torch.zeros(2, dtype=torch.float32, device=dev)
@@ -86,7 +86,7 @@ class FusedAdam:
                 p.grad.zero_()
 
     def _device_hyper(self):
-        """True when the Adam launches read lr / the clipping coefficient from the device (the _hyper kernels)."""
+        """True when the Adam launches read lr / the clipping coefficient from the device (dsr_adam_args.hyper)."""
         return self.max_grad_norm is not None or isinstance(self.lr, torch.Tensor)
 
     def _buffer(self, name, nbytes):
@@ -136,10 +136,9 @@ class FusedAdam:
         dense head's factor gather, so every rank forms the same coefficient -- and read lr and coefficient on the device."""
         lib = _lib.lib()
         st = _stream()
-        amp = scaler is not None and scaler.enabled
         hyper = self._device_hyper()
         scale = found = None
-        if amp:
+        if scaler is not None and scaler.enabled:
             if self.grad_scale != 1.0:
                 raise ValueError(f"FusedAdam(grad_scale={self.grad_scale}) under a DynamicLossScaler would un-scale the "
                                  "gradients twice: leave grad_scale at 1.0")
@@ -148,11 +147,11 @@ class FusedAdam:
                                  "never exists as a tensor that could be checked for overflow, and the bf16 GAN step it "
                                  "serves needs no loss scale")
             scale, found = scaler._state(self.step_t.device)
-            check(lib.dsr_pw_incr_unless(_ptr(self.step_t), _ptr(found), st))
-        else:
-            check(lib.dsr_pw_incr(_ptr(self.step_t), st))
-        b1, b2 = self.betas
-        hp = _ptr(self._hyper)
+        check(lib.dsr_pw_incr(_ptr(self.step_t), _ptr(found), st))
+        # one argument block for every Adam launch of this step (dsr_adam_args: the C side reads it during each call)
+        self._args = _lib.AdamArgs(_ptr(self.step_t), 0.0 if hyper else self.lr, self.betas[0], self.betas[1], self.eps,
+                                   self.grad_scale, _ptr(self._hyper) if hyper else None, _ptr(scale), _ptr(found))
+        args = C.byref(self._args)
         deferred, grads, factors = [], [], []     # device hyper block: the Adam launches follow the norm pass
 
         def launch(fn, p, sh):
@@ -177,14 +176,9 @@ class FusedAdam:
                     sh = shadow_for_update(p)
                     if hyper:
                         factors.append(f)
-                        launch(lambda f=f, p=p, m=m, v=v, sh=sh: lib.dsr_linear_wgrad_adam_hyper(
-                            f.dt, _ptr(f.dyt), _ptr(f.xt), f.bp, f.o, f.k, f.ranks, f.scale, _ptr(p), _ptr(m), _ptr(v),
-                            _ptr(sh), _ptr(self.step_t), hp, b1, b2, self.eps, self.grad_scale, _ptr(scale), _ptr(found),
-                            st), p, sh)
-                    else:
-                        launch(lambda f=f, p=p, m=m, v=v, sh=sh: lib.dsr_linear_wgrad_adam(
-                            f.dt, _ptr(f.dyt), _ptr(f.xt), f.bp, f.o, f.k, f.ranks, f.scale, _ptr(p), _ptr(m), _ptr(v),
-                            _ptr(sh), _ptr(self.step_t), self.lr, b1, b2, self.eps, self.grad_scale, st), p, sh)
+                    launch(lambda f=f, p=p, m=m, v=v, sh=sh: lib.dsr_linear_wgrad_adam(
+                        f.dt, _ptr(f.dyt), _ptr(f.xt), f.bp, f.o, f.k, f.ranks, f.scale, _ptr(p), _ptr(m), _ptr(v),
+                        _ptr(sh), args, st), p, sh)
                     continue
                 # several backward passes since zero_grad (or a .grad from elsewhere): accumulate like autograd would
                 for f in pending:
@@ -199,38 +193,20 @@ class FusedAdam:
             grads.append(g)
             sh = shadow_for_update(p)        # bf16 image kept by DenseHead for this matrix (or None)
             if sh is None and p.numel() <= self.MULTI_MAX and p.is_contiguous():
-                small.append((p, g, m, v))
+                if p.numel():                # (a zero-element parameter has nothing to update, in any mode)
+                    small.append((p, g, m, v))
                 bump(p)                      # (rewritten by the multi-tensor launch below, before anything reads it)
                 continue
-            if hyper:
-                launch(lambda p=p, g=g, m=m, v=v, sh=sh: lib.dsr_pw_adam_hyper(
-                    _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), hp, b1, b2, self.eps, _ptr(self.step_t),
-                    self.grad_scale, _ptr(scale), _ptr(found), _ptr(sh), st), p, sh)
-            elif amp:
-                launch(lambda p=p, g=g, m=m, v=v, sh=sh: lib.dsr_pw_adam_amp(
-                    _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), self.lr, b1, b2, self.eps, _ptr(self.step_t),
-                    _ptr(scale), _ptr(found), _ptr(sh), st), p, sh)
-            else:
-                launch(lambda p=p, g=g, m=m, v=v, sh=sh: lib.dsr_pw_adam(
-                    _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), self.lr, b1, b2, self.eps, _ptr(self.step_t),
-                    self.grad_scale, _ptr(sh), st), p, sh)
+            launch(lambda p=p, g=g, m=m, v=v, sh=sh: lib.dsr_pw_adam(
+                _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(sh), args, st), p, sh)
         if hyper:
             self._write_hyper(grads, factors, scale)
             for run in deferred:
                 run()
         if small:                            # every small tensor in one launch per 64 (dsr_pw_adam_multi)
-            k = len(small)
             arr = [ptr_table([t[i] for t in small]) for i in range(4)]
             ns = size_table([t[0].numel() for t in small])
-            if hyper:
-                check(lib.dsr_pw_adam_multi_hyper(k, arr[0], arr[1], arr[2], arr[3], ns, hp, b1, b2, self.eps,
-                                                  _ptr(self.step_t), self.grad_scale, _ptr(scale), _ptr(found), st))
-            elif amp:
-                check(lib.dsr_pw_adam_multi_amp(k, arr[0], arr[1], arr[2], arr[3], ns, self.lr, self.betas[0],
-                                                self.betas[1], self.eps, _ptr(self.step_t), _ptr(scale), _ptr(found), st))
-            else:
-                check(lib.dsr_pw_adam_multi(k, arr[0], arr[1], arr[2], arr[3], ns, self.lr, self.betas[0], self.betas[1],
-                                            self.eps, _ptr(self.step_t), self.grad_scale, st))
+            check(lib.dsr_pw_adam_multi(len(small), arr[0], arr[1], arr[2], arr[3], ns, args, st))
         # packed 16-bit conv weight images follow in one launch, not one per layer (after a skipped step the same bits again:
         # the launch sequence stays fixed for graph replay)
         repack_cached(self.params)

@@ -228,68 +228,73 @@ int dsr_pw_axpby_f32(const float* x, const float* y, float a, float b, const flo
 int dsr_pw_diff_loss(const float* pred, const float* tgt, float* grad, size_t n, int mode, float* partial, int blocks,
                      dsr_stream_t s);
 int dsr_pw_bce_const(const float* p, int n, float target, float* loss, float* grad, int accumulate, dsr_stream_t s);
-/* torch.optim.Adam defaults; g is multiplied by grad_scale first (1/S when a static loss scale S is in use);
- * shadow_bf16 (nullable): also write the bf16 image of the updated parameter (same layout) */
-int dsr_pw_adam(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps,
-                const int* step, float grad_scale, void* shadow_bf16, dsr_stream_t s);
+/* ---- Adam (torch.optim.Adam defaults, no weight decay): ONE argument block for the three launch shapes -- one tensor
+ * (dsr_pw_adam), up to 64 small tensors per launch (dsr_pw_adam_multi) and the dense head's weight gradient + Adam in one
+ * pass (dsr_linear_wgrad_adam, below).  The block says where the coefficients come from; the three device pointers are
+ * independently nullable:
+ *   all three NULL       lr and grad_scale from the host (1/S when a static loss scale S is in use).
+ *   loss_scale           the gradient multiplier is 1 / loss_scale[0] (optim.DynamicLossScaler: exact, the scale is a power of
+ *                        two) and grad_scale is NOT read.
+ *   found_inf            found_inf[0] != 0: the launch writes nothing -- not p, m, v nor the shadow.
+ *   hyper                lr = hyper[0], and the multiplier chosen above is multiplied ONCE by hyper[1], the clipping coefficient
+ *                        (dsr_clip_finalize writes both): hyper[1] == 1 gives the bits of the same call without hyper.
+ * With all three NULL the kernels that run hold no trace of the pointers; any other combination is resolved on the device.
+ * Every entry point checks the same things before its first launch (DSR_E_ARG): args and args->step non-NULL and 4-byte
+ * aligned, hyper / loss_scale / found_inf 4-byte aligned when set, every tensor non-NULL, aligned (4 bytes; the shadow 2)
+ * and of n > 0 elements, count > 0.  An empty tensor is refused in every mode, on purpose: one rule instead of one per mode.
+ * optim.FusedAdam leaves zero-element parameters out of its tables, so such a parameter is a no-op in every mode. */
+typedef struct dsr_adam_args {
+  const int*   step;        /* device step counter, already advanced for this step; required            */
+  float        lr, b1, b2, eps;
+  float        grad_scale;  /* host multiplier of g; unused when loss_scale != NULL                      */
+  const float* hyper;       /* nullable: device {lr, clip coefficient}: lr = hyper[0], multiplier *= hyper[1] */
+  const float* loss_scale;  /* nullable: multiplier = 1 / loss_scale[0]                                  */
+  const float* found_inf;   /* nullable: found_inf[0] != 0 -> the launch writes nothing                  */
+} dsr_adam_args;
+/* shadow_bf16 (nullable): also write the bf16 image of the updated parameter (same layout) */
+int dsr_pw_adam(float* p, const float* g, float* m, float* v, size_t n, void* shadow_bf16, const dsr_adam_args* args,
+                dsr_stream_t s);
 /* the same update for `count` tensors in as few launches as possible (64 tensors per launch); the four pointer
  * arrays and n[] are HOST arrays of device pointers / element counts, read before the call returns */
 int dsr_pw_adam_multi(int count, float* const* p, const float* const* g, float* const* m, float* const* v,
-                      const size_t* n, float lr, float b1, float b2, float eps, const int* step, float grad_scale,
-                      dsr_stream_t s);
-int dsr_pw_incr(int* step, dsr_stream_t s);
+                      const size_t* n, const dsr_adam_args* args, dsr_stream_t s);
+/* step[0] += 1, unless found_inf (nullable) is set: the step counter of a step the loss scaler skips stays */
+int dsr_pw_incr(int* step, const float* found_inf, dsr_stream_t s);
 
 /* ------------------------------------------------------------------ dynamic loss scale (optim.DynamicLossScaler)
  * What torch.amp.GradScaler is to torch.optim, with nothing read on the host: the state is three device words, scale
  * (fp32, always a power of two, so that un-scaling is exact), growth_tracker (int32) and found_inf (fp32, 0 or 1), and the
- * skipped step is decided inside the kernels.  Order within a step: dsr_amp_check, dsr_pw_incr_unless, the _amp Adam
- * launches, dsr_amp_update.
+ * skipped step is decided inside the kernels.  Order within a step: dsr_amp_check, dsr_pw_incr with found_inf, the Adam
+ * launches with loss_scale and found_inf in their dsr_adam_args, dsr_amp_update.
  * dsr_amp_check: found_inf[0] = 1 if any element of the `count` fp32 tensors is Inf or NaN (HOST tables of device pointers
  * and element counts, read before the call returns; a NULL entry is a parameter without a gradient and is skipped; 64 tensors
  * per launch).  Never writes 0: dsr_amp_update clears the flag.
- * dsr_pw_adam_amp / dsr_pw_adam_multi_amp: dsr_pw_adam / dsr_pw_adam_multi with the gradient multiplied by 1 / scale[0],
- * and no write at all to p, m, v or the shadow when found_inf[0] != 0.  dsr_pw_incr_unless: the step counter likewise.
  * dsr_amp_update: torch's _amp_update_scale_ -- found_inf: scale *= backoff_factor, tracker = 0; otherwise tracker += 1 and,
  * when it reaches growth_interval, scale *= growth_factor (unless that is not finite) and tracker = 0 -- then found_inf = 0.
  * growth_factor = 2^k, backoff_factor = 2^-k, k >= 1; growth_interval >= 1.  stats (nullable): int32[2], steps taken and
  * steps skipped, incremented here. */
 int dsr_amp_check(int count, const float* const* grads, const size_t* numel, float* found_inf, dsr_stream_t s);
-int dsr_pw_adam_amp(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps,
-                    const int* step, const float* scale, const float* found_inf, void* shadow_bf16, dsr_stream_t s);
-int dsr_pw_adam_multi_amp(int count, float* const* p, const float* const* g, float* const* m, float* const* v,
-                          const size_t* n, float lr, float b1, float b2, float eps, const int* step, const float* scale,
-                          const float* found_inf, dsr_stream_t s);
-int dsr_pw_incr_unless(int* step, const float* found_inf, dsr_stream_t s);
 int dsr_amp_update(float* scale, int* growth_tracker, float* found_inf, float growth_factor, float backoff_factor,
                    int growth_interval, int* stats, dsr_stream_t s);
 
 /* ------------------------------------------------------------------ gradient-norm clipping and a device-resident learning rate
  * (optim.FusedAdam(lr=<tensor>, max_grad_norm=c)).  torch.nn.utils.clip_grad_norm_(params, c, norm_type=2) followed by
  * torch.optim.Adam, with nothing read on the host and no gradient rewritten: the coefficient is applied inside the Adam
- * kernels.  Order within a step: (dsr_amp_check,) dsr_pw_incr[_unless], dsr_clip_sumsq and / or dsr_linear_factor_gram,
- * dsr_clip_finalize, the _hyper Adam launches.
+ * kernels.  Order within a step: (dsr_amp_check,) dsr_pw_incr, dsr_clip_sumsq and / or dsr_linear_factor_gram,
+ * dsr_clip_finalize, the Adam launches with dsr_adam_args.hyper set.
  * dsr_clip_sumsq: one fp32 partial sum of squares per block over `count` fp32 tensors (HOST tables as dsr_amp_check takes
  * them: a NULL entry is skipped, 64 tensors per launch, views 4 / 8 / 12 bytes off a 16-byte boundary are fine), written
  * with plain stores at partials[0 .. dsr_clip_sumsq_partials()): no atomics, bit-reproducible.
  * dsr_clip_finalize: sums partials (fp32) and gram_partials (fp64) in fp64 in a fixed order; norm = sqrt(sum) * |grad_scale|,
  * or sqrt(sum) / scale[0] when scale (the dynamic loss scaler's word) is non-NULL; coef = min(1, max_norm / (norm + 1e-6)),
  * torch's formula (max_norm <= 0: coef = 1, no clipping); writes grad_norm[0], clip_coef[0] (both nullable) and the hyper
- * block hyper[0] = lr (lr_dev[0] when lr_dev is non-NULL, else lr_host), hyper[1] = coef.  Either count may be 0.
- * dsr_pw_adam_hyper / dsr_pw_adam_multi_hyper: dsr_pw_adam / dsr_pw_adam_multi with lr = hyper[0] and the gradient multiplied
- * by the ONE fp32 product grad_scale * hyper[1] (scale non-NULL: (1 / scale[0]) * hyper[1]); found_inf non-NULL and set:
- * no write at all.  hyper[1] == 1 gives the bits of the kernels they shadow. */
+ * block hyper[0] = lr (lr_dev[0] when lr_dev is non-NULL, else lr_host), hyper[1] = coef.  Either count may be 0. */
 size_t dsr_clip_sumsq_partials(int count, const float* const* grads, const size_t* numel);
 int dsr_clip_sumsq(int count, const float* const* grads, const size_t* numel, float* partials, size_t n_partials,
                    dsr_stream_t s);
 int dsr_clip_finalize(const float* partials, int n_partials, const double* gram_partials, int n_gram, float grad_scale,
                       const float* scale, float max_norm, const float* lr_dev, float lr_host, float* grad_norm,
                       float* clip_coef, float* hyper, dsr_stream_t s);
-int dsr_pw_adam_hyper(float* p, const float* g, float* m, float* v, size_t n, const float* hyper, float b1, float b2,
-                      float eps, const int* step, float grad_scale, const float* scale, const float* found_inf,
-                      void* shadow_bf16, dsr_stream_t s);
-int dsr_pw_adam_multi_hyper(int count, float* const* p, const float* const* g, float* const* m, float* const* v,
-                            const size_t* n, const float* hyper, float b1, float b2, float eps, const int* step,
-                            float grad_scale, const float* scale, const float* found_inf, dsr_stream_t s);
 
 /* ------------------------------------------------------------------ discriminator dense head (linear.hip)
  * models/GAN/discriminator.py:37-45,65-72: flatten(C,H,W) -> Linear(K,O) -> LeakyReLU(0.2) -> Linear(O,1) -> Sigmoid */
@@ -314,12 +319,11 @@ int dsr_linear_wgrad_gathered(int dtype, const void* dyT16_all, const void* xT16
 /* the same contraction with torch.optim.Adam's update applied to p / m / v (and p's bf16 shadow) in the epilogue: the
  * gradient is never written (R = 1, scale = 1: bit-identical to dsr_linear_wgrad followed by dsr_pw_adam); K % 64 == 0.
  * p / m / v and the two factor tables are accessed 16 bytes at a time and the shadow 8: they must be aligned to that
- * (step to 4), in this form and in the _hyper one; a misaligned pointer is DSR_E_ARG.
+ * (the words of dsr_adam_args to 4); a misaligned pointer is DSR_E_ARG.  args: as for dsr_pw_adam, every mode.
  * Replaces loss.backward() writing dense1.weight.grad + optimizer.step() reading it (train_GAN.py:52-53 on
  * discriminator.py:54). */
 int dsr_linear_wgrad_adam(int dtype, const void* dyT16_all, const void* xT16_all, int Bp, int O, size_t K, int R, float scale,
-                          float* p, float* m, float* v, void* shadow_bf16, const int* step, float lr, float b1, float b2,
-                          float eps, float grad_scale, dsr_stream_t s);
+                          float* p, float* m, float* v, void* shadow_bf16, const dsr_adam_args* args, dsr_stream_t s);
 /* squared Frobenius norm of the factored gradient dW = scale * sum_{(r,b)} dyT[r][:,b] (x) xT[r][:,b] WITHOUT forming it:
  * |dW|^2 = scale^2 * sum_{i,j} Gx[i][j] Gdy[i][j] over the (R Bp)^2 Gram matrices of the two tables (same arguments as
  * dsr_linear_wgrad_adam).  The workspace (16-byte aligned, dsr_linear_factor_gram_workspace() bytes) starts with
@@ -329,12 +333,6 @@ size_t dsr_linear_factor_gram_workspace(int Bp, int O, size_t K, int R);
 int dsr_linear_factor_gram_dots(int Bp, int R);
 int dsr_linear_factor_gram(int dtype, const void* dyT16_all, const void* xT16_all, int Bp, int O, size_t K, int R, float scale,
                            void* workspace, size_t ws_bytes, dsr_stream_t s);
-/* dsr_linear_wgrad_adam with the device hyper block (lr = hyper[0], gradient multiplier grad_scale * hyper[1]; loss_scale and
- * found_inf nullable, as in dsr_pw_adam_hyper) */
-int dsr_linear_wgrad_adam_hyper(int dtype, const void* dyT16_all, const void* xT16_all, int Bp, int O, size_t K, int R,
-                                float scale, float* p, float* m, float* v, void* shadow_bf16, const int* step,
-                                const float* hyper, float b1, float b2, float eps, float grad_scale, const float* loss_scale,
-                                const float* found_inf, dsr_stream_t s);
 /* out[b] = sigmoid(h[b][:] . w2 + b2[0]);  b2 is required (a one-element device tensor): NULL is DSR_E_ARG */
 int dsr_dense2_fwd(const float* h, const float* w2, const float* b2, int B, int K1, float* out, dsr_stream_t s);
 /* backward of the fp32 tail; also emits the 16-bit dy / dy^T operands of the two dense1 GEMMs */

@@ -7,6 +7,8 @@ import re
 
 import pytest
 
+from adam_args import adam_args
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = "deep-super-resolution_amd"
 
@@ -42,7 +44,7 @@ def test_ctypes_signatures_match_header(so):
     for name, (_, args) in L.SIGNATURES.items():
         assert len(args) == decl[name], (name, len(args), decl[name])
     L.lib()
-    assert L.lib().dsr_abi_version() == L.ABI_VERSION == 7
+    assert L.lib().dsr_abi_version() == L.ABI_VERSION == 8
 
 
 def test_host_side_descriptor_checks(so):
@@ -115,9 +117,9 @@ def test_bad_arguments_return_codes_not_crashes(so):
         lambda: lib.dsr_pw_diff_loss(N, N, N, 16, 0, N, 1, st),
         lambda: lib.dsr_pw_diff_loss(one, one, one, 16, 7, one, 1, st),           # mode
         lambda: lib.dsr_pw_bce_const(N, 4, 1.0, N, N, 0, st),
-        lambda: lib.dsr_pw_adam(N, N, N, N, 16, 1e-3, 0.9, 0.999, 1e-8, N, 1.0, N, st),
-        lambda: lib.dsr_pw_adam_multi(2, N, N, N, N, N, 1e-3, 0.9, 0.999, 1e-8, N, 1.0, st),
-        lambda: lib.dsr_pw_incr(N, st),
+        lambda: lib.dsr_pw_adam(N, N, N, N, 16, N, adam_args(None), st),
+        lambda: lib.dsr_pw_adam_multi(2, N, N, N, N, N, adam_args(None), st),
+        lambda: lib.dsr_pw_incr(N, N, st),
         lambda: lib.dsr_cast16(0, N, N, 16, st),
         lambda: lib.dsr_flatten(0, N, N, 2, 4, 8, 8, 0, 0, st),
         lambda: lib.dsr_linear_fwd(0, N, N, N, 1, 0.2, N, 4, 64, 8, N, 0, st),
@@ -143,8 +145,8 @@ def test_bad_arguments_return_codes_not_crashes(so):
         lambda: lib.dsr_conv_wgrad_batched(1, None, None, None, None, N, 0, st),
         lambda: lib.dsr_conv_wgrad_batched(0, ctypes.byref(d), None, None, None, N, 0, st),
         lambda: lib.dsr_conv_wgrad_batched(100000, ctypes.byref(d), None, None, None, N, 0, st),
-        lambda: lib.dsr_linear_wgrad_adam(0, N, N, 32, 8, 64, 1, 1.0, N, N, N, N, N, 1e-3, 0.9, 0.999, 1e-8, 1.0, st),
-        lambda: lib.dsr_linear_wgrad_adam(0, one, one, 32, 8, 40, 1, 1.0, one, one, one, N, one, 1e-3, 0.9, 0.999, 1e-8, 1.0, st),  # K % 64
+        lambda: lib.dsr_linear_wgrad_adam(0, N, N, 32, 8, 64, 1, 1.0, N, N, N, N, adam_args(None), st),
+        lambda: lib.dsr_linear_wgrad_adam(0, one, one, 32, 8, 40, 1, 1.0, one, one, one, N, adam_args(one), st),  # K % 64
         lambda: lib.dsr_dense2_fwd(N, N, N, 4, 8, N, st),
         lambda: lib.dsr_dense2_bwd(0, N, N, N, N, 4, 8, 32, 0.2, N, N, N, N, N, st),
         lambda: lib.dsr_maxpool2_fwd(0, N, N, 1, 4, 4, 8, st),
@@ -175,6 +177,52 @@ def test_bad_arguments_return_codes_not_crashes(so):
     assert lib.dsr_conv_stats_rows(N) < 0 and lib.dsr_conv_fwd_affine_supported(N) == 0
     assert lib.dsr_conv_kernel_name(N, 0, N) == b"invalid"
     assert lib.dsr_ssim_blocks(3, 8, 32) == 0 and lib.dsr_ssim_blocks(3, 42, 18) == 3 * 4 * 1
+
+
+def test_adam_argument_block_is_checked_alike_by_every_launcher(so):
+    """dsr_adam_args: a null block, a null step counter, and a block, step counter, hyper, loss_scale or found_inf at an address
+    no 4-byte word lives at are DSR_E_ARG for the per-tensor, the multi-tensor and the fused dense launch, in every mode.  The
+    multi-tensor launch refuses count <= 0, a null table entry, a misaligned or a zero-element tensor in the plain mode as in
+    the others; the per-tensor launch a misaligned tensor or shadow.  Well-formed blocks pass these checks: the same calls
+    with K % 64 != 0 get DSR_E_UNSUPPORTED, which is tested after the block.  Nothing is launched."""
+    L = importlib.import_module(PKG + "._lib")
+    lib = L.lib()
+    N, st = None, None
+    a = ctypes.c_void_p(64)                   # never dereferenced: validation fails first
+    ptrs = (ctypes.c_void_p * 2)(64, 128)
+    holes = (ctypes.c_void_p * 2)(64, None)
+    oddp = (ctypes.c_void_p * 2)(64, 130)
+    sizes = (ctypes.c_size_t * 2)(400, 600)
+    zeros = (ctypes.c_size_t * 2)(400, 0)
+    launchers = (lambda blk: lib.dsr_pw_adam(a, a, a, a, 16, N, blk, st),
+                 lambda blk: lib.dsr_pw_adam_multi(2, ptrs, ptrs, ptrs, ptrs, sizes, blk, st),
+                 lambda blk: lib.dsr_linear_wgrad_adam(0, a, a, 32, 8, 64, 1, 1.0, a, a, a, N, blk, st))
+    modes = ({}, {"loss_scale": 64, "found_inf": 64}, {"hyper": 64}, {"hyper": 64, "loss_scale": 64, "found_inf": 64})
+    good = adam_args(64)
+    skewed = ctypes.cast(ctypes.addressof((ctypes.c_char * 128)()) | 2, ctypes.POINTER(L.AdamArgs))   # refused before it is read
+    for launch in launchers:
+        bad = [N, skewed]
+        for mode in modes:
+            bad += [adam_args(None, **mode), adam_args(66, **mode)]
+            bad += [adam_args(64, **{**mode, word: 66}) for word in ("hyper", "loss_scale", "found_inf")]
+        for i, blk in enumerate(bad):
+            assert launch(blk) == -1, i
+            assert lib.dsr_last_error(), i
+    for mode in modes:
+        blk = adam_args(64, **mode)
+        for call in (lambda: lib.dsr_pw_adam_multi(0, ptrs, ptrs, ptrs, ptrs, sizes, blk, st),
+                     lambda: lib.dsr_pw_adam_multi(-1, ptrs, ptrs, ptrs, ptrs, sizes, blk, st),
+                     lambda: lib.dsr_pw_adam_multi(2, ptrs, ptrs, ptrs, ptrs, zeros, blk, st),
+                     lambda: lib.dsr_pw_adam_multi(2, ptrs, holes, ptrs, ptrs, sizes, blk, st),
+                     lambda: lib.dsr_pw_adam_multi(2, ptrs, ptrs, oddp, ptrs, sizes, blk, st),
+                     lambda: lib.dsr_pw_adam_multi(2, ptrs, ptrs, ptrs, N, sizes, blk, st),
+                     lambda: lib.dsr_pw_adam(a, a, a, a, 0, N, blk, st),
+                     lambda: lib.dsr_pw_adam(a, a, ctypes.c_void_p(66), a, 16, N, blk, st),
+                     lambda: lib.dsr_pw_adam(a, a, a, a, 16, ctypes.c_void_p(65), blk, st)):
+            assert call() == -1
+        assert lib.dsr_linear_wgrad_adam(0, a, a, 32, 8, 40, 1, 1.0, a, a, a, N, blk, st) == -4      # the block itself passed
+    big = (ctypes.c_size_t * 2)(400, 1 << 32)
+    assert lib.dsr_pw_adam_multi(2, ptrs, ptrs, ptrs, ptrs, big, good, st) == -4                    # 32-bit element indices
 
 
 def test_entry_point_without_return_does_not_compile(tmp_path):

@@ -1,4 +1,5 @@
-"""GPU: the device-side dynamic loss scaler (optim.DynamicLossScaler, the dsr_amp_* / *_amp kernels of csrc/pointwise.hip).
+"""GPU: the device-side dynamic loss scaler (optim.DynamicLossScaler, the dsr_amp_* kernels of csrc/pointwise.hip and the Adam
+entry points with loss_scale / found_inf in their dsr_adam_args).
 
 The yardstick is torch's own scaler on the device: torch.amp.GradScaler beside torch.optim.Adam and the two ops under it
 (torch._amp_foreach_non_finite_check_and_unscale_, torch._amp_update_scale_).  Scale, growth counter, overflow flag and the
@@ -12,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from adam_args import adam_args
 from oracle import dip, downsampler, filler, gan
 
 pytestmark = pytest.mark.gpu
@@ -149,30 +151,32 @@ def _equal(a, b):
 @pytest.mark.parametrize("multi", [False, True])
 @pytest.mark.parametrize("S", [1.0, 1024.0, 65536.0])
 def test_predicated_adam_bit_for_bit(dev, S, multi):
-    """found_inf = 0: p, m, v, the bf16 shadow and the step counter after the _amp kernels (+ dsr_pw_incr_unless) equal those
-    after the existing kernels with grad_scale = 1/S (+ dsr_pw_incr), three steps in a row.  found_inf = 1: nothing moves, NaN
-    gradients included.  (The multi-tensor launch has no shadow; its shadow buffers stay zero on both sides.)"""
+    """found_inf = 0: p, m, v, the bf16 shadow and the step counter after the Adam launches in the scaler's mode of dsr_adam_args
+    (loss_scale, found_inf; dsr_pw_incr with found_inf) equal those after the plain mode with grad_scale = 1/S (dsr_pw_incr
+    without), three steps in a row.  found_inf = 1: nothing moves, NaN gradients included.  (The multi-tensor launch has no
+    shadow; its shadow buffers stay zero on both sides.)"""
     L = P("_lib")
     lib, st = L.lib(), stream()
     a, b = _adam_state(dev, 3), _adam_state(dev, 3)
     scale = torch.full((1,), S, device=dev)
     found = torch.zeros(1, device=dev)
-    for it in range(3):
-        gs = _grads(dev, 100 + it, S)
-        L.check(lib.dsr_pw_incr(ptr(a["step"]), st))
-        L.check(lib.dsr_pw_incr_unless(ptr(b["step"]), ptr(found), st))
+    plain = adam_args(a["step"], *ADAM, grad_scale=1.0 / S)
+    amp = adam_args(b["step"], *ADAM, loss_scale=scale, found_inf=found)
+
+    def adam(s, gs, args):
         if multi:
-            k, pp, ns = table(a["p"])
-            L.check(lib.dsr_pw_adam_multi(k, pp, table(gs)[1], table(a["m"])[1], table(a["v"])[1], ns, *ADAM, ptr(a["step"]),
-                                          1.0 / S, st))
-            L.check(lib.dsr_pw_adam_multi_amp(k, table(b["p"])[1], table(gs)[1], table(b["m"])[1], table(b["v"])[1], ns, *ADAM,
-                                              ptr(b["step"]), ptr(scale), ptr(found), st))
+            k, pp, ns = table(s["p"])
+            L.check(lib.dsr_pw_adam_multi(k, pp, table(gs)[1], table(s["m"])[1], table(s["v"])[1], ns, args, st))
         else:
             for i, g in enumerate(gs):
-                L.check(lib.dsr_pw_adam(ptr(a["p"][i]), ptr(g), ptr(a["m"][i]), ptr(a["v"][i]), g.numel(), *ADAM,
-                                        ptr(a["step"]), 1.0 / S, ptr(a["sh"][i]), st))
-                L.check(lib.dsr_pw_adam_amp(ptr(b["p"][i]), ptr(g), ptr(b["m"][i]), ptr(b["v"][i]), g.numel(), *ADAM,
-                                            ptr(b["step"]), ptr(scale), ptr(found), ptr(b["sh"][i]), st))
+                L.check(lib.dsr_pw_adam(ptr(s["p"][i]), ptr(g), ptr(s["m"][i]), ptr(s["v"][i]), g.numel(), ptr(s["sh"][i]), args, st))
+
+    for it in range(3):
+        gs = _grads(dev, 100 + it, S)
+        L.check(lib.dsr_pw_incr(ptr(a["step"]), None, st))
+        L.check(lib.dsr_pw_incr(ptr(b["step"]), ptr(found), st))
+        adam(a, gs, plain)
+        adam(b, gs, amp)
         assert _equal(_snapshot(a), _snapshot(b)), (S, multi, it)
     assert b["step"].item() == 3 and found.item() == 0.0
     before = _snapshot(b)
@@ -182,15 +186,8 @@ def test_predicated_adam_bit_for_bit(dev, S, multi):
         if poison is not None:
             for g in gs:
                 g[g.numel() // 2] = poison
-        L.check(lib.dsr_pw_incr_unless(ptr(b["step"]), ptr(found), st))
-        if multi:
-            k, pp, ns = table(b["p"])
-            L.check(lib.dsr_pw_adam_multi_amp(k, pp, table(gs)[1], table(b["m"])[1], table(b["v"])[1], ns, *ADAM, ptr(b["step"]),
-                                              ptr(scale), ptr(found), st))
-        else:
-            for i, g in enumerate(gs):
-                L.check(lib.dsr_pw_adam_amp(ptr(b["p"][i]), ptr(g), ptr(b["m"][i]), ptr(b["v"][i]), g.numel(), *ADAM,
-                                            ptr(b["step"]), ptr(scale), ptr(found), ptr(b["sh"][i]), st))
+        L.check(lib.dsr_pw_incr(ptr(b["step"]), ptr(found), st))
+        adam(b, gs, amp)
         assert _equal(before, _snapshot(b)), (S, multi, poison)
     assert found.item() == 1.0 and scale.item() == S
 
@@ -467,8 +464,11 @@ def test_dip_dynamic_step_replays_in_a_graph(dev):
     assert skipped_flags[1] and not skipped_flags[-1], skipped_flags     # the transition happens among the replays
     first_taken = skipped_flags.index(False)
     assert names[1] == names[first_taken] == names[-1]
-    assert "dsr_amp_check" in names[1] and "dsr_amp_update" in names[1] and "dsr_pw_incr_unless" in names[1]
-    assert "dsr_pw_adam_multi_amp" in names[1] and "dsr_pw_incr" not in names[1]
+    assert "dsr_amp_check" in names[1] and "dsr_amp_update" in names[1] and "dsr_pw_adam_multi" in names[1]
+    # the counter is the predicated one: one launch per step, and it stood still through the skipped iterations
+    assert all(n.count("dsr_pw_incr") == 1 for n in names)
+    taken = eager_sc.counts()[0]
+    assert eager.opt.step_t.item() == taken == iters - sum(skipped_flags) < iters
 
     sc = O.DynamicLossScaler(init_scale=start, growth_interval=10 ** 9)
     run = _dip(dev, sc)[0]

@@ -1,5 +1,5 @@
 """GPU: device-side gradient-norm clipping and the tensor learning rate of optim.FusedAdam (dsr_clip_sumsq,
-dsr_linear_factor_gram, dsr_clip_finalize and the *_hyper Adam kernels).
+dsr_linear_factor_gram, dsr_clip_finalize and the Adam entry points with dsr_adam_args.hyper set).
 
 The reference project has neither clipping nor a schedule; the yardstick is torch itself: torch.nn.utils.clip_grad_norm_
 followed by torch.optim.Adam, modelled in float64 by tests/clip_ref.py (which tests/test_host_clip.py checks against torch).
@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import clip_ref
+from adam_args import adam_args
 from oracle import dip, downsampler, filler, gan
 
 pytestmark = pytest.mark.gpu
@@ -314,10 +315,10 @@ def test_identity_cases_are_bit_equal(dev):
         assert all(n == want for n in names), names[0]
         huge, hn, _ = _run_plain(dev, w0, grads, mm, lr=3e-3, max_grad_norm=1e30)
         assert all_same(huge, base)                          # a bound never reached: the coefficient is exactly 1
-        assert hn[0] == ["dsr_pw_incr", "dsr_clip_sumsq", "dsr_clip_finalize"] + ["dsr_pw_adam_hyper"] * n_big + ["dsr_pw_adam_multi_hyper"]
+        assert hn[0] == ["dsr_pw_incr", "dsr_clip_sumsq", "dsr_clip_finalize"] + ["dsr_pw_adam"] * n_big + ["dsr_pw_adam_multi"]
         tl, tn, opt = _run_plain(dev, w0, grads, mm, lr=torch.tensor(3e-3, device=dev))
         assert all_same(tl, base)                            # a tensor lr holding the fp32 value of the float
-        assert tn[0] == ["dsr_pw_incr", "dsr_clip_finalize"] + ["dsr_pw_adam_hyper"] * n_big + ["dsr_pw_adam_multi_hyper"]
+        assert tn[0] == ["dsr_pw_incr", "dsr_clip_finalize"] + ["dsr_pw_adam"] * n_big + ["dsr_pw_adam_multi"]
         both, _, _ = _run_plain(dev, w0, grads, mm, lr=torch.tensor(3e-3), max_grad_norm=1e30)
         assert all_same(both, base)
         clipped, _, _ = _run_plain(dev, w0, grads, mm, lr=3e-3, max_grad_norm=1.0)
@@ -514,8 +515,9 @@ def test_bad_arguments_return_codes(dev):
     h16 = torch.zeros(64 * 64, dtype=torch.bfloat16, device=dev)
     N, st = None, stream()
     k, ptrs, ns = table([t, t])
-    ad = (0.9, 0.999, 1e-8)
     off = C.c_void_p(t.data_ptr() + 2)
+    # the device-hyper mode of dsr_adam_args; a null hyper selects the plain mode, so the refused block has a misaligned one
+    hy = lambda **kw: adam_args(**{**dict(step=t, hyper=t), **kw})
     calls = [
         lambda: lib.dsr_clip_sumsq(0, ptrs, ns, ptr(t), 64, st),
         lambda: lib.dsr_clip_sumsq(k, N, ns, ptr(t), 64, st),
@@ -525,21 +527,21 @@ def test_bad_arguments_return_codes(dev):
         lambda: lib.dsr_clip_finalize(ptr(t), 2, N, 0, 1.0, N, 1.0, N, 1e-3, N, N, N, st),
         lambda: lib.dsr_clip_finalize(N, 2, N, 0, 1.0, N, 1.0, N, 1e-3, N, N, ptr(t), st),
         lambda: lib.dsr_clip_finalize(off, 2, N, 0, 1.0, N, 1.0, N, 1e-3, N, N, ptr(t), st),
-        lambda: lib.dsr_pw_adam_hyper(ptr(t), ptr(t), ptr(t), ptr(t), 0, ptr(t), *ad, ptr(t), 1.0, N, N, N, st),
-        lambda: lib.dsr_pw_adam_hyper(ptr(t), ptr(t), ptr(t), ptr(t), 64, N, *ad, ptr(t), 1.0, N, N, N, st),
-        lambda: lib.dsr_pw_adam_hyper(ptr(t), off, ptr(t), ptr(t), 16, ptr(t), *ad, ptr(t), 1.0, N, N, N, st),
-        lambda: lib.dsr_pw_adam_multi_hyper(0, ptrs, ptrs, ptrs, ptrs, ns, ptr(t), *ad, ptr(t), 1.0, N, N, st),
-        lambda: lib.dsr_pw_adam_multi_hyper(k, ptrs, N, ptrs, ptrs, ns, ptr(t), *ad, ptr(t), 1.0, N, N, st),
-        lambda: lib.dsr_pw_adam_multi_hyper(k, ptrs, ptrs, ptrs, ptrs, ns, N, *ad, ptr(t), 1.0, N, N, st),
+        lambda: lib.dsr_pw_adam(ptr(t), ptr(t), ptr(t), ptr(t), 0, N, hy(), st),
+        lambda: lib.dsr_pw_adam(ptr(t), ptr(t), ptr(t), ptr(t), 64, N, hy(hyper=off), st),
+        lambda: lib.dsr_pw_adam(ptr(t), off, ptr(t), ptr(t), 16, N, hy(), st),
+        lambda: lib.dsr_pw_adam_multi(0, ptrs, ptrs, ptrs, ptrs, ns, hy(), st),
+        lambda: lib.dsr_pw_adam_multi(k, ptrs, N, ptrs, ptrs, ns, hy(), st),
+        lambda: lib.dsr_pw_adam_multi(k, ptrs, ptrs, ptrs, ptrs, ns, hy(hyper=off), st),
         lambda: lib.dsr_linear_factor_gram(0, N, ptr(h16), 32, 8, 64, 1, 1.0, ptr(t), 256, st),
         lambda: lib.dsr_linear_factor_gram(0, ptr(h16), ptr(h16), 48, 8, 64, 1, 1.0, ptr(t), 256, st),
         lambda: lib.dsr_linear_factor_gram(0, ptr(h16), ptr(h16), 32, 8, 64, 1, 1.0, ptr(t), 256, st),      # short workspace
         lambda: lib.dsr_linear_factor_gram(0, ptr(h16), ptr(h16), 64, 8, 64, 9, 1.0, ptr(t), 256, st),
         lambda: lib.dsr_linear_factor_gram(0, off, ptr(h16), 32, 8, 64, 1, 1.0, ptr(t), 256, st),
-        lambda: lib.dsr_linear_wgrad_adam_hyper(0, ptr(h16), ptr(h16), 16, 8, 64, 1, 1.0, ptr(t), ptr(t), ptr(t), N, ptr(t), ptr(t), *ad, 1.0, N, N, st),
-        lambda: lib.dsr_linear_wgrad_adam_hyper(0, ptr(h16), ptr(h16), 32, 8, 64, 1, 1.0, ptr(t), ptr(t), ptr(t), N, ptr(t), N, *ad, 1.0, N, N, st),
-        lambda: lib.dsr_linear_wgrad_adam_hyper(0, ptr(h16), ptr(h16), 32, 8, 40, 1, 1.0, ptr(t), ptr(t), ptr(t), N, ptr(t), ptr(t), *ad, 1.0, N, N, st),
-        lambda: lib.dsr_linear_wgrad_adam_hyper(0, ptr(h16), ptr(h16), 32, 8, 64, 1, 1.0, off, ptr(t), ptr(t), N, ptr(t), ptr(t), *ad, 1.0, N, N, st),
+        lambda: lib.dsr_linear_wgrad_adam(0, ptr(h16), ptr(h16), 16, 8, 64, 1, 1.0, ptr(t), ptr(t), ptr(t), N, hy(), st),
+        lambda: lib.dsr_linear_wgrad_adam(0, ptr(h16), ptr(h16), 32, 8, 64, 1, 1.0, ptr(t), ptr(t), ptr(t), N, hy(hyper=off), st),
+        lambda: lib.dsr_linear_wgrad_adam(0, ptr(h16), ptr(h16), 32, 8, 40, 1, 1.0, ptr(t), ptr(t), ptr(t), N, hy(), st),
+        lambda: lib.dsr_linear_wgrad_adam(0, ptr(h16), ptr(h16), 32, 8, 64, 1, 1.0, off, ptr(t), ptr(t), N, hy(), st),
     ]
     for i, call in enumerate(calls):
         assert call() < 0, i

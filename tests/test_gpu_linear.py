@@ -17,6 +17,7 @@ import torch
 
 import clip_ref
 import linear_ref as R
+from adam_args import adam_args
 from canaries import Canaries
 
 pytestmark = pytest.mark.gpu
@@ -226,7 +227,7 @@ def test_linear_wgrad_exact(dev, dtype, Bp):
                 same_bits(got, want, f"wgrad Bp {Bp} {(O, K)} dtype {dtype} {what}")
 
 
-# ----------------------------------------------------------------------------- dsr_linear_wgrad_adam / _hyper
+# ----------------------------------------------------------------------------- dsr_linear_wgrad_adam, every mode of dsr_adam_args
 class AdamRun:
     """One set of p / m / v / shadow buffers with three sentinel rows below row O, and the launches that update them."""
 
@@ -251,28 +252,24 @@ class AdamRun:
             assert self.k.can.untouched(t[self.O:]), what + ": a row o >= O was written"
 
 
+def _args(step, gs, hyper=None, loss_scale=None, found_inf=None):
+    """dsr_adam_args of the sweep: R.ADAM's constants, the mode given by which of the three device words are set."""
+    A = R.ADAM
+    return adam_args(step, A["lr"], A["b1"], A["b2"], A["eps"], gs, hyper, loss_scale, found_inf)
+
+
 def _two_launch(k, a, b, Bp, O, K, Rr, scale, run, step, gs, hyper=None, loss_scale=None, found_inf=None):
     g = k.out((O, K), torch.float32, "g", float("nan"))
     if Rr == 1 and scale == 1.0:
         k.call("linear_wgrad", k.dtype, ptr(a), ptr(b), ptr(g), Bp, O, K)
     else:
         k.call("linear_wgrad_gathered", k.dtype, ptr(a), ptr(b), ptr(g), Bp, O, K, Rr, scale)
-    A = R.ADAM
-    if hyper is None:
-        k.call("pw_adam", ptr(run.p), ptr(g), ptr(run.m), ptr(run.v), O * K, A["lr"], A["b1"], A["b2"], A["eps"], ptr(step), gs, ptr(run.sh))
-    else:
-        k.call("pw_adam_hyper", ptr(run.p), ptr(g), ptr(run.m), ptr(run.v), O * K, ptr(hyper), A["b1"], A["b2"], A["eps"], ptr(step), gs,
-               ptr(loss_scale), ptr(found_inf), ptr(run.sh))
+    k.call("pw_adam", ptr(run.p), ptr(g), ptr(run.m), ptr(run.v), O * K, ptr(run.sh), _args(step, gs, hyper, loss_scale, found_inf))
 
 
 def _fused(k, a, b, Bp, O, K, Rr, scale, run, step, gs, hyper=None, loss_scale=None, found_inf=None):
-    A = R.ADAM
-    if hyper is None:
-        k.call("linear_wgrad_adam", k.dtype, ptr(a), ptr(b), Bp, O, K, Rr, scale, ptr(run.p), ptr(run.m), ptr(run.v), ptr(run.sh),
-               ptr(step), A["lr"], A["b1"], A["b2"], A["eps"], gs)
-    else:
-        k.call("linear_wgrad_adam_hyper", k.dtype, ptr(a), ptr(b), Bp, O, K, Rr, scale, ptr(run.p), ptr(run.m), ptr(run.v),
-               ptr(run.sh), ptr(step), ptr(hyper), A["b1"], A["b2"], A["eps"], gs, ptr(loss_scale), ptr(found_inf))
+    k.call("linear_wgrad_adam", k.dtype, ptr(a), ptr(b), Bp, O, K, Rr, scale, ptr(run.p), ptr(run.m), ptr(run.v), ptr(run.sh),
+           _args(step, gs, hyper, loss_scale, found_inf))
 
 
 def _kpb(monkeypatch, kpb):
@@ -338,8 +335,8 @@ def test_wgrad_adam_equals_two_launches_and_float64(dev, dtype, Bp, monkeypatch)
 @pytest.mark.parametrize("Bp", R.WG_BP)
 @pytest.mark.parametrize("dtype", DT)
 def test_wgrad_adam_hyper_write_discipline(dev, dtype, Bp, monkeypatch):
-    """dsr_linear_wgrad_adam_hyper at every case of wa_cases(), with and without the shadow: hyper[1] = 1 gives the bits of the
-    non-hyper form; hyper[1] = 0.5 the bits of dsr_linear_wgrad(_gathered) + dsr_pw_adam_hyper; loss_scale = 4 on gradients
+    """dsr_linear_wgrad_adam with the hyper block at every case of wa_cases(), with and without the shadow: hyper[1] = 1 gives the
+    bits of the plain mode; hyper[1] = 0.5 the bits of dsr_linear_wgrad(_gathered) + dsr_pw_adam in that mode; loss_scale = 4 on gradients
     times 4 the bits of the unscaled run (a power of two: exact); found_inf = 1 leaves p, m, v and the shadow bit-identical;
     rows o >= O keep the sentinel throughout."""
     A = R.ADAM
@@ -353,7 +350,7 @@ def test_wgrad_adam_hyper_write_discipline(dev, dtype, Bp, monkeypatch):
         h1 = k.hold(torch.tensor([A["lr"], 1.0], dtype=torch.float32))
         h5 = k.hold(torch.tensor([A["lr"], 0.5], dtype=torch.float32))
         four, one, zero = (k.hold(torch.tensor([v], dtype=torch.float32)) for v in (4.0, 1.0, 0.0))
-        what = f"wgrad_adam_hyper dtype {dtype} Bp {Bp} kpb {kpb} R {Rr} {(O, K)} step {t} grad_scale {gs}"
+        what = f"wgrad_adam with hyper dtype {dtype} Bp {Bp} kpb {kpb} R {Rr} {(O, K)} step {t} grad_scale {gs}"
         for shadow in (True, False):
             plain, hy1, hy5, two5, ls4, ls0, inf = (AdamRun(k, O, K, shadow) for _ in range(7))
             _fused(k, a, b, Bp, O, K, Rr, scale, plain, step, gs)
@@ -375,6 +372,142 @@ def test_wgrad_adam_hyper_write_discipline(dev, dtype, Bp, monkeypatch):
                 same_bits(f, f0, f"{what}: {name} written although found_inf is set")
             assert not torch.equal(bits(hy5.p), bits(plain.p)), what + ": the clipping coefficient changed nothing"
             k.fresh()
+
+
+def _smallest_wa_cases():
+    """The two smallest (O, K) of wa_cases() (O = 1: not a multiple of the 64-row tile), with their R, step, grad_scale, kpb."""
+    return sorted(R.wa_cases(), key=lambda c: c[1] * c[2])[:2]
+
+
+@pytest.mark.parametrize("Bp", R.WG_BP)
+@pytest.mark.parametrize("dtype", DT)
+def test_wgrad_adam_scaler_without_hyper_block(dev, dtype, Bp, monkeypatch):
+    """The one mode of dsr_adam_args without an ancestor on the dense launch: loss_scale and found_inf set, hyper NULL.
+    loss_scale = 4, found_inf = 0 on gradients built 4 x too large is BIT-EQUAL in p, m, v and the shadow to the plain mode with
+    grad_scale = 0.25 on the same inputs (1 / 4 is exact); found_inf = 1 with NaN in both factors leaves all four tensors and the
+    sentinel rows below row O bit-identical.  With and without the shadow."""
+    for Rr, O, K, t, gs, kpb in _smallest_wa_cases():
+        _kpb(monkeypatch, kpb)
+        scale = R.WA_SCALE[Rr]
+        k = Calls(dev, dtype)
+        dyT, xT = R.wgrad_case(Bp, O, K, Rr)
+        a4, b = k.up16(dyT * 4.0), k.up16(xT)
+        nan_a, nan_b = (k.hold(torch.full_like(t16, float("nan"))) for t16 in (a4, b))
+        step = k.hold(torch.tensor([t], dtype=torch.int32))
+        four, one, zero = (k.hold(torch.tensor([v], dtype=torch.float32)) for v in (4.0, 1.0, 0.0))
+        what = f"wgrad_adam scaler-only dtype {dtype} Bp {Bp} kpb {kpb} R {Rr} {(O, K)} step {t}"
+        for shadow in (True, False):
+            plain, amp, inf = (AdamRun(k, O, K, shadow) for _ in range(3))
+            _fused(k, a4, b, Bp, O, K, Rr, scale, plain, step, 0.25)
+            _fused(k, a4, b, Bp, O, K, Rr, scale, amp, step, 1.0, None, four, zero)
+            before = inf.snapshot()
+            _fused(k, nan_a, nan_b, Bp, O, K, Rr, scale, inf, step, 1.0, None, four, one)
+            k.can.check()
+            for run in (plain, amp, inf):
+                run.rows_below_untouched(what)
+            for name, x, y, f, f0 in zip("pmvs", plain.state(), amp.state(), inf.state(), before):
+                same_bits(y, x, f"{what}: {name}, loss_scale 4 against the plain mode with grad_scale 0.25")
+                same_bits(f, f0, f"{what}: {name} written although found_inf is set")
+            assert not torch.equal(bits(plain.p), bits(before[0])), what + ": the plain run moved nothing"
+            k.fresh()
+
+
+def _scaler_modes(dev):
+    """(hyper, loss_scale, found_inf): the scaler alone, and the scaler with a hyper block."""
+    four, zero = (torch.tensor([v], dtype=torch.float32, device=dev) for v in (4.0, 0.0))
+    h5 = torch.tensor([R.ADAM["lr"], 0.5], dtype=torch.float32, device=dev)
+    return ((None, four, zero), (h5, four, None))
+
+
+@pytest.mark.parametrize("Bp", R.WG_BP)
+@pytest.mark.parametrize("dtype", DT)
+def test_grad_scale_is_ignored_under_a_scaler(dev, dtype, Bp, monkeypatch):
+    """loss_scale = 4 with grad_scale = 123 gives the bits of loss_scale = 4 with grad_scale = 1, with and without the hyper
+    block, on the dense launch: the two smallest cases, with and without the shadow."""
+    modes = _scaler_modes(dev)
+    for Rr, O, K, t, gs, kpb in _smallest_wa_cases():
+        _kpb(monkeypatch, kpb)
+        scale = R.WA_SCALE[Rr]
+        k = Calls(dev, dtype)
+        dyT, xT = R.wgrad_case(Bp, O, K, Rr)
+        a, b = k.up16(dyT), k.up16(xT)
+        step = k.hold(torch.tensor([t], dtype=torch.int32))
+        what = f"grad_scale under a scaler dtype {dtype} Bp {Bp} R {Rr} {(O, K)}"
+        for shadow in (True, False):
+            for mode in modes:
+                r1, r123 = AdamRun(k, O, K, shadow), AdamRun(k, O, K, shadow)
+                before = r1.snapshot()
+                _fused(k, a, b, Bp, O, K, Rr, scale, r1, step, 1.0, *mode)
+                _fused(k, a, b, Bp, O, K, Rr, scale, r123, step, 123.0, *mode)
+                k.can.check()
+                for name, x, y in zip("pmvs", r1.state(), r123.state()):
+                    same_bits(y, x, f"{what}: {name}, dense launch, hyper {mode[0] is not None}")
+                assert not torch.equal(bits(r1.p), bits(before[0])), what
+            k.fresh()
+
+
+def test_grad_scale_is_ignored_under_a_scaler_pointwise(dev):
+    """The same on the per-tensor and the multi-tensor launch, over 3 ragged tensors of 1, 4097 and 1027 (= 3 mod 4) elements."""
+    modes = _scaler_modes(dev)
+    k = Calls(dev)
+    step = k.hold(torch.tensor([3], dtype=torch.int32))
+    gen = torch.Generator().manual_seed(77)
+    sizes = (1, 4097, 1027)
+    gs = [k.hold(torch.randn(n, generator=gen)) for n in sizes]
+    for mode in modes:
+        state = {}
+        for launch in ("one", "multi"):
+            for grad_scale in (1.0, 123.0):
+                gen.manual_seed(78)
+                ps, ms, vs = ([k.out((n,), torch.float32, w) for n in sizes] for w in "pmv")
+                for p_, m_, v_ in zip(ps, ms, vs):
+                    p_.copy_(torch.randn(p_.numel(), generator=gen))
+                    m_.copy_(0.1 * torch.randn(p_.numel(), generator=gen))
+                    v_.copy_(0.5 + torch.rand(p_.numel(), generator=gen))
+                p0 = [p_.clone() for p_ in ps]
+                blk = _args(step, grad_scale, *mode)
+                if launch == "one":
+                    for p_, g_, m_, v_ in zip(ps, gs, ms, vs):
+                        k.call("pw_adam", ptr(p_), ptr(g_), ptr(m_), ptr(v_), p_.numel(), None, blk)
+                else:
+                    tab = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+                    k.call("pw_adam_multi", len(sizes), tab(ps), tab(gs), tab(ms), tab(vs), (C.c_size_t * len(sizes))(*sizes), blk)
+                k.can.check()
+                assert all(not torch.equal(bits(x), bits(y)) for x, y in zip(ps, p0)), launch
+                state[launch, grad_scale] = ps + ms + vs
+            for x, y in zip(state[launch, 1.0], state[launch, 123.0]):
+                same_bits(y, x, f"grad_scale under a scaler: {launch} launch, hyper {mode[0] is not None}")
+
+
+@pytest.mark.parametrize("mode", ["scaler", "clip"])
+def test_empty_parameter_is_a_no_op_in_every_mode(dev, mode):
+    """optim.FusedAdam over [p0 of 0 elements, p1 of 5 elements], each with a gradient, takes three steps under a
+    DynamicLossScaler and under max_grad_norm = 1.0 without raising, and leaves p1 bit-equal to the same run without p0: an empty
+    parameter is a no-op in every mode."""
+    O = P("optim")
+    gen = torch.Generator().manual_seed(11)
+    w1 = torch.randn(5, generator=gen)
+    grads = [torch.randn(5, generator=gen) * 3.0 for _ in range(3)]            # norm > 1: the clipping coefficient bites
+
+    def run(with_empty):
+        p1 = w1.clone().to(dev).requires_grad_(True)
+        ps = ([torch.zeros(0, device=dev, requires_grad=True)] if with_empty else []) + [p1]
+        opt = O.FusedAdam(ps, lr=1e-2, max_grad_norm=1.0 if mode == "clip" else None)
+        scaler = O.DynamicLossScaler(init_scale=4.0) if mode == "scaler" else None
+        for g in grads:
+            for p in ps:
+                p.grad = torch.zeros(0, device=dev) if p.numel() == 0 else (g * (4.0 if scaler else 1.0)).to(dev)
+            if scaler:
+                scaler.step(opt)
+                scaler.update()
+            else:
+                opt.step()
+        assert opt.step_t.item() == 3
+        return p1.detach()
+
+    alone, beside = run(False), run(True)
+    assert not torch.equal(alone.cpu(), w1)
+    same_bits(beside, alone, f"p1 beside an empty parameter, {mode}")
 
 
 # ----------------------------------------------------------------------------- dsr_linear_factor_gram

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import clip_ref
+from adam_args import adam_args
 
 PKG = "deep-super-resolution_amd"
 
@@ -23,8 +24,8 @@ def so():
     return P("_build").build()
 
 
-LAUNCHING = ("dsr_clip_sumsq", "dsr_clip_finalize", "dsr_pw_adam_hyper", "dsr_pw_adam_multi_hyper", "dsr_linear_factor_gram",
-             "dsr_linear_wgrad_adam_hyper")
+LAUNCHING = ("dsr_clip_sumsq", "dsr_clip_finalize", "dsr_pw_adam", "dsr_pw_adam_multi", "dsr_linear_factor_gram",
+             "dsr_linear_wgrad_adam")
 QUERIES = ("dsr_clip_sumsq_partials", "dsr_linear_factor_gram_workspace", "dsr_linear_factor_gram_dots")
 
 
@@ -37,7 +38,7 @@ def test_clip_symbols_declared_and_bound(so):
         assert len(L.SIGNATURES[name][1]) == decl[name], name
         assert hasattr(ctypes.CDLL(so), name)
         assert (name in L._NO_LAUNCH) == (name in QUERIES), name
-    assert L.ABI_VERSION == 7 and L.lib().dsr_abi_version() == 7
+    assert L.ABI_VERSION == 8 and L.lib().dsr_abi_version() == 8
 
 
 def test_constructor_validation():
@@ -91,7 +92,8 @@ def test_new_entry_points_reject_bad_arguments(so):
     holes = (ctypes.c_void_p * 2)(64, None)
     sizes = (ctypes.c_size_t * 2)(400, 600)
     zeros = (ctypes.c_size_t * 2)(400, 0)
-    ad = (0.9, 0.999, 1e-8)
+    # the device-hyper mode of the Adam entry points: hyper set, the scaler's words null
+    hy = lambda **kw: adam_args(**{**dict(step=64, hyper=64), **kw})
     calls = [
         lambda: lib.dsr_clip_sumsq(2, N, sizes, one, 8, st),
         lambda: lib.dsr_clip_sumsq(2, ptrs, N, one, 8, st),
@@ -111,20 +113,20 @@ def test_new_entry_points_reject_bad_arguments(so):
         lambda: lib.dsr_clip_finalize(one, 1, ctypes.c_void_p(68), 4, 1.0, N, 1.0, N, 1e-3, one, one, one, st),   # fp64, 4 off
         lambda: lib.dsr_clip_finalize(one, 1, N, 0, 1.0, N, float("nan"), N, 1e-3, one, one, one, st),
         lambda: lib.dsr_clip_finalize(one, 1, N, 0, 1.0, N, 1.0, N, float("nan"), one, one, one, st),
-        lambda: lib.dsr_pw_adam_hyper(N, one, one, one, 16, one, *ad, one, 1.0, N, N, N, st),
-        lambda: lib.dsr_pw_adam_hyper(one, N, one, one, 16, one, *ad, one, 1.0, N, N, N, st),
-        lambda: lib.dsr_pw_adam_hyper(one, one, one, one, 16, N, *ad, one, 1.0, N, N, N, st),     # no hyper block
-        lambda: lib.dsr_pw_adam_hyper(one, one, one, one, 16, one, *ad, N, 1.0, N, N, N, st),     # no step counter
-        lambda: lib.dsr_pw_adam_hyper(one, one, one, one, 0, one, *ad, one, 1.0, N, N, N, st),
-        lambda: lib.dsr_pw_adam_hyper(one, odd, one, one, 16, one, *ad, one, 1.0, N, N, N, st),
-        lambda: lib.dsr_pw_adam_hyper(one, one, one, one, 16, odd, *ad, one, 1.0, N, N, N, st),
-        lambda: lib.dsr_pw_adam_multi_hyper(2, N, ptrs, ptrs, ptrs, sizes, one, *ad, one, 1.0, N, N, st),
-        lambda: lib.dsr_pw_adam_multi_hyper(2, ptrs, ptrs, ptrs, ptrs, N, one, *ad, one, 1.0, N, N, st),
-        lambda: lib.dsr_pw_adam_multi_hyper(0, ptrs, ptrs, ptrs, ptrs, sizes, one, *ad, one, 1.0, N, N, st),
-        lambda: lib.dsr_pw_adam_multi_hyper(2, ptrs, ptrs, ptrs, ptrs, sizes, N, *ad, one, 1.0, N, N, st),
-        lambda: lib.dsr_pw_adam_multi_hyper(2, ptrs, holes, ptrs, ptrs, sizes, one, *ad, one, 1.0, N, N, st),
-        lambda: lib.dsr_pw_adam_multi_hyper(2, ptrs, ptrs, ptrs, ptrs, zeros, one, *ad, one, 1.0, N, N, st),
-        lambda: lib.dsr_pw_adam_multi_hyper(2, ptrs, oddp, ptrs, ptrs, sizes, one, *ad, one, 1.0, N, N, st),
+        lambda: lib.dsr_pw_adam(N, one, one, one, 16, N, hy(), st),
+        lambda: lib.dsr_pw_adam(one, N, one, one, 16, N, hy(), st),
+        lambda: lib.dsr_pw_adam(one, one, one, one, 16, N, N, st),                # no argument block
+        lambda: lib.dsr_pw_adam(one, one, one, one, 16, N, hy(step=None), st),    # no step counter
+        lambda: lib.dsr_pw_adam(one, one, one, one, 0, N, hy(), st),
+        lambda: lib.dsr_pw_adam(one, odd, one, one, 16, N, hy(), st),
+        lambda: lib.dsr_pw_adam(one, one, one, one, 16, N, hy(hyper=66), st),
+        lambda: lib.dsr_pw_adam_multi(2, N, ptrs, ptrs, ptrs, sizes, hy(), st),
+        lambda: lib.dsr_pw_adam_multi(2, ptrs, ptrs, ptrs, ptrs, N, hy(), st),
+        lambda: lib.dsr_pw_adam_multi(0, ptrs, ptrs, ptrs, ptrs, sizes, hy(), st),
+        lambda: lib.dsr_pw_adam_multi(2, ptrs, ptrs, ptrs, ptrs, sizes, hy(hyper=66), st),
+        lambda: lib.dsr_pw_adam_multi(2, ptrs, holes, ptrs, ptrs, sizes, hy(), st),
+        lambda: lib.dsr_pw_adam_multi(2, ptrs, ptrs, ptrs, ptrs, zeros, hy(), st),
+        lambda: lib.dsr_pw_adam_multi(2, ptrs, oddp, ptrs, ptrs, sizes, hy(), st),
         lambda: lib.dsr_linear_factor_gram(0, N, one, 32, 8, 64, 1, 1.0, one, 1 << 20, st),
         lambda: lib.dsr_linear_factor_gram(0, one, N, 32, 8, 64, 1, 1.0, one, 1 << 20, st),
         lambda: lib.dsr_linear_factor_gram(0, one, one, 32, 8, 64, 1, 1.0, N, 1 << 20, st),
@@ -137,13 +139,13 @@ def test_new_entry_points_reject_bad_arguments(so):
         lambda: lib.dsr_linear_factor_gram(0, odd, one, 32, 8, 64, 1, 1.0, one, 1 << 20, st),     # alignment
         lambda: lib.dsr_linear_factor_gram(0, one, one, 32, 8, 64, 1, 1.0, ctypes.c_void_p(72), 1 << 20, st),
         lambda: lib.dsr_linear_factor_gram(0, one, one, 32, 8, 64, 1, 1.0, one, 64, st),          # short workspace
-        lambda: lib.dsr_linear_wgrad_adam_hyper(0, N, N, 32, 8, 64, 1, 1.0, N, N, N, N, N, N, *ad, 1.0, N, N, st),
-        lambda: lib.dsr_linear_wgrad_adam_hyper(0, one, one, 32, 8, 64, 1, 1.0, one, one, one, N, one, N, *ad, 1.0, N, N, st),
-        lambda: lib.dsr_linear_wgrad_adam_hyper(0, one, one, 32, 8, 40, 1, 1.0, one, one, one, N, one, one, *ad, 1.0, N, N, st),
-        lambda: lib.dsr_linear_wgrad_adam_hyper(0, one, one, 16, 8, 64, 1, 1.0, one, one, one, N, one, one, *ad, 1.0, N, N, st),
-        lambda: lib.dsr_linear_wgrad_adam_hyper(0, one, one, 32, 8, 64, 0, 1.0, one, one, one, N, one, one, *ad, 1.0, N, N, st),
-        lambda: lib.dsr_linear_wgrad_adam_hyper(0, one, one, 32, 8, 64, 1, 1.0, odd, one, one, N, one, one, *ad, 1.0, N, N, st),
-        lambda: lib.dsr_linear_wgrad_adam_hyper(0, one, one, 32, 8, 64, 1, 1.0, one, one, one, N, one, odd, *ad, 1.0, N, N, st),
+        lambda: lib.dsr_linear_wgrad_adam(0, N, N, 32, 8, 64, 1, 1.0, N, N, N, N, hy(step=None, hyper=None), st),
+        lambda: lib.dsr_linear_wgrad_adam(0, one, one, 32, 8, 64, 1, 1.0, one, one, one, N, N, st),      # no argument block
+        lambda: lib.dsr_linear_wgrad_adam(0, one, one, 32, 8, 40, 1, 1.0, one, one, one, N, hy(), st),
+        lambda: lib.dsr_linear_wgrad_adam(0, one, one, 16, 8, 64, 1, 1.0, one, one, one, N, hy(), st),
+        lambda: lib.dsr_linear_wgrad_adam(0, one, one, 32, 8, 64, 0, 1.0, one, one, one, N, hy(), st),
+        lambda: lib.dsr_linear_wgrad_adam(0, one, one, 32, 8, 64, 1, 1.0, odd, one, one, N, hy(), st),
+        lambda: lib.dsr_linear_wgrad_adam(0, one, one, 32, 8, 64, 1, 1.0, one, one, one, N, hy(hyper=66), st),
     ]
     for i, call in enumerate(calls):
         rc = call()

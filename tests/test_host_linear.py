@@ -17,6 +17,7 @@ import torch.nn.functional as TF
 
 import clip_ref
 import linear_ref as R
+from adam_args import adam_args
 
 PKG = "deep-super-resolution_amd"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -366,19 +367,20 @@ def test_argument_checks(lib):
     each_null(lib.dsr_linear_wgrad_gathered, wgg, (1, 2, 3))
     vary(lib.dsr_linear_wgrad_gathered, wgg, 4, (0, 48), E_UNSUPPORTED)
     vary(lib.dsr_linear_wgrad_gathered, wgg, 7, (0, -1), E_ARG)
-    wa = [BF, a, a, 32, 8, 64, 1, 1.0, a, a, a, N, a, 1e-3, 0.9, 0.999, 1e-8, 1.0, st]
-    wah = [BF, a, a, 32, 8, 64, 1, 1.0, a, a, a, N, a, a, 0.9, 0.999, 1e-8, 1.0, N, N, st]
-    for fn, args, nulls in ((lib.dsr_linear_wgrad_adam, wa, (1, 2, 8, 9, 10, 12)), (lib.dsr_linear_wgrad_adam_hyper, wah, (1, 2, 8, 9, 10, 12, 13))):
-        each_null(fn, args, nulls)
-        vary(fn, args, 3, (0, 48), E_UNSUPPORTED)
-        vary(fn, args, 5, (32, 72, 100), E_UNSUPPORTED)
-        vary(fn, args, 5, (0,), E_ARG)
-        vary(fn, args, 6, (0, -2), E_ARG)
+    fn = lib.dsr_linear_wgrad_adam
+    for mode in ({}, {"hyper": a}):                                  # the plain mode of dsr_adam_args and the device-hyper one
+        wa = [BF, a, a, 32, 8, 64, 1, 1.0, a, a, a, N, adam_args(a, **mode), st]
+        each_null(fn, wa, (1, 2, 8, 9, 10, 12))                      # slot 12: the argument block
+        vary(fn, wa, 3, (0, 48), E_UNSUPPORTED)
+        vary(fn, wa, 5, (32, 72, 100), E_UNSUPPORTED)
+        vary(fn, wa, 5, (0,), E_ARG)
+        vary(fn, wa, 6, (0, -2), E_ARG)
         for slot in (1, 2, 8, 9, 10):                                # 16-byte accesses
-            vary(fn, args, slot, (off(4), off(8)), E_ARG)
-        vary(fn, args, 11, (off(2), off(4)), E_ARG)                  # the shadow: 8-byte stores
-        vary(fn, args, 12, (off(2),), E_ARG)
-    vary(lib.dsr_linear_wgrad_adam_hyper, wah, 13, (off(2),), E_ARG)
+            vary(fn, wa, slot, (off(4), off(8)), E_ARG)
+        vary(fn, wa, 11, (off(2), off(4)), E_ARG)                    # the shadow: 8-byte stores
+        vary(fn, wa, 12, (adam_args(None, **mode), adam_args(off(2), **mode)), E_ARG)       # the step counter
+        for word in ("hyper", "loss_scale", "found_inf"):
+            vary(fn, wa, 12, (adam_args(a, **{**mode, word: off(2)}),), E_ARG)
     gr = [BF, a, a, 32, 8, 64, 1, 1.0, a, 1 << 22, st]
     each_null(lib.dsr_linear_factor_gram, gr, (1, 2, 8))
     vary(lib.dsr_linear_factor_gram, gr, 3, (16, 48), E_UNSUPPORTED)

@@ -39,15 +39,15 @@ def main():
     dw = torch.empty(o, k, device=dev)
     n = o * k
     t_w = timeit(lambda: L.check(lib.dsr_linear_wgrad(L.BF16, dyt.data_ptr(), xt.data_ptr(), dw.data_ptr(), bp, o, k, st)))
-    t_a = timeit(lambda: L.check(lib.dsr_pw_adam(p.data_ptr(), dw.data_ptr(), m.data_ptr(), v.data_ptr(), n, 1e-4, 0.9, 0.999,
-                                                 1e-8, step.data_ptr(), 1.0, sh.data_ptr(), st)))
+    args = L.AdamArgs(step.data_ptr(), 1e-4, 0.9, 0.999, 1e-8, 1.0, None, None, None)      # the plain mode of dsr_adam_args
+    t_a = timeit(lambda: L.check(lib.dsr_pw_adam(p.data_ptr(), dw.data_ptr(), m.data_ptr(), v.data_ptr(), n, sh.data_ptr(),
+                                                 args, st)))
     print(f"dsr_linear_wgrad      {t_w*1e3:7.3f} ms  {4*n/t_w/1e12:5.2f} TB/s (4 B/param written)")
     print(f"dsr_pw_adam           {t_a*1e3:7.3f} ms  {30*n/t_a/1e12:5.2f} TB/s (16 read + 14 written B/param)")
     for kpb in os.environ.get("KPB", "1,2,4,8").split(","):
         os.environ["DSR_WGRAD_ADAM_KPB"] = kpb
         t_f = timeit(lambda: L.check(lib.dsr_linear_wgrad_adam(L.BF16, dyt.data_ptr(), xt.data_ptr(), bp, o, k, 1, 1.0, p.data_ptr(),
-                                                               m.data_ptr(), v.data_ptr(), sh.data_ptr(), step.data_ptr(), 1e-4, 0.9,
-                                                               0.999, 1e-8, 1.0, st)))
+                                                               m.data_ptr(), v.data_ptr(), sh.data_ptr(), args, st)))
         print(f"dsr_linear_wgrad_adam {t_f*1e3:7.3f} ms  {26*n/t_f/1e12:5.2f} TB/s (12 read + 14 written B/param)  kpb={kpb}   "
               f"two launches / fused = {(t_w+t_a)/t_f:.2f}")
 

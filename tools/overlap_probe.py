@@ -37,8 +37,8 @@ def main():
     nel = 268 * 1024 * 1024
     p, g, m, v = (torch.rand(nel, device=dev) for _ in range(4))
     step = torch.ones(1, dtype=torch.int32, device=dev)
-    adam = lambda st: L.check(lib.dsr_pw_adam(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), nel, 1e-4, 0.9, 0.999, 1e-8,
-                                              step.data_ptr(), 1.0, None, st))
+    args = L.AdamArgs(step.data_ptr(), 1e-4, 0.9, 0.999, 1e-8, 1.0, None, None, None)      # the plain mode of dsr_adam_args
+    adam = lambda st: L.check(lib.dsr_pw_adam(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), nel, None, args, st))
     y_bn = (torch.rand(32 * 256 * 256, 64, device=dev) - 0.5).to(torch.bfloat16)
     o_bn = torch.empty_like(y_bn)
     sc = torch.rand(64, device=dev)
