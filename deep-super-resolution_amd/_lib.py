@@ -16,6 +16,7 @@ F32 = 2                  # the luma entry points (csrc/luma.hip) also read fp32 
 ACT_NONE, ACT_LEAKY, ACT_PRELU, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_ELU = range(7)
 PAD_ZERO, PAD_REFLECT, PAD_REPLICATE = range(3)
 FEAT_L1, FEAT_MSE = 0, 1  # modes of the feature-loss taps (csrc/featloss.hip)
+GAN_VANILLA, GAN_LSGAN, GAN_HINGE = range(3)   # kinds of dsr_gan_loss (csrc/pointwise.hip)
 
 
 class ConvDesc(C.Structure):
@@ -219,6 +220,14 @@ SIGNATURES = {
     "dsr_conv_rdb_supported": (_I, [C.POINTER(RdbConv)]),
     "dsr_conv_rdb_fwd": (_I, [C.POINTER(RdbConv), _P]),
     "dsr_scale_add16": (_I, [_I, _P, _F, _P, _P, _Z, _P]),
+    "dsr_spectral_norm_workspace": (_Z, [_I, C.POINTER(_I), C.POINTER(_I)]),
+    "dsr_spectral_norm_bwd_workspace": (_Z, [_I, C.POINTER(_I), C.POINTER(_I)]),
+    "dsr_spectral_norm_fwd": (_I, [_I, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(_I),
+                                   C.POINTER(_I), _I, _F, _P, C.POINTER(C.c_void_p), _P, _Z, _P]),
+    "dsr_spectral_norm_bwd": (_I, [_I, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                   C.POINTER(_I), C.POINTER(_I), _P, C.POINTER(C.c_void_p), _P, _Z, _P]),
+    "dsr_gan_loss_blocks": (_I, [_Z]),
+    "dsr_gan_loss": (_I, [_P, _Z, _I, _I, _I, _P, _P, _P, _P]),
 }
 
 _lib = None
@@ -233,7 +242,8 @@ _NO_LAUNCH = ("dsr_last_error", "dsr_abi_version", "dsr_conv_dgrad_ps_supported"
               "dsr_ssim_img_blocks", "dsr_psnr_blocks", "dsr_lbfgs_workspace", "dsr_lbfgs_vector_floats", "dsr_clip_sumsq_partials",
               "dsr_linear_factor_gram_workspace", "dsr_linear_factor_gram_dots", "dsr_downsample_dense_wgrad_workspace",
               "dsr_msssim_min_size", "dsr_msssim_pyramid_floats", "dsr_ssim_cs_img_blocks", "dsr_msssim_bwd_blocks", "dsr_luma_blocks",
-              "dsr_featloss_blocks", "dsr_jpeg_workspace", "dsr_conv_rdb_supported")
+              "dsr_featloss_blocks", "dsr_jpeg_workspace", "dsr_conv_rdb_supported", "dsr_spectral_norm_workspace",
+              "dsr_spectral_norm_bwd_workspace", "dsr_gan_loss_blocks")
 
 
 class _Lib:

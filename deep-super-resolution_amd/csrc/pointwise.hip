@@ -1058,6 +1058,57 @@ __global__ void bce_const_kernel(const float* __restrict__ p, int n, float targe
   }
 }
 
+// GAN loss on logits x[n] against a constant label (BasicSR's GANLoss, the three pointwise kinds), mean over all elements.
+//   vanilla  BCEWithLogits: softplus(z) = max(z, 0) + log1p(exp(-|z|)), z = -x (real) | x (fake)
+//   lsgan    (x - t)^2, t = 1 | 0
+//   hinge    discriminator: relu(1 + z); generator: -x
+// One pass: grad[i] = d(mean)/dx[i] and one partial per block, summed in double (a thread adds its strided elements in index
+// order, the block folds in a fixed order); gan_loss_fold_kernel adds the partials in block order.  No atomics.
+__device__ __forceinline__ float gan_sigmoid(float z) {      // no overflow on either side
+  if (z >= 0.f) return 1.f / (1.f + expf(-z));
+  const float e = expf(z);
+  return e / (1.f + e);
+}
+__global__ __launch_bounds__(256) void gan_loss_kernel(const float* __restrict__ x, size_t n, int kind, int real, int is_disc,
+                                                       float* __restrict__ grad, double* __restrict__ partial) {
+  __shared__ double red[4];
+  const float fn = (float)n;
+  const float sgn = real ? -1.f : 1.f;
+  double s = 0.0;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float xi = x[i];
+    float val, g;
+    if (kind == DSR_GAN_VANILLA) {
+      const float z = sgn * xi;
+      val = fmaxf(z, 0.f) + log1pf(expf(-fabsf(z)));
+      g = sgn * gan_sigmoid(z);
+    } else if (kind == DSR_GAN_LSGAN) {
+      const float d = xi - (real ? 1.f : 0.f);
+      val = d * d;
+      g = 2.f * d;
+    } else if (is_disc) {
+      const float h = 1.f + sgn * xi;
+      val = fmaxf(h, 0.f);
+      g = h > 0.f ? sgn : 0.f;
+    } else {
+      val = -xi;
+      g = -1.f;
+    }
+    s += (double)val;
+    grad[i] = g / fn;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+__global__ void gan_loss_fold_kernel(const double* __restrict__ partial, int blocks, size_t n, float* __restrict__ loss) {
+  double s = 0.0;
+  for (int b = 0; b < blocks; ++b) s += partial[b];
+  loss[0] = (float)(s / (double)n);
+}
+
 // ------------------------------------------------------------------ Adam (torch.optim.Adam defaults, no weight decay)
 // step counter lives on the device so the launch is graph-capturable.  Where lr and the gradient multiplier come from
 // -- the host, the dynamic loss scaler's words, the hyper block of the clipping pass -- is dsr_adam_args (dsr_common.h
@@ -1521,6 +1572,19 @@ extern "C" int dsr_pw_bce_const(const float* p, int n, float target, float* loss
   DSR_REQUIRE(p && loss && n > 0, "bce_const: null pointer or empty");
   hipLaunchKernelGGL(bce_const_kernel, dim3(1), dim3(256), 0, st, p, n, target, loss, grad, accumulate);
   return dsr_launch_status("dsr_pw_bce_const");
+}
+extern "C" int dsr_gan_loss_blocks(size_t n) { return n ? (int)(n + 1023 < 1024 * (size_t)1024 ? (n + 1023) / 1024 : 1024) : 0; }
+extern "C" int dsr_gan_loss(const float* x, size_t n, int kind, int target_is_real, int is_disc, float* grad, double* partial,
+                            float* loss, hipStream_t st) {
+  DSR_REQUIRE(x && grad && partial && loss && n > 0, "gan_loss: null pointer or empty");
+  DSR_REQUIRE(kind == DSR_GAN_VANILLA || kind == DSR_GAN_LSGAN || kind == DSR_GAN_HINGE, "gan_loss: unknown kind %d", kind);
+  DSR_REQUIRE((((uintptr_t)x | (uintptr_t)grad | (uintptr_t)loss) & 3) == 0 && ((uintptr_t)partial & 7) == 0,
+              "gan_loss: misaligned pointer");
+  const int blocks = dsr_gan_loss_blocks(n);
+  hipLaunchKernelGGL(gan_loss_kernel, dim3(blocks), dim3(256), 0, st, x, n, kind, target_is_real ? 1 : 0, is_disc ? 1 : 0, grad,
+                     partial);
+  hipLaunchKernelGGL(gan_loss_fold_kernel, dim3(1), dim3(1), 0, st, partial, blocks, n, loss);
+  return dsr_launch_status("dsr_gan_loss");
 }
 extern "C" int dsr_pw_adam(float* p, const float* g, float* m, float* v, size_t n, void* shadow_bf16,
                            const dsr_adam_args* args, hipStream_t st) {

@@ -101,12 +101,14 @@ def check_prelu_slopes(module):
 
 def packed_weights(weight, desc, dtype):
     """16-bit [T][Cout_p][Cin_p] (forward) and [T][Cin_p][Cout_p] (dgrad) images of an OIHW fp32 weight."""
-    key = (id(weight), dtype, tuple(weight.shape))
-    ver = _version(weight)
-    hit = _pack_cache.get(key)
-    # ids (and allocator addresses) are recycled once a tensor dies: a hit must be THIS tensor object
-    if hit is not None and hit[0] == ver and hit[3]() is weight:
-        return hit[1], hit[2]
+    derived = getattr(weight, "_dsr_derived", False)
+    if not derived:
+        key = (id(weight), dtype, tuple(weight.shape))
+        ver = _version(weight)
+        hit = _pack_cache.get(key)
+        # ids (and allocator addresses) are recycled once a tensor dies: a hit must be THIS tensor object
+        if hit is not None and hit[0] == ver and hit[3]() is weight:
+            return hit[1], hit[2]
     lib = _lib.lib()
     nf = lib.dsr_conv_packed_elems(C.byref(desc), 0)
     nd = lib.dsr_conv_packed_elems(C.byref(desc), 1)
@@ -116,6 +118,10 @@ def packed_weights(weight, desc, dtype):
     if not w.is_contiguous():
         w = w.contiguous()
     check(lib.dsr_conv_pack_weight(C.byref(desc), _ptr(w), _ptr(wf), _ptr(wd), _stream()))
+    if derived:
+        # a weight computed anew by every forward (SpectralNormWeight): its images belong to that one call -- they never enter
+        # the cache, which would otherwise pin them until 4096 dead entries have piled up
+        return wf, wd
     _pack_cache[key] = (ver, wf, wd, weakref.ref(weight))
     if len(_pack_cache) > 4096:          # dead entries of short-lived tensors (tests); live models are far smaller
         for k in [k for k, v in _pack_cache.items() if v[3]() is None]:
@@ -424,8 +430,9 @@ def _conv_backward(desc, x, dy, wd, need_dx, need_dw, weight_shape, weight=None,
                                                                      _stream())))
     if addend is not None:
         dx = addend if dx is None else dx + addend
-    if (need_dw and _wgrad_batch is not None and weight is not None and weight.grad is None
-            and _wgrad_batch.batchable(weight)                                # (an earlier use returned a real gradient / was launched early)
+    if (need_dw and _wgrad_batch is not None and weight is not None and weight.is_leaf and weight.grad is None
+            # (a derived weight -- SpectralNormWeight's -- has a backward node that reads its gradient at once: no placeholder)
+            and _wgrad_batch.batchable(weight)                               # (an earlier use returned a real gradient / was launched early)
             and not getattr(weight, "_post_accumulate_grad_hooks", None)      # (a hook would read the gradient at once)
             and lib.dsr_conv_wgrad_batchable(C.byref(desc))):
         return dx, _wgrad_batch.add(weight, desc, x, dy, weight_shape)
@@ -988,6 +995,144 @@ class BCEConst(torch.autograd.Function):
 
 def bce_const(p, target):
     return BCEConst.apply(p, target)
+
+
+_GAN_KINDS = {"vanilla": _lib.GAN_VANILLA, "lsgan": _lib.GAN_LSGAN, "hinge": _lib.GAN_HINGE}
+
+
+class GanLoss(torch.autograd.Function):
+    """BasicSR's GANLoss on logits against a constant label, mean over all elements (dsr_gan_loss): one pass writes the
+    per-element gradient and the block partials, a fixed-order fold makes the mean; nothing is read on the host."""
+
+    @staticmethod
+    def forward(ctx, logits, target_is_real, kind, is_disc):
+        _need_gpu(logits)
+        x = logits.contiguous().float()
+        n = x.numel()
+        if n == 0:
+            raise ValueError("gan_loss: empty logits")
+        lib = _lib.lib()
+        part = torch.empty(lib.dsr_gan_loss_blocks(n), dtype=torch.float64, device=x.device)
+        grad = torch.empty_like(x)
+        loss = torch.empty(1, dtype=torch.float32, device=x.device)
+        check(lib.dsr_gan_loss(_ptr(x), n, kind, int(bool(target_is_real)), int(bool(is_disc)), _ptr(grad), _ptr(part),
+                               _ptr(loss), _stream()))
+        ctx.save_for_backward(grad)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return axpby(grad, None, 1.0, 0.0, g), None, None, None
+
+
+def gan_loss(logits, target_is_real, kind="vanilla", is_disc=False):
+    """GANLoss(gan_type=kind)(logits, target_is_real, is_disc) of BasicSR, unweighted: 'vanilla' = BCEWithLogits against a
+    constant 1 / 0, 'lsgan' = (x - t)^2, 'hinge' = relu(1 -+ x) for the discriminator and -x for the generator."""
+    if kind not in _GAN_KINDS:
+        raise ValueError(f"gan_loss: kind must be one of {sorted(_GAN_KINDS)}, got {kind!r}")
+    return GanLoss.apply(logits, target_is_real, _GAN_KINDS[kind], is_disc)
+
+
+# ----------------------------------------------------------------------------- spectral normalisation
+SN_EPS = 1e-12           # torch.nn.utils.spectral_norm's default
+_sn_pending = {}         # id(weight_orig) -> results of a group launch that SpectralNormWeight.forward picks up
+
+
+def _sn_check(weight, u, v):
+    _need_gpu(weight)
+    cout = weight.shape[0]
+    k = weight.numel() // max(cout, 1)
+    for name, t, n in (("weight_orig", weight, cout * k), ("u", u, cout), ("v", v, k)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n or t.device != weight.device or n == 0:
+            raise ValueError(f"spectral norm: {name} must be a contiguous fp32 tensor of {n} elements beside the weight, "
+                             f"got {tuple(t.shape)} {t.dtype} on {t.device}")
+    return cout, k
+
+
+def _sn_forward(weights, us, vs, training):
+    """W_sn (a new tensor per weight) and sigma ([len] fp32) of a list of layers, 64 per launch group; in train mode u and v
+    advance in place."""
+    lib = _lib.lib()
+    outs, sigmas = [], []
+    for i0 in range(0, len(weights), 64):
+        ws, uu, vv = weights[i0:i0 + 64], us[i0:i0 + 64], vs[i0:i0 + 64]
+        n = len(ws)
+        shapes = [_sn_check(w, u, v) for w, u, v in zip(ws, uu, vv)]
+        ci, ki = (C.c_int * n)(*[s[0] for s in shapes]), (C.c_int * n)(*[s[1] for s in shapes])
+        out = [torch.empty_like(w) for w in ws]
+        sigma = torch.empty(n, dtype=torch.float32, device=ws[0].device)
+        nbytes = lib.dsr_spectral_norm_workspace(n, ci, ki)
+        work = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=ws[0].device)
+        check(lib.dsr_spectral_norm_fwd(n, _lib.ptr_table(ws), _lib.ptr_table(uu), _lib.ptr_table(vv), ci, ki, int(bool(training)),
+                                        SN_EPS, _ptr(sigma), _lib.ptr_table(out), _ptr(work), nbytes, _stream()))
+        outs += out
+        sigmas += [sigma[j:j + 1] for j in range(n)]
+    return outs, sigmas
+
+
+class SpectralNormWeight(torch.autograd.Function):
+    """W_sn = weight_orig / sigma of torch.nn.utils.spectral_norm (one power iteration, eps 1e-12; csrc/spectral_norm.hip).
+    In train mode `u` and `v` advance in place; in eval mode they are only read.  The backward treats the iterated vectors
+    as constants, as torch does: dW = (G - <G, W_sn> u v^T) / sigma, on copies of u and v taken by this forward (a later
+    forward may move them on before this one's backward runs).  A frozen weight_orig has no backward node at all.  The
+    result is marked as a derived weight: its packed conv images are not cached (packed_weights) and its weight gradient
+    never joins a batched_wgrad group (_conv_backward)."""
+
+    @staticmethod
+    def forward(ctx, weight_orig, u, v, training):
+        pend = _sn_pending.pop(id(weight_orig), None)
+        need = ctx.needs_input_grad[0]
+        if pend is None:
+            w = weight_orig.detach()
+            (w_sn,), (sigma,) = _sn_forward([w], [u], [v], training)
+            us, vs = (u.clone(), v.clone()) if need else (None, None)
+        else:
+            w_sn, sigma, us, vs = pend
+        if need:
+            ctx.save_for_backward(w_sn, sigma, us, vs)
+        w_sn._dsr_derived = True
+        return w_sn
+
+    @staticmethod
+    def backward(ctx, g):
+        w_sn, sigma, u, v = ctx.saved_tensors
+        lib = _lib.lib()
+        g = g.contiguous().float()
+        cout = w_sn.shape[0]
+        ci, ki = (C.c_int * 1)(cout), (C.c_int * 1)(w_sn.numel() // cout)
+        dw = torch.empty_like(w_sn)
+        nbytes = lib.dsr_spectral_norm_bwd_workspace(1, ci, ki)
+        work = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=g.device)
+        check(lib.dsr_spectral_norm_bwd(1, _lib.ptr_table([g]), _lib.ptr_table([w_sn]), _lib.ptr_table([u]), _lib.ptr_table([v]),
+                                        ci, ki, _ptr(sigma), _lib.ptr_table([dw]), _ptr(work), nbytes, _stream()))
+        return dw, None, None, None
+
+
+def spectral_norm_weights(weights, us, vs, training):
+    """[SpectralNormWeight(w, u, v, training) for every layer], with the iterations of all layers in ONE launch group
+    (dsr_spectral_norm_fwd takes 64 layers a call) instead of one group per layer."""
+    weights, us, vs = list(weights), list(us), list(vs)
+    outs, sigmas = _sn_forward([w.detach() for w in weights], us, vs, training)
+    saved = {}
+    need = [i for i, w in enumerate(weights) if w.requires_grad and torch.is_grad_enabled()]
+    if need:
+        # this forward's vectors for the backward passes: one copy launch for all of them
+        flat = torch.cat([us[i].reshape(-1) for i in need] + [vs[i].reshape(-1) for i in need])
+        sizes = [us[i].numel() for i in need] + [vs[i].numel() for i in need]
+        parts = flat.split(sizes)
+        for j, i in enumerate(need):
+            saved[i] = (parts[j], parts[len(need) + j])
+    res = []
+    for i, w in enumerate(weights):
+        _sn_pending[id(w)] = (outs[i], sigmas[i]) + saved.get(i, (None, None))
+        try:
+            w_sn = SpectralNormWeight.apply(w, us[i], vs[i], training)
+        finally:
+            _sn_pending.pop(id(w), None)
+        w_sn._dsr_derived = True
+        res.append(w_sn)
+    return res
 
 
 class AddScalars(torch.autograd.Function):

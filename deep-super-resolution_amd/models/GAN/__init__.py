@@ -1,0 +1,1 @@
+from .unet_discriminator import UNetDiscriminatorSN  # noqa: F401

@@ -5,6 +5,7 @@ gen_lpips_step : the same step with the perceptual fine-tuning loss l1_weight * 
 gen_msssim_step : the same step with the structural loss alpha * (1 - MS-SSIM(fake, hr)) + (1 - alpha) * L1.
 gen_perceptual_step : the same step with the content loss l1_weight * L1 + VggFeatureLoss(fake, hr) (ESRGAN / Real-ESRGAN).
 gan_step    : train_GAN.py:38-71 (do_epoch): D step, then G step with the detached adversarial term.
+realesrgan_step : the GAN stage of Real-ESRGAN (L1 + VGG features + a logits GAN loss whose gradient flows through D into G).
 dip_step    : DIP.py:47-95 closure + utils/DIP.py:33-40 Adam iteration.
 """
 import os
@@ -204,6 +205,58 @@ def gan_step(gen, disc, perceptual, opt_g, opt_d, lr_patches, hr_patches, sync_g
         adv.record_stream(main)
     loss_g = F.add_losses(content.detach(), adv)                  # :59 value (unweighted sum, utils/GAN.py:122)
     return loss_d, loss_g, fake_det
+
+
+def realesrgan_step(gen, disc, vggfeat, opt_g, opt_d, lq, gt, *, l1_weight=1.0, gan_weight=0.1, gan_type="vanilla", ema=None):
+    """One GAN-stage step of the Real-ESRGAN recipe (BasicSR RealESRGANModel.optimize_parameters without the USM variants:
+    `gt` is the target of all three terms).  Unlike gan_step, the adversarial gradient flows through D into G.
+
+    Generator half, D frozen (no weight gradient and no spectral-norm backward runs for it):
+        fake = gen(lq);  l_g = l1_weight * L1(fake, gt) + vggfeat(fake, gt) + gan_weight * gan_loss(disc(fake), real)
+    Discriminator half: gan_loss(disc(gt), real, is_disc) and gan_loss(disc(fake.detach()), fake, is_disc), each with a
+    backward of its own, then opt_d.step().
+
+    `disc`: a models.GAN.UNetDiscriminatorSN (any module of fp32 NCHW in, logits out) and is left in the mode it came in;
+    in train mode one step advances every u and v by three power iterations, as the published loop does.  Returns (l_pix,
+    l_percep, l_g_gan, l_d_real, l_d_fake, fake): the unweighted L1, the (weighted) content term, the unweighted three GAN
+    terms and the generator's output, as detached device tensors.  One stream, no host read: usable inside GraphedStep with a
+    FusedAdam for each optimiser."""
+    d_params = [p for p in disc.parameters()]
+    was = [p.requires_grad for p in d_params]
+    # --- generator
+    for p in d_params:
+        p.requires_grad_(False)
+    try:
+        opt_g.zero_grad()
+        fake = gen(lq)
+        l_pix = F.l1_loss(fake, gt)
+        l_percep = vggfeat(fake, gt)
+        l_g_gan = F.gan_loss(disc(fake), True, gan_type, is_disc=False)
+        l_g = F.add_losses(F.add_losses(F.scale_loss(l_pix, float(l1_weight)), l_percep), F.scale_loss(l_g_gan, float(gan_weight)))
+        with F.batched_wgrad():
+            l_g.backward()
+        opt_g.step()
+        if ema is not None:
+            ema.update()
+    finally:
+        for p, r in zip(d_params, was):
+            p.requires_grad_(r)
+    # --- discriminator
+    for p in d_params:
+        p.requires_grad_(True)
+    try:
+        opt_d.zero_grad()
+        l_d_real = F.gan_loss(disc(gt), True, gan_type, is_disc=True)
+        with F.batched_wgrad():
+            l_d_real.backward()
+        l_d_fake = F.gan_loss(disc(fake.detach()), False, gan_type, is_disc=True)
+        with F.batched_wgrad():
+            l_d_fake.backward()
+        opt_d.step()
+    finally:
+        for p, r in zip(d_params, was):
+            p.requires_grad_(r)
+    return l_pix.detach(), l_percep.detach(), l_g_gan.detach(), l_d_real.detach(), l_d_fake.detach(), fake.detach()
 
 
 class GraphedStep:

@@ -783,6 +783,42 @@ int dsr_conv_rdb_fwd(const dsr_rdb_conv* c, dsr_stream_t s);
 /* out = r16(fmaf(a, beta, b)) on nvec 16-byte vectors of 16-bit values; b may be NULL (out = r16(a * beta)); out may be a or b */
 int dsr_scale_add16(int dtype, const void* a, float beta, const void* b, void* out, size_t nvec, dsr_stream_t s);
 
+/* ------------------------------------------------------------------ spectral normalisation (spectral_norm.hip)
+ * torch.nn.utils.spectral_norm(conv) with n_power_iterations = 1 for up to 64 layers per call.  HOST tables of `count`
+ * entries: w[i] the fp32 weight viewed as [cout[i]][k[i]] row-major (k = Cin KH KW), u[i] [cout[i]], v[i] [k[i]], w_sn[i] the
+ * output of w[i]'s shape (another buffer than w[i]); sigma: DEVICE fp32 [count]; ws: DEVICE workspace, 16-byte aligned, of
+ * dsr_spectral_norm_workspace() bytes (0 for a bad shape table).
+ *   training != 0:  t = W^T u;  v = t / max(|t|, eps);  s = W v;  u = s / max(|s|, eps);  sigma = u . s;  u and v are rewritten
+ *   training == 0:  sigma = u . (W v); u and v are only read
+ *   W_sn = W / sigma (a true division per element).
+ * Four launches (two in eval mode) for the whole group, no host read, no atomics, every sum in a fixed order: the same state
+ * gives the same bits, and a captured call advances the iteration on every replay.
+ * dsr_spectral_norm_bwd: dw[i] = (g[i] - <g[i], w_sn[i]> u[i] v[i]^T) / sigma[i] with u, v, sigma, w_sn as that forward left
+ * them (torch treats u and v as constants); two launches; ws of dsr_spectral_norm_bwd_workspace() bytes.
+ * count outside 1..64, a null table / entry / sigma / ws, a cout or k below 1, a layer of 2^31 elements or more, a pointer off
+ * its alignment or a workspace that is too small return DSR_E_ARG before anything is launched. */
+size_t dsr_spectral_norm_workspace(int count, const int* cout, const int* k);
+size_t dsr_spectral_norm_bwd_workspace(int count, const int* cout, const int* k);
+int dsr_spectral_norm_fwd(int count, const float* const* w, float* const* u, float* const* v, const int* cout, const int* k,
+                          int training, float eps, float* sigma, float* const* w_sn, float* ws, size_t ws_bytes, dsr_stream_t s);
+int dsr_spectral_norm_bwd(int count, const float* const* g, const float* const* w_sn, const float* const* u,
+                          const float* const* v, const int* cout, const int* k, const float* sigma, float* const* dw, float* ws,
+                          size_t ws_bytes, dsr_stream_t s);
+
+/* ------------------------------------------------------------------ GAN loss on logits (pointwise.hip)
+ * BasicSR's GANLoss against a constant label, mean over the n fp32 logits x:
+ *   DSR_GAN_VANILLA  BCEWithLogits: softplus(z) = max(z, 0) + log1p(exp(-|z|)), z = -x (target_is_real) or x
+ *   DSR_GAN_LSGAN    (x - t)^2, t = 1 or 0
+ *   DSR_GAN_HINGE    is_disc: relu(1 + z); otherwise -x (the generator's form, whatever the label)
+ * loss[0] = the mean (elements added in double, in a fixed order, one rounding to fp32); grad[i] = d loss / d x[i].
+ * partial: dsr_gan_loss_blocks(n) doubles of scratch.  Two launches, no host read, no atomics. */
+#define DSR_GAN_VANILLA 0
+#define DSR_GAN_LSGAN 1
+#define DSR_GAN_HINGE 2
+int dsr_gan_loss_blocks(size_t n);
+int dsr_gan_loss(const float* x, size_t n, int kind, int target_is_real, int is_disc, float* grad, double* partial, float* loss,
+                 dsr_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

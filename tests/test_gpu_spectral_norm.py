@@ -1,0 +1,358 @@
+"""GPU: the spectral-norm launch group (csrc/spectral_norm.hip) against tests/spectral_ref.py (float64), through the C ABI
+with every buffer inside sentinel margins.
+
+1. an exact case (Hadamard rows): bit for bit whatever the summation order, forward and backward;
+2. float data: derived bounds, per shape and for a group of eight layers in one call;
+3. the sentinel margins (every launch here runs between them), also with every pointer 4 bytes off a 16-byte boundary;
+4. two runs from one state: the same bits;  5. eval mode leaves u and v alone;  6. graph replay = eager, bit for bit;
+7. W = 0: finishes, with torch's non-finite pattern."""
+import ctypes as C
+import importlib
+
+import pytest
+import torch
+import torch.nn as nn
+
+import spectral_ref as SR
+
+pytestmark = pytest.mark.gpu
+
+PKG = "deep-super-resolution_amd"
+MARGIN = 1024          # sentinel elements on each side of a raw buffer (4096 bytes: the payload keeps the allocation's alignment)
+SENTINEL = 7777.0
+EPS32 = 2.0 ** -24
+
+
+def P(sub):
+    return importlib.import_module(PKG + "." + sub)
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs the MI355X")
+    P("_lib").lib()
+    return torch.device("cuda:0")
+
+
+class Raw:
+    """fp32 device buffers inside sentinel-filled allocations (the idiom of tests/test_gpu_rrdb.py); `shift`: extra elements in
+    front of the payload, so that it starts 4 * shift bytes off the allocation's 16-byte alignment."""
+
+    def __init__(self, dev, shift=0):
+        self.dev, self.shift, self.flats = dev, shift, []
+
+    def put(self, t):
+        t = t.to(torch.float32).contiguous()
+        flat = torch.full((t.numel() + 2 * MARGIN + self.shift,), SENTINEL, dtype=torch.float32, device=self.dev)
+        lo = MARGIN + self.shift
+        flat[lo:lo + t.numel()] = t.reshape(-1).to(self.dev)
+        self.flats.append((flat, lo, t.numel()))
+        return flat[lo:lo + t.numel()].view(t.shape)
+
+    def empty(self, shape):
+        return self.put(torch.full(shape, float("nan")))
+
+    def check(self):
+        torch.cuda.synchronize()
+        for flat, lo, n in self.flats:
+            assert bool((flat[:lo] == SENTINEL).all()) and bool((flat[lo + n:] == SENTINEL).all()), "write outside a buffer"
+
+
+def _tables(layers):
+    n = len(layers)
+    couts = [w.shape[0] for w, _, _ in layers]
+    ks = [w.numel() // w.shape[0] for w, _, _ in layers]
+    return n, (C.c_int * n)(*couts), (C.c_int * n)(*ks)
+
+
+def run_fwd(dev, layers, training, shift=0):
+    """layers: [(W, u, v)] CPU tensors.  Returns ([(u, v, W_sn)] device views, sigma [n], the Raw that holds them)."""
+    L, F = P("_lib"), P("functional")
+    lib = L.lib()
+    raw = Raw(dev, shift)
+    n, ci, ki = _tables(layers)
+    ws = [raw.put(w) for w, _, _ in layers]
+    us = [raw.put(u) for _, u, _ in layers]
+    vs = [raw.put(v) for _, _, v in layers]
+    outs = [raw.empty(w.shape) for w, _, _ in layers]
+    sigma = raw.empty((n,))
+    nbytes = lib.dsr_spectral_norm_workspace(n, ci, ki)
+    assert nbytes > 0 and nbytes % 16 == 0
+    raw_work = Raw(dev)                                                  # (the workspace must be 16-byte aligned: no shift)
+    work = raw_work.put(torch.full((nbytes // 4,), float("nan")))
+    L.check(lib.dsr_spectral_norm_fwd(n, L.ptr_table(ws), L.ptr_table(us), L.ptr_table(vs), ci, ki, int(training), SR.EPS,
+                                      C.c_void_p(sigma.data_ptr()), L.ptr_table(outs), C.c_void_p(work.data_ptr()), nbytes,
+                                      F._stream()))
+    raw.check()
+    raw_work.check()
+    for w_dev, (w, _, _) in zip(ws, layers):
+        assert torch.equal(w_dev.cpu(), w.float()), "the weight was modified"
+    return list(zip(us, vs, outs)), sigma, raw
+
+
+def run_bwd(dev, items, shift=0):
+    """items: [(G, W_sn, u, v, sigma)] (sigma a float).  Returns [dW] device views."""
+    L, F = P("_lib"), P("functional")
+    lib = L.lib()
+    raw = Raw(dev, shift)
+    n, ci, ki = _tables([(g, None, None) for g, _, _, _, _ in items])
+    gs = [raw.put(g) for g, _, _, _, _ in items]
+    wsn = [raw.put(w) for _, w, _, _, _ in items]
+    us = [raw.put(u) for _, _, u, _, _ in items]
+    vs = [raw.put(v) for _, _, _, v, _ in items]
+    sigma = raw.put(torch.tensor([s for _, _, _, _, s in items]))
+    dws = [raw.empty(g.shape) for g, _, _, _, _ in items]
+    nbytes = lib.dsr_spectral_norm_bwd_workspace(n, ci, ki)
+    assert nbytes > 0 and nbytes % 16 == 0
+    raw_work = Raw(dev)
+    work = raw_work.put(torch.full((nbytes // 4,), float("nan")))
+    L.check(lib.dsr_spectral_norm_bwd(n, L.ptr_table(gs), L.ptr_table(wsn), L.ptr_table(us), L.ptr_table(vs), ci, ki,
+                                      C.c_void_p(sigma.data_ptr()), L.ptr_table(dws), C.c_void_p(work.data_ptr()), nbytes,
+                                      F._stream()))
+    raw.check()
+    raw_work.check()
+    return dws
+
+
+# ----------------------------------------------------------------------------- 1. exact
+@pytest.mark.parametrize("k", [0, 3, -2])
+def test_exact_hadamard(dev, k):
+    """W = 16 rows of the 256-column Sylvester Hadamard matrix times 2^k, u = e0: t = W^T u = +-2^k, |t| = 16 2^k, v = +-1/16,
+    s = W v = 16 2^k e0, u' = e0, sigma = 16 2^k, W_sn = +-1/16 -- every intermediate and every partial sum is a small integer
+    times a power of two, so any summation order gives these bits.  Backward on an integer G: <G, W_sn> is an integer / 16,
+    d u v^T a multiple of 1/256, the difference and the division by a power of two exact."""
+    rows = [37, 0, 5, 255, 128, 64, 77, 200, 13, 99, 1, 2, 3, 180, 254, 101]
+    H = SR.hadamard(256)[rows]
+    W = (H * 2.0 ** k).reshape(16, 16, 4, 4)
+    u = torch.zeros(16, dtype=torch.float64)
+    u[0] = 1.0
+    v = torch.full((256,), 0.123, dtype=torch.float64)          # (the train-mode forward does not read it)
+    (res,), sigma, _ = run_fwd(dev, [(W, u, v)], True)
+    ur, vr, sr, wr = SR.iterate(W, u, v)
+    assert torch.equal(vr, H[0] / 16) and torch.equal(ur, u) and float(sr) == 16 * 2.0 ** k and torch.equal(wr, H.reshape(W.shape) / 16)
+    assert torch.equal(res[0].double().cpu(), ur) and torch.equal(res[1].double().cpu(), vr)
+    assert float(sigma[0]) == float(sr) and torch.equal(res[2].double().cpu(), wr)
+    g = torch.Generator().manual_seed(k + 10)
+    G = torch.randint(-4, 5, W.shape, generator=g).double()
+    (dw,) = run_bwd(dev, [(G, wr, ur, vr, float(sr))])
+    want = SR.backward(G, wr, ur, vr, sr)
+    assert torch.equal(want.float().double(), want)
+    assert torch.equal(dw.double().cpu(), want)
+
+
+# ----------------------------------------------------------------------------- 2. float data
+def _block_sum_roundings(n):
+    """Roundings on a block's sum over n values: ceil(n / 256) multiply-adds per thread, 6 butterfly steps, 3 wave sums."""
+    return -(-n // 256) + 9
+
+
+def forward_bound(W, u):
+    """First-order a-priori bounds (|du'|, |dv'|, |dsigma|, |dW_sn|) of the train-mode forward as the kernels sum it, from
+    absolute values in float64 (e = 2^-24; the chain lengths are those of test_float_data's docstring)."""
+    Wm = SR.mat(W)
+    Cn, K = Wm.shape
+    aW, e = Wm.abs(), EPS32
+    u = u.double()
+    n_t = min(Cn, 32) + -(-Cn // 32) - 1            # t[k]: 32 multiply-adds, then the chunks' partials in order
+    n_v = 4 * -(-K // 4096) + 21                    # |t|^2: one block of 1024 threads (4 multiply-adds a turn, 6 + 15 adds)
+    n_s = -(-K // 64) + 6                           # s[r]: K / 64 multiply-adds per lane, 6 butterfly steps
+    t = Wm.t() @ u
+    dt = n_t * e * (aW.t() @ u.abs())
+    nt = t.norm()
+    dnt = dt.norm() + (n_v / 2 + 1) * e * nt       # (the square root halves the sum's relative error)
+    v = t / nt
+    dv = dt / nt + v.abs() * dnt / nt + e * v.abs()
+    s = Wm @ v
+    ds = aW @ dv + n_s * e * (aW @ v.abs())
+    ns = s.norm()
+    dns = ds.norm() + (_block_sum_roundings(Cn) / 2 + 1) * e * ns
+    un = s / ns
+    du = ds / ns + un.abs() * dns / ns + e * un.abs()
+    sigma = un @ s
+    dsig = un.abs() @ ds + du @ s.abs() + _block_sum_roundings(Cn) * e * (un.abs() @ s.abs())
+    dw = (Wm / sigma).abs() * (dsig / sigma.abs() + e)
+    return du, dv, dsig, dw.reshape(W.shape)
+
+
+def backward_bound(G, w_sn, u, v, sigma):
+    """|d dW| of (G - d u v^T) / sigma with d = <G, W_sn> summed as the kernels do: 16 products per thread, a block of 256,
+    then at most 512 partials over 256 threads -- fewer than 64 roundings on sum |G W_sn|."""
+    Gm, Wm, e = SR.mat(G), SR.mat(w_sn), EPS32
+    d = (Gm * Wm).sum()
+    uv = torch.outer(u.double().abs(), v.double().abs())
+    num = Gm - d * torch.outer(u.double(), v.double())
+    b = (e * num.abs() + (64 * e * (Gm.abs() * Wm.abs()).sum() + 3 * e * d.abs()) * uv) / abs(sigma) + e * (num / sigma).abs()
+    return b.reshape(G.shape)
+
+
+def _data(cout, k, kind, seed):
+    g = torch.Generator().manual_seed(seed)
+    if kind == "positive":
+        W = (torch.rand(cout, k, generator=g) + 0.5) * 0.05
+        u = torch.rand(cout, generator=g) + 0.5
+        v = torch.rand(k, generator=g) + 0.5
+    else:
+        W = torch.randn(cout, k, generator=g) * 0.05
+        u, v = torch.randn(cout, generator=g), torch.randn(k, generator=g)
+    return W.float(), (u / u.norm()).float(), (v / v.norm()).float()
+
+
+def _check_layer(tag, W, u, v, res, sigma, kind, dev_bwd=None):
+    """Forward of one layer against the yardstick; returns the observed errors relative to the max norm."""
+    ur, vr, sr, wr = SR.iterate(W, u, v)
+    du, dv, dsig, dw = forward_bound(W, u)
+    cout, k = SR.mat(W).shape
+    got = (res[0].double().cpu(), res[1].double().cpu(), sigma.double().cpu().reshape(()), res[2].double().cpu())
+    out = []
+    for name, g, r, b in zip("u v sigma W_sn".split(), got, (ur, vr, sr, wr), (du, dv, dsig, dw)):
+        err = float((g - r).abs().max())
+        half_ulp = EPS32 * float(r.abs().max())                   # the reference itself is compared after one fp32 rounding
+        bound = float(b.abs().max()) + half_ulp
+        unit = (cout + k) * EPS32 * float(r.abs().max())
+        out.append(f"{name} {err / unit:.3f} (c {bound / unit:.2f})")
+        assert err <= bound, (tag, name, err, bound)
+        if kind == "positive":
+            assert err <= 6 * unit, (tag, name, err, 6 * unit)
+    print(f"spectral norm {tag} [{cout}, {k}] {kind}: error / ((Cout + K) 2^-24 max|ref|): " + ", ".join(out))
+    return ur, vr, sr, wr
+
+
+SHAPES = [(8, 27), (64, 576), (128, 1024), (512, 4096)]
+GROUP = [(8, 27), (16, 128), (32, 256), (64, 512), (32, 576), (16, 288), (8, 144), (130, 52)]
+
+
+@pytest.mark.parametrize("kind", ["signed", "positive"])
+@pytest.mark.parametrize("cout,k", SHAPES)
+def test_float_data(dev, cout, k, kind):
+    """u', v', sigma, W_sn and dW against float64, max-norm errors, e = 2^-24.
+
+    The accumulation order actually used (roundings per sum): t[k] is 32 fused multiply-adds, then the ceil(Cout / 32)
+    partials added in order: n_t = min(Cout, 32) + ceil(Cout / 32) - 1 <= Cout; |t|^2 is summed by one block of 1024 threads,
+    4 multiply-adds per thread and turn, 6 butterfly steps, 15 wave sums: n_v = 4 ceil(K / 4096) + 21 <= K / 256 + 25; s[r] is
+    ceil(K / 64) multiply-adds per lane and a 6-step butterfly: n_s = ceil(K / 64) + 6; a 256-thread block's sum over n values
+    (|s|^2, sigma = u . s) is ceil(n / 256) multiply-adds per thread, 6 butterfly steps and 3 wave sums: n_b(n) = ceil(n / 256) +
+    9; the square root of a norm halves the sum's relative error and adds its own rounding.  forward_bound() carries exactly
+    these counts through the iteration with absolute values (|W|^T |u| for t, |W| |dv| + n_s e |W| |v| for s, ...); half an ulp
+    is added for the yardstick's own rounding to fp32.
+      * data without cancellation (W, u > 0: then t, v, s, u' > 0 too) turns every absolute-value sum into the value itself, and
+        the counts add up in relative terms:  v: Cout + (Cout + n_v / 2 + 1) + 1 <= 2 Cout + K/512 + 15;
+        s: v + K/64 + 7;  u': 2 s + n_b(Cout) / 2 + 2 = 4 Cout + K/256 + K/32 + Cout/512 + 51;
+        sigma: u' + s + n_b(Cout) <= 6.006 Cout + 0.053 K + 83 <= 6 (Cout + K) once K >= 14 + Cout / 990.  So
+            max|q - q64| <= c (Cout + K) 2^-24 max|q64|,  c = 6,   q in {u', v', sigma, W_sn}
+        which the 'positive' cases assert as it stands;
+      * signed data multiplies c by the cancellation ratios sum|terms| / |sum| of the same sums, which forward_bound()
+        evaluates from the data; the 'signed' cases (N(0, 0.05^2) weights, random unit vectors) are held to that, and
+        the c it amounts to is printed beside the observed error.
+    The backward is held to backward_bound() in both cases, from the forward's own fp32 outputs on both sides.
+
+    Observed on the MI355X, errors of u', v', sigma, W_sn in units of (Cout + K) 2^-24 max|ref| (and the c of forward_bound):
+        [8, 27]      signed   0.018 (4.78)  0.025 (1.15)  0.004 (8.37)   0.016 (8.40)    positive 0.047  0.060  0.058  0.072
+        [64, 576]    signed   0.002 (4.29)  0.004 (0.39)  0.001 (8.03)   0.002 (8.03)    positive 0.003  0.006  0.001  0.002
+        [128, 1024]  signed   0.001 (4.88)  0.002 (0.30)  <5e-4 (9.00)   0.001 (9.00)    positive 0.001  0.003  <5e-4  0.001
+        [512, 4096]  signed   <5e-4 (6.18)  0.001 (0.19)  <5e-4 (12.30)  0.001 (12.30)   positive 0.001  0.001  <5e-4  <5e-4
+    backward, max|dW - dW64| / max|dW64| (signed): 3.6e-8, 6.7e-8, 9.2e-8, 7.7e-8; the largest (error - bound) is -3.4e-10."""
+    W, u, v = _data(cout, k, kind, 100 * cout + k)
+    (res,), sigma, _ = run_fwd(dev, [(W, u, v)], True)
+    _check_layer("single", W, u, v, res, sigma[0], kind)
+    # backward, from the device's own forward outputs
+    g = torch.Generator().manual_seed(7)
+    G = (torch.rand(cout, k, generator=g) + 0.5 if kind == "positive" else torch.randn(cout, k, generator=g)).float()
+    u1, v1, w1, s1 = res[0].cpu(), res[1].cpu(), res[2].cpu(), float(sigma[0])
+    (dw,) = run_bwd(dev, [(G, w1, u1, v1, s1)])
+    want = SR.backward(G, w1, u1, v1, s1)
+    b = backward_bound(G, w1, u1, v1, s1) + EPS32 * want.abs()
+    err = (dw.double().cpu() - want).abs()
+    print(f"spectral norm backward [{cout}, {k}] {kind}: max error {float(err.max()):.3e}, max (error - bound) "
+          f"{float((err - b).max()):.3e}, max|dW| {float(want.abs().max()):.3e}")
+    assert float((err - b).max()) <= 0.0
+
+
+@pytest.mark.parametrize("shift", [0, 1])
+def test_group_of_eight(dev, shift):
+    """Eight layers of mixed sizes in one call (and, shift = 1, with every pointer 4 bytes off a 16-byte boundary: the
+    4-byte-access path on K % 4 == 0 too): each layer as in test_float_data, the same bits as that layer alone, margins."""
+    layers = [_data(c, k, "signed", 100 * c + k) for c, k in GROUP]
+    res, sigma, _ = run_fwd(dev, layers, True, shift)
+    items = []
+    g = torch.Generator().manual_seed(9)
+    for i, ((W, u, v), r) in enumerate(zip(layers, res)):
+        _check_layer(f"group[{i}] shift {shift}", W, u, v, r, sigma[i], "signed")
+        (alone,), sig1, _ = run_fwd(dev, [(W, u, v)], True, shift)
+        assert all(torch.equal(a, b) for a, b in zip(alone, r)) and torch.equal(sig1[0], sigma[i])
+        G = torch.randn(W.shape, generator=g).float()
+        items.append((G, r[2].cpu(), r[0].cpu(), r[1].cpu(), float(sigma[i])))
+    dws = run_bwd(dev, items, shift)
+    for it, dw in zip(items, dws):
+        want = SR.backward(*it)
+        b = backward_bound(*it) + EPS32 * want.abs()
+        assert float(((dw.double().cpu() - want).abs() - b).max()) <= 0.0
+        (alone,) = run_bwd(dev, [it], shift)
+        assert torch.equal(alone, dw)
+
+
+# ----------------------------------------------------------------------------- 4, 5. reproducibility, eval mode
+def test_two_runs_same_bits(dev):
+    layers = [_data(c, k, "signed", c + k) for c, k in [(512, 4096), (64, 576), (8, 27)]]
+    a, sa, _ = run_fwd(dev, layers, True)
+    b, sb, _ = run_fwd(dev, layers, True)
+    assert torch.equal(sa, sb)
+    assert all(torch.equal(x, y) for ra, rb in zip(a, b) for x, y in zip(ra, rb))
+    items = [(torch.randn(w.shape, generator=torch.Generator().manual_seed(1)).float(), r[2].cpu(), r[0].cpu(), r[1].cpu(), float(s))
+             for (w, _, _), r, s in zip(layers, a, sa)]
+    assert all(torch.equal(x, y) for x, y in zip(run_bwd(dev, items), run_bwd(dev, items)))
+
+
+@pytest.mark.parametrize("cout,k", [(8, 27), (64, 576)])
+def test_eval_mode_leaves_the_vectors(dev, cout, k):
+    W, u, v = _data(cout, k, "signed", 5)
+    (res,), sigma, _ = run_fwd(dev, [(W, u, v)], False)
+    assert torch.equal(res[0].cpu(), u) and torch.equal(res[1].cpu(), v)
+    sr, wr = SR.evaluate(W, u, v)
+    aW = SR.mat(W).abs()
+    ds = (-(-k // 64) + 6) * EPS32 * (aW @ v.double().abs())      # s = W v: n_s roundings (test_float_data)
+    dsig = float(u.double().abs() @ ds + _block_sum_roundings(cout) * EPS32 * (u.double().abs() @ (SR.mat(W) @ v.double()).abs()))
+    dsig += EPS32 * abs(float(sr))
+    assert abs(float(sigma[0]) - float(sr)) <= dsig
+    assert float((res[2].double().cpu() - wr).abs().max()) <= float(wr.abs().max()) * (dsig / abs(float(sr)) + 2 * EPS32)
+
+
+# ----------------------------------------------------------------------------- 6. graph replay
+def test_graph_replay_equals_eager(dev):
+    """Three replays of a captured launch group = three eager calls: every replay advances the iteration."""
+    F, S = P("functional"), P("steps")
+    layers = [_data(c, k, "signed", c) for c, k in [(64, 576), (8, 27), (128, 1024)]]
+
+    def state():
+        return ([w.to(dev) for w, _, _ in layers], [u.clone().to(dev) for _, u, _ in layers], [v.clone().to(dev) for _, _, v in layers])
+
+    ws, us, vs = state()
+    eager = []
+    for _ in range(3):
+        outs, sig = F._sn_forward(ws, us, vs, True)
+        eager.append(([o.clone() for o in outs], torch.cat(sig).clone(), [u.clone() for u in us], [v.clone() for v in vs]))
+    ws2, us2, vs2 = state()
+    graphed = S.GraphedStep(lambda: tuple(F._sn_forward(ws2, us2, vs2, True)[0]), warmup=0)
+    for i in range(3):
+        outs = graphed()
+        torch.cuda.synchronize()
+        assert all(torch.equal(a, b) for a, b in zip(outs, eager[i][0]))
+        assert all(torch.equal(a, b) for a, b in zip(us2, eager[i][2])) and all(torch.equal(a, b) for a, b in zip(vs2, eager[i][3]))
+    assert not torch.equal(eager[0][2][0], eager[2][2][0])          # (the iteration did move)
+
+
+# ----------------------------------------------------------------------------- 7. degenerate input
+def test_zero_weight_finishes_with_torch_pattern(dev):
+    conv = nn.utils.spectral_norm(nn.Conv2d(4, 8, 3, 1, 1, bias=False))
+    with torch.no_grad():
+        conv.weight_orig.zero_()
+    u, v = conv.weight_u.detach().clone(), conv.weight_v.detach().clone()
+    conv.train()
+    with torch.no_grad():
+        conv(torch.zeros(1, 4, 4, 4))
+    (res,), sigma, _ = run_fwd(dev, [(torch.zeros(8, 4, 3, 3), u, v)], True)
+    want_w = conv.weight.detach()
+    got_w = res[2].cpu()
+    assert torch.equal(torch.isnan(got_w), torch.isnan(want_w)) and torch.equal(torch.isinf(got_w), torch.isinf(want_w))
+    assert torch.equal(res[0].cpu(), conv.weight_u) and torch.equal(res[1].cpu(), conv.weight_v)     # all zero
+    assert float(sigma[0]) == 0.0
