@@ -228,6 +228,11 @@ SIGNATURES = {
                                    C.POINTER(_I), C.POINTER(_I), _P, C.POINTER(C.c_void_p), _P, _Z, _P]),
     "dsr_gan_loss_blocks": (_I, [_Z]),
     "dsr_gan_loss": (_I, [_P, _Z, _I, _I, _I, _P, _P, _P, _P]),
+    "dsr_filter2d_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "dsr_noise_gaussian_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "dsr_noise_poisson_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "dsr_usm_mask": (_I, [_P, _P, _F, _P, _Z, _P]),
+    "dsr_usm_combine": (_I, [_P, _P, _P, _F, _P, _Z, _P]),
 }
 
 _lib = None

@@ -207,9 +207,13 @@ def gan_step(gen, disc, perceptual, opt_g, opt_d, lr_patches, hr_patches, sync_g
     return loss_d, loss_g, fake_det
 
 
-def realesrgan_step(gen, disc, vggfeat, opt_g, opt_d, lq, gt, *, l1_weight=1.0, gan_weight=0.1, gan_type="vanilla", ema=None):
-    """One GAN-stage step of the Real-ESRGAN recipe (BasicSR RealESRGANModel.optimize_parameters without the USM variants:
-    `gt` is the target of all three terms).  Unlike gan_step, the adversarial gradient flows through D into G.
+def realesrgan_step(gen, disc, vggfeat, opt_g, opt_d, lq, gt, *, l1_weight=1.0, gan_weight=0.1, gan_type="vanilla", ema=None,
+                    gt_usm=None, l1_gt_usm=True, percep_gt_usm=True, gan_gt_usm=False):
+    """One GAN-stage step of the Real-ESRGAN recipe (BasicSR RealESRGANModel.optimize_parameters).  Unlike gan_step, the
+    adversarial gradient flows through D into G.  With ``gt_usm=None`` `gt` is the target of all three terms.  With a tensor
+    (``utils.degradation.usm_sharp(gt)``, the unsharp-masked ground truth) the L1 term, the content term and the
+    discriminator's real pass each take `gt_usm` or `gt` by their flag `l1_gt_usm`, `percep_gt_usm`, `gan_gt_usm` (the
+    published defaults); the launches are the same, only the tensors they read differ.
 
     Generator half, D frozen (no weight gradient and no spectral-norm backward runs for it):
         fake = gen(lq);  l_g = l1_weight * L1(fake, gt) + vggfeat(fake, gt) + gan_weight * gan_loss(disc(fake), real)
@@ -221,6 +225,9 @@ def realesrgan_step(gen, disc, vggfeat, opt_g, opt_d, lq, gt, *, l1_weight=1.0, 
     l_percep, l_g_gan, l_d_real, l_d_fake, fake): the unweighted L1, the (weighted) content term, the unweighted three GAN
     terms and the generator's output, as detached device tensors.  One stream, no host read: usable inside GraphedStep with a
     FusedAdam for each optimiser."""
+    l1_gt = gt_usm if (gt_usm is not None and l1_gt_usm) else gt
+    percep_gt = gt_usm if (gt_usm is not None and percep_gt_usm) else gt
+    gan_gt = gt_usm if (gt_usm is not None and gan_gt_usm) else gt
     d_params = [p for p in disc.parameters()]
     was = [p.requires_grad for p in d_params]
     # --- generator
@@ -229,8 +236,8 @@ def realesrgan_step(gen, disc, vggfeat, opt_g, opt_d, lq, gt, *, l1_weight=1.0, 
     try:
         opt_g.zero_grad()
         fake = gen(lq)
-        l_pix = F.l1_loss(fake, gt)
-        l_percep = vggfeat(fake, gt)
+        l_pix = F.l1_loss(fake, l1_gt)
+        l_percep = vggfeat(fake, percep_gt)
         l_g_gan = F.gan_loss(disc(fake), True, gan_type, is_disc=False)
         l_g = F.add_losses(F.add_losses(F.scale_loss(l_pix, float(l1_weight)), l_percep), F.scale_loss(l_g_gan, float(gan_weight)))
         with F.batched_wgrad():
@@ -246,7 +253,7 @@ def realesrgan_step(gen, disc, vggfeat, opt_g, opt_d, lq, gt, *, l1_weight=1.0, 
         p.requires_grad_(True)
     try:
         opt_d.zero_grad()
-        l_d_real = F.gan_loss(disc(gt), True, gan_type, is_disc=True)
+        l_d_real = F.gan_loss(disc(gan_gt), True, gan_type, is_disc=True)
         with F.batched_wgrad():
             l_d_real.backward()
         l_d_fake = F.gan_loss(disc(fake.detach()), False, gan_type, is_disc=True)

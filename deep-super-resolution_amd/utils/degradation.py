@@ -197,6 +197,140 @@ def random_kernels(n, size=21, sigma=(0.2, 3.0), iso_prob=0.5, rng=None):
     return out
 
 
+def _rotated_q(size, sigma_x, sigma_y, theta, who):
+    """u^2 / sigma_x^2 + v^2 / sigma_y^2 on the grid of ``gaussian_kernel``, with its statements"""
+    size = int(size)
+    if size < 1 or size % 2 == 0:
+        raise ValueError(f"{who}: size {size} is not a positive odd number")
+    sigma_y = sigma_x if sigma_y is None else sigma_y
+    if not (sigma_x > 0 and sigma_y > 0):
+        raise ValueError(f"{who}: sigmas must be positive")
+    r = size // 2
+    y, x = np.meshgrid(np.arange(size, dtype=np.float64) - r, np.arange(size, dtype=np.float64) - r, indexing="ij")
+    c, sn = math.cos(theta), math.sin(theta)
+    u, v = c * x + sn * y, -sn * x + c * y
+    return u * u / (float(sigma_x) ** 2) + v * v / (float(sigma_y) ** 2)
+
+
+def generalized_gaussian_kernel(size, sigma_x, sigma_y=None, theta=0.0, beta=1.0):
+    """fp32 [size, size] generalised Gaussian ``exp(-0.5 q^beta)``, q = u^2 / sigma_x^2 + v^2 / sigma_y^2 in the rotated
+    coordinates of ``gaussian_kernel`` (same grid, float64, normalised to sum 1, rounded to fp32 once).  ``beta == 1`` takes
+    no power at all and equals ``gaussian_kernel`` bit for bit."""
+    q = _rotated_q(size, sigma_x, sigma_y, theta, "generalized_gaussian_kernel")
+    k = np.exp(-0.5 * (q if beta == 1 else np.power(q, float(beta))))
+    return (k / k.sum()).astype(np.float32)
+
+
+def plateau_kernel(size, sigma_x, sigma_y=None, theta=0.0, beta=1.0):
+    """fp32 [size, size] plateau-shaped kernel ``1 / (q^beta + 1)`` with q as in ``generalized_gaussian_kernel``, normalised."""
+    q = _rotated_q(size, sigma_x, sigma_y, theta, "plateau_kernel")
+    k = 1.0 / (np.power(q, float(beta)) + 1.0)
+    return (k / k.sum()).astype(np.float32)
+
+
+_J1_TAU = (np.arange(128, dtype=np.float64) + 0.5) * (math.pi / 128)
+
+
+def bessel_j1(x):
+    """The Bessel function J1 in float64 by the midpoint rule on Bessel's integral, J1(x) = mean_k cos(tau_k - x sin tau_k),
+    tau_k = (k + 1/2) pi / 128, k < 128: the integrand is smooth and periodic, so the rule converges geometrically (7.1e-16
+    from scipy.special.j1 on [0, 45], the range ``sinc_kernel`` needs).  No scipy in the product."""
+    x = np.asarray(x, dtype=np.float64)
+    return np.cos(_J1_TAU - x[..., None] * np.sin(_J1_TAU)).mean(axis=-1)
+
+
+def sinc_kernel64(cutoff, size):
+    """``sinc_kernel`` before its rounding to fp32: float64 [size, size], normalised to sum 1"""
+    size = int(size)
+    if size < 1 or size % 2 == 0:
+        raise ValueError(f"sinc_kernel: size {size} is not a positive odd number")
+    cutoff = float(cutoff)
+    if not cutoff > 0:
+        raise ValueError("sinc_kernel: cutoff must be positive")
+    r = size // 2
+    y, x = np.meshgrid(np.arange(size, dtype=np.float64) - r, np.arange(size, dtype=np.float64) - r, indexing="ij")
+    rho = np.hypot(x, y)
+    rho[r, r] = 1.0
+    k = cutoff * bessel_j1(cutoff * rho) / (2.0 * math.pi * rho)
+    k[r, r] = cutoff * cutoff / (4.0 * math.pi)
+    return k / k.sum()
+
+
+def sinc_kernel(cutoff, size, pad_to=0):
+    """fp32 circular low-pass (2-D sinc) filter ``cutoff J1(cutoff rho) / (2 pi rho)``, rho = hypot(x, y) on the grid of
+    ``gaussian_kernel``, the centre tap ``cutoff^2 / (4 pi)``; float64, normalised to sum 1, rounded to fp32 once, then
+    zero-padded symmetrically to [pad_to, pad_to] when pad_to > size."""
+    return _pad_kernel(sinc_kernel64(cutoff, size).astype(np.float32), pad_to)
+
+
+def _pad_kernel(k, pad_to):
+    size = k.shape[0]
+    if pad_to <= size:
+        return k
+    if (pad_to - size) % 2:
+        raise ValueError(f"a {size}x{size} kernel cannot be padded symmetrically to {pad_to}")
+    p = (pad_to - size) // 2
+    return np.pad(k, ((p, p), (p, p)))
+
+
+KERNEL_LIST = ("iso", "aniso", "generalized_iso", "generalized_aniso", "plateau_iso", "plateau_aniso")
+
+
+def random_mixed_kernels(n, kernel_list=KERNEL_LIST, kernel_prob=(0.45, 0.25, 0.12, 0.03, 0.12, 0.03), size=21, sigma_x=(0.2, 3.0),
+                         sigma_y=(0.2, 3.0), rotation=(-math.pi, math.pi), betag=(0.5, 4.0), betap=(1.0, 2.0), sinc_prob=0.1,
+                         rng=None, pad_to=21):
+    """fp32 [n, pad_to, pad_to] kernels of the Real-ESRGAN family, made on the host.  Per sample, in this order, from `rng`
+    (defaults to numpy's global generator; a seeded ``np.random.RandomState`` repeats itself):
+      1. only when `size` is a sequence: ``rng.randint(len(size))`` picks the kernel size (the recipe: 7, 9, ..., 21);
+      2. ``rng.uniform(0, 1)`` < sinc_prob takes the sinc branch: one more draw, the cutoff, uniform in [pi / 3, pi) for sizes
+         below 13 and in [pi / 5, pi) otherwise -> ``sinc_kernel``; nothing else is drawn for this sample;
+      3. otherwise ``rng.uniform(0, 1)`` picks the entry of `kernel_list` by the cumulative `kernel_prob` (normalised), then
+         sigma_x, sigma_y and theta are drawn uniformly from their ranges, all three always (an ``*iso`` kernel uses sigma_x
+         alone and no rotation);
+      4. a ``generalized_*`` kernel draws ``rng.uniform(0, 1)`` < 0.5 and then beta uniform in [betag[0], 1) or, otherwise, in
+         [1, betag[1]); a ``plateau_*`` kernel the same two draws with `betap`.
+    Every kernel is normalised at its own size and then zero-padded symmetrically to `pad_to`."""
+    rng = np.random if rng is None else rng
+    names = tuple(kernel_list)
+    for name in names:
+        if name not in KERNEL_LIST:
+            raise ValueError(f"random_mixed_kernels: unknown kernel {name!r}; one of {KERNEL_LIST}")
+    prob = np.asarray(kernel_prob, dtype=np.float64)
+    if prob.shape != (len(names),) or not (prob >= 0).all() or not prob.sum() > 0:
+        raise ValueError("random_mixed_kernels: kernel_prob must hold one non-negative weight per kernel")
+    cum = np.cumsum(prob / prob.sum())
+    sizes = [int(s) for s in size] if isinstance(size, (tuple, list, np.ndarray)) else None
+    for s in (sizes if sizes is not None else [int(size)]):
+        if s < 1 or s % 2 == 0 or s > pad_to:
+            raise ValueError(f"random_mixed_kernels: size {s} is not an odd number in 1..{pad_to}")
+
+    def draw_beta(lo_hi):
+        low = float(rng.uniform(0.0, 1.0)) < 0.5
+        return float(rng.uniform(lo_hi[0], 1.0)) if low else float(rng.uniform(1.0, lo_hi[1]))
+
+    out = np.zeros((n, pad_to, pad_to), dtype=np.float32)
+    for b in range(n):
+        ks = int(size) if sizes is None else sizes[int(rng.randint(len(sizes)))]
+        if float(rng.uniform(0.0, 1.0)) < sinc_prob:
+            cutoff = float(rng.uniform(math.pi / 3 if ks < 13 else math.pi / 5, math.pi))
+            out[b] = sinc_kernel(cutoff, ks, pad_to)
+            continue
+        name = names[min(int(np.searchsorted(cum, float(rng.uniform(0.0, 1.0)), side="right")), len(names) - 1)]
+        sx = float(rng.uniform(sigma_x[0], sigma_x[1]))
+        sy = float(rng.uniform(sigma_y[0], sigma_y[1]))
+        theta = float(rng.uniform(rotation[0], rotation[1]))
+        if name.endswith("_iso") or name == "iso":
+            sy, theta = sx, 0.0
+        if name.startswith("generalized"):
+            k = generalized_gaussian_kernel(ks, sx, sy, theta, draw_beta(betag))
+        elif name.startswith("plateau"):
+            k = plateau_kernel(ks, sx, sy, theta, draw_beta(betap))
+        else:
+            k = gaussian_kernel(ks, sx, sy, theta)
+        out[b] = _pad_kernel(k, pad_to)
+    return out
+
+
 def _device_kernels(kernels, n, device):
     """-> contiguous fp32 [n, ks, ks] on `device` (one upload when the kernels come from the host)"""
     k = torch.from_numpy(np.ascontiguousarray(kernels, dtype=np.float32)) if isinstance(kernels, np.ndarray) else kernels
@@ -396,3 +530,204 @@ class BlindDegradation:
             if len(q) != 2 or not all(_is_int(v) for v in q) or not 1 <= q[0] <= q[1] <= 100:
                 raise ValueError(f"BlindDegradation: jpeg_quality {q} is not (low, high) with integers 1 <= low <= high <= 100")
         _subsampling(self.jpeg_subsampling)
+
+
+# ------------------------------------------------------------------ second-order Real-ESRGAN degradation (csrc/filter2d.hip,
+# csrc/degrade_noise.hip): the stage functions that utils/realesrgan.py runs in sequence.  Data ops: no autograd.
+def _batch_f32(x, who, channels=None):
+    if not (torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() == 4 and x.numel() > 0):
+        raise TypeError(f"{who}: an fp32 [B, C, H, W] tensor is expected")
+    if channels is not None and x.shape[1] != channels:
+        raise TypeError(f"{who}: {channels} channels are expected, got {x.shape[1]}")
+    _need_gpu(x)
+    return x.detach().contiguous()
+
+
+def filter2d(x, kernels):
+    """BasicSR's ``filter2D``: fp32 [B, C, H, W] device batch correlated with a kernel per sample (fp32 [B, ks, ks]) or with one
+    kernel for all ([ks, ks]), borders reflected as torch's 'reflect'; a new tensor.  ks odd in 1..21 and H, W >= ks // 2 + 1.
+    One fmaf per tap in row-major tap order (dsr_filter2d_f32): the result is defined bit for bit, and a kernel zero-padded
+    to a larger size gives the bits of the kernel itself.  Kernels may be numpy arrays (uploaded once)."""
+    x = _batch_f32(x, "filter2d")
+    k = torch.from_numpy(np.ascontiguousarray(kernels, dtype=np.float32)) if isinstance(kernels, np.ndarray) else kernels
+    if not torch.is_tensor(k) or k.dtype != torch.float32 or k.dim() not in (2, 3) or k.shape[-1] != k.shape[-2]:
+        raise ValueError("filter2d: kernels must be fp32 [B, ks, ks] or [ks, ks]")
+    b, c, h, w = (int(v) for v in x.shape)
+    shared = k.dim() == 2
+    if not shared and k.shape[0] != b:
+        raise ValueError(f"filter2d: {k.shape[0]} kernels for {b} samples")
+    ks = int(k.shape[-1])
+    if ks % 2 == 0 or ks > KERNEL_SIZE_MAX:
+        raise ValueError(f"filter2d: kernel size {ks} is not an odd number in 1..{KERNEL_SIZE_MAX}")
+    if min(h, w) < ks // 2 + 1:
+        raise ValueError(f"filter2d: a {ks}x{ks} kernel cannot be reflected in a {h}x{w} image")
+    k = k.to(x.device).contiguous()
+    y = torch.empty_like(x)
+    check(_lib.lib().dsr_filter2d_f32(_ptr(x), _ptr(y), _ptr(k), b, c, h, w, ks, int(shared), _stream()))
+    return y
+
+
+def _per_sample(v, n, device, dtype, who):
+    """-> contiguous `dtype` [n] on `device` from a scalar, a sequence or a tensor"""
+    if not torch.is_tensor(v):
+        v = torch.tensor([v] * n if isinstance(v, (int, float, bool, np.integer, np.floating, np.bool_)) else list(v))
+    if v.numel() != n:
+        raise ValueError(f"{who}: {v.numel()} values for {n} samples")
+    return v.reshape(n).to(device=device, dtype=dtype).contiguous()
+
+
+def _draw_like(shape, given, x, who):
+    if given is None:
+        return None
+    if not (torch.is_tensor(given) and given.dtype == torch.float32 and tuple(given.shape) == tuple(shape)):
+        raise ValueError(f"{who}: a draw must be fp32 {tuple(shape)}")
+    return given.to(x.device).contiguous()
+
+
+def add_gaussian_noise_batch(x, sigma, gray, generator=None, z=None, zg=None):
+    """Real-ESRGAN's Gaussian noise on an fp32 [B, 3, H, W] device batch in [0, 1] scaling (dsr_noise_gaussian_f32; a new
+    tensor): ``clamp(x + sigma_b / 255 * n, 0, 1)`` with n = z, fp32 [B, 3, H, W], or, for a sample whose `gray` flag is set,
+    zg, fp32 [B, H, W], on all three channels.  sigma (0..255 units) and gray: per sample, scalars, sequences or device
+    tensors (not read back).  The draws z and then zg are ``torch.randn`` on the device from `generator`; given ones are used
+    as they are."""
+    x = _batch_f32(x, "add_gaussian_noise_batch", 3)
+    b, _, h, w = (int(v) for v in x.shape)
+    sigma = _per_sample(sigma, b, x.device, torch.float32, "add_gaussian_noise_batch: sigma")
+    gray = _per_sample(gray, b, x.device, torch.uint8, "add_gaussian_noise_batch: gray")
+    z = _draw_like((b, 3, h, w), z, x, "add_gaussian_noise_batch")
+    zg = _draw_like((b, h, w), zg, x, "add_gaussian_noise_batch")
+    if z is None:
+        z = torch.randn((b, 3, h, w), dtype=torch.float32, device=x.device, generator=generator)
+    if zg is None:
+        zg = torch.randn((b, h, w), dtype=torch.float32, device=x.device, generator=generator)
+    y = torch.empty_like(x)
+    check(_lib.lib().dsr_noise_gaussian_f32(_ptr(x), _ptr(z), _ptr(zg), _ptr(sigma), _ptr(gray), _ptr(y), b, h, w, _stream()))
+    return y
+
+
+_GRAY_WEIGHTS = (0.2989, 0.587, 0.114)
+
+
+def poisson_levels(x, gray):
+    """(q, g, vals) of ``add_poisson_noise_batch`` from torch ops on x's device, with no host read: q = round(clamp(255 x, 0,
+    255)) / 255, fp32 [B, 3, H, W]; g = 0.2989 q_r + 0.587 q_g + 0.114 q_b, fp32 [B, H, W]; vals, fp32 [B], the smallest power
+    of two that is >= the number of distinct grey levels of the sample -- of round(255 q) over its three channels, or, for a
+    sample whose `gray` flag is set, of round(255 g): ``2 ** ceil(log2(len(unique(plane))))``."""
+    q = torch.round(torch.clamp(x * 255.0, 0.0, 255.0)) / 255.0
+    g = _GRAY_WEIGHTS[0] * q[:, 0] + _GRAY_WEIGHTS[1] * q[:, 1] + _GRAY_WEIGHTS[2] * q[:, 2]
+    b = x.shape[0]
+
+    def distinct(levels):                                            # int64 [B, n] in 0..255 -> how many differ, per row
+        seen = torch.zeros((b, 256), dtype=torch.float32, device=x.device)
+        seen.scatter_(1, levels, 1.0)
+        return seen.sum(dim=1)
+
+    count_c = distinct(torch.round(q * 255.0).to(torch.int64).reshape(b, -1))
+    count_g = distinct(torch.round(g * 255.0).clamp_(0.0, 255.0).to(torch.int64).reshape(b, -1))
+    count = torch.where(gray.to(torch.bool), count_g, count_c)
+    powers = torch.tensor([float(1 << e) for e in range(9)], dtype=torch.float32, device=x.device)      # 1 .. 256
+    vals = torch.exp2((count[:, None] > powers[None, :]).sum(dim=1).to(torch.float32))
+    return q, g, vals
+
+
+def add_poisson_noise_batch(x, scale, gray, generator=None, z=None, zg=None, vals=None):
+    """Real-ESRGAN's Poisson (shot) noise on an fp32 [B, 3, H, W] device batch in [0, 1] scaling (dsr_noise_poisson_f32; a
+    new tensor).  With q, g and vals of ``poisson_levels``: colour samples add ``scale_b * (z / vals_b - q)``, z ~
+    Poisson(q vals_b); samples whose `gray` flag is set add ``scale_b * (zg / vals_b - g)`` to all three channels, zg ~
+    Poisson(g vals_b); then clamp to [0, 1].  The draws (z, then zg: ``torch.poisson`` on the device from `generator`) and
+    vals are made here unless given, without a host read."""
+    x = _batch_f32(x, "add_poisson_noise_batch", 3)
+    b, _, h, w = (int(v) for v in x.shape)
+    scale = _per_sample(scale, b, x.device, torch.float32, "add_poisson_noise_batch: scale")
+    gray = _per_sample(gray, b, x.device, torch.uint8, "add_poisson_noise_batch: gray")
+    z = _draw_like((b, 3, h, w), z, x, "add_poisson_noise_batch")
+    zg = _draw_like((b, h, w), zg, x, "add_poisson_noise_batch")
+    if vals is not None:
+        vals = _per_sample(vals, b, x.device, torch.float32, "add_poisson_noise_batch: vals")
+    if z is None or zg is None or vals is None:
+        q, g, own = poisson_levels(x, gray)
+        vals = own if vals is None else vals
+        if z is None:
+            z = torch.poisson(q * vals[:, None, None, None], generator=generator)
+        if zg is None:
+            zg = torch.poisson(g * vals[:, None, None], generator=generator)
+    y = torch.empty_like(x)
+    check(_lib.lib().dsr_noise_poisson_f32(_ptr(x), _ptr(z), _ptr(zg), _ptr(vals), _ptr(scale), _ptr(gray), _ptr(y), b, h, w,
+                                           _stream()))
+    return y
+
+
+# ------------------------------------------------------------------ unsharp mask
+_usm_cache = {}
+
+
+def usm_kernel(radius=50, sigma=0):
+    """OpenCV's ``getGaussianKernel(radius, sigma)`` as float64 [k]: an even radius is made odd (k = radius + 1), sigma <= 0
+    means 0.3 ((k - 1) / 2 - 1) + 0.8; ``exp(-(i - (k - 1) / 2)^2 / (2 sigma^2))`` normalised to sum 1."""
+    k = int(radius)
+    if k < 1:
+        raise ValueError(f"usm_kernel: radius {radius}")
+    if k % 2 == 0:
+        k += 1
+    s = float(sigma) if sigma > 0 else 0.3 * ((k - 1) * 0.5 - 1.0) + 0.8
+    i = np.arange(k, dtype=np.float64) - (k - 1) / 2.0
+    g = np.exp(-(i * i) / (2.0 * s * s))
+    return g / g.sum()
+
+
+def _usm_tables(n, radius, sigma, device):
+    """``AxisTables`` of the 1-D blur at unchanged size n: k taps per output with torch-'reflect'ed indices (cached)."""
+    from .imresize import AxisTables
+    key = (int(n), int(radius), float(sigma), str(device))
+    hit = _usm_cache.get(key)
+    if hit is None:
+        g = usm_kernel(radius, sigma)
+        r = g.shape[0] // 2
+        pos = np.arange(n, dtype=np.int64)[:, None] + np.arange(-r, r + 1, dtype=np.int64)[None, :]
+        pos = np.abs(pos)
+        pos = np.where(pos > n - 1, 2 * (n - 1) - pos, pos)
+        hit = _usm_cache[key] = AxisTables(n, n, 1.0, np.ascontiguousarray(np.broadcast_to(g, pos.shape)), pos, device)
+    return hit
+
+
+def usm_sharp(x, weight=0.5, threshold=10, radius=50, sigma=0):
+    """BasicSR's ``USMSharp`` on an fp32 [B, C, H, W] device batch in [0, 1] scaling; a new tensor.  With G the Gaussian of
+    ``usm_kernel`` (51 taps, sigma 8 at the defaults), borders reflected:
+        blur = G * x;  res = x - blur;  mask = |res| 255 > threshold;  soft = G * mask
+        sharp = clamp(x + weight res, 0, 1);  y = soft sharp + (1 - soft) x
+    G is rank 1, and the blur is defined here as the separable pass, rows of taps along H and then along W: the separable
+    form of BasicSR's 51 x 51 ``filter2D``, equal to it up to rounding.  Four launches: dsr_imresize_f32 at unchanged size
+    with k-tap tables for each blur, dsr_usm_mask, dsr_usm_combine; no res or sharp tensor exists.  H, W >= k // 2 + 1 (26 at
+    the defaults), otherwise ValueError; k <= 63."""
+    from ..functional import _imresize_launch
+    if not (torch.is_tensor(x) and x.dtype == torch.float32 and x.dim() == 4 and x.numel() > 0):
+        raise TypeError("usm_sharp: an fp32 [B, C, H, W] tensor is expected")
+    k = usm_kernel(radius, sigma).shape[0]
+    b, c, h, w = (int(v) for v in x.shape)
+    if min(h, w) < k // 2 + 1:
+        raise ValueError(f"usm_sharp: a {k}-tap blur cannot be reflected in a {h}x{w} image ({k // 2 + 1} pixels are needed)")
+    _need_gpu(x)
+    x = x.detach().contiguous()
+    th, tw = _usm_tables(h, radius, sigma, x.device), _usm_tables(w, radius, sigma, x.device)
+    lib = _lib.lib()
+    blur, mask, soft, y = (torch.empty_like(x) for _ in range(4))
+    _imresize_launch(x, blur, b * c, h, w, h, w, th.idx, th.w, th.taps, tw.idx, tw.w, tw.taps)
+    check(lib.dsr_usm_mask(_ptr(x), _ptr(blur), float(threshold), _ptr(mask), x.numel(), _stream()))
+    _imresize_launch(mask, soft, b * c, h, w, h, w, th.idx, th.w, th.taps, tw.idx, tw.w, tw.taps)
+    check(lib.dsr_usm_combine(_ptr(x), _ptr(blur), _ptr(soft), float(weight), _ptr(y), x.numel(), _stream()))
+    return y
+
+
+class USMSharp(torch.nn.Module):
+    """``usm_sharp`` as a module with the same arguments: no parameters, no buffers."""
+
+    def __init__(self, weight=0.5, threshold=10, radius=50, sigma=0):
+        super().__init__()
+        usm_kernel(radius, sigma)
+        self.weight, self.threshold, self.radius, self.sigma = float(weight), float(threshold), int(radius), float(sigma)
+
+    def forward(self, x):
+        return usm_sharp(x, self.weight, self.threshold, self.radius, self.sigma)
+
+    def extra_repr(self):
+        return f"weight={self.weight}, threshold={self.threshold}, radius={self.radius}, sigma={self.sigma}"

@@ -174,6 +174,103 @@ def imresize(x, scale=None, size=None, kernel="bicubic", antialiasing=True):
     return restore(out)
 
 
+# ------------------------------------------------------------------ torch-convention resize on the same kernel
+INTERPOLATE_MODES = ("area", "bilinear", "bicubic")
+
+
+def _cubic_torch(t, a=-0.75):
+    """the four weights of torch's bicubic (a = -0.75) for the fraction t, taps floor(s) - 1 .. floor(s) + 2"""
+    def near(x):
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0
+
+    def far(x):
+        return ((a * x - 5.0 * a) * x + 8.0 * a) * x - 4.0 * a
+    return np.stack([far(t + 1.0), near(t), near(1.0 - t), far(2.0 - t)], axis=1)
+
+
+def interpolate_out_size(n_in, size=None, scale_factor=None):
+    """Output length of one axis: `size` itself, or ``floor(n_in * scale_factor)`` computed in float64 as torch does."""
+    if (size is None) == (scale_factor is None):
+        raise ValueError("interpolate: exactly one of `size` and `scale_factor` is expected")
+    n_out = int(size) if size is not None else int(math.floor(float(n_in) * float(scale_factor)))
+    if n_out < 1:
+        raise ValueError(f"interpolate: an axis of {n_in} pixels would become {n_out} long")
+    return n_out
+
+
+def interpolate_axis_weights(n_in, n_out, mode, scale_factor=None):
+    """Host float64 (weights [n_out, taps], indices int64 [n_out, taps]) of one axis of ``torch.nn.functional.interpolate``
+    with ``align_corners=False`` and no antialias.  The coordinate ratio is rho = n_in / n_out, or 1 / scale_factor when one is
+    given (torch with ``recompute_scale_factor=None``).
+      area      output o averages the sources floor(o n_in / n_out) .. ceil((o + 1) n_in / n_out) - 1 with equal weights
+                (shorter lists are padded with weight 0);
+      bilinear  s = max((o + 1/2) rho - 1/2, 0), taps floor(s) and min(floor(s) + 1, n_in - 1), weights 1 - l and l;
+      bicubic   s = (o + 1/2) rho - 1/2 (not clamped), the cubic with a = -0.75 on taps floor(s) - 1 .. floor(s) + 2, indices
+                clamped to the axis."""
+    if mode not in INTERPOLATE_MODES:
+        raise ValueError(f"interpolate: unknown mode {mode!r}; one of {INTERPOLATE_MODES}")
+    o = np.arange(n_out, dtype=np.int64)
+    if mode == "area":
+        start = (o * n_in) // n_out
+        end = -((-(o + 1) * n_in) // n_out)
+        taps = int((end - start).max())
+        t = np.arange(taps, dtype=np.int64)[None, :]
+        live = t < (end - start)[:, None]
+        w = np.where(live, 1.0 / (end - start)[:, None].astype(np.float64), 0.0)
+        idx = np.minimum(start[:, None] + t, n_in - 1)
+        return np.ascontiguousarray(w), np.ascontiguousarray(idx)
+    rho = (1.0 / float(scale_factor)) if scale_factor is not None else float(n_in) / float(n_out)
+    s = (o.astype(np.float64) + 0.5) * rho - 0.5
+    if mode == "bilinear":
+        s = np.maximum(s, 0.0)
+        i0 = np.floor(s).astype(np.int64)
+        lam = s - i0
+        i0 = np.minimum(i0, n_in - 1)
+        idx = np.stack([i0, np.minimum(i0 + 1, n_in - 1)], axis=1)
+        return np.stack([1.0 - lam, lam], axis=1), idx
+    fl = np.floor(s)
+    w = _cubic_torch(s - fl)
+    idx = np.clip(fl.astype(np.int64)[:, None] + np.arange(-1, 3, dtype=np.int64)[None, :], 0, n_in - 1)
+    return w, idx
+
+
+def interpolate_tables(n_in, n_out, mode, scale_factor=None, device="cuda:0"):
+    """The ``AxisTables`` (forward and transposed, the layout of ``imresize_tables``) of one axis of
+    ``interpolate_axis_weights`` on `device`, cached per argument tuple."""
+    if mode not in INTERPOLATE_MODES:
+        raise ValueError(f"interpolate: unknown mode {mode!r}; one of {INTERPOLATE_MODES}")
+    key = ("interpolate", int(n_in), int(n_out), mode, None if scale_factor is None else float(scale_factor), str(device))
+    hit = _cache.get(key)
+    if hit is None:
+        if key[1] < 1 or key[2] < 1 or (key[4] is not None and not key[4] > 0):
+            raise ValueError(f"interpolate: axis of {n_in} -> {n_out} pixels at scale factor {scale_factor}")
+        w64, idx = interpolate_axis_weights(key[1], key[2], mode, key[4])
+        hit = _cache[key] = AxisTables(key[1], key[2], key[2] / key[1], w64, idx, device)
+    return hit
+
+
+def interpolate(x, size=None, scale_factor=None, mode="bilinear"):
+    """``torch.nn.functional.interpolate(x, size=, scale_factor=, mode=, align_corners=False)`` without antialias, for mode
+    "area", "bilinear" or "bicubic", on a floating-point ``[N, C, H, W]`` device tensor: the tables of ``interpolate_tables``
+    run through ``functional.Imresize`` (dsr_imresize_f32; fp32 out, differentiable with respect to `x`).  Exactly one of
+    ``size`` = (OH, OW) and ``scale_factor`` (a float or a pair; the output is ``floor(n s)`` long)."""
+    if not (torch.is_tensor(x) and x.is_floating_point() and x.dim() == 4):
+        raise TypeError("interpolate: a floating-point [N, C, H, W] tensor is expected")
+    if mode not in INTERPOLATE_MODES:
+        raise ValueError(f"interpolate: unknown mode {mode!r}; one of {INTERPOLATE_MODES}")
+    if (size is None) == (scale_factor is None):
+        raise ValueError("interpolate: exactly one of `size` and `scale_factor` is expected")
+    h, w = int(x.shape[2]), int(x.shape[3])
+    if size is not None:
+        oh, ow = (interpolate_out_size(n, size=v) for n, v in zip((h, w), size))
+        sh = sw = None
+    else:
+        sh, sw = (scale_factor if isinstance(scale_factor, (tuple, list)) else (scale_factor, scale_factor))
+        oh, ow = interpolate_out_size(h, scale_factor=sh), interpolate_out_size(w, scale_factor=sw)
+    _need_gpu(x)
+    return F.Imresize.apply(x, interpolate_tables(h, oh, mode, sh, x.device), interpolate_tables(w, ow, mode, sw, x.device))
+
+
 def modcrop(image, scale):
     """`image` with H and W cropped (at the bottom / right) to multiples of `scale`: ``[..., H, W]`` for a floating-point
     tensor, ``[H, W, C]`` for a uint8 tensor or numpy array, or a PIL image."""

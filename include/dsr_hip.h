@@ -819,6 +819,35 @@ int dsr_gan_loss_blocks(size_t n);
 int dsr_gan_loss(const float* x, size_t n, int kind, int target_is_real, int is_disc, float* grad, double* partial, float* loss,
                  dsr_stream_t s);
 
+/* ------------------------------------------------------------------ second-order Real-ESRGAN degradation
+ * fp32 [B][C][H][W] batches in [0, 1] scaling; every call only enqueues on `s` (no allocation, no sync, no host read).
+ *
+ * dsr_filter2d_f32 (filter2d.hip), BasicSR's filter2D: a correlation with a kernel per sample, reflected borders,
+ *   acc = 0;  for i, for j:  acc = fmaf(k[b][i][j], x[b][c][refl(Y + i - r)][refl(X + j - r)], acc),  r = ks / 2
+ * one fmaf per tap in row-major tap order (taps whose weight is 0 may be left out: they add exact zeros), no atomics: the
+ * result is defined bit for bit and does not depend on the tiling.  kernels: fp32 [B][ks][ks], or [ks][ks] for every sample
+ * when shared == 1.  ks odd in 1..21, H, W >= ks / 2 + 1, B C H W < 2^31, y must not overlap x: otherwise DSR_E_ARG.
+ *
+ * dsr_noise_gaussian_f32 / dsr_noise_poisson_f32 (degrade_noise.hip), C == 3.  z: fp32 [B][3][H][W] and zg: fp32 [B][H][W]
+ * draws made by the caller; gray: uint8 [B], non-zero = the sample takes zg for all three channels; sigma (0..255 units),
+ * vals, scale: fp32 [B]; all on the device.  y may be x.
+ *   Gaussian: y = clamp(fmaf(sigma[b] / 255, gray[b] ? zg : z, x), 0, 1)
+ *   Poisson:  q = rintf(clamp(255 x, 0, 255)) / 255;  colour n = z / vals[b] - q;  grey n = zg / vals[b] - (0.2989 q_r + 0.587 q_g
+ *             + 0.114 q_b, as one product and two fmaf);  y = clamp(fmaf(scale[b], n, x), 0, 1)
+ *
+ * dsr_usm_mask / dsr_usm_combine (degrade_noise.hip), the pointwise steps of the unsharp mask on n < 2^31 elements:
+ *   mask = |x - blur| * 255 > threshold ? 1 : 0
+ *   res = x - blur;  sharp = clamp(fmaf(weight, res, x), 0, 1);  y = fmaf(soft, sharp - x, x)
+ * A null pointer or a size out of range is DSR_E_ARG before anything is launched. */
+int dsr_filter2d_f32(const float* x, float* y, const float* kernels, int B, int C, int H, int W, int ks, int shared,
+                     dsr_stream_t s);
+int dsr_noise_gaussian_f32(const float* x, const float* z, const float* zg, const float* sigma, const unsigned char* gray,
+                           float* y, int B, int H, int W, dsr_stream_t s);
+int dsr_noise_poisson_f32(const float* x, const float* z, const float* zg, const float* vals, const float* scale,
+                          const unsigned char* gray, float* y, int B, int H, int W, dsr_stream_t s);
+int dsr_usm_mask(const float* x, const float* blur, float threshold, float* mask, size_t n, dsr_stream_t s);
+int dsr_usm_combine(const float* x, const float* blur, const float* soft, float weight, float* y, size_t n, dsr_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
