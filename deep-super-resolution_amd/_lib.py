@@ -39,6 +39,22 @@ class RdbConv(C.Structure):
                 ("ldy", C.c_int), ("y_off", C.c_int), ("max_blocks", C.c_int)]
 
 
+class RdbDgrad(C.Structure):
+    """dsr_rdb_dgrad: one input gradient on a dense block's growth buffers (csrc/conv_rdb.hip)."""
+    _fields_ = [("dtype", C.c_int), ("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("K", C.c_int), ("Cout", C.c_int),
+                ("dy", C.c_void_p), ("lddy", C.c_int), ("dy_off", C.c_int), ("wd", C.c_void_p), ("scale", C.c_float),
+                ("dx", C.c_void_p), ("lddx", C.c_int), ("accumulate", C.c_int), ("g", C.c_void_p), ("ldg", C.c_int),
+                ("g_limit", C.c_int), ("g_scale", C.c_float), ("act_out", C.c_void_p), ("ldact", C.c_int),
+                ("mask_lo", C.c_int), ("slope", C.c_float), ("max_blocks", C.c_int)]
+
+
+class RdbWgrad(C.Structure):
+    """dsr_rdb_wgrad: the ten parameter gradients of one dense block (csrc/conv_rdb_bwd.hip)."""
+    _fields_ = [("dtype", C.c_int), ("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("x", C.c_void_p), ("ldx", C.c_int),
+                ("dy", C.c_void_p), ("lddy", C.c_int), ("g", C.c_void_p), ("ldg", C.c_int), ("gscale", C.c_float),
+                ("dw", C.c_void_p * 5), ("db", C.c_void_p * 5)]
+
+
 class AdamArgs(C.Structure):
     """dsr_adam_args: where an Adam launch takes its coefficients from (hyper, loss_scale, found_inf: device words, each
     nullable); one block for dsr_pw_adam, dsr_pw_adam_multi and dsr_linear_wgrad_adam."""
@@ -219,6 +235,12 @@ SIGNATURES = {
     "dsr_imresize_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
     "dsr_conv_rdb_supported": (_I, [C.POINTER(RdbConv)]),
     "dsr_conv_rdb_fwd": (_I, [C.POINTER(RdbConv), _P]),
+    "dsr_conv_rdb_dgrad_supported": (_I, [C.POINTER(RdbDgrad)]),
+    "dsr_conv_rdb_dgrad": (_I, [C.POINTER(RdbDgrad), _P]),
+    "dsr_conv_rdb_wgrad_supported": (_I, [C.POINTER(RdbWgrad)]),
+    "dsr_conv_rdb_wgrad_workspace": (_Z, [C.POINTER(RdbWgrad)]),
+    "dsr_conv_rdb_wgrad_chunks": (_I, [C.POINTER(RdbWgrad)]),
+    "dsr_conv_rdb_wgrad": (_I, [C.POINTER(RdbWgrad), _P, _Z, _P]),
     "dsr_scale_add16": (_I, [_I, _P, _F, _P, _P, _Z, _P]),
     "dsr_spectral_norm_workspace": (_Z, [_I, C.POINTER(_I), C.POINTER(_I)]),
     "dsr_spectral_norm_bwd_workspace": (_Z, [_I, C.POINTER(_I), C.POINTER(_I)]),
@@ -247,7 +269,8 @@ _NO_LAUNCH = ("dsr_last_error", "dsr_abi_version", "dsr_conv_dgrad_ps_supported"
               "dsr_ssim_img_blocks", "dsr_psnr_blocks", "dsr_lbfgs_workspace", "dsr_lbfgs_vector_floats", "dsr_clip_sumsq_partials",
               "dsr_linear_factor_gram_workspace", "dsr_linear_factor_gram_dots", "dsr_downsample_dense_wgrad_workspace",
               "dsr_msssim_min_size", "dsr_msssim_pyramid_floats", "dsr_ssim_cs_img_blocks", "dsr_msssim_bwd_blocks", "dsr_luma_blocks",
-              "dsr_featloss_blocks", "dsr_jpeg_workspace", "dsr_conv_rdb_supported", "dsr_spectral_norm_workspace",
+              "dsr_featloss_blocks", "dsr_jpeg_workspace", "dsr_conv_rdb_supported", "dsr_conv_rdb_dgrad_supported",
+              "dsr_conv_rdb_wgrad_supported", "dsr_conv_rdb_wgrad_workspace", "dsr_conv_rdb_wgrad_chunks", "dsr_spectral_norm_workspace",
               "dsr_spectral_norm_bwd_workspace", "dsr_gan_loss_blocks")
 
 

@@ -19,6 +19,24 @@
 // and no fence in here.  A 64-byte segment written next to segments other XCDs read leaves its L2 through byte-masked
 // write-back; the next launch on the stream sees it by the ordinary kernel-boundary visibility ("Residual dense
 // block on a growth buffer").
+//
+// INPUT-GRADIENT FORM (conv_rdb_kernel<DT, COUT, true>, dsr_conv_rdb_dgrad; the forward instantiations are the parent's
+// code: `if constexpr` keeps every addition out of them).  A 3x3 / stride-1 input gradient is the same convolution with the
+// mirrored taps and the transposed weights, so the kernel runs unchanged on the dgrad image [9][Cout][K] of
+// dsr_conv_pack_weight (tap 8 - t in the loader's address), with
+//   * an input channel OFFSET: the K = 32 | 64 channels [x_off, x_off + K) of dy (one or two K-blocks);
+//   * Cout = 64 .. 192 outputs as Cout / COUT work items per tile (COUT = 64 where 64 divides Cout, else 32): the slices of
+//     a tile are consecutive work items, so its halo is fetched from L2 again, not from HBM.  Staging the halo once and
+//     looping over the slices inside a work item has not been measured;
+//   * the epilogue  v = acc * gscale;  v += dx (the 16-bit value already in the range, `self_acc`);  below channel r1_lim
+//     v = fmaf(g, beta1, v);  from channel mask_lo on  v *= (B >= 0 ? 1 : slope)  with B the block's forward buffer at the
+//     same pixel and channel -- the LeakyReLU mask of the slice whose LAST contribution this launch stores (for a positive
+//     slope the stored output carries the sign of its pre-activation; ConvAct's convention).  All of it in fp32 on fp32
+//     accumulations of products of 16-bit operands; every store is ONE rounding to nearest even.
+// In place, the rule that replaces "no byte is read and written by one launch": the OUTPUT bytes of a (tile, slice) are read
+// (the addend) and then written by the one block that owns that work item, in its epilogue; halo reads -- the only reads of
+// other blocks' pixels -- touch the other channel range [x_off, x_off + K) only, which no block writes (the entry point
+// refuses dy == dx with x_off < Cout).  So there is still no hand-off between blocks and no fence.  No atomics anywhere.
 #include <stdlib.h>
 
 #include "../../include/dsr_hip.h"
@@ -45,6 +63,11 @@ struct RdbArgs {
   float slope, beta1, beta2;
   int tiles_y, tiles_x, ntiles;
   unsigned w_bytes, x_img, y_img, r1_img, r2_img;       // bytes of the weight image and of ONE image of each tensor
+  // input-gradient form only (BWD): the input is the channel range [x_off, x_off + Cin) and a work item is one of `nslices`
+  // COUT-channel slices of one tile's output; rows of the dgrad image per tap; channels below r1_lim take res1; channels from
+  // mask_lo on are multiplied by the LeakyReLU mask read from res2; `self_acc`: the output range is also the addend
+  int x_off, nslices, w_rows, r1_lim, mask_lo, self_acc;
+  float gscale;
 };
 
 template <int COUT>
@@ -53,7 +76,7 @@ constexpr int rdb_lds() {
 }
 }   // namespace
 
-template <int DT, int COUT>
+template <int DT, int COUT, bool BWD = false>
 __global__ __launch_bounds__(512, 2) void conv_rdb_kernel(const RdbArgs a) {
   constexpr int NT = COUT / 32;                         // 16-channel MFMA row blocks per wave
   constexpr int WPIECES = 9 * COUT / 16;                // 36 | 18 pieces: 9 taps x COUT output channels x 64 B
@@ -90,16 +113,29 @@ __global__ __launch_bounds__(512, 2) void conv_rdb_kernel(const RdbArgs a) {
 #pragma unroll
   for (int v = 0; v < NWU; ++v) {
     const int row = 16 * (wave + 8 * v) + (lane >> 2);
-    w_part[v] = (row * a.Cin + (lane & 3) * 8) * 2;
+    if constexpr (BWD) {
+      // row tap * COUT + c of the stage is row (8 - tap) * w_rows + slice * COUT + c of the dgrad image [9][w_rows][Cin]: the
+      // input gradient is the correlation with the mirrored kernel
+      const int tap = row / COUT, c = row - tap * COUT;
+      w_part[v] = (((8 - tap) * a.w_rows + c) * a.Cin + (lane & 3) * 8) * 2;
+    } else {
+      w_part[v] = (row * a.Cin + (lane & 3) * 8) * 2;
+    }
   }
   const BufSrd wsrd = make_srd(a.w, a.w_bytes);
   const int per_img = a.tiles_y * a.tiles_x;
 
   struct TileXY {
-    int n, ty, tx;
+    int n, ty, tx, sl;
   };
   auto decomp = [&](int t) {
     TileXY c;
+    c.sl = 0;
+    if constexpr (BWD) {                                // slices of one tile are consecutive work items: its halo stays in L2
+      const int tile = t / a.nslices;
+      c.sl = t - tile * a.nslices;
+      t = tile;
+    }
     c.n = t / per_img;
     const int rem = t - c.n * per_img;
     c.ty = rem / a.tiles_x;
@@ -110,7 +146,7 @@ __global__ __launch_bounds__(512, 2) void conv_rdb_kernel(const RdbArgs a) {
     const int oy0 = tc.ty * RDB_TR - 1, ox0 = tc.tx * RDB_TC - 1;
     // per-image resource: halo rows above / below the image fall outside it and read as zeros
     const BufSrd xsrd = make_srd(reinterpret_cast<const unsigned char*>(a.x) + (size_t)tc.n * a.x_img, a.x_img);
-    const int sbase = (oy0 * a.W + ox0) * a.ldx * 2 + kb * 64;
+    const int sbase = (oy0 * a.W + ox0) * a.ldx * 2 + kb * 64 + (BWD ? a.x_off * 2 : 0);
     const bool interior = ox0 >= 0 && ox0 + RDB_HP <= a.W;
     unsigned char* hdst = sHalo + buf * RDB_HALO;
 #pragma unroll
@@ -127,7 +163,7 @@ __global__ __launch_bounds__(512, 2) void conv_rdb_kernel(const RdbArgs a) {
 #pragma unroll
     for (int v = 0; v < NWU; ++v) {
       if (wave + 8 * v >= WPIECES) continue;
-      lds_dma16(wsrd, wdst + (wave + 8 * v) * 1024, (unsigned)(w_part[v] + kb * 64));
+      lds_dma16(wsrd, wdst + (wave + 8 * v) * 1024, (unsigned)(w_part[v] + kb * 64 + (BWD ? tc.sl * COUT * a.Cin * 2 : 0)));
     }
   };
 
@@ -146,7 +182,7 @@ __global__ __launch_bounds__(512, 2) void conv_rdb_kernel(const RdbArgs a) {
   fetch(cur, 0, 0);
   int buf = 0;
   const float slope = a.slope;
-  const bool leaky = a.act == DSR_ACT_LEAKY;
+  const bool leaky = !BWD && a.act == DSR_ACT_LEAKY;
 
   for (; t < a.ntiles; t += tstep) {
     const bool has_next = t + tstep < a.ntiles;
@@ -157,7 +193,7 @@ __global__ __launch_bounds__(512, 2) void conv_rdb_kernel(const RdbArgs a) {
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
         float bv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (a.bias) {
+        if (!BWD && a.bias) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) bv[r] = a.bias[chb + 16 * nt + 4 * g + r];
         }
@@ -222,6 +258,7 @@ __global__ __launch_bounds__(512, 2) void conv_rdb_kernel(const RdbArgs a) {
     const __amdgpu_buffer_rsrc_t r2rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(r2p)) + (size_t)cur.n * a.r2_img, 0, a.r2_img, 0x00020000);
     const int px = ox0 + 16 * wq + r16;                 // this lane's pixel column
+    const int ych = a.y_off + (BWD ? cur.sl * COUT : 0);  // first channel of the stored range
     auto residual = [&](const __amdgpu_buffer_rsrc_t& rs, unsigned off, float beta, float* v) {
       typedef __attribute__((ext_vector_type(2))) unsigned U2;
       const U2 rv = __builtin_bit_cast(U2, __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 0));
@@ -248,11 +285,45 @@ __global__ __launch_bounds__(512, 2) void conv_rdb_kernel(const RdbArgs a) {
             v[r] = leaky ? (s >= 0.f ? s : s * slope) : s;
           }
           const int c0 = chb + 16 * nt + 4 * g;
-          if (a.res1) {
+          if constexpr (BWD) {
+            // v = acc * gscale (+ what the range holds) (+ beta1 * res1 below channel r1_lim), times the mask from mask_lo on:
+            // all in fp32, one rounding below.  The addend is read by the block that owns the tile, before it stores it.
+            typedef __attribute__((ext_vector_type(2))) unsigned U2;
+            const unsigned pix = inside ? (unsigned)(py * a.W + px) : 0u;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] *= a.gscale;
+            if (a.self_acc) {
+              const unsigned off = inside ? (pix * a.ldy + ych + c0) * 2 : OOB;
+              const U2 rv = __builtin_bit_cast(U2, __builtin_amdgcn_raw_buffer_load_b64(yrsrc, off, 0, 0));
+              v[0] += h2f<DT>((unsigned short)(rv.x & 0xffff));
+              v[1] += h2f<DT>((unsigned short)(rv.x >> 16));
+              v[2] += h2f<DT>((unsigned short)(rv.y & 0xffff));
+              v[3] += h2f<DT>((unsigned short)(rv.y >> 16));
+            }
+            const int cabs = ych + c0;
+            if (a.res1 && cabs < a.r1_lim) {
+              const unsigned off = inside ? (pix * a.ldr1 + a.r1_off + cabs) * 2 : OOB;
+              const U2 rv = __builtin_bit_cast(U2, __builtin_amdgcn_raw_buffer_load_b64(r1rsrc, off, 0, 0));
+              v[0] = fmaf(h2f<DT>((unsigned short)(rv.x & 0xffff)), a.beta1, v[0]);
+              v[1] = fmaf(h2f<DT>((unsigned short)(rv.x >> 16)), a.beta1, v[1]);
+              v[2] = fmaf(h2f<DT>((unsigned short)(rv.y & 0xffff)), a.beta1, v[2]);
+              v[3] = fmaf(h2f<DT>((unsigned short)(rv.y >> 16)), a.beta1, v[3]);
+            }
+            if (a.res2 && cabs >= a.mask_lo) {
+              const unsigned off = inside ? (pix * a.ldr2 + a.r2_off + cabs) * 2 : OOB;
+              const U2 rv = __builtin_bit_cast(U2, __builtin_amdgcn_raw_buffer_load_b64(r2rsrc, off, 0, 0));
+              // (the stored activation carries the sign of its pre-activation for a positive slope; -0.0 counts as >= 0)
+              v[0] *= h2f<DT>((unsigned short)(rv.x & 0xffff)) >= 0.f ? 1.f : slope;
+              v[1] *= h2f<DT>((unsigned short)(rv.x >> 16)) >= 0.f ? 1.f : slope;
+              v[2] *= h2f<DT>((unsigned short)(rv.y & 0xffff)) >= 0.f ? 1.f : slope;
+              v[3] *= h2f<DT>((unsigned short)(rv.y >> 16)) >= 0.f ? 1.f : slope;
+            }
+          }
+          if (!BWD && a.res1) {
             const unsigned off = inside ? (unsigned)(((py * a.W + px) * a.ldr1 + a.r1_off + c0) * 2) : OOB;
             residual(r1rsrc, off, a.beta1, v);
           }
-          if (a.res2) {
+          if (!BWD && a.res2) {
             const unsigned off = inside ? (unsigned)(((py * a.W + px) * a.ldr2 + a.r2_off + c0) * 2) : OOB;
             residual(r2rsrc, off, a.beta2, v);
           }
@@ -272,7 +343,7 @@ __global__ __launch_bounds__(512, 2) void conv_rdb_kernel(const RdbArgs a) {
         const int row = pl >> 6, col = pl & 63;
         const U4 v = *reinterpret_cast<const U4*>(sC + (row * 64 + col) * CSTRIDE + chunk * 16);
         const int sy = oy0 + half * 4 + row, sx = ox0 + col;
-        unsigned off = (unsigned)(((sy * a.W + sx) * a.ldy + a.y_off) * 2 + chunk * 16);
+        unsigned off = (unsigned)(((sy * a.W + sx) * a.ldy + ych) * 2 + chunk * 16);
         if (!(sy < a.H && sx < a.W)) off = OOB;
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v), yrsrc, off, 0, 0);
       }
@@ -388,6 +459,96 @@ extern "C" int dsr_conv_rdb_fwd(const dsr_rdb_conv* c, hipStream_t st) {
   }
 #undef RDB_LAUNCH
   return dsr_launch_status("dsr_conv_rdb_fwd");
+}
+
+// ---- input gradient on growth buffers
+static const char* rdb_dgrad_shape_error(const dsr_rdb_dgrad* c) {
+  if (!DSR_DTYPE_OK(c->dtype)) return "dtype is neither DSR_BF16 nor DSR_F16";
+  if (c->N < 1 || c->H < 1 || c->W < 1) return "N, H, W must be positive";
+  if (c->K != 32 && c->K != 64) return "K must be 32 or 64";
+  if (!rdb_mult32(c->Cout) || c->Cout > 1024) return "Cout must be a multiple of 32 in 32..1024";
+  if (!rdb_mult32(c->lddy) || c->dy_off < 0 || c->dy_off % 32 || c->dy_off + c->K > c->lddy) return "lddy / dy_off: multiples of 32 with dy_off + K <= lddy";
+  if (!rdb_mult32(c->lddx) || c->Cout > c->lddx) return "lddx must be a multiple of 32 and >= Cout";
+  if (c->g_limit < 0 || c->g_limit % 32 || c->g_limit > c->Cout) return "g_limit must be a multiple of 32 in 0..Cout";
+  if (c->g_limit && (!rdb_mult32(c->ldg) || c->g_limit > c->ldg)) return "ldg must be a multiple of 32 and >= g_limit";
+  if (c->mask_lo < 0 || c->mask_lo % 32 || c->mask_lo > c->Cout) return "mask_lo must be a multiple of 32 in 0..Cout";
+  if (c->mask_lo < c->Cout && (!rdb_mult32(c->ldact) || c->Cout > c->ldact || !(c->slope > 0.f))) return "ldact must be a multiple of 32 and >= Cout, slope > 0";
+  const size_t pix = (size_t)c->H * c->W;
+  int ld_max = c->lddy > c->lddx ? c->lddy : c->lddx;
+  if (c->g_limit && c->ldg > ld_max) ld_max = c->ldg;
+  if (c->mask_lo < c->Cout && c->ldact > ld_max) ld_max = c->ldact;
+  if (pix * ld_max * 2 >= 0x7FFFFF00ull) return "a tensor of 2^31 bytes or more per image";
+  if (pix * ld_max * 2 * c->N >= 0x100000000ull) return "a tensor of 2^32 bytes or more";
+  return nullptr;
+}
+
+extern "C" int dsr_conv_rdb_dgrad_supported(const dsr_rdb_dgrad* c) {
+  if (!c) return 0;
+  return rdb_dgrad_shape_error(c) == nullptr ? 1 : 0;
+}
+
+extern "C" int dsr_conv_rdb_dgrad(const dsr_rdb_dgrad* c, hipStream_t st) {
+  DSR_REQUIRE(c, "conv_rdb_dgrad: null descriptor");
+  DSR_REQUIRE(c->dy && c->wd && c->dx, "conv_rdb_dgrad: null pointer (dy, wd or dx)");
+  const char* err = rdb_dgrad_shape_error(c);
+  DSR_REQUIRE(!err, "conv_rdb_dgrad: %s", err);
+  DSR_REQUIRE(!c->g_limit || c->g, "conv_rdb_dgrad: g_limit > 0 without g");
+  DSR_REQUIRE(c->mask_lo >= c->Cout || c->act_out, "conv_rdb_dgrad: mask_lo < Cout without act_out");
+  DSR_REQUIRE(!(c->dy == c->dx && c->dy_off < c->Cout), "conv_rdb_dgrad: the output range overlaps the input range (dy == dx and dy_off %d < Cout %d)",
+              c->dy_off, c->Cout);
+  DSR_REQUIRE(!(c->g_limit && c->g == c->dx) && !(c->mask_lo < c->Cout && c->act_out == c->dx), "conv_rdb_dgrad: g / act_out must not be the output tensor");
+  const int cout = c->Cout % 64 == 0 ? 64 : 32;         // channels per work item
+  RdbArgs a{};
+  a.x = c->dy;
+  a.w = c->wd;
+  a.y = c->dx;
+  a.res1 = c->g_limit ? c->g : nullptr;
+  a.res2 = c->mask_lo < c->Cout ? c->act_out : nullptr;
+  a.H = c->H;
+  a.W = c->W;
+  a.Cin = c->K;
+  a.ldx = c->lddy;
+  a.kblocks = c->K / 32;
+  a.ldy = c->lddx;
+  a.y_off = 0;
+  a.ldr1 = a.res1 ? c->ldg : 0;
+  a.ldr2 = a.res2 ? c->ldact : 0;
+  a.act = DSR_ACT_NONE;
+  a.slope = c->slope;
+  a.beta1 = c->g_scale;
+  a.tiles_y = (c->H + RDB_TR - 1) / RDB_TR;
+  a.tiles_x = (c->W + RDB_TC - 1) / RDB_TC;
+  a.nslices = c->Cout / cout;
+  a.ntiles = c->N * a.tiles_y * a.tiles_x * a.nslices;
+  const size_t pix = (size_t)c->H * c->W;
+  a.w_bytes = (unsigned)(9 * c->Cout * c->K * 2);
+  a.x_img = (unsigned)(pix * c->lddy * 2);
+  a.y_img = (unsigned)(pix * c->lddx * 2);
+  a.r1_img = (unsigned)(pix * a.ldr1 * 2);
+  a.r2_img = (unsigned)(pix * a.ldr2 * 2);
+  a.x_off = c->dy_off;
+  a.w_rows = c->Cout;
+  a.r1_lim = c->g_limit;
+  a.mask_lo = c->mask_lo;
+  a.self_acc = c->accumulate ? 1 : 0;
+  a.gscale = c->scale;
+  int cap = c->max_blocks > 0 ? c->max_blocks : 256;
+  const int blocks = a.ntiles < cap ? a.ntiles : cap;
+  static LdsOptIn optin[4];
+#define RDB_LAUNCH(I, DTV, COUTV)                                                                                   \
+  do {                                                                                                              \
+    optin[I].ensure((const void*)conv_rdb_kernel<DTV, COUTV, true>, rdb_lds<COUTV>());                              \
+    hipLaunchKernelGGL((conv_rdb_kernel<DTV, COUTV, true>), dim3(blocks), dim3(512), rdb_lds<COUTV>(), st, a);      \
+  } while (0)
+  if (c->dtype == DSR_DTYPE_BF16) {
+    if (cout == 64) RDB_LAUNCH(0, DSR_DTYPE_BF16, 64);
+    else RDB_LAUNCH(1, DSR_DTYPE_BF16, 32);
+  } else {
+    if (cout == 64) RDB_LAUNCH(2, DSR_DTYPE_F16, 64);
+    else RDB_LAUNCH(3, DSR_DTYPE_F16, 32);
+  }
+#undef RDB_LAUNCH
+  return dsr_launch_status("dsr_conv_rdb_dgrad");
 }
 
 extern "C" int dsr_scale_add16(int dtype, const void* a, float beta, const void* b, void* out, size_t nvec, hipStream_t st) {

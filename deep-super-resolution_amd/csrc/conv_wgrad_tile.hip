@@ -133,8 +133,19 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tile_kernel(const WgradTile
 //     (pixel index & 7), depends on the lane and the tap COLUMN only: every read address is one per-lane register
 //     plus an immediate -- the 9-tap loop carries no address arithmetic (the older kernel spent ~6 VALU
 //     instructions per MFMA on it).
-template <int DT>
-__device__ __forceinline__ void conv_wgrad_dma_body(const WgradTileArgs& a, const int pair, const int ychunk) {
+// (pixel strides and channel offsets of the two operands: the padded channel counts and 0 for a dense tensor; fields of their
+//  own for a channel range of a wider tensor, WgradRdbArgs -- conv_rdb_bwd.hip)
+__device__ __forceinline__ int wg_ldx(const WgradTileArgs& a) { return a.CinP; }
+__device__ __forceinline__ int wg_ldy(const WgradTileArgs& a) { return a.CoutP; }
+__device__ __forceinline__ int wg_xoff(const WgradTileArgs&) { return 0; }
+__device__ __forceinline__ int wg_yoff(const WgradTileArgs&) { return 0; }
+__device__ __forceinline__ int wg_ldx(const WgradRdbArgs& a) { return a.ldx; }
+__device__ __forceinline__ int wg_ldy(const WgradRdbArgs& a) { return a.ldy; }
+__device__ __forceinline__ int wg_xoff(const WgradRdbArgs& a) { return a.x_off; }
+__device__ __forceinline__ int wg_yoff(const WgradRdbArgs& a) { return a.y_off; }
+
+template <int DT, class Args>
+__device__ __forceinline__ void conv_wgrad_dma_body(const Args& a, const int pair, const int ychunk) {
   constexpr int R = 2, HC = 40, HR = R + 2;
   constexpr int XB = HR * HC * 128, YB = R * 32 * 128, STAGE = XB + YB;
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE];
@@ -147,6 +158,7 @@ __device__ __forceinline__ void conv_wgrad_dma_body(const WgradTileArgs& a, cons
   // accumulator still sums the same products in the same order: bit-identical.
   const int g = lane >> 4, l16 = lane & 15, q4 = l16 >> 2, cc = 4 * (l16 & 3);
   const int co0 = (pair / a.tiles_ci) * 64, ci0 = (pair % a.tiles_ci) * 64;
+  const int ldx = wg_ldx(a), ldy = wg_ldy(a), cx0 = wg_xoff(a) + ci0, cy0 = wg_yoff(a) + co0;
 
   f32x4 acc[9][4];
 #pragma unroll
@@ -188,15 +200,15 @@ __device__ __forceinline__ void conv_wgrad_dma_body(const WgradTileArgs& a, cons
   for (int u = 0; u < NX; ++u) {
     const int q = pb + 32 * u;
     const int hr = q / HC, hc = q - hr * HC;
-    xpart[u] = (xc_ok && hc < 34) ? ((hr * a.IW + hc) * a.CinP + ci0 + chunk * 8) * 2 : FAR;
+    xpart[u] = (xc_ok && hc < 34) ? ((hr * a.IW + hc) * ldx + cx0 + chunk * 8) * 2 : FAR;
     hc_pack |= (unsigned)hc << (6 * u);
   }
 #pragma unroll
   for (int u = 0; u < NY; ++u) {
     const int p = pb + 32 * u;
-    ypart[u] = yc_ok ? (((p >> 5) * a.OW + (p & 31)) * a.CoutP + co0 + chunk * 8) * 2 : FAR;
+    ypart[u] = yc_ok ? (((p >> 5) * a.OW + (p & 31)) * ldy + cy0 + chunk * 8) * 2 : FAR;
   }
-  const unsigned ximg = (unsigned)(a.IH * a.IW * a.CinP * 2), yimg = (unsigned)(a.OH * a.OW * a.CoutP * 2);
+  const unsigned ximg = (unsigned)(a.IH * a.IW * ldx * 2), yimg = (unsigned)(a.OH * a.OW * ldy * 2);
   const bool fast = a.pad_mode == DSR_PAD_ZERO;
   struct TileXY {
     int n, ty, tx;
@@ -208,8 +220,8 @@ __device__ __forceinline__ void conv_wgrad_dma_body(const WgradTileArgs& a, cons
     if (fast) {
       const BufSrd xr = make_srd(const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(a.x)) + (size_t)n * ximg, ximg);
       const BufSrd yr = make_srd(const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(a.dy)) + (size_t)n * yimg, yimg);
-      const int xs = ((oy0 - a.pad) * a.IW + ox0 - a.pad) * a.CinP * 2;       // negative above the image: out of range
-      const int ys = (oy0 * a.OW + ox0) * a.CoutP * 2;
+      const int xs = ((oy0 - a.pad) * a.IW + ox0 - a.pad) * ldx * 2;           // negative above the image: out of range
+      const int ys = (oy0 * a.OW + ox0) * ldy * 2;
       unsigned char* dx = st + 8 * wave * 128;
       if (ox0 - a.pad >= 0 && ox0 - a.pad + 34 <= a.IW) {                        // interior columns
 #pragma unroll
@@ -240,14 +252,14 @@ __device__ __forceinline__ void conv_wgrad_dma_body(const WgradTileArgs& a, cons
       bool ok = xc_ok && hc < 34;
       const int iy = pad_index(oy0 + hr - a.pad, a.IH, a.pad_mode, ok);
       const int ix = pad_index(ox0 + hc - a.pad, a.IW, a.pad_mode, ok);
-      lds_dma16(xrsrc, st + (32 * u + 8 * wave) * 128, ok ? (unsigned)((((n * a.IH + iy) * a.IW + ix) * a.CinP + ci0 + chunk * 8) * 2) : OOB);
+      lds_dma16(xrsrc, st + (32 * u + 8 * wave) * 128, ok ? (unsigned)((((n * a.IH + iy) * a.IW + ix) * ldx + cx0 + chunk * 8) * 2) : OOB);
     }
 #pragma unroll
     for (int u = 0; u < (R * 32) / 32; ++u) {       // 2 per wave: the dY tile
       const int p = pb + 32 * u;
       const int oy = oy0 + (p >> 5), ox = ox0 + (p & 31);
       const bool ok = yc_ok && oy < a.OH && ox < a.OW;
-      lds_dma16(yrsrc, st + XB + (32 * u + 8 * wave) * 128, ok ? (unsigned)((((n * a.OH + oy) * a.OW + ox) * a.CoutP + co0 + chunk * 8) * 2) : OOB);
+      lds_dma16(yrsrc, st + XB + (32 * u + 8 * wave) * 128, ok ? (unsigned)((((n * a.OH + oy) * a.OW + ox) * ldy + cy0 + chunk * 8) * 2) : OOB);
     }
   };
   auto next_tile = [&](TileXY c) {                   // tiles of a block are consecutive
@@ -574,6 +586,20 @@ static void launch_dt(const WgradTileArgs& a, int KH, int stride, dim3 grid, hip
     hipLaunchKernelGGL((conv_wgrad_dma_s2_kernel<DT>), grid, dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL((conv_wgrad_tile_kernel<DT, 1, 1, 1>), grid, dim3(256), 0, st, a);
+}
+
+// conv_wgrad_dma_body on channel ranges of wider tensors (a dense block's growth buffers, conv_rdb_bwd.hip): grid.x walks the
+// list of (co tile, ci tile) pairs that hold a weight, four bits each in pair_map.
+template <int DT>
+__global__ __launch_bounds__(256, 2) void conv_wgrad_rdb_kernel(const WgradRdbArgs a) {
+  conv_wgrad_dma_body<DT>(a, (int)((a.pair_map >> (4 * blockIdx.x)) & 15u), blockIdx.y);
+}
+
+void dsr_launch_wgrad_rdb(const WgradRdbArgs& a, int npairs, int ychunks, int dtype, hipStream_t st) {
+  if (dtype == DSR_DTYPE_BF16)
+    hipLaunchKernelGGL((conv_wgrad_rdb_kernel<DSR_DTYPE_BF16>), dim3(npairs, ychunks), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((conv_wgrad_rdb_kernel<DSR_DTYPE_F16>), dim3(npairs, ychunks), dim3(256), 0, st, a);
 }
 
 void dsr_launch_wgrad_dma_batch(const WgradBatchArgs& b, int dtype, hipStream_t st) {

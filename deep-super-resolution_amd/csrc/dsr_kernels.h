@@ -117,6 +117,13 @@ struct WgradReduceBatchArgs {
   int count, total_blocks;
 };
 void dsr_launch_wgrad_reduce_batch(const WgradReduceBatchArgs& r, hipStream_t st);
+// the 3x3 / stride-1 kernel on channel ranges of wider tensors (conv_rdb_bwd.hip): x is read in channels [x_off, x_off + CinP) of
+// a tensor with pixel stride ldx, dy in [y_off, y_off + CoutP) at stride ldy; block x of the grid owns pair (pair_map >> 4 x) & 15
+struct WgradRdbArgs : WgradTileArgs {
+  int ldx, x_off, ldy, y_off;
+  unsigned pair_map;
+};
+void dsr_launch_wgrad_rdb(const WgradRdbArgs& a, int npairs, int ychunks, int dtype, hipStream_t st);
 // returns the number of partial slabs (ychunks) the launch will write, 0 if the shape is not handled
 int dsr_wgrad_tile_plan(int KH, int KW, int stride, int N, int OH, int OW, int CinP, int CoutP, WgradTileArgs* a);
 void dsr_launch_wgrad_tile(const WgradTileArgs& a, int KH, int stride, int ychunks, int dtype, hipStream_t st);

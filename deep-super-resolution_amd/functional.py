@@ -1821,6 +1821,195 @@ def rdb_forward(buf_in, weights, biases, buf_out, res2=None, slope=0.2, beta=0.2
             rdb_conv(buf_in, cin, wf, bk, buf_out, 0, nf, res1=buf_in, beta1=beta, res2=res2, beta2=beta)
 
 
+# ----------------------------------------------------------------------------- ... and its backward on the same buffers
+RDB_WGRAD_MIN_TILES = 8      # csrc/conv_rdb_bwd.hip: the pixel range is split into chunks of at least this many 2 x 32 tiles
+
+
+def rdb_dgrad(dy, dy_off, k, wd, dx, cout, scale=1.0, accumulate=False, g=None, g_limit=0, g_scale=1.0, act_out=None,
+              mask_lo=None, slope=0.0, max_blocks=0):
+    """One dsr_conv_rdb_dgrad launch: channels [dy_off, dy_off + k) of dy against the dgrad image wd [9][cout][k] into
+    channels [0, cout) of dx (see include/dsr_hip.h for the epilogue).  mask_lo=None: no mask."""
+    _need_gpu(dy)
+    for t in (dy, dx, g, act_out):
+        if t is not None and not (t.is_contiguous() and t.dim() == 4 and t.dtype == dy.dtype and t.shape[:3] == dy.shape[:3]):
+            raise ValueError("rdb_dgrad: contiguous NHWC tensors of one N, H, W and dtype are expected")
+    n, h, w, lddy = dy.shape
+    d = _lib.RdbDgrad(_dt(dy), n, h, w, k, cout, dy.data_ptr(), lddy, dy_off, wd.data_ptr(), float(scale), dx.data_ptr(),
+                      dx.shape[3], int(bool(accumulate)), None if g is None else g.data_ptr(), 0 if g is None else g.shape[3],
+                      g_limit if g is not None else 0, float(g_scale), None if act_out is None else act_out.data_ptr(),
+                      0 if act_out is None else act_out.shape[3], cout if mask_lo is None else mask_lo, float(slope),
+                      int(max_blocks))
+    return check(_lib.lib().dsr_conv_rdb_dgrad(C.byref(d), _stream()))
+
+
+def _rdb_wgrad_desc(n, h, w, dt, x=None, dy=None, g=None, ldg=64, gscale=1.0, dws=None, dbs=None):
+    tab = lambda ts: (C.c_void_p * 5)(*[None if t is None else t.data_ptr() for t in (ts or [None] * 5)])
+    p = lambda t: None if t is None else t.data_ptr()
+    return _lib.RdbWgrad(dt, n, h, w, p(x), 192, p(dy), 192, p(g), ldg, float(gscale), tab(dws), tab(dbs))
+
+
+def rdb_wgrad_workspace(n, h, w, dtype):
+    """Bytes of workspace of dsr_conv_rdb_wgrad on [n, h, w, 192] buffers, and the number of pixel chunks it sums over."""
+    d = _rdb_wgrad_desc(n, h, w, BF16 if dtype == torch.bfloat16 else F16)
+    return _lib.lib().dsr_conv_rdb_wgrad_workspace(C.byref(d)), _lib.lib().dsr_conv_rdb_wgrad_chunks(C.byref(d))
+
+
+def rdb_wgrad(x, dy, g, gscale, dws, dbs, ws=None):
+    """dsr_conv_rdb_wgrad: the weight / bias gradients of one dense block into the fp32 tensors dws / dbs (five entries each,
+    None: not computed) from its forward buffer x, the gradient buffer dy (channels [64, 192) final) and dL/dout g."""
+    _need_gpu(x)
+    n, h, w, ld = x.shape
+    if not (x.is_contiguous() and dy.is_contiguous() and g.is_contiguous() and dy.shape == x.shape and ld == 192
+            and g.shape[:3] == x.shape[:3] and dy.dtype == x.dtype and g.dtype == x.dtype):
+        raise ValueError("rdb_wgrad: contiguous [N,H,W,192] buffers and a g of the same N, H, W and dtype are expected")
+    for k, (dw, db) in enumerate(zip(dws, dbs)):
+        cout, cin = (32, 64 + 32 * k) if k < 4 else (64, 192)
+        if dw is not None and not (dw.is_contiguous() and dw.dtype == torch.float32 and tuple(dw.shape) == (cout, cin, 3, 3)):
+            raise ValueError(f"rdb_wgrad: dw[{k}] must be a contiguous fp32 [{cout},{cin},3,3] tensor")
+        if db is not None and not (db.is_contiguous() and db.dtype == torch.float32 and tuple(db.shape) == (cout,)):
+            raise ValueError(f"rdb_wgrad: db[{k}] must be a contiguous fp32 [{cout}] tensor")
+    d = _rdb_wgrad_desc(n, h, w, _dt(x), x, dy, g, g.shape[3], gscale, dws, dbs)
+    lib = _lib.lib()
+    need = lib.dsr_conv_rdb_wgrad_workspace(C.byref(d))
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
+    return check(lib.dsr_conv_rdb_wgrad(C.byref(d), _ptr(ws), ws.numel(), _stream()))
+
+
+def rdb_train_supported(x_shape, dtype, num_feat, num_grow_ch):
+    """rdb_supported(...) and do dsr_conv_rdb_dgrad / dsr_conv_rdb_wgrad take the backward of such a block?"""
+    if not rdb_supported(x_shape, dtype, num_feat, num_grow_ch) or (num_feat, num_grow_ch) != (64, 32):
+        return False
+    n, h, w = x_shape[:3]
+    key = (n, h, w, dtype)
+    hit = _rdb_train_cache.get(key)
+    if hit is None:
+        if len(_rdb_train_cache) > 1024:
+            _rdb_train_cache.clear()
+        lib = _lib.lib()
+        dt = BF16 if dtype == torch.bfloat16 else F16
+        hit = bool(lib.dsr_conv_rdb_wgrad_supported(C.byref(_rdb_wgrad_desc(n, h, w, dt))))
+        for k in range(5):
+            kk, cout = (32, 64 + 32 * k) if k < 4 else (64, 192)
+            d = _lib.RdbDgrad(dt, n, h, w, kk, cout, None, 192 if k < 4 else 64, cout if k < 4 else 0, None, 1.0, None, 192, 1, None,
+                              64, 64, 1.0, None, 192, max(cout - 32, 0) if k else cout, 0.2, 0)
+            hit = hit and bool(lib.dsr_conv_rdb_dgrad_supported(C.byref(d)))
+        _rdb_train_cache[key] = hit
+    return hit
+
+
+_rdb_train_cache = {}
+
+
+class RRDBBody(torch.autograd.Function):
+    """The whole body of an RRDBNet (every RRDB, three dense blocks each) as ONE autograd node on growth buffers:
+    ``RRDBBody.apply(feat, cfg, w, b, w, b, ...)`` with feat [N,H,W,64], cfg = dict(slope=, beta=) and the weight and bias of
+    conv1..5 of every dense block in network order (30 tensors per RRDB).
+
+    Forward: one [N,H,W,192] buffer per dense block and the five dsr_conv_rdb_fwd launches of rdb_forward on each -- the bits
+    of the no-grad forward; the buffers are the saved activations (192 channels per block: x, x1..x4), with the forward-time
+    dgrad images of the weights.  Backward, per dense block in reverse order, on a gradient buffer G of the same shape (three
+    of them rotate): dgrad5 fills G from g = dL/dout, dgrad4..1 accumulate into channel prefixes of G in place, each applying
+    the LeakyReLU mask of the slice it completes (dsr_conv_rdb_dgrad); one dsr_conv_rdb_wgrad forms the block's ten
+    parameter gradients from (buffer, G, g).  No concatenation or split copy, no activation-backward pass, nothing read on
+    the host; the only box copies are feat into the first buffer and G[..., :64] of the first block out as dL/dfeat."""
+
+    @staticmethod
+    def forward(ctx, feat, cfg, *params):
+        _need_gpu(feat)
+        feat = feat.contiguous()
+        n, h, w, nf = feat.shape
+        nd = len(params) // 10
+        if nf != 64 or nd == 0 or nd % 3 or len(params) != 10 * nd:
+            raise ValueError("RRDBBody: feat [N,H,W,64] and ten parameters per dense block, three blocks per RRDB")
+        if not rdb_train_supported(feat.shape, feat.dtype, 64, 32):
+            raise RuntimeError("RRDBBody: the growth-buffer kernels do not take this shape (or DSR_RRDB_FUSED=0)")
+        slope, beta = float(cfg["slope"]), float(cfg["beta"])
+        if not slope > 0.0:
+            raise ValueError("RRDBBody: the LeakyReLU slope must be > 0 (the mask is derived from the stored output)")
+        dt = _dt(feat)
+        bufs = [torch.empty((n, h, w, 192), dtype=feat.dtype, device=feat.device) for _ in range(nd)]
+        out = torch.empty((n, h, w, 64), dtype=feat.dtype, device=feat.device)
+        _box_copy(feat, bufs[0], n, h, w, 64, 0, 0, 0, 0, 0, 0)
+        wds = []
+        for d in range(nd):
+            buf, dst = bufs[d], (bufs[d + 1] if d + 1 < nd else out)
+            for k in range(5):
+                wk, bk = params[10 * d + 2 * k], params[10 * d + 2 * k + 1]
+                cin, cout = 64 + 32 * k, (32 if k < 4 else 64)
+                if tuple(wk.shape) != (cout, cin, 3, 3):
+                    raise ValueError(f"RRDBBody: conv{k + 1} weight of shape {tuple(wk.shape)}")
+                wf, wd = packed_weights(wk, ConvDesc(dt, n, h, w, cin, cout, 3, 3, 1, 1, PAD_ZERO), feat.dtype)
+                wds.append(wd)
+                bk = None if bk is None else bk.detach()
+                if k < 4:
+                    rdb_conv(buf, cin, wf, bk, buf, cin, 32, act=ACT_LEAKY, slope=slope)
+                elif d % 3 < 2:
+                    rdb_conv(buf, cin, wf, bk, dst, 0, 64, res1=buf, beta1=beta)
+                else:
+                    rdb_conv(buf, cin, wf, bk, dst, 0, 64, res1=buf, beta1=beta, res2=bufs[d - 2], beta2=beta)
+        ctx.nd, ctx.slope, ctx.beta = nd, slope, beta
+        ctx.shapes = [None if p is None else tuple(p.shape) for p in params]
+        ctx.save_for_backward(*bufs, *wds)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        nd = ctx.nd
+        saved = ctx.saved_tensors
+        bufs, wds = saved[:nd], saved[nd:]
+        g = gout.contiguous()
+        n, h, w, _ = g.shape
+        dev = g.device
+        need_feat = ctx.needs_input_grad[0]
+        need_p = ctx.needs_input_grad[2:]
+        f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))
+        beta = f32(ctx.beta)
+        beta_sq = float(torch.tensor(ctx.beta, dtype=torch.float32) * torch.tensor(ctx.beta, dtype=torch.float32))
+        grads = [None] * (10 * nd)
+        free, ws = [], None
+        take = lambda: free.pop() if free else torch.empty((n, h, w, 192), dtype=g.dtype, device=dev)
+        g_rrdb = g               # dL/d(output of the RRDB being walked): its input receives it too
+        for d in range(nd - 1, -1, -1):
+            j = d % 3
+            buf, G = bufs[d], take()
+            if j == 2:
+                g_rrdb = g
+            bp = beta_sq if j == 2 else beta
+            wd = wds[5 * d:5 * d + 5]
+            # G[..., 0:192] = bp * dgrad5(g), channels [0, 64) + g (third block: + beta * g), channels [160, 192) masked by x4
+            rdb_dgrad(g, 0, 64, wd[4], G, 192, scale=bp, g=g, g_limit=64, g_scale=(beta if j == 2 else 1.0), act_out=buf,
+                      mask_lo=160, slope=ctx.slope)
+            for k in (3, 2, 1):
+                c = 64 + 32 * k          # slice [c, c + 32) = dY_{k+1} is final; its input gradient goes to [0, c)
+                rdb_dgrad(G, c, 32, wd[k], G, c, accumulate=True, act_out=buf, mask_lo=c - 32, slope=ctx.slope)
+            if any(need_p[10 * d:10 * d + 10]):
+                dws = [torch.empty(ctx.shapes[10 * d + 2 * k], dtype=torch.float32, device=dev)
+                       if need_p[10 * d + 2 * k] else None for k in range(5)]
+                dbs = [torch.empty(ctx.shapes[10 * d + 2 * k + 1], dtype=torch.float32, device=dev)
+                       if ctx.shapes[10 * d + 2 * k + 1] is not None and need_p[10 * d + 2 * k + 1] else None for k in range(5)]
+                if ws is None:
+                    ws = torch.empty(max(rdb_wgrad_workspace(n, h, w, g.dtype)[0], 16), dtype=torch.uint8, device=dev)
+                rdb_wgrad(buf, G, g, bp, dws, dbs, ws)
+                for k in range(5):
+                    grads[10 * d + 2 * k], grads[10 * d + 2 * k + 1] = dws[k], dbs[k]
+            if d > 0 or need_feat:
+                # the first block of an RRDB also hands the RRDB's own dL/dout to its input (the outer residual)
+                rdb_dgrad(G, 64, 32, wd[0], G, 64, accumulate=True, g=g_rrdb if j == 0 else None, g_limit=64, g_scale=1.0)
+            # g of this block is dead now; a G buffer goes back to the pool unless the RRDB still needs it as g_rrdb
+            if g.shape[3] == 192 and not (j != 0 and g is g_rrdb):
+                free.append(g)
+            if j == 0 and g_rrdb is not g and g_rrdb.shape[3] == 192:
+                free.append(g_rrdb)
+            g = G
+        dfeat = None
+        if need_feat:
+            dfeat = torch.empty((n, h, w, 64), dtype=g.dtype, device=dev)
+            _box_copy(g, dfeat, n, h, w, 64, 0, 0, 0, 0, 0, 0)
+        return (dfeat, None) + tuple(grads)
+
+
 class BNAct(torch.autograd.Function):
     """act(BatchNorm2d(x)) on a tensor that does not come straight out of a conv (DIP: BN after Concat,
     models/DIP/skip.py:51)."""

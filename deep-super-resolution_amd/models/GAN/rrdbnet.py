@@ -19,8 +19,12 @@ The child nn.Conv2d objects are parameter holders only, as in generator.py.  Two
     residual scalings ride in conv5's epilogue (csrc/conv_rdb.hip);
   * composed (autograd): ConvAct / ConcatChannels / ScaleAdd, which trains through the existing input- and weight-gradient
     kernels.  Channel counts the fused kernel does not take (anything but num_feat 64, num_grow_ch 32), and
-    DSR_RRDB_FUSED=0, take this form without a gradient too.
-Neither form reads anything on the host, so both replay from a HIP graph.
+    DSR_RRDB_FUSED=0, take this form without a gradient too;
+  * fused training (autograd, opt-in: ``net.set_fused_training()``): the whole body is one functional.RRDBBody node -- the
+    fused forward with one growth buffer per dense block kept as the saved activations, and a backward that runs on
+    gradient buffers of the same shape (csrc/conv_rdb.hip's input-gradient form, csrc/conv_rdb_bwd.hip).  Same forward
+    bits as the fused form; taken where functional.rdb_train_supported says so, else the composed form.
+No form reads anything on the host, so all replay from a HIP graph.
 """
 import torch
 import torch.nn as nn
@@ -96,6 +100,12 @@ class RRDBNet(nn.Module):
         self.conv_last = nn.Conv2d(num_feat, num_out_ch, 3, 1, 1)
         self.num_feat, self.num_grow_ch = num_feat, num_grow_ch
         self.compute_dtype = torch.bfloat16     # float16 is accepted too
+        self.fused_training = False             # a plain attribute (not in the state_dict): see set_fused_training
+
+    def set_fused_training(self, on=True):
+        """Train the body on its growth buffers (functional.RRDBBody) where the kernels take the shape; returns self."""
+        self.fused_training = bool(on)
+        return self
 
     def receptive_halo(self):
         """Input pixels of context a tile needs for its interior to equal the whole-image result: conv_first and conv_body
@@ -124,6 +134,14 @@ class RRDBNet(nn.Module):
                 block.rdb3._fused(c, b, res2=a)
         return out
 
+    def _body_train(self, feat):
+        params = []
+        for block in self.body:
+            for rdb in (block.rdb1, block.rdb2, block.rdb3):
+                for conv in rdb._convs():
+                    params += [conv.weight, conv.bias]
+        return F.RRDBBody.apply(feat, dict(slope=SLOPE, beta=BETA), *params)
+
     def forward(self, x):
         f = self.unshuffle
         if f > 1:
@@ -136,6 +154,8 @@ class RRDBNet(nn.Module):
             body = feat
         elif not self._wants_grad(x) and F.rdb_supported(feat.shape, feat.dtype, self.num_feat, self.num_grow_ch):
             body = self._body_fused(feat)
+        elif self.fused_training and F.rdb_train_supported(feat.shape, feat.dtype, self.num_feat, self.num_grow_ch):
+            body = self._body_train(feat)
         else:
             body = feat
             for block in self.body:

@@ -780,6 +780,71 @@ typedef struct {
 } dsr_rdb_conv;
 int dsr_conv_rdb_supported(const dsr_rdb_conv* c);
 int dsr_conv_rdb_fwd(const dsr_rdb_conv* c, dsr_stream_t s);
+
+/* Backward of a dense block on its growth buffers (conv_rdb.hip, conv_rdb_bwd.hip).  B is the block's forward buffer
+ * [N][H][W][192] (x in [0, 64), x_k in [64 + 32 (k - 1), 64 + 32 k)), G a gradient buffer of B's shape.
+ *
+ * dsr_conv_rdb_dgrad, one 3x3 / stride 1 / pad 1 input gradient: the K in {32, 64} channels [dy_off, dy_off + K) of dy are
+ * correlated with the mirrored kernel (wd: the dgrad image [9][Cout][K] of dsr_conv_pack_weight for a [K][Cout][3][3] weight),
+ * giving Cout (a multiple of 32) channels that land in channels [0, Cout) of dx:
+ *     v = scale * sum_taps sum_k dy[n, y-dy, x-dx, dy_off + k] * w[k, c, dy, dx]    products of 16-bit operands, fp32 sums
+ *     if accumulate: v = v + dx[n, y, x, c]                                        (the 16-bit value already there)
+ *     if c < g_limit: v = fmaf(g[n, y, x, c], g_scale, v)
+ *     if c >= mask_lo: v = v * (act_out[n, y, x, c] >= 0 ? 1 : slope)              LeakyReLU mask from the stored OUTPUT
+ *     dx[n, y, x, c] = r16(v)                                                      one rounding, to nearest even
+ * dy may be dx itself (in place) when the ranges are disjoint, dy_off >= Cout: a tile's output bytes are read and written
+ * only by the one block that owns the tile, and halo reads touch only the other channel range.  g and act_out are other
+ * tensors than dx.  DSR_E_ARG before anything is launched for a NULL dy / wd / dx (or g with g_limit > 0, act_out with
+ * mask_lo < Cout), a bad dtype, size, stride, offset or limit, overlapping ranges, a tensor of 2^31 bytes or more per image or
+ * 2^32 bytes or more in total.  dsr_conv_rdb_dgrad_supported looks at the shape fields only. */
+typedef struct {
+  int dtype;               /* DSR_BF16 | DSR_F16 */
+  int N, H, W;
+  int K, Cout;
+  const void* dy;          /* [N][H][W][lddy], channels [dy_off, dy_off + K) are read */
+  int lddy, dy_off;
+  const void* wd;          /* [9][Cout][K] */
+  float scale;
+  void* dx;                /* [N][H][W][lddx], channels [0, Cout) are written */
+  int lddx;
+  int accumulate;
+  const void* g;           /* [N][H][W][ldg] or NULL, channels [0, g_limit) */
+  int ldg, g_limit;
+  float g_scale;
+  const void* act_out;     /* [N][H][W][ldact] or NULL: the forward buffer, read in channels [mask_lo, Cout) */
+  int ldact, mask_lo;      /* mask_lo == Cout: no mask */
+  float slope;
+  int max_blocks;
+} dsr_rdb_dgrad;
+int dsr_conv_rdb_dgrad_supported(const dsr_rdb_dgrad* c);
+int dsr_conv_rdb_dgrad(const dsr_rdb_dgrad* c, dsr_stream_t s);
+
+/* dsr_conv_rdb_wgrad: the ten parameter gradients of one dense block (num_feat 64, num_grow_ch 32) once dgrad_2 has run, i.e.
+ * when channels [64, 192) of dy hold the masked dY_1 .. dY_4:
+ *     dw[k][co, ci, i, j] = sum_{n,y,x} x[n, y+i-1, x+j-1, ci] * dY_{k+1}[n, y, x, co],  zero outside the image, ci < 64 + 32 k
+ *     db[k][co] = sum_{n,y,x} dY_{k+1}[n, y, x, co]                    dY_5 = gscale * g (the factor is applied to the sums)
+ * fp32, PyTorch layouts; a NULL dw[k] / db[k] is not computed.  Products of 16-bit operands, fp32 sums, the pixel range cut
+ * into dsr_conv_rdb_wgrad_chunks() chunks whose partial sums are added in chunk order: no atomics, two runs give equal
+ * bits.  The bias gradients come from a column-sum pass of their own inside the call.  workspace: device memory, 16-byte
+ * aligned, dsr_conv_rdb_wgrad_workspace() bytes (too small: DSR_E_WORKSPACE); the queries return 0 for a shape the call
+ * refuses (DSR_E_ARG: ldx or lddy other than 192, ldg < 64, sizes as above). */
+typedef struct {
+  int dtype;
+  int N, H, W;
+  const void* x;           /* B  [N][H][W][ldx] */
+  int ldx;
+  const void* dy;          /* G  [N][H][W][lddy] */
+  int lddy;
+  const void* g;           /* dL/dout [N][H][W][ldg], channels [0, 64) */
+  int ldg;
+  float gscale;
+  float* dw[5];
+  float* db[5];
+} dsr_rdb_wgrad;
+int dsr_conv_rdb_wgrad_supported(const dsr_rdb_wgrad* c);
+size_t dsr_conv_rdb_wgrad_workspace(const dsr_rdb_wgrad* c);
+int dsr_conv_rdb_wgrad_chunks(const dsr_rdb_wgrad* c);
+int dsr_conv_rdb_wgrad(const dsr_rdb_wgrad* c, void* workspace, size_t workspace_bytes, dsr_stream_t s);
 /* out = r16(fmaf(a, beta, b)) on nvec 16-byte vectors of 16-bit values; b may be NULL (out = r16(a * beta)); out may be a or b */
 int dsr_scale_add16(int dtype, const void* a, float beta, const void* b, void* out, size_t nvec, dsr_stream_t s);
 
