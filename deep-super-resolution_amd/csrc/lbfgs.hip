@@ -10,9 +10,8 @@
 //            torch/optim/lbfgs.py (lines 463, 510-526) -> device flag
 //   combine  d = sum_j coef_j b_j, pending s = t d into the free ring slot, p += s                      one read of the history
 //
-// Vector storage `vecs` (fp32, n_pad = n rounded up to 4 floats per vector, padding stays 0):
-//   S slot j (j <= m) at j, Y slot j at m+1+j, gradient buffer b (2) at 2(m+1)+b, each n_pad floats.
-// m + 1 ring slots: the pending pair lives in the free slot until the next scalar kernel commits or drops it.
+// The layout of `vecs` (S slot j at j, Y slot j at m+1+j, gradient buffer b at 2(m+1)+b, n_pad floats each), the ring of
+// m + 1 slots with its pending pair, and the five public header ints are part of the state contract: include/dsr_hip.h.
 // Gram indices are the vector indices of the S / Y slots; the current gradient is Gram index 2(m+1).
 // Every reduction has a fixed order (per-thread fp64 sums, butterfly within a wave, waves in order, blocks in order):
 // results are bitwise deterministic.

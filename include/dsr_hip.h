@@ -628,8 +628,19 @@ int dsr_jpeg_batch_f32(const float* in, float* out, int count, int h, int w, con
  * passes.  A flat vector of n fp32 elements is split into `count` tensors (HOST tables of device pointers and element counts,
  * read before the call returns, summing to n).  history: 1 .. 1024 pairs.
  * ws: dsr_lbfgs_workspace(history, n, count) bytes, zero-filled before the first call (that is the fresh state); vecs:
- * dsr_lbfgs_vector_floats(history, n) floats, zero-filled.  The pair (ws, vecs) is the optimizer's whole state; the first
- * five ints of ws are n_iter, func_evals, n_iter of the running step, closure calls of the running step, live pairs.
+ * dsr_lbfgs_vector_floats(history, n) floats, zero-filled.  The pair (ws, vecs) is the optimizer's whole state.
+ * vecs, with m = history: 2 (m + 1) + 2 fp32 vectors of n_pad floats each, n_pad = n rounded up to a multiple of 4; the
+ * n_pad - n padding floats of every vector stay 0.  Vector j (0 <= j <= m) is S slot j, vector m + 1 + j is Y slot j, vector
+ * 2 (m + 1) + b is gradient buffer b (0 or 1; one holds the current flat gradient, the other the previous one, and they swap
+ * on every pass that computes a direction).  The ring has m + 1 slots: at most m hold committed pairs, and one free slot
+ * holds the pending pair (s = t d of the last direction, y = g - g_prev written by the gather pass) until the next scalar
+ * pass commits it (ys > 1e-10: it becomes the newest pair, and a full ring frees its oldest slot) or drops it.  A pass
+ * writes the current gradient buffer, Y of the free slot and, if it computes a direction, S of the slot that is free
+ * afterwards; it writes no other float of vecs.
+ * The first five ints of ws: [0] n_iter and [1] func_evals (state["n_iter"], state["func_evals"] of torch's optimizer, over
+ * all step() calls), [2] iterations and [3] closure calls of the running step(), [4] live pairs: the committed pairs held
+ * in the ring, 0 .. history, after the last scalar pass (a dropped pair does not count; it stays at history once the ring
+ * wraps).  The rest of ws is private.
  * Per closure call: dsr_lbfgs_gather (the .grad tensors; NULL entries are zero gradients), dsr_lbfgs_dots, dsr_lbfgs_scalar
  * (loss: the closure's device scalar; first = 1 for the first closure of a step()), dsr_lbfgs_combine (the parameters).
  * The scalar pass writes stop[0] = 1 when torch would not call the closure again (every break of lbfgs.py). */
