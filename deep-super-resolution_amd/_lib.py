@@ -255,6 +255,9 @@ SIGNATURES = {
     "dsr_noise_poisson_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "dsr_usm_mask": (_I, [_P, _P, _F, _P, _Z, _P]),
     "dsr_usm_combine": (_I, [_P, _P, _P, _F, _P, _Z, _P]),
+    "dsr_niqe_plane": (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "dsr_niqe_moments": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "dsr_niqe_features": (_I, [_P, _P, _I, _I, _P, _P, _P]),
 }
 
 _lib = None

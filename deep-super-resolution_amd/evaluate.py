@@ -115,7 +115,8 @@ def bicubic_pairs(hr_images, scale):
 
 
 def evaluate_generator(gen, pairs, tile=None, out_dir=None, data_range=None, dtype=torch.float16, to_unit=None,
-                       with_ssim=True, lpips_model=None, self_ensemble=False, ema=None, y_channel=False, shave=None):
+                       with_ssim=True, lpips_model=None, self_ensemble=False, ema=None, y_channel=False, shave=None,
+                       niqe_model=None):
     """eval_GAN.py:21-69 for an iterable of (LR [1,3,h,w], HR [1,3,H,W], name) on the device.
 
     Returns {'avg_psnr': ..., 'psnr': {name: value}, 'avg_ssim': ..., 'ssim': {name: value}}, and with ``lpips_model`` (an
@@ -130,18 +131,26 @@ def evaluate_generator(gen, pairs, tile=None, out_dir=None, data_range=None, dty
     are: 'avg_psnr_y', 'psnr_y' and (with ``with_ssim``) 'avg_ssim_y', 'ssim_y' -- PSNR and SSIM of the BT.601 luma of the
     8-bit-quantised output against that of the target, ``shave`` pixels cut from each border (``metrics.PSNR_Y`` /
     ``metrics.SSIM_Y``; the images are taken to be in [0, 1]).  ``shave=None`` is the scale factor, HR height // LR height.
-    That path reads nothing on the host inside the loop: the per-image values stay on the device and cross once at the end."""
+    That path reads nothing on the host inside the loop: the per-image values stay on the device and cross once at the end.
+
+    ``niqe_model`` (a ``metrics.NaturalnessImageQualityEvaluator``) adds 'avg_niqe' and 'niqe': {name: value}, the no-reference
+    score of each super-resolved image (the target is not looked at; images too small for two 96 x 96 blocks are a ValueError).
+    The block statistics stay on the device inside the loop and cross once at the end."""
+    if niqe_model is not None and not (hasattr(niqe_model, "statistics") and hasattr(niqe_model, "mu_p")):
+        raise TypeError(f"evaluate_generator: niqe_model must be a metrics.NaturalnessImageQualityEvaluator, got "
+                        f"{type(niqe_model).__name__}")
     if ema is not None:
         if ema.module is not gen:
             raise ValueError("evaluate_generator: `ema` averages another module than `gen`")
         with ema.average_parameters():
             return evaluate_generator(gen, pairs, tile=tile, out_dir=out_dir, data_range=data_range, dtype=dtype,
                                       to_unit=to_unit, with_ssim=with_ssim, lpips_model=lpips_model,
-                                      self_ensemble=self_ensemble, y_channel=y_channel, shave=shave)
+                                      self_ensemble=self_ensemble, y_channel=y_channel, shave=shave, niqe_model=niqe_model)
     if shave is not None and (isinstance(shave, bool) or not isinstance(shave, int) or shave < 0):
         raise ValueError(f"evaluate_generator: shave must be None or a non-negative integer, got {shave!r}")
     per, ssims, lps = OrderedDict(), OrderedDict(), OrderedDict()
     y_names, y_psnr, y_ssim = [], [], []                    # device tensors, one [1] per image
+    q_names, q_stats = [], []                               # NIQE: device statistics, one [1, 1333] per image
     for lr_image, hr_image, name in pairs:
         if isinstance(name, (list, tuple)):
             name = name[0]                                  # DataLoader collation of a batch of one (eval_GAN.py:40)
@@ -158,6 +167,9 @@ def evaluate_generator(gen, pairs, tile=None, out_dir=None, data_range=None, dty
             y_names.append(name)
             y_psnr.append(p_y)
             y_ssim.append(s_y)
+        if niqe_model is not None:
+            q_names.append(name)
+            q_stats.append(niqe_model.statistics(resolved))
         if out_dir is not None:
             from PIL import Image
             img_dir = os.path.join(out_dir, "images")
@@ -175,4 +187,36 @@ def evaluate_generator(gen, pairs, tile=None, out_dir=None, data_range=None, dty
         for key, vals in zip(("psnr_y", "ssim_y"), host):
             out["avg_" + key] = sum(vals) / max(len(vals), 1)
             out[key] = OrderedDict(zip(y_names, vals))
+    if niqe_model is not None:
+        vals = _niqe_values(niqe_model, q_stats)
+        out.update(avg_niqe=sum(vals) / max(len(vals), 1), niqe=OrderedDict(zip(q_names, vals)))
     return out
+
+
+def _niqe_values(niqe_model, stats):
+    """Host floats, one per image, from a list of device statistics: one transfer."""
+    if not stats:
+        return []
+    from . import metrics
+    return metrics.niqe_score(torch.cat(stats).cpu().numpy(), niqe_model.mu_p, niqe_model.cov_p).tolist()
+
+
+def score_niqe(gen, lr_images, niqe_model, **super_resolve_kwargs):
+    """NIQE of the super-resolved images of LR inputs that have no HR counterpart -- the real-world protocol of Real-ESRGAN.
+
+    ``lr_images``: an iterable of [N, 3, h, w] device tensors in [0, 1], or of ``(tensor, name)`` pairs (the default name is the
+    position; an image of a batch N > 1 is named ``<name>/<i>``).  ``niqe_model``: a ``metrics.NaturalnessImageQualityEvaluator``.
+    The keyword arguments go to ``infer.super_resolve`` (``tile``, ``halo``, ``dtype``, ``self_ensemble``, ``ensemble_batch``).
+    Returns {'avg_niqe': ..., 'niqe': {name: value}}; the statistics cross to the host once, after the loop."""
+    if not (hasattr(niqe_model, "statistics") and hasattr(niqe_model, "mu_p")):
+        raise TypeError(f"score_niqe: niqe_model must be a metrics.NaturalnessImageQualityEvaluator, got "
+                        f"{type(niqe_model).__name__}")
+    names, stats = [], []
+    for i, item in enumerate(lr_images):
+        lr, name = item if isinstance(item, (tuple, list)) else (item, str(i))
+        resolved = infer.super_resolve(gen, lr, **super_resolve_kwargs)
+        stats.append(niqe_model.statistics(resolved))
+        n = resolved.shape[0]
+        names += [name] if n == 1 else [f"{name}/{k}" for k in range(n)]
+    vals = _niqe_values(niqe_model, stats)
+    return {"avg_niqe": sum(vals) / max(len(vals), 1), "niqe": OrderedDict(zip(names, vals))}

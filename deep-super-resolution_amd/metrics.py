@@ -48,6 +48,15 @@ Device work (csrc/luma.hip), reading fp32 / fp16 / bf16 [N,3,H,W] as they are:
                            same partial sums: one read of each frame for both metrics;
   dsr_rgb_to_y             one tensor's plane;
   dsr_luma_psnr_finalize   per-image 10 log10(count / SSE_n), the reduction's total and the running state.
+
+``NaturalnessImageQualityEvaluator`` (``NIQE``) and ``niqe_features`` score an image WITHOUT a ground truth, the way the
+Real-ESRGAN paper and BasicSR's ``calculate_niqe`` do -- PARITY UNPINNED again; the definition is in the class docstring and, in
+float64 numpy, in tests/niqe_ref.py.  Device work (csrc/niqe.hip), float64 from the luma plane onward:
+  dsr_niqe_plane           the rounded 8-bit luma, shaved and cropped to whole 96 x 96 blocks (bit-exact integer arithmetic);
+  dsr_imresize_f32         its half-size copy for scale 2 (csrc/imresize.hip);
+  dsr_niqe_moments         per block the MSCN image in LDS and the five sums of each of its five maps, one launch per scale;
+  dsr_niqe_features        the AGGD fits: 36 features per block.
+The block statistics are a few float64 torch ops on the device; the 36 x 36 pseudo-inverse is numpy's, on the host.
 """
 import ctypes as C
 import math
@@ -720,3 +729,269 @@ SSIM = StructuralSimilarityIndexMeasure
 MS_SSIM = MultiScaleStructuralSimilarityIndexMeasure
 PSNR_Y = LumaPeakSignalNoiseRatio
 SSIM_Y = LumaStructuralSimilarityIndexMeasure
+
+
+# ============================================================================= NIQE: the no-reference score of blind SR
+_NIQE_BLOCK = 96
+_NIQE_FEATS = 36
+_NIQE_GRID = 9801                         # np.arange(0.2, 10.001, 0.001)
+_NIQE_KEYS = (("mu_pris_param", (1, 36)), ("cov_pris_param", (36, 36)), ("gaussian_window", (7, 7)))
+_niqe_cache = {}
+_niqe_warned = False
+
+
+def niqe_gaussian_window():
+    """float64 numpy [7, 7]: the published window, MATLAB's ``fspecial('gaussian', 7, 7 / 6)``."""
+    import numpy as np
+    r = np.arange(7, dtype=np.float64) - 3.0
+    g = np.exp(-(r[:, None] ** 2 + r[None, :] ** 2) / (2.0 * (7.0 / 6.0) ** 2))
+    return g / g.sum()
+
+
+def niqe_gamma_tables():
+    """float64 numpy [3, 9801] over alpha = arange(0.2, 10.001, 0.001): Gamma(2/a)^2 / (Gamma(1/a) Gamma(3/a)), sqrt(Gamma(1/a) /
+    Gamma(3/a)) and Gamma(2/a) / Gamma(1/a), from ``math.gamma`` (no scipy in the product).  Built once."""
+    hit = _niqe_cache.get("tables")
+    if hit is None:
+        import numpy as np
+        grid = np.arange(0.2, 10.001, 0.001)
+        g1 = np.array([math.gamma(1.0 / a) for a in grid])
+        g2 = np.array([math.gamma(2.0 / a) for a in grid])
+        g3 = np.array([math.gamma(3.0 / a) for a in grid])
+        hit = np.stack([g2 * g2 / (g1 * g3), np.sqrt(g1 / g3), g2 / g1])
+        if hit.shape != (3, _NIQE_GRID) or not (np.diff(hit[0]) > 0).all():
+            raise RuntimeError("niqe: the Gamma ratio table is not strictly increasing over the alpha grid")
+        _niqe_cache["tables"] = hit
+    return hit
+
+
+def _niqe_device_tables(dev):
+    key = ("tables", str(dev))
+    hit = _niqe_cache.get(key)
+    if hit is None:
+        hit = _niqe_cache[key] = torch.from_numpy(niqe_gamma_tables()).to(dev).contiguous()
+    return hit
+
+
+def load_niqe_params(params):
+    """(mu [1, 36], cov [36, 36], window [7, 7]) as float64 numpy arrays from a path to a local ``.npz`` with the keys
+    ``mu_pris_param``, ``cov_pris_param`` and ``gaussian_window`` (BasicSR's ``niqe_pris_params.npz`` as it is) or from a
+    ``(mu, cov, window)`` tuple.  A missing key or a wrong shape is named in the error."""
+    import numpy as np
+    if isinstance(params, (tuple, list)):
+        if len(params) != 3:
+            raise ValueError(f"niqe params: expected (mu, cov, window), got {len(params)} items")
+        given = dict(zip((k for k, _ in _NIQE_KEYS), params))
+    else:
+        with np.load(params, allow_pickle=False) as f:
+            missing = [k for k, _ in _NIQE_KEYS if k not in f.files]
+            if missing:
+                raise KeyError(f"niqe params: {params!r} has no {missing[0]!r} (keys: {sorted(f.files)})")
+            given = {k: f[k] for k, _ in _NIQE_KEYS}
+    out = []
+    for key, shape in _NIQE_KEYS:
+        a = given[key]
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        if key == "mu_pris_param" and a.shape == (36,):
+            a = a.reshape(1, 36)
+        if a.shape != shape:
+            raise ValueError(f"niqe params: {key} has shape {tuple(a.shape)}, expected {shape}")
+        if not np.issubdtype(a.dtype, np.number) or not np.isfinite(a.astype(np.float64)).all():
+            raise ValueError(f"niqe params: {key} holds values that are not finite numbers")
+        out.append(np.ascontiguousarray(a, dtype=np.float64))
+    return tuple(out)
+
+
+def _niqe_check(name, x, shave):
+    """(N, H, W, hc, wc) of a floating-point [N, 3, H, W] tensor that leaves two 96 x 96 blocks; the device check comes last."""
+    n, h, w = _check_rgb(name, x, shave, 1)
+    nby, nbx = (h - 2 * shave) // _NIQE_BLOCK, (w - 2 * shave) // _NIQE_BLOCK
+    if nby * nbx < 2:
+        raise ValueError(f"{name}: shave={shave} leaves {h - 2 * shave}x{w - 2 * shave} of a {h}x{w} image; NIQE needs at least "
+                         f"two 96x96 blocks")
+    if n * nby * nbx * _NIQE_BLOCK * _NIQE_BLOCK >= 1 << 31:
+        raise ValueError(f"{name}: {tuple(x.shape)} has more than 2^31 pixels; score it in smaller batches")
+    if not x.is_cuda:
+        raise RuntimeError("deep-super-resolution_amd: tensors must live on the MI355X (cuda device); "
+                           "there is no CPU implementation of this path")
+    return n, h, w, nby * _NIQE_BLOCK, nbx * _NIQE_BLOCK
+
+
+def _niqe_window(window, dev):
+    """The device fp64 [49] window: None = the published Gaussian (cached per device), else a [7, 7] array or tensor."""
+    if window is None:
+        key = ("window", str(dev))
+        hit = _niqe_cache.get(key)
+        if hit is None:
+            hit = _niqe_cache[key] = torch.from_numpy(niqe_gaussian_window()).to(dev).reshape(49).contiguous()
+        return hit
+    w = window if torch.is_tensor(window) else torch.as_tensor(window)
+    if tuple(w.shape) != (7, 7):
+        raise ValueError(f"niqe: the window has shape {tuple(w.shape)}, expected (7, 7)")
+    return w.detach().to(device=dev, dtype=torch.float64).reshape(49).contiguous()
+
+
+def _niqe_features(x, shave, win, sizes, keep=None):
+    """fp64 [N, nb, 36] on the device: dsr_niqe_plane, dsr_imresize_f32 (x0.5), dsr_niqe_moments per scale, dsr_niqe_features.
+    `keep` (a dict) receives the intermediate tensors."""
+    n, h, w, hc, wc = sizes
+    dt, xx = _luma_in(x)
+    plane = torch.empty(n, hc, wc, dtype=torch.float32, device=x.device)
+    check(_lib.lib().dsr_niqe_plane(dt, _ptr(xx), n, 3, h, w, shave, _ptr(plane), _stream()))
+    return _niqe_from_plane(plane, win, keep)
+
+
+def _niqe_from_plane(plane, win, keep=None):
+    """The passes behind dsr_niqe_plane on a contiguous fp32 [N, hc, wc] plane whose sides are multiples of 96."""
+    from .functional import _imresize_launch
+    from .utils.imresize import imresize_tables
+    n, hc, wc = plane.shape
+    lib = _lib.lib()
+    dev = plane.device
+    st = _stream()
+    th = imresize_tables(hc, hc // 2, 0.5, "bicubic", True, dev)
+    tw = imresize_tables(wc, wc // 2, 0.5, "bicubic", True, dev)
+    half = torch.empty(n, hc // 2, wc // 2, dtype=torch.float32, device=dev)
+    _imresize_launch(plane, half, n, hc, wc, hc // 2, wc // 2, th.idx, th.w, th.taps, tw.idx, tw.w, tw.taps)
+    nb = (hc // _NIQE_BLOCK) * (wc // _NIQE_BLOCK)
+    m1 = torch.empty(n, nb, 5, 5, dtype=torch.float64, device=dev)
+    m2 = torch.empty(n, nb, 5, 5, dtype=torch.float64, device=dev)
+    check(lib.dsr_niqe_moments(_ptr(plane), n, hc, wc, _NIQE_BLOCK, _ptr(win), _ptr(m1), st))
+    check(lib.dsr_niqe_moments(_ptr(half), n, hc // 2, wc // 2, _NIQE_BLOCK // 2, _ptr(win), _ptr(m2), st))
+    feat = torch.empty(n, nb, _NIQE_FEATS, dtype=torch.float64, device=dev)
+    check(lib.dsr_niqe_features(_ptr(m1), _ptr(m2), n, nb, _ptr(_niqe_device_tables(dev)), _ptr(feat), st))
+    if keep is not None:
+        keep.update(plane=plane, half=half, m1=m1, m2=m2)
+    return feat
+
+
+def niqe_features(x, shave=0, window=None):
+    """fp64 [N, blocks, 36] on the device: the NIQE feature table of an [N, 3, H, W] tensor in [0, 1] (fp32, fp16 or bf16, read
+    as it is) -- see ``NaturalnessImageQualityEvaluator`` for the definition.  ``window``: a [7, 7] array or tensor, default the
+    published Gaussian (sigma 7/6).  Blocks are in row-major order; scale 1's 18 features come first.  Nothing is read on the
+    host.  PARITY UNPINNED."""
+    shave = _check_shave("niqe_features", shave)
+    if window is not None:
+        window = window if torch.is_tensor(window) else torch.as_tensor(window)
+        if tuple(window.shape) != (7, 7):
+            raise ValueError(f"niqe_features: the window has shape {tuple(window.shape)}, expected (7, 7)")
+    sizes = _niqe_check("niqe_features", x, shave)
+    return _niqe_features(x, shave, _niqe_window(window, x.device), sizes)
+
+
+def niqe_statistics(feat):
+    """fp64 [N, 36 + 36 * 36 + 1] on the device from a feature table [N, nb, 36]: per image the column-wise ``nanmean``, the
+    ``np.cov(rowvar=False)`` (ddof 1) of the rows without a NaN, and the number of those rows.  Torch device ops in float64
+    (elementwise and ``sum`` only, nothing read on the host).  Fewer than two such rows leave a non-finite covariance."""
+    n, nb, f = feat.shape
+    mu = torch.nanmean(feat, dim=1)
+    good = ~torch.isnan(feat).any(dim=2)                                   # [N, nb]
+    cnt = good.sum(dim=1).to(torch.float64)                                # [N]
+    z = torch.where(good[:, :, None], feat, torch.zeros((), dtype=feat.dtype, device=feat.device))
+    mean = z.sum(dim=1) / cnt[:, None]
+    d = torch.where(good[:, :, None], z - mean[:, None, :], torch.zeros((), dtype=feat.dtype, device=feat.device))
+    cov = (d[:, :, :, None] * d[:, :, None, :]).sum(dim=1) / (cnt - 1.0)[:, None, None]
+    return torch.cat([mu, cov.reshape(n, f * f), cnt[:, None]], dim=1)
+
+
+def niqe_score(stats, mu_p, cov_p):
+    """float64 numpy [N] from the HOST copy of ``niqe_statistics``: sqrt((mu_p - mu_d) pinv((cov_p + cov_d) / 2) (mu_p -
+    mu_d)^T) per image; NaN (no exception) where fewer than two blocks are NaN-free or a feature column is NaN throughout."""
+    import numpy as np
+    stats = np.asarray(stats, dtype=np.float64)
+    out = np.full(stats.shape[0], np.nan)
+    for i, row in enumerate(stats):
+        mu_d, cov_d, cnt = row[:36], row[36:36 + 1296].reshape(36, 36), row[-1]
+        if cnt < 2 or not np.isfinite(mu_d).all() or not np.isfinite(cov_d).all():
+            continue
+        d = mu_p.reshape(1, 36) - mu_d.reshape(1, 36)
+        out[i] = float(np.sqrt(d @ np.linalg.pinv((cov_p + cov_d) / 2.0) @ d.T).item())
+    return out
+
+
+class NaturalnessImageQualityEvaluator(nn.Module):
+    """NIQE (Mittal, Soundararajan, Bovik 2013), the no-reference score real-world super-resolution is reported by (Real-ESRGAN;
+    BasicSR ``calculate_niqe``), on the HIP path -- PARITY UNPINNED: BasicSR, OpenCV and ``niqe_pris_params.npz`` are not
+    installed here, the formulas are BasicSR's, restated; the float64 statement is tests/niqe_ref.py.  Lower is better.
+
+    Per image of ``preds`` ([N, 3, H, W] in [0, 1]; fp32, fp16 or bf16, read as it is):
+      1. each channel becomes its 8-bit code, ``shave`` pixels are cut from each border, ``Y = round_half_even(16 + (65481 r +
+         128553 g + 24966 b) / 255000)`` in integer arithmetic, and the plane is cropped at the bottom and right to multiples of
+         96; at least two 96 x 96 blocks must remain (ValueError otherwise);
+      2. at scale 1 on that plane and at scale 2 on its MATLAB-style bicubic antialiased x0.5 (``dsr_imresize_f32``), with the
+         7 x 7 window w over replicated borders: ``mu = w (*) x``, ``sigma = sqrt(|w (*) x^2 - mu^2|)``, ``v = (x - mu) /
+         (sigma + 1)``, in float64.  The resize runs on the plane in its 0..255 scale and in fp32, which is exact there (the
+         x0.5 weights are (-3, -9, 29, 111, 111, 29, -9, -3) / 256: 8 + 8 + 8 bits); BasicSR resizes ``img / 255`` in float64
+         and multiplies back: the operator is linear, so the two differ by rounding only -- which can still move an alpha by
+         one grid step;
+      3. per 96 x 96 block (48 x 48 at scale 2) an asymmetric generalised Gaussian is fitted to v and to its products with the
+         neighbour rolled by (0, 1), (1, 0), (1, 1), (1, -1) inside the block: 18 features per scale, 36 per block.  A map with
+         no negative or no positive element (a flat block) takes alpha = 0.2 with NaN betas, as ``np.argmin`` of NaNs does;
+      4. ``mu_d`` = the column-wise nanmean of the [blocks, 36] table, ``cov_d`` = the covariance (ddof 1) of its NaN-free rows,
+         ``NIQE = sqrt((mu_p - mu_d) pinv((cov_p + cov_d) / 2) (mu_p - mu_d)^T)``; NaN when fewer than two rows are NaN-free.
+    Inside a textured block a flat neighbourhood leaves x - mu as rounding residue, whose sign then counts in the fit; BasicSR has
+    the same property and nothing here hides it.
+
+    ``params``: a path to a local ``.npz`` with ``mu_pris_param`` [1, 36], ``cov_pris_param`` [36, 36] and ``gaussian_window``
+    [7, 7] (BasicSR's file as it is), or a ``(mu, cov, window)`` tuple.  ``None`` uses stand-ins -- ``mu_p = 0``, ``cov_p = I`` and
+    the published sigma = 7/6 window -- and warns once: such scores rank images under the same stand-ins but are NOT comparable
+    with published NIQE numbers.  ``reduction``: 'elementwise_mean', 'sum' or 'none' / None.
+
+    ``update`` launches the device work (five launches and a few float64 torch ops for the statistics) and reads nothing on the
+    host; ``compute`` / ``forward`` copy ``36 + 36^2 + 1`` numbers per image to the host once and take the pseudo-inverse there
+    in numpy, so their result is a HOST float64 tensor.  Not differentiable."""
+
+    def __init__(self, params=None, shave=0, reduction="elementwise_mean"):
+        super().__init__()
+        global _niqe_warned
+        name = type(self).__name__
+        self.shave = _check_shave(name, shave)
+        self.reduction = _check_reduction(name, reduction)
+        self.pretrained = params is not None
+        if params is None:
+            import numpy as np
+            self.mu_p, self.cov_p, self.window = np.zeros((1, 36)), np.eye(36), None
+            if not _niqe_warned:
+                _niqe_warned = True
+                import warnings
+                warnings.warn("NaturalnessImageQualityEvaluator: no `params` given; using stand-ins (mu = 0, cov = I, the "
+                              "sigma = 7/6 window). Scores are not comparable with published NIQE numbers; pass BasicSR's "
+                              "niqe_pris_params.npz.", stacklevel=2)
+        else:
+            self.mu_p, self.cov_p, self.window = load_niqe_params(params)
+        self._stats = []
+
+    def reset(self):
+        self._stats = []
+
+    def statistics(self, preds):
+        """fp64 [N, 36 + 36^2 + 1] on the device (``niqe_statistics`` of the batch's features); the running state is not
+        touched and nothing is read on the host.  ``niqe_score(stats.cpu().numpy(), self.mu_p, self.cov_p)`` turns any stack
+        of these into scores: how ``evaluate_generator`` crosses to the host once after its loop."""
+        sizes = _niqe_check(type(self).__name__, preds, self.shave)
+        return niqe_statistics(_niqe_features(preds, self.shave, _niqe_window(self.window, preds.device), sizes))
+
+    def _batch(self, preds):
+        stats = self.statistics(preds)
+        self._stats.append(stats)
+        return stats
+
+    def _reduce(self, stats):
+        scores = torch.from_numpy(niqe_score(stats.cpu().numpy(), self.mu_p, self.cov_p))
+        if self.reduction == "none":
+            return scores
+        return scores.sum() if self.reduction == "sum" else scores.mean()
+
+    def update(self, preds):
+        self._batch(preds)
+
+    def forward(self, preds):
+        return self._reduce(self._batch(preds))
+
+    def compute(self):
+        if not self._stats:
+            raise RuntimeError(f"{type(self).__name__}.compute() called before update()")
+        return self._reduce(torch.cat(self._stats))
+
+
+NIQE = NaturalnessImageQualityEvaluator

@@ -924,6 +924,29 @@ int dsr_noise_poisson_f32(const float* x, const float* z, const float* zg, const
 int dsr_usm_mask(const float* x, const float* blur, float threshold, float* mask, size_t n, dsr_stream_t s);
 int dsr_usm_combine(const float* x, const float* blur, const float* soft, float weight, float* y, size_t n, dsr_stream_t s);
 
+/* ------------------------------------------------------------------ NIQE, the no-reference quality score (niqe.hip)
+ * Mittal, Soundararajan, Bovik 2013 as BasicSR's calculate_niqe computes it (metrics.NaturalnessImageQualityEvaluator,
+ * metrics.niqe_features; PARITY UNPINNED: restated, the float64 statement is tests/niqe_ref.py).
+ * dsr_niqe_plane: x [N][3][H][W] of dtype DSR_BF16, DSR_F16 or DSR_F32 -> plane [N][hc][wc] fp32, hc = (H - 2 shave) / 96 * 96,
+ *   wc likewise: per pixel of rows [shave, shave + hc), columns [shave, shave + wc) the 8-bit codes c = rintf(fminf(fmaxf(x, 0),
+ *   1) * 255.0f) and Y = 16 + round_half_even((65481 r + 128553 g + 24966 b) / 255000) in integer arithmetic.  Fewer than two
+ *   96 x 96 blocks, or N hc wc >= 2^31, is DSR_E_ARG.
+ * dsr_niqe_moments: plane [N][hc][wc] fp32 with hc, wc multiples of block (96: scale 1; 48: scale 2, on the half-size plane);
+ *   window: DEVICE fp64 [7][7].  In fp64, borders replicated, one separately rounded multiply and add per tap in row-major
+ *   window order:  mu = w (*) x,  sigma = sqrt(|w (*) x^2 - mu^2|),  v = (x - mu) / (sigma + 1)  ((*): convolution, the window
+ *   flipped).  Per block (row-major grid, nb = (hc / block)(wc / block)) and map m in { v, v roll(v,(0,1)), v roll(v,(1,0)),
+ *   v roll(v,(1,1)), v roll(v,(1,-1)) } -- numpy's circular roll inside the block -- out [N][nb][5][5] fp64 holds
+ *   count(m < 0), count(m > 0), sum of m^2 over m < 0, over m > 0, sum |m|.  Fixed summation order, no atomics.
+ * dsr_niqe_features: m1, m2 = the moments of scale 1 and 2 over the same block grid; tables: DEVICE fp64 [3][9801] over alpha =
+ *   arange(0.2, 10.001, 0.001): Gamma(2/a)^2 / (Gamma(1/a) Gamma(3/a)) (strictly increasing), sqrt(Gamma(1/a) / Gamma(3/a)),
+ *   Gamma(2/a) / Gamma(1/a).  feat [N][nb][36] fp64: per scale (1 first) [alpha, (beta_l + beta_r) / 2] of v and [alpha,
+ *   (beta_r - beta_l) Gamma(2/alpha) / Gamma(1/alpha), beta_l, beta_r] of each product; alpha is written as 0.2 + 0.001 index,
+ *   the index that of np.argmin((table - r_norm)^2), 0 when r_norm is not finite (a map with no negative or no positive value).
+ * A null pointer or a size out of range is DSR_E_ARG before anything is launched. */
+int dsr_niqe_plane(int dtype, const void* x, int N, int C, int H, int W, int shave, float* plane, dsr_stream_t s);
+int dsr_niqe_moments(const float* plane, int N, int hc, int wc, int block, const double* window, double* out, dsr_stream_t s);
+int dsr_niqe_features(const double* m1, const double* m2, int N, int nb, const double* tables, double* feat, dsr_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
