@@ -380,44 +380,101 @@ class batched_wgrad:
 
 FIRST_BWD_RECOMPUTE = os.environ.get("DSR_FIRST_BWD_RECOMPUTE", "1") != "0"   # 0: the first-layer backward reads the stored activation
 
-ACT_LINKS = True      # development switch: False makes every layer run its own activation-backward pass (A/B of ActLink)
+ACT_LINKS = True      # development switch: False makes every layer run its own activation-backward pass (A/B of kind "act")
+FIRST2_BACKWARD = os.environ.get("DSR_FIRST2_BACKWARD", "1") != "0"   # 0: the first two layers' backward as separate launches
+DGRAD_BN = os.environ.get("DSR_DGRAD_BN_LINK", "1") != "0"             # 0: BatchNorm-backward sums always by their own reduce pass
+DGRAD_PS = os.environ.get("DSR_DGRAD_PS_LINK", "1") != "0"             # 0: the PixelShuffle-PReLU backward always as its own pass
 
 
-class ActLink:
-    """Hand-over of an activation's backward between two neighbouring autograd nodes: the node that CONSUMES an activation
-    output x (a conv's input-gradient launch, a max-pool backward) can multiply its result by act'(x) on the way out
-    (dsr_conv_dgrad_masked, dsr_maxpool2_relu_bwd); it then sets `premasked`, and the node that PRODUCED x skips its own
-    activation-backward pass.  One link per activation and forward call; only for an x with exactly one consumer (the VGG19
-    trunk, utils/GAN.py:19-57)."""
-    __slots__ = ("act", "slope", "premasked")
-
-    def __init__(self, act, slope=0.0):
-        self.act, self.slope, self.premasked = act, float(slope), False
+def _identity(t):
+    return (t.data_ptr(), t._version, tuple(t.shape))
 
 
-def _conv_backward(desc, x, dy, wd, need_dx, need_dw, weight_shape, weight=None, addend=None, in_link=None, bn_link=None):
+def zero_placeholder(shape, dtype, device):
+    """The gradient a consumer returns to autograd when the real one went through a Handover: zeros of `shape` over ONE
+    element (stride 0), so that a reader the link did not foresee adds zero.  Allocated per use (a captured backward pass
+    replays the fill)."""
+    return torch.zeros(1, dtype=dtype, device=device).expand(shape)
+
+
+class Handover:
+    """Part of one node's backward done by its neighbour: the node that CONSUMES an activation x runs some of the backward
+    of the node that PRODUCED x inside its own input-gradient launch, and the producer skips that work.  The model makes one
+    empty Handover per activation and forward call and gives it to the producer as cfg["out_link"] and to the consumer as
+    cfg["in_link"] (MaxPool2: the second argument).
+
+      offer   (producer, forward)   `kind` and the payload the consumer's kernel needs -- only when the producer will be able
+                                    to use what comes back:
+                "act"     act, slope                           the consumer multiplies dx by act'(x): dsr_conv_dgrad_masked,
+                                                               dsr_maxpool2_relu_bwd; deposits True
+                "bn"      y, scale, shift, act, slope          the consumer also forms the BatchNorm-backward sums:
+                                                               dsr_conv_dgrad_bn; deposits (part, rows)
+                "ps"      prelu                                the consumer also runs the PixelShuffle + PReLU backward:
+                                                               dsr_conv_dgrad_ps; deposits (dy, part, rows), dx a placeholder
+                "first2"  img, w0, b0, slope, versions of w0, b0   the consumer runs the image layer's whole backward:
+                                                               dsr_conv_dgrad_first_bwd; deposits (dw0, db0), dx a placeholder
+      deposit (consumer, backward)  the result, with the identity (data_ptr, _version, shape) of the dx it returns to autograd
+      collect (producer, backward)  the deposit, if `dout` IS that dx.
+
+    The precondition of every kind is that x has exactly one consumer and no hook: autograd then hands the producer the very
+    tensor the consumer returned.  Anything summed into it on the way -- a second consumer, a hook -- changes its address or
+    its version.  The sums of "bn" are then recomputed by the producer from the complete `dout`; for the other kinds the
+    link's contribution cannot be recovered and collect raises.  collect spends the link and drops everything it holds: a
+    second backward over a retained graph finds it without an offer and takes the separate launches, whatever the kind.
+    (offer starts the link afresh: a forward that is recomputed may reuse it.)"""
+    __slots__ = ("kind", "payload", "_deposit", "_dx")
+    _SWITCH = {"act": "functional.ACT_LINKS = False", "bn": "DSR_DGRAD_BN_LINK=0 (functional.DGRAD_BN)",
+               "ps": "DSR_DGRAD_PS_LINK=0 (functional.DGRAD_PS)", "first2": "DSR_FIRST2_BACKWARD=0 (functional.FIRST2_BACKWARD)"}
+
+    def __init__(self):
+        self.kind = self.payload = self._deposit = self._dx = None
+
+    def offer(self, kind, *payload):
+        assert kind in self._SWITCH
+        self.kind, self.payload, self._deposit, self._dx = kind, payload, None, None
+
+    def deposit(self, dx, result=True):
+        if self.kind is None:
+            raise RuntimeError("Handover.deposit: the link holds no offer (never made, or spent by an earlier backward pass)")
+        self._deposit, self._dx = result, _identity(dx)
+
+    def collect(self, dout):
+        kind, got, dx = self.kind, self._deposit, self._dx
+        self.kind = self.payload = self._deposit = self._dx = None
+        if got is None or dx == _identity(dout):
+            return got
+        if kind == "bn":
+            return None
+        raise RuntimeError(
+            f"Handover '{kind}': the gradient that reached the producer is not the tensor its consumer returned -- the "
+            "activation has a second consumer or a hook, and the part of the backward that went through the link cannot be "
+            f"separated from what was added.  Turn the fusion off for such a graph: {self._SWITCH[kind]}")
+
+
+def _conv_backward(desc, x, dy, wd, need_dx, need_dw, weight_shape, weight=None, addend=None, in_link=None):
     """dx (+ `addend`: the gradient that reaches x along a skip path, summed in the dgrad epilogue where the kernel can; or
-    `in_link`: the activation that produced x, whose backward mask is folded into the dgrad stores where the kernel can; or
-    `bn_link`: x is the output of a BatchNorm + LeakyReLU layer that left its raw conv output and affine map there -- the
-    dgrad launch then also forms that layer's BatchNorm-backward sums, dsr_conv_dgrad_bn, and leaves the partial rows in
-    the link) and dw."""
+    `in_link`, the Handover of the layer that produced x -- "act": its activation's backward mask is folded into the dgrad
+    stores, "bn": the dgrad launch also forms its BatchNorm-backward sums -- where the kernel can) and dw."""
     lib = _lib.lib()
     dx = dw = None
+    kind = in_link.kind if (in_link is not None and addend is None) else None
     if need_dx:
         dx = torch.empty_like(x)
-        if (bn_link is not None and "y" in bn_link and addend is None and DGRAD_BN and bn_link["act"] in (ACT_NONE, ACT_LEAKY)
-                and bn_link["y"].shape == x.shape and lib.dsr_conv_dgrad_bn_supported(C.byref(desc))):
+        if (kind == "bn" and DGRAD_BN and in_link.payload[3] in (ACT_NONE, ACT_LEAKY) and in_link.payload[0].shape == x.shape
+                and lib.dsr_conv_dgrad_bn_supported(C.byref(desc))):
+            y0, scale0, shift0, act0, slope0 = in_link.payload
             rows = lib.dsr_conv_dgrad_bn_rows(C.byref(desc))
             cp = x.shape[-1]
             part = torch.empty((rows + _scr()) * 3 * cp, dtype=torch.float32, device=x.device)
             check(_timed("dgrad", desc, lambda: lib.dsr_conv_dgrad_bn(
-                C.byref(desc), _ptr(dy), _ptr(wd), _ptr(dx), _ptr(bn_link["y"]), _ptr(bn_link["scale"]), _ptr(bn_link["shift"]),
-                bn_link["act"], float(bn_link["slope"]), _ptr(part), _stream()), name="conv_dgrad_s2_kernel<bn>"))
-            bn_link["part"] = (part, rows, dx.data_ptr())
-        elif in_link is not None and addend is None and lib.dsr_conv_dgrad_masked_supported(C.byref(desc)):
-            check(_timed("dgrad", desc, lambda: lib.dsr_conv_dgrad_masked(C.byref(desc), _ptr(dy), _ptr(wd), _ptr(x), in_link.act,
-                                                                            in_link.slope, _ptr(dx), _stream())))
-            in_link.premasked = True
+                C.byref(desc), _ptr(dy), _ptr(wd), _ptr(dx), _ptr(y0), _ptr(scale0), _ptr(shift0), act0, slope0, _ptr(part),
+                _stream()), name="conv_dgrad_s2_kernel<bn>"))
+            in_link.deposit(dx, (part, rows))
+        elif kind == "act" and ACT_LINKS and lib.dsr_conv_dgrad_masked_supported(C.byref(desc)):
+            act0, slope0 = in_link.payload
+            check(_timed("dgrad", desc, lambda: lib.dsr_conv_dgrad_masked(C.byref(desc), _ptr(dy), _ptr(wd), _ptr(x), act0, slope0,
+                                                                            _ptr(dx), _stream())))
+            in_link.deposit(dx)
         elif addend is not None and lib.dsr_conv_dgrad_add_supported(C.byref(desc)):
             addend = addend.contiguous()
             check(_timed("dgrad", desc, lambda: lib.dsr_conv_dgrad_add(C.byref(desc), _ptr(dy), _ptr(wd), _ptr(addend), _ptr(dx),
@@ -544,19 +601,29 @@ class ConvAct(torch.autograd.Function):
             check(_timed("fwd", desc, lambda: _lib.lib().dsr_conv_fwd(C.byref(desc), _ptr(x), _ptr(wf), C.byref(ep), _ptr(y),
                                                                         _stream()), ep))
         # (defer: nothing is launched here -- the layer that consumes y computes this layer inside its own forward kernel and
-        #  fills y only if a backward pass will need it: ConvBNAct with cfg["first2"], the discriminator's first two layers)
+        #  fills y only if a backward pass will need it: ConvBNAct whose in_link offers "first2", the discriminator's first two
+        #  layers)
         ctx.desc, ctx.cfg, ctx.ps, ctx.act = desc, cfg, ps, act
-        opl = cfg.get("out_ps_link")
-        if opl is not None:
-            # the 9x9 tail that consumes y may run this layer's activation backward inside its input-gradient launch
-            opl.clear()
-            if ps and act == ACT_PRELU and prelu is not None and cout == 256:
-                opl["prelu"] = prelu.detach()
         ctx.wshape = tuple(weight.shape)
         ctx.weight_ref = weight
         ctx.weight_version = _version(weight)
         ctx.has_bias = bias is not None
         ctx.bias_ref = bias
+        ctx.bias_version = _version(bias) if bias is not None else None
+        out_link = cfg.get("out_link")
+        if out_link is not None:
+            # what the consumer of y may do of this layer's backward inside its own launch (Handover)
+            slope = float(cfg.get("slope", 0.0))
+            if cfg.get("defer", False):
+                out_link.offer("first2", x, weight, bias, slope, ctx.weight_version, ctx.bias_version)
+            elif ps:
+                if act == ACT_PRELU and prelu is not None and cout == 256:
+                    out_link.offer("ps", prelu.detach())
+            elif (prelu is None and act in (ACT_RELU, ACT_LEAKY) and not (ctx.has_bias and ctx.needs_input_grad[2])
+                    and (ctx.needs_input_grad[0] or not ctx.needs_input_grad[1])):
+                # (a bias gradient needs this layer's own pass over the unmasked gradient; an image layer -- weight gradient and
+                #  no input gradient -- applies the mask inside its one-pass backward, dsr_conv_first_bwd)
+                out_link.offer("act", act, slope)
         ctx.save_for_backward(x, y, wd, prelu if prelu is not None else torch.empty(0, device=x.device))
         return y
 
@@ -566,18 +633,15 @@ class ConvAct(torch.autograd.Function):
         prelu = prelu if prelu.numel() else None
         lib = _lib.lib()
         desc = ctx.desc
-        link = ctx.cfg.get("first2_link")
-        if link is not None and "grads" in link:
-            # the layer on top of this one (ConvBNAct with cfg["first2"]) ran this layer's whole backward inside its own input-
-            # gradient kernel (dsr_conv_dgrad_first_bwd) and left the results here; `dout` is a placeholder without storage
-            dw, db = link.pop("grads")
-            return None, dw, db, None, None
-        opl = ctx.cfg.get("out_ps_link")
-        got = opl.pop("dy", None) if opl is not None else None
-        if opl is not None:
-            opl.clear()
+        out_link = ctx.cfg.get("out_link")
+        kind = out_link.kind if out_link is not None else None
+        got = out_link.collect(dout) if out_link is not None else None
+        if kind == "first2" and got is not None:
+            # the layer on top of this one (ConvBNAct) ran this layer's whole backward inside its own input-gradient kernel
+            # (dsr_conv_dgrad_first_bwd) and left the results in the link; `dout` is a placeholder
+            return None, got[0], got[1], None, None
         if got is None:
-            dout = dout.contiguous()     # (otherwise a placeholder without storage: see below)
+            dout = dout.contiguous()     # (otherwise premasked and contiguous already, or a placeholder: see below)
         cout = desc.Cout
         n = x.shape[0]
         oh, ow = _out_hw(desc)
@@ -592,11 +656,12 @@ class ConvAct(torch.autograd.Function):
             wsz = lib.dsr_conv_first_bwd_workspace(C.byref(desc))
             ws = torch.empty(wsz, dtype=torch.uint8, device=x.device)
             w0 = getattr(ctx, "weight_ref", None)
+            b0 = ctx.bias_ref
             if (FIRST_BWD_RECOMPUTE and w0 is not None and w0.dtype == torch.float32 and w0.is_contiguous()
-                    and _version(w0) == ctx.weight_version):
+                    and _version(w0) == ctx.weight_version and (b0 is None or _version(b0) == ctx.bias_version)):
                 # the activation output y is not read: the sign of the pre-activation is recomputed inside the pass from the
-                # image and the layer's own weights (unchanged since the forward: same version) -- 1.07 GB less per pass at 512^2
-                b0 = ctx.bias_ref
+                # image and the layer's own weight and bias (unchanged since the forward: same versions) -- 1.07 GB less per
+                # pass at 512^2
                 check(_timed("wgrad", desc, lambda: lib.dsr_conv_first_bwd_recompute(
                     C.byref(desc), _ptr(x), _ptr(dout), _ptr(w0.detach()), _ptr(b0.detach() if b0 is not None else None), ctx.act,
                     float(ctx.cfg.get("slope", 0.0)), _ptr(dw), _ptr(db), _ptr(ws), wsz, _stream()), name="conv_first_bwd_kernel"))
@@ -605,10 +670,9 @@ class ConvAct(torch.autograd.Function):
                     C.byref(desc), _ptr(x), _ptr(dout), _ptr(y), ctx.act, float(ctx.cfg.get("slope", 0.0)), _ptr(dw), _ptr(db),
                     _ptr(ws), wsz, _stream()), name="conv_first_bwd_kernel"))
             return None, dw, db, None, None
-        out_link = ctx.cfg.get("out_link")
-        if got is not None:
+        if kind == "ps" and got is not None:
             # the tail's input-gradient launch (dsr_conv_dgrad_ps) already produced the masked, un-shuffled gradient of this
-            # layer's conv output and the partial sums; `dout` is a placeholder without storage
+            # layer's conv output and the partial sums; `dout` is a placeholder
             dy, part, blocks = got
             db = dprelu = None
             if ctx.has_bias:
@@ -618,10 +682,8 @@ class ConvAct(torch.autograd.Function):
             check(lib.dsr_pw_sum_rows(_ptr(part), blocks, 2 * cyp, cyp, cyp, 1.0, _ptr(chan), 0, 1, _stream()))
             dprelu = torch.empty(1, dtype=torch.float32, device=x.device)
             check(lib.dsr_pw_sum_rows(_ptr(chan), cyp, 1, 0, 1, 1.0, _ptr(dprelu), 0, 0, _stream()))
-        elif (out_link is not None and out_link.premasked and prelu is None and not ctx.ps
-                and not (ctx.has_bias and ctx.needs_input_grad[2])):
-            # the consumer of this layer's output already multiplied dout by act'(y) (ActLink): nothing left to do here
-            out_link.premasked = False
+        elif kind == "act" and got is not None:
+            # the consumer of this layer's output already multiplied dout by act'(y): nothing left to do here
             dy = dout
             db = dprelu = None
         elif ctx.act == ACT_NONE and not ctx.ps:
@@ -650,23 +712,19 @@ class ConvAct(torch.autograd.Function):
         return dx, dw, db, dprelu, None
 
 
-FIRST2_BACKWARD = os.environ.get("DSR_FIRST2_BACKWARD", "1") != "0"   # 0: the first two layers' backward as separate launches
-DGRAD_BN = os.environ.get("DSR_DGRAD_BN_LINK", "1") != "0"             # 0: BatchNorm-backward sums always by their own reduce pass
-DGRAD_PS = os.environ.get("DSR_DGRAD_PS_LINK", "1") != "0"             # 0: the PixelShuffle-PReLU backward always as its own pass
-
-
 def _first2_backward(ctx, desc, x, dy, wd):
     """discriminator.py:25-29 in a step that needs no image gradient (the discriminator's own update): this layer's input
     gradient and the image layer's whole backward (mask, bias and weight gradient) as one launch, dsr_conv_dgrad_first_bwd --
     the gradient of the 64-channel activation between the two (1.07 GB at 512x512, batch 32) is never written.  Returns the
     placeholder to hand to autograd as that gradient (the image layer's gradients are left in the link its ConvAct node
     reads), or None when the pair does not qualify: then the caller takes the separate launches."""
-    first2 = ctx.cfg.get("first2")
-    if not FIRST2_BACKWARD or first2 is None or len(first2) < 5 or first2[4] is None or not ctx.needs_input_grad[0]:
+    link = ctx.cfg.get("in_link")
+    if not FIRST2_BACKWARD or link is None or link.kind != "first2" or not ctx.train or not ctx.needs_input_grad[0]:
         return None
-    img, w0, b0, slope0, link = first2
+    img, w0, b0, slope0, w0_version, b0_version = link.payload
+    # (the kernel rebuilds the activation's sign from the live w0 and b0: both must be what the forward used)
     if (img.requires_grad or not w0.requires_grad or w0.dtype != torch.float32 or not w0.is_contiguous()
-            or _version(w0) != getattr(ctx, "first2_w0_version", None) or (b0 is not None and not b0.requires_grad)):
+            or _version(w0) != w0_version or (b0 is not None and (not b0.requires_grad or _version(b0) != b0_version))):
         return None
     lib = _lib.lib()
     d0 = make_desc(img, w0.shape[0], 3, 3, 1, 1, PAD_ZERO, w0.shape[1])
@@ -679,8 +737,9 @@ def _first2_backward(ctx, desc, x, dy, wd):
     check(_timed("dgrad", desc, lambda: lib.dsr_conv_dgrad_first_bwd(
         C.byref(d0), C.byref(desc), _ptr(dy), _ptr(wd), _ptr(img), _ptr(w0.detach()), _ptr(b0.detach() if b0 is not None else None),
         ACT_LEAKY, float(slope0), _ptr(dw0), _ptr(db0), _ptr(ws), wsz, _stream()), name="conv_dgrad_s2_kernel<first_bwd>"))
-    link["grads"] = (dw0, db0)
-    return torch.empty(1, dtype=x.dtype, device=x.device).expand(x.shape)
+    dx = zero_placeholder(x.shape, x.dtype, x.device)
+    link.deposit(dx, (dw0, db0))
+    return dx
 
 
 # ----------------------------------------------------------------------------- conv + BatchNorm + activation (+ residual)
@@ -719,13 +778,12 @@ class ConvBNAct(torch.autograd.Function):
         mean = torch.empty(cp, dtype=torch.float32, device=dev)
         rstd = torch.empty(cp, dtype=torch.float32, device=dev)
         count = n * oh * ow
-        first2 = cfg.get("first2") if train else None
-        if first2 is not None:
+        in_link = cfg.get("in_link")
+        if train and in_link is not None and in_link.kind == "first2":
             # x is the (not yet computed) output of the image layer in front of this one: both convolutions run in ONE kernel
             # that recomputes that activation per tile in LDS (dsr_conv_first2_fwd) and writes it to x only when a backward
             # pass will read it (this layer's weight gradient); the forward itself never reads it back from HBM
-            img, w0, b0, slope0 = first2[:4]
-            ctx.first2_w0_version = _version(w0)
+            img, w0, b0, slope0 = in_link.payload[:4]
             d0 = make_desc(img, w0.shape[0], 3, 3, 1, 1, PAD_ZERO, w0.shape[1])
             wf0, _ = packed_weights(w0, d0, x.dtype)
             rows = lib.dsr_conv_first2_stats_rows(C.byref(d0))
@@ -788,12 +846,10 @@ class ConvBNAct(torch.autograd.Function):
         check(lib.dsr_pw_bn_act_fwd(_dt(x), _ptr(y), _ptr(scale), _ptr(shift), _ptr(res), _ptr(out), count, cp, act,
                                     float(cfg.get("slope", 0.0)), _ptr(prelu), _stream()))
         ctx.desc, ctx.cfg, ctx.act, ctx.train, ctx.count = desc, cfg, act, train, count
-        bol = cfg.get("bn_out_link")
-        if bol is not None:
+        out_link = cfg.get("out_link")
+        if out_link is not None and train and residual is None and prelu is None and not cfg.get("infer", False):
             # the layer that consumes `out` may form this layer's BatchNorm-backward sums inside its input-gradient launch
-            bol.clear()
-            if train and residual is None and prelu is None and not cfg.get("infer", False):
-                bol.update(y=y, scale=scale, shift=shift, act=act, slope=float(cfg.get("slope", 0.0)))
+            out_link.offer("bn", y, scale, shift, act, float(cfg.get("slope", 0.0)))
         ctx.wshape = tuple(weight.shape)
         ctx.weight_ref = weight
         ctx.has_res = residual is not None
@@ -824,13 +880,11 @@ class ConvBNAct(torch.autograd.Function):
         dgamma = torch.empty(cout, dtype=torch.float32, device=dev)
         dbeta = torch.empty(cout, dtype=torch.float32, device=dev)
         dprelu = torch.empty(1, dtype=torch.float32, device=dev) if prelu is not None else None
-        bol = ctx.cfg.get("bn_out_link")
-        got = bol.pop("part", None) if bol is not None else None
-        if bol is not None:
-            bol.clear()
-        if got is not None and got[2] == dout.data_ptr():
+        out_link = ctx.cfg.get("out_link")
+        got = out_link.collect(dout) if out_link is not None else None
+        if got is not None:
             # the launch that produced `dout` (the next layer's input gradient, dsr_conv_dgrad_bn) formed the two sums already
-            part, blocks = got[0], got[1]
+            part, blocks = got
         else:
             blocks, rpb = _bn_bwd_blocks(p, ctx.act)
             part = torch.empty((blocks + _scr()) * 3 * cp, dtype=torch.float32, device=dev)
@@ -846,12 +900,12 @@ class ConvBNAct(torch.autograd.Function):
         fused = _first2_backward(ctx, desc, x, dy, wd) if dcarry is None else None
         if fused is not None:
             # the input gradient (of the image layer's activation) was consumed where it was formed: autograd gets a
-            # placeholder of the right shape without storage, and the image layer's ConvAct node finds its gradients in the link
+            # placeholder of the right shape, and the image layer's ConvAct node finds its gradients in the link
             dx = fused
             _, dw = _conv_backward(desc, x, dy, wd, False, ctx.needs_input_grad[1], ctx.wshape, getattr(ctx, "weight_ref", None))
         else:
             dx, dw = _conv_backward(desc, x, dy, wd, ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.wshape,
-                                     getattr(ctx, "weight_ref", None), dcarry, bn_link=ctx.cfg.get("bn_in_link"))
+                                     getattr(ctx, "weight_ref", None), dcarry, in_link=ctx.cfg.get("in_link"))
         db = None
         if ctx.has_bias and not ctx.train:
             # a bias in front of a train-mode BatchNorm has an analytically zero gradient (the reference holds ~1e-9
@@ -881,7 +935,7 @@ class ConvOutNCHW(torch.autograd.Function):
         check(_timed("fwd", desc, lambda: _lib.lib().dsr_conv_fwd(C.byref(desc), _ptr(x), _ptr(wf), C.byref(ep), None,
                                                                     _stream()), ep))
         ctx.desc, ctx.act = desc, act
-        ctx.ps_link = cfg.get("in_ps_link")
+        ctx.in_link = cfg.get("in_link")
         ctx.wshape = tuple(weight.shape)
         ctx.weight_ref = weight
         ctx.has_bias = bias is not None
@@ -898,8 +952,8 @@ class ConvOutNCHW(torch.autograd.Function):
         check(_lib.lib().dsr_pw_act_bwd_nchw(_dt(x), _ptr(dout), _ptr(out), _ptr(dy), n, c, h, w, r8(c), ctx.act,
                                              _stream()))
         lib = _lib.lib()
-        link = getattr(ctx, "ps_link", None)
-        if (link is not None and "prelu" in link and DGRAD_PS and ctx.needs_input_grad[0]
+        link = ctx.in_link
+        if (link is not None and link.kind == "ps" and DGRAD_PS and ctx.needs_input_grad[0]
                 and lib.dsr_conv_dgrad_ps_supported(C.byref(desc))):
             # x is PReLU(PixelShuffle(conv)) (generator.py:37-39 in front of :78): that activation's backward rides in this
             # layer's input-gradient launch (dsr_conv_dgrad_ps) -- the 64-channel gradient at the high resolution is never
@@ -908,11 +962,11 @@ class ConvOutNCHW(torch.autograd.Function):
             rows = lib.dsr_conv_dgrad_ps_rows(C.byref(desc))
             dyu = torch.empty((n_, h_ // 2, w_ // 2, 256), dtype=x.dtype, device=x.device)
             part = torch.empty((rows + _scr()) * 2 * 256, dtype=torch.float32, device=x.device)
-            check(_timed("dgrad", desc, lambda: lib.dsr_conv_dgrad_ps(C.byref(desc), _ptr(dy), _ptr(wd), _ptr(x), _ptr(link["prelu"]),
+            check(_timed("dgrad", desc, lambda: lib.dsr_conv_dgrad_ps(C.byref(desc), _ptr(dy), _ptr(wd), _ptr(x), _ptr(link.payload[0]),
                                                                        _ptr(dyu), _ptr(part), _stream()),
                          name="conv_dgrad_toeplitz9_kernel<ps>"))
-            link["dy"] = (dyu, part, rows)
-            dx = torch.empty(1, dtype=x.dtype, device=x.device).expand(x.shape)       # placeholder without storage
+            dx = zero_placeholder(x.shape, x.dtype, x.device)
+            link.deposit(dx, (dyu, part, rows))
             _, dw = _conv_backward(desc, x, dy, wd, False, ctx.needs_input_grad[1], ctx.wshape, getattr(ctx, "weight_ref", None))
         else:
             dx, dw = _conv_backward(desc, x, dy, wd, ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.wshape,
@@ -1505,7 +1559,7 @@ class MaxPool2(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, *rest):
-        in_link = rest[0] if rest else None               # (optional second argument: the ActLink of the ReLU that produced x)
+        in_link = rest[0] if rest else None               # (optional second argument: the Handover of the ReLU that produced x)
         ctx.nin = 1 + len(rest)
         x = x.contiguous()
         n, h, w, cp = x.shape
@@ -1521,10 +1575,10 @@ class MaxPool2(torch.autograd.Function):
         n, h, w, cp = x.shape
         dx = torch.empty_like(x)
         link = ctx.in_link
-        if link is not None and link.act == ACT_RELU:
-            # x is a ReLU output with this pool as its only consumer: the ReLU's backward rides in the routing (ActLink)
+        if link is not None and link.kind == "act" and ACT_LINKS and link.payload[0] == ACT_RELU:
+            # x is a ReLU output with this pool as its only consumer: the ReLU's backward rides in the routing (Handover "act")
             check(_lib.lib().dsr_maxpool2_relu_bwd(_dt(x), _ptr(x), _ptr(dy.contiguous()), _ptr(dx), n, h, w, cp, _stream()))
-            link.premasked = True
+            link.deposit(dx)
         else:
             check(_lib.lib().dsr_maxpool2_bwd(_dt(x), _ptr(x), _ptr(dy.contiguous()), _ptr(dx), n, h, w, cp, _stream()))
         return (dx, None) if ctx.nin == 2 else dx

@@ -21,14 +21,8 @@ class DiscriminatorConvBlock(nn.Module):
         self.stride = stride
         self.compute_dtype = torch.bfloat16
 
-    def _block(self, x, first2=None, bn_out_link=None, bn_in_link=None):
-        cfg = dict(stride=self.stride, pad=1, act=F.ACT_LEAKY, slope=0.2, train=self.training)
-        if first2 is not None:
-            cfg["first2"] = first2
-        if bn_out_link is not None:
-            cfg["bn_out_link"] = bn_out_link
-        if bn_in_link is not None:
-            cfg["bn_in_link"] = bn_in_link
+    def _block(self, x, in_link=None, out_link=None):
+        cfg = dict(stride=self.stride, pad=1, act=F.ACT_LEAKY, slope=0.2, train=self.training, in_link=in_link, out_link=out_link)
         return F.ConvBNAct.apply(x, self.conv1.weight, self.conv1.bias, self.bn1.weight, self.bn1.bias,
                                  self.bn1.running_mean, self.bn1.running_var, self.bn1.num_batches_tracked,
                                  None, None, cfg)                                           # discriminator.py:15-17
@@ -74,18 +68,19 @@ class Discriminator(nn.Module):
         fused = blk0.training and F.first2_supported(xi, self.conv.weight, blk0.conv1.weight, blk0.stride)
         # fused: the first layer is computed INSIDE the second layer's forward kernel (its 64-channel activation, 1.07 GB at
         # 512x512 x 32, is recomputed per tile and written only for a backward pass); ConvAct then only allocates and records
-        # (`link`: where the fused backward of the two layers, dsr_conv_dgrad_first_bwd, leaves the first layer's gradients for
-        #  its autograd node -- a step that needs no image gradient never writes the gradient of the activation between them)
-        link = {} if fused else None
+        # (`link`: the first layer offers the second what both fused kernels need, and the fused backward of the two layers,
+        #  dsr_conv_dgrad_first_bwd, leaves the first layer's gradients there for its autograd node -- a step that needs no image
+        #  gradient never writes the gradient of the activation between them: functional.Handover)
+        link = F.Handover() if fused else None
         z = F.ConvAct.apply(xi, self.conv.weight, self.conv.bias, None,
-                            dict(stride=1, pad=1, act=F.ACT_LEAKY, slope=0.2, defer=fused, first2_link=link))  # :60-61
-        # (`bnl`: a stride-2 block's input-gradient launch also forms the BatchNorm-backward sums of the block in front of it,
-        #  dsr_conv_dgrad_bn: that block leaves its raw conv output and affine map in the link, and finds the partial rows there)
+                            dict(stride=1, pad=1, act=F.ACT_LEAKY, slope=0.2, defer=fused, out_link=link))     # :60-61
+        # (a stride-2 block's input-gradient launch also forms the BatchNorm-backward sums of the block in front of it,
+        #  dsr_conv_dgrad_bn: that block offers its raw conv output and affine map, and finds the partial rows in the link)
         nb = len(self.convblocks)
-        bnl = [{} if (i + 1 < nb and self.convblocks[i + 1].stride == 2) else None for i in range(nb)]
         for i, blk in enumerate(self.convblocks):                                             # :63
-            z = blk._block(z, (xi, self.conv.weight, self.conv.bias, 0.2, link) if (fused and i == 0) else None,
-                           bn_out_link=bnl[i], bn_in_link=bnl[i - 1] if i > 0 else None)
+            out_link = F.Handover() if (i + 1 < nb and self.convblocks[i + 1].stride == 2) else None
+            z = blk._block(z, link, out_link)
+            link = out_link
         return z
 
     def head(self, z):

@@ -6,7 +6,7 @@ resize-256 / crop-224 preset.  The published recipes use something else:
   Real-ESRGAN and later five taps conv1_2 .. conv5_4 with weights 0.1, 0.1, 1, 1, 1, compared by L1, on the image at its own size
 VggFeatureLoss expresses both (the constructor follows basicsr's PerceptualLoss, restated from its documented behaviour; no
 style / Gram term).  Each tap is ONE pass over the 16-bit NHWC map where it already lives (functional.FeatureTap,
-csrc/featloss.hip): no fp32 NCHW copy of a map, and the ActLink chain that removed the trunk's activation-backward passes
+csrc/featloss.hip): no fp32 NCHW copy of a map, and the Handover chain that removed the trunk's activation-backward passes
 stays intact on every untapped layer.
 """
 import ctypes as C
@@ -168,8 +168,7 @@ class VggFeatureLoss(nn.Module):
         Otherwise: the tuple of taps of the other image; returns the per-tap means in tap order."""
         tapped = {(o, post): i for i, (o, post, _, _) in enumerate(self.taps)}
         out = [None] * len(self.taps)
-        link = None                   # the ActLink of the activation that produced x (see Vgg19Loss.features)
-        grad = targets is not None and torch.is_grad_enabled()
+        link = None                   # the Handover of the activation that produced x (see Vgg19Loss.features)
         for k, m in enumerate(self._convs()):
             pre, post = tapped.get((k, False)), tapped.get((k, True))
             last = k == self.depth - 1
@@ -185,9 +184,9 @@ class VggFeatureLoss(nn.Module):
                     x, out[pre] = F.FeatureTap.apply(y, targets[pre], self.mode, need_relu, m.out_channels)
                 link = None
             else:
-                # a relu tap gives the activation two consumers, so the ActLink chain ends at that layer: it runs its own
+                # a relu tap gives the activation two consumers, so the Handover chain ends at that layer: it runs its own
                 # activation backward on the sum the tap hands back
-                out_link = F.ActLink(F.ACT_RELU) if (grad and F.ACT_LINKS and post is None) else None
+                out_link = F.Handover() if post is None else None
                 x = F.ConvAct.apply(x, m.weight, m.bias, None,
                                     dict(stride=1, pad=1, act=F.ACT_RELU, in_link=link, out_link=out_link))
                 link = out_link

@@ -303,7 +303,7 @@ def test_tail_backward_with_the_pixel_shuffle_prelu_backward_inside(dev, factor,
     module, weights and batch: identical output, the launch taken exactly when expected, every parameter gradient and the
     input gradient equal to the rounding of that one tensor (rounded once instead of twice) -- cosine and norm, as everywhere
     in this file -- and the fused gradients no further from the oracle's than the unfused ones."""
-    F = P("functional")
+    F, L = P("functional"), P("_lib")
     x = filler.tensor("in:tailps", (2, 3) + hw, 0.5, 0.5)
     probe = filler.tensor("probe:tailps", (2, 3, hw[0] * factor, hw[1] * factor))
     res = {}
@@ -312,15 +312,19 @@ def test_tail_backward_with_the_pixel_shuffle_prelu_backward_inside(dev, factor,
         g, sd = build(dev, factor, 2)
         g.train()
         xg = x.to(dev).requires_grad_(True)
-        F.KERNEL_LOG = []
+        F.KERNEL_LOG, L.LAUNCH_LOG = [], []
         try:
             y = g(xg)
             (y * probe.to(dev)).sum().backward()
             torch.cuda.synchronize()
             names = [e[4] for e in F.KERNEL_LOG]
+            launches = [e[0] for e in L.LAUNCH_LOG]
         finally:
-            F.KERNEL_LOG = None
+            F.KERNEL_LOG = L.LAUNCH_LOG = None
         assert any("kernel<ps>" in nm for nm in names) == on, names
+        # the producer side: the last shuffle block skips its own activation-backward pass (one such pass per shuffle block and
+        # one for the 9x9 head otherwise)
+        assert launches.count("dsr_pw_act_bwd") == int(np.log2(factor)) + (0 if on else 1), launches
         res[on] = (y.detach().clone(), {k: p.grad.clone() for k, p in g.named_parameters() if p.grad is not None}, xg.grad.clone())
     (ya, ga, dxa), (yb, gb, dxb) = res[True], res[False]
     assert torch.equal(ya, yb) and set(ga) == set(gb)

@@ -327,12 +327,13 @@ def test_discriminator_fused_first_two_layers_equal_two_launches(dev, need_dx, m
 
 def test_discriminator_batchnorm_sums_in_the_next_layers_input_gradient(dev, monkeypatch):
     """A stride-2 block's input-gradient launch also forms the BatchNorm-backward sums of the block in front of it
-    (dsr_conv_dgrad_bn through the link Discriminator.features sets up); functional.DGRAD_BN off runs the separate reduce pass.
+    (dsr_conv_dgrad_bn through the functional.Handover Discriminator.features sets up); functional.DGRAD_BN off runs the separate
+    reduce pass.
     Same module, weights and batch at 128 x 128 (blocks 1 and 3 qualify: tiles of whole rows of one image; block 5's 8 x 8
     gradient map does not and keeps its reduce pass): identical output, the same launches taken as expected, every gradient
     equal to fp32 summation order."""
     Dm = P("models.GAN.discriminator")
-    F = P("functional")
+    F, L = P("functional"), P("_lib")
     hw = (128, 128)
     n = 2
     sd = filler.fill_state_dict(gan.template(gan.discriminator_shapes(hw)))
@@ -345,15 +346,18 @@ def test_discriminator_batchnorm_sums_in_the_next_layers_input_gradient(dev, mon
         d.load_state_dict(sd)
         d.to(dev).train()
         xg = x.to(dev).requires_grad_(True)
-        F.KERNEL_LOG = []
+        F.KERNEL_LOG, L.LAUNCH_LOG = [], []
         try:
             y = d(xg)
             (y * probe).sum().backward()
             torch.cuda.synchronize()
             names = [e[4] for e in F.KERNEL_LOG]
+            launches = [e[0] for e in L.LAUNCH_LOG]
         finally:
-            F.KERNEL_LOG = None
+            F.KERNEL_LOG = L.LAUNCH_LOG = None
         assert sum("kernel<bn>" in nm for nm in names) == (2 if on else 0), names
+        # the producer side: the two blocks whose sums came through the link skip their own reduce pass (7 blocks)
+        assert launches.count("dsr_pw_bn_act_bwd_reduce") == (5 if on else 7), launches
         res[on] = (y.detach().clone(), {k: p.grad.clone() for k, p in d.named_parameters() if p.grad is not None}, xg.grad.clone())
     (ya, ga, dxa), (yb, gb, dxb) = res[True], res[False]
     assert torch.equal(ya, yb) and set(ga) == set(gb)
@@ -373,7 +377,7 @@ def test_discriminator_fused_backward_of_first_two_layers(dev, monkeypatch):
     an image row of 512 pixels (a tile is 256 gradient pixels of ONE row); with an image that requires grad the launch is
     not taken and the two settings are bit-identical throughout."""
     Dm = P("models.GAN.discriminator")
-    F = P("functional")
+    F, L = P("functional"), P("_lib")
     hw = (16, 512)
     n = 2
     sd = filler.fill_state_dict(gan.template(gan.discriminator_shapes(hw)))
@@ -388,16 +392,22 @@ def test_discriminator_fused_backward_of_first_two_layers(dev, monkeypatch):
             d.load_state_dict(sd)
             d.to(dev).train()
             xg = x.to(dev).requires_grad_(need_dx)
-            F.KERNEL_LOG = []
+            F.KERNEL_LOG, L.LAUNCH_LOG = [], []
             try:
                 y = d(xg)
                 (y * probe).sum().backward()
                 torch.cuda.synchronize()
                 names = [e[4] for e in F.KERNEL_LOG]
+                launches = [e[0] for e in L.LAUNCH_LOG]
             finally:
-                F.KERNEL_LOG = None
+                F.KERNEL_LOG = L.LAUNCH_LOG = None
             took = any("first_bwd>" in nm for nm in names)
             assert took == (on and not need_dx), (need_dx, on, names)
+            # the producer side: the image layer's own backward launch runs exactly when the fused one did not (with an image
+            # gradient it is the plain activation backward + weight gradient instead)
+            assert launches.count("dsr_conv_dgrad_first_bwd") == int(took), launches
+            assert launches.count("dsr_conv_first_bwd_recompute") == int(not took and not need_dx), launches
+            assert launches.count("dsr_conv_first_bwd") == 0, launches
             res[(need_dx, on)] = (y.detach().clone(), {k: p.grad.clone() for k, p in d.named_parameters() if p.grad is not None})
     for need_dx in (False, True):
         (ya, ga), (yb, gb) = res[(need_dx, True)], res[(need_dx, False)]
@@ -1274,9 +1284,10 @@ def test_batched_wgrad_exception_drops_placeholder_grads(dev):
 
 
 def test_vgg_trunk_act_links_equal_separate_passes(dev):
-    """utils.GAN.Vgg19Loss with functional.ActLink (every ReLU's backward folded into its consumer's input-gradient / max-pool
-    backward launch) against the same trunk with one activation-backward pass per layer: loss and image gradient bit for bit."""
-    GANu, F = P("utils.GAN"), P("functional")
+    """utils.GAN.Vgg19Loss with functional.Handover "act" links (every ReLU's backward folded into its consumer's input-gradient
+    / max-pool backward launch) against the same trunk with one activation-backward pass per layer: loss and image gradient bit
+    for bit; of the 16 activation-backward passes only the last layer's remains."""
+    GANu, F, L = P("utils.GAN"), P("functional"), P("_lib")
     loss_mod = GANu.Vgg19Loss().to(dev)
     img = filler.tensor("in:vl_a", (2, 3, 96, 96)).to(dev)
     tgt = filler.tensor("in:vl_b", (2, 3, 96, 96)).to(dev)
@@ -1285,11 +1296,14 @@ def test_vgg_trunk_act_links_equal_separate_passes(dev):
         for links in (False, True):
             F.ACT_LINKS = links
             a = img.clone().requires_grad_(True)
+            L.LAUNCH_LOG = []
             loss = loss_mod(a, tgt)
             loss.backward()
             torch.cuda.synchronize()
+            assert [e[0] for e in L.LAUNCH_LOG].count("dsr_pw_act_bwd") == (1 if links else 16)
             res.append((loss.detach().clone(), a.grad.clone()))
     finally:
         F.ACT_LINKS = True
+        L.LAUNCH_LOG = None
     assert torch.isfinite(res[1][1]).all() and float(res[1][1].abs().max()) > 0
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])

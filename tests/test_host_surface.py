@@ -291,11 +291,35 @@ def test_bench_dump_outputs_sampling(tmp_path):
 
 
 def test_act_link_and_batched_wgrad_contexts_without_gpu():
-    """functional.ActLink is a plain hand-over cell; functional.batched_wgrad is re-entrant-safe bookkeeping: an empty block
-    launches nothing, a nested block defers to the outer one, an exception discards the batch."""
+    """functional.Handover (offer / deposit / collect, on CPU tensors): the deposit comes back only for the very tensor it was
+    made with -- another address, or the same tensor after an in-place add, gives None for "bn" and RuntimeError for the other
+    kinds -- and a collected link is spent.  functional.batched_wgrad is re-entrant-safe bookkeeping: an empty block launches
+    nothing, a nested block defers to the outer one, an exception discards the batch."""
     F = P("functional")
-    link = F.ActLink(F.ACT_RELU)
-    assert (link.act, link.slope, link.premasked) == (F.ACT_RELU, 0.0, False)
+    link = F.Handover()
+    assert link.kind is None and link.payload is None and link.collect(torch.zeros(2)) is None
+    for kind in ("act", "bn", "ps", "first2"):
+        dx, result = torch.ones(2, 3), (torch.ones(1), 7)
+        link = F.Handover()
+        link.offer(kind, 1, 0.5)
+        assert (link.kind, link.payload) == (kind, (1, 0.5))
+        link.deposit(dx, result)
+        assert link.collect(dx) is result
+        assert link.kind is None and link.payload is None and link.collect(dx) is None     # spent: nothing is kept
+        with pytest.raises(RuntimeError):
+            link.deposit(dx, result)                                                        # ... and no deposit is taken
+        for spoil in (lambda t: t.clone(), lambda t: t.add_(1.0)):
+            link = F.Handover()
+            link.offer(kind, 1, 0.5)
+            link.deposit(dx, result)
+            if kind == "bn":
+                assert link.collect(spoil(dx)) is None
+            else:
+                with pytest.raises(RuntimeError, match=f"'{kind}'.*second consumer or a hook"):
+                    link.collect(spoil(dx))
+            assert link.kind is None and link.collect(dx) is None                           # spent either way
+    ph = F.zero_placeholder((2, 4, 4, 8), torch.bfloat16, "cpu")
+    assert ph.shape == (2, 4, 4, 8) and ph.dtype == torch.bfloat16 and ph.stride() == (0, 0, 0, 0) and not ph.any()
     with F.batched_wgrad() as outer:
         assert F._wgrad_batch is outer
         with F.batched_wgrad() as inner:

@@ -73,7 +73,7 @@ def main():
         for k, conv in enumerate(convs):
             i = tap_of.get(k)
             if i is None:
-                out_link = F.ActLink(F.ACT_RELU) if F.ACT_LINKS else None
+                out_link = F.Handover()
                 h = F.ConvAct.apply(h, conv.weight, conv.bias, None, dict(stride=1, pad=1, act=F.ACT_RELU, in_link=link, out_link=out_link))
                 link = out_link
             else:
