@@ -16,6 +16,7 @@ F32 = 2                  # the luma entry points (csrc/luma.hip) also read fp32 
 ACT_NONE, ACT_LEAKY, ACT_PRELU, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_ELU = range(7)
 PAD_ZERO, PAD_REFLECT, PAD_REPLICATE = range(3)
 FEAT_L1, FEAT_MSE = 0, 1  # modes of the feature-loss taps (csrc/featloss.hip)
+GRAM_LOSS_PARTIALS = 64   # doubles of scratch per image that dsr_gram_loss takes (DSR_GRAM_LOSS_PARTIALS, csrc/featstyle.hip)
 GAN_VANILLA, GAN_LSGAN, GAN_HINGE = range(3)   # kinds of dsr_gan_loss (csrc/pointwise.hip)
 
 
@@ -231,6 +232,11 @@ SIGNATURES = {
     "dsr_featloss_relu": (_I, [_I, _P, _P, _Z, _I, _P]),
     "dsr_featloss_combine": (_I, [_I, C.POINTER(C.c_void_p), C.POINTER(_F), _P, _P]),
     "dsr_featloss_combine_bwd": (_I, [_I, C.POINTER(_F), _P, _P, _P]),
+    "dsr_gram_chunks": (_I, [_I]),
+    "dsr_gram_workspace": (_Z, [_I, _I, _I]),
+    "dsr_gram_fwd": (_I, [_I, _P, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "dsr_gram_loss": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "dsr_featstyle_tap_bwd": (_I, [_I, _P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _F, _P, _I, _I, _I, _P]),
     "dsr_imresize_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
     "dsr_imresize_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
     "dsr_conv_rdb_supported": (_I, [C.POINTER(RdbConv)]),
@@ -274,7 +280,7 @@ _NO_LAUNCH = ("dsr_last_error", "dsr_abi_version", "dsr_conv_dgrad_ps_supported"
               "dsr_msssim_min_size", "dsr_msssim_pyramid_floats", "dsr_ssim_cs_img_blocks", "dsr_msssim_bwd_blocks", "dsr_luma_blocks",
               "dsr_featloss_blocks", "dsr_jpeg_workspace", "dsr_conv_rdb_supported", "dsr_conv_rdb_dgrad_supported",
               "dsr_conv_rdb_wgrad_supported", "dsr_conv_rdb_wgrad_workspace", "dsr_conv_rdb_wgrad_chunks", "dsr_spectral_norm_workspace",
-              "dsr_spectral_norm_bwd_workspace", "dsr_gan_loss_blocks")
+              "dsr_spectral_norm_bwd_workspace", "dsr_gan_loss_blocks", "dsr_gram_chunks", "dsr_gram_workspace")
 
 
 class _Lib:

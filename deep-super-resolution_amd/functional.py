@@ -1307,6 +1307,103 @@ class FeatureTap(torch.autograd.Function):
         return df, None, None, None, None
 
 
+def _gram(x, c):
+    n, h, w, cp = x.shape
+    lib = _lib.lib()
+    ws = torch.empty(max(lib.dsr_gram_workspace(n, h * w, cp), 1), dtype=torch.float32, device=x.device)
+    gram = torch.empty((n, c, c), dtype=torch.float32, device=x.device)
+    check(lib.dsr_gram_fwd(_dt(x), _ptr(x), n, h * w, c, cp, 1.0 / (c * h * w), _ptr(ws), _ptr(gram), _stream()))
+    return gram
+
+
+def gram16(x, c):
+    """Gram matrices of a 16-bit NHWC map, no gradient: fp32 [N, c, c], gram[n][i][j] = sum_p x[n][p][i] x[n][p][j] / (c H W) over
+    the c real channels (dsr_gram_fwd).  What FeatureStyleTap takes as ``gram_t`` for the target."""
+    _need_gpu(x)
+    if x.dim() != 4 or not 1 <= int(c) <= x.shape[3]:
+        raise ValueError(f"gram16: an NHWC map and 1 <= c <= Cp, got {tuple(x.shape)} and c = {c!r}")
+    return _gram(x.detach().contiguous(), int(c))
+
+
+class FeatureStyleTap(torch.autograd.Function):
+    """FeatureTap with the style (Gram-matrix) term on the same map (csrc/featstyle.hip).
+
+    forward(f, t, gram_t, mode, want_relu, c, with_content) -> (x_next, content_value, style_value).  style_value is the mean
+    of |G - gram_t| (FEAT_L1) or (G - gram_t)^2 (FEAT_MSE) over the N c c entries of G = gram16(f, c); content_value is
+    FeatureTap's value when with_content is set and None otherwise (t may then be None: no content launch runs).  x_next and
+    the single-consumer contract are FeatureTap's.  The backward is ONE launch with one rounding per element: the gradient
+    arriving through x_next (masked when want_relu), the content term and the style term, a per-image GEMM of f with the
+    16-bit order-one matrix that the forward left, every scalar factor applied in fp32 in its epilogue.  t and gram_t get no
+    gradient."""
+
+    @staticmethod
+    def forward(ctx, f, t, gram_t, mode, want_relu, c, with_content):
+        _need_gpu(f)
+        if mode not in (FEAT_L1, FEAT_MSE):
+            raise ValueError(f"FeatureStyleTap: mode {mode!r} is neither FEAT_L1 nor FEAT_MSE")
+        if f.dim() != 4:
+            raise RuntimeError(f"FeatureStyleTap: the map is NHWC, got {tuple(f.shape)}")
+        f = f.contiguous()
+        n, h, w, cp = f.shape
+        c = int(c)
+        p = n * h * w
+        if gram_t.shape != (n, c, c) or gram_t.dtype != torch.float32:
+            raise RuntimeError(f"FeatureStyleTap: gram_t must be fp32 {(n, c, c)}, got {gram_t.dtype} {tuple(gram_t.shape)}")
+        gram_t = gram_t.contiguous()
+        lib = _lib.lib()
+        content, x_next = None, None
+        if with_content:
+            if t is None or f.shape != t.shape or f.dtype != t.dtype:
+                raise RuntimeError("FeatureStyleTap: with_content needs a target map of f's shape and dtype")
+            t = t.contiguous()
+            blocks = lib.dsr_featloss_blocks(p)
+            part = torch.empty(max(blocks, 1), dtype=torch.float32, device=f.device)
+            x_next = torch.empty_like(f) if want_relu else None
+            check(lib.dsr_featloss_tap_fwd(_dt(f), _ptr(f), _ptr(t), _ptr(x_next), p, cp, mode, _ptr(part), _stream()))
+            content = torch.empty(1, dtype=torch.float32, device=f.device)
+            check(lib.dsr_featloss_fold(_ptr(part), blocks, float(p * c), _ptr(content), _stream()))
+        else:
+            t = None
+            if want_relu:
+                x_next = torch.empty_like(f)
+                check(lib.dsr_featloss_relu(_dt(f), _ptr(f), _ptr(x_next), p, cp, _stream()))
+        gram = _gram(f, c)
+        sums = torch.empty(_lib.GRAM_LOSS_PARTIALS * n, dtype=torch.float64, device=f.device)
+        style = torch.empty(1, dtype=torch.float32, device=f.device)
+        s16 = torch.empty((n, cp, cp), dtype=f.dtype, device=f.device)
+        s_scale = torch.empty(n, dtype=torch.float32, device=f.device)
+        check(lib.dsr_gram_loss(_dt(f), _ptr(gram), _ptr(gram_t), n, c, cp, mode, _ptr(sums), _ptr(style), _ptr(s16), _ptr(s_scale),
+                                _stream()))
+        # d value / d f = [2 for MSE] * (D + D^T) f * scale / (N c c), D symmetric because both Gram matrices are
+        ctx.coef_style = (2.0 if mode == FEAT_L1 else 4.0) / (c * h * w) / (n * c * c)
+        ctx.mode, ctx.masked, ctx.coef, ctx.dims = mode, bool(want_relu), 1.0 / (p * c), (n, h * w, cp)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(f, t, s16, s_scale)
+        return (x_next if want_relu else f), content, style
+
+    @staticmethod
+    def backward(ctx, d_next, g_content, g_style):
+        f, t, s16, s_scale = ctx.saved_tensors
+        none = (None,) * 7
+        if not ctx.needs_input_grad[0] or (d_next is None and g_content is None and g_style is None):
+            return none
+        if g_content is None and g_style is None and not ctx.masked:
+            return (d_next,) + none[1:]
+
+        def scalar(g):
+            return torch.zeros(1, dtype=torch.float32, device=f.device) if g is None else g.reshape(1).contiguous().float()
+
+        gs = scalar(g_style)
+        gc = None if t is None else scalar(g_content)
+        if d_next is not None:
+            d_next = d_next.contiguous()
+        n, hw, cp = ctx.dims
+        df = torch.empty_like(f)
+        check(_lib.lib().dsr_featstyle_tap_bwd(_dt(f), _ptr(f), _ptr(t), _ptr(d_next), _ptr(gc), ctx.coef, ctx.mode, int(ctx.masked),
+                                               _ptr(s16), _ptr(s_scale), _ptr(gs), ctx.coef_style, _ptr(df), n, hw, cp, _stream()))
+        return (df,) + none[1:]
+
+
 class WeightedSum(torch.autograd.Function):
     """sum_k w_k * v_k over one-element device scalars with host weights, one launch each way (dsr_featloss_combine): the
     weighted sum of a multi-tap loss without a chain of scale_loss / add_losses launches.  forward(weights, *values)."""

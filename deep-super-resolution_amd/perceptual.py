@@ -1,13 +1,16 @@
-"""Multi-layer VGG19 feature loss on the HIP path: the content term of SRGAN / ESRGAN / Real-ESRGAN.
+"""Multi-layer VGG19 feature loss on the HIP path: the content term of SRGAN / ESRGAN / Real-ESRGAN, and the style
+(Gram-matrix) term of EnhanceNet / SRFeat and of basicsr's ``style_weight``.
 
 utils.GAN.Vgg19Loss is the reference's choice: one tap (relu5_4, after the activation), MSE, behind torchvision's
 resize-256 / crop-224 preset.  The published recipes use something else:
   SRGAN paper, ESRGAN   conv5_4 BEFORE the activation
   Real-ESRGAN and later five taps conv1_2 .. conv5_4 with weights 0.1, 0.1, 1, 1, 1, compared by L1, on the image at its own size
-VggFeatureLoss expresses both (the constructor follows basicsr's PerceptualLoss, restated from its documented behaviour; no
-style / Gram term).  Each tap is ONE pass over the 16-bit NHWC map where it already lives (functional.FeatureTap,
-csrc/featloss.hip): no fp32 NCHW copy of a map, and the Handover chain that removed the trunk's activation-backward passes
-stays intact on every untapped layer.
+VggFeatureLoss expresses both (the constructor follows basicsr's PerceptualLoss, restated from its documented behaviour; parity
+with basicsr itself is not pinned by a test, for the content term or the style term).  Each tap is ONE pass over the 16-bit NHWC
+map where it already lives (functional.FeatureTap, csrc/featloss.hip): no fp32 NCHW copy of a map, and the Handover chain that
+removed the trunk's activation-backward passes stays intact on every untapped layer.  With style_weight > 0 a tap also forms
+the map's Gram matrices by MFMA over the same 16-bit map and its backward is still one launch with one rounding per element
+(functional.FeatureStyleTap, csrc/featstyle.hip).
 """
 import ctypes as C
 import math
@@ -57,11 +60,17 @@ class _IdentityTables:
 
 
 class VggFeatureLoss(nn.Module):
-    """loss = perceptual_weight * sum_k w_k * mean_crit(phi_k(image1), phi_k(image2)) over taps phi_k of a frozen VGG19 trunk.
+    """loss = perceptual_weight * sum_k w_k * mean_crit(phi_k(image1), phi_k(image2))
+            + style_weight * sum_k w_k * mean_crit(gram(phi_k(image1)), gram(phi_k(image2)))
+    over taps phi_k of a frozen VGG19 trunk; gram(phi)[n][i][j] = sum_p phi[n][i][p] phi[n][j][p] / (C H W) over the H W pixels.
 
     layer_weights   {name: weight}; 'conv{b}_{i}' taps the map BEFORE the activation, 'relu{b}_{i}' after it (b = 1..5, i over
                     the block's 2, 2, 4, 4, 4 convolutions).  Weights are finite and >= 0, at least one > 0.
-    criterion       'l1' or 'mse' ('l2' is an alias of 'mse'); the mean runs over all N C H W elements of a map.
+    criterion       'l1' or 'mse' ('l2' is an alias of 'mse'); the mean runs over all N C H W elements of a map, and over the
+                    N C C entries of its Gram matrices in the style term.  basicsr's 'fro' is not offered (ValueError).
+    perceptual_weight, style_weight   finite and >= 0, at least one > 0.  style_weight = 0.0 (default): the content term alone,
+                    the launches and the bits of a module built without the keyword.  perceptual_weight = 0: the style term
+                    alone, and no content launch runs.  The style term needs C <= 512 (every VGG19 layer).
     use_input_norm  apply the ImageNet mean / std; range_norm maps [-1, 1] -> [0, 1] first.  Both fold into one affine map per
                     channel inside the pass that makes the 16-bit NHWC input.
     state_dict      a torchvision ``vgg19().features`` state dict (keys '<i>.weight' / '<i>.bias'); None: the deterministic
@@ -73,13 +82,18 @@ class VggFeatureLoss(nn.Module):
     compute_dtype   torch.bfloat16 (default, the tested path) or torch.float16.  fp16 goes through the same kernels with NO
                     internal gradient scale: the caller's loss scale (optim.DynamicLossScaler) has to cover it.
 
-    forward(image1, image2, features2=None) gives a gradient for image1 ONLY: an image2 that requires grad raises ValueError
-    (detach it).  target_features(image) runs under no_grad and returns the tuple of 16-bit taps that ``features2=`` accepts,
-    so a step can compute the target's half ahead of time on another stream (steps.gan_step does).  After a call
-    ``last_terms`` holds the unweighted per-tap means, {name: 1-element device tensor}; nothing is read on the host."""
+    forward(image1, image2, features2=None, grams2=None) returns ONE scalar, content + style, so every caller of a content
+    loss (steps.gen_perceptual_step, steps.realesrgan_step, steps.gan_step, utils.GAN.PerceptualLoss(vgg_loss=...)) takes a
+    style-weighted module as it is; the content term those report then includes the style term.  It gives a gradient for
+    image1 ONLY: an image2 that requires grad raises ValueError (detach it).  terms(...) takes the same arguments and returns
+    the two halves (percep, style) as basicsr's forward does, None for a zero weight.  target_features(image) runs under
+    no_grad and returns the tuple of 16-bit taps that ``features2=`` accepts, target_grams(features2) the tuple of their fp32
+    [N, C, C] Gram matrices that ``grams2=`` accepts, so a step can compute the target's half ahead of time on another stream
+    (steps.gan_step does).  After a call ``last_terms`` / ``last_style_terms`` hold the unweighted per-tap means of the two
+    halves, {name: 1-element device tensor} (empty for a zero weight); nothing is read on the host."""
 
     def __init__(self, layer_weights=None, criterion='l1', perceptual_weight=1.0, use_input_norm=True, range_norm=False,
-                 state_dict=None, resize_to=None, crop=None, compute_dtype=torch.bfloat16):
+                 state_dict=None, resize_to=None, crop=None, compute_dtype=torch.bfloat16, style_weight=0.0):
         super().__init__()
         layer_weights = {'conv5_4': 1.0} if layer_weights is None else dict(layer_weights)
         if not layer_weights:
@@ -102,6 +116,14 @@ class VggFeatureLoss(nn.Module):
         pw = float(perceptual_weight)
         if not math.isfinite(pw) or pw < 0.0:
             raise ValueError(f"VggFeatureLoss: perceptual_weight must be finite and >= 0, got {perceptual_weight!r}")
+        try:
+            sw = float(style_weight)
+        except (TypeError, ValueError):
+            raise ValueError(f"VggFeatureLoss: style_weight is not a number: {style_weight!r}")
+        if not math.isfinite(sw) or sw < 0.0:
+            raise ValueError(f"VggFeatureLoss: style_weight must be finite and >= 0, got {style_weight!r}")
+        if pw == 0.0 and sw == 0.0:
+            raise ValueError("VggFeatureLoss: perceptual_weight and style_weight are both 0; at least one must be > 0")
         if (resize_to is None) != (crop is None):
             raise ValueError("VggFeatureLoss: give both resize_to and crop (the preset) or neither (no resampling)")
         if compute_dtype not in (torch.bfloat16, torch.float16):
@@ -109,7 +131,7 @@ class VggFeatureLoss(nn.Module):
         taps.sort(key=lambda e: (e[0], e[1]))                     # trunk order; a layer's conv tap comes before its relu tap
         self.taps = tuple(taps)
         self.layer_names = tuple(name for _, _, name, _ in taps)
-        self.mode, self.criterion, self.perceptual_weight = crit, criterion, pw
+        self.mode, self.criterion, self.perceptual_weight, self.style_weight = crit, criterion, pw, sw
         self.depth = taps[-1][0] + 1                              # convolutions that run
         layers = []
         cin = 3
@@ -133,6 +155,7 @@ class VggFeatureLoss(nn.Module):
         self.resize_to, self.crop = resize_to, crop
         self.compute_dtype = compute_dtype
         self.last_terms = {}
+        self.last_style_terms = {}
         self._tables = {}
 
     # ------------------------------------------------------------------ input
@@ -163,11 +186,19 @@ class VggFeatureLoss(nn.Module):
     def _convs(self):
         return [m for m in self.net[0].children() if isinstance(m, nn.Conv2d)][:self.depth]
 
-    def _run(self, x, targets):
+    def _run(self, x, targets, grams=None):
         """The trunk up to the deepest tap.  targets None: the target's half (no gradient), returns the tuple of taps.
-        Otherwise: the tuple of taps of the other image; returns the per-tap means in tap order."""
+        Otherwise: the tuple of taps of the other image; returns the per-tap means in tap order.  grams: the target's Gram
+        matrices, for a style-weighted module; the return is then (content means or Nones, style means)."""
         tapped = {(o, post): i for i, (o, post, _, _) in enumerate(self.taps)}
         out = [None] * len(self.taps)
+        sout = [None] * len(self.taps)
+        content = self.perceptual_weight > 0.0
+
+        def tap(y, i, need_relu, c):
+            if grams is None:
+                return F.FeatureTap.apply(y, targets[i], self.mode, need_relu, c) + (None,)
+            return F.FeatureStyleTap.apply(y, targets[i] if content else None, grams[i], self.mode, need_relu, c, content)
         link = None                   # the Handover of the activation that produced x (see Vgg19Loss.features)
         for k, m in enumerate(self._convs()):
             pre, post = tapped.get((k, False)), tapped.get((k, True))
@@ -181,7 +212,7 @@ class VggFeatureLoss(nn.Module):
                     out[pre] = y
                     x = F.relu16(y) if need_relu else y
                 else:
-                    x, out[pre] = F.FeatureTap.apply(y, targets[pre], self.mode, need_relu, m.out_channels)
+                    x, out[pre], sout[pre] = tap(y, pre, need_relu, m.out_channels)
                 link = None
             else:
                 # a relu tap gives the activation two consumers, so the Handover chain ends at that layer: it runs its own
@@ -194,19 +225,28 @@ class VggFeatureLoss(nn.Module):
                 if targets is None:
                     out[post] = x
                 else:
-                    x, out[post] = F.FeatureTap.apply(x, targets[post], self.mode, False, m.out_channels)
+                    x, out[post], sout[post] = tap(x, post, False, m.out_channels)
                 link = None
             if k in _POOL_AFTER and not last:
                 x = F.MaxPool2.apply(x, link)
                 link = None
-        return tuple(out)
+        return tuple(out) if grams is None else (tuple(out), tuple(sout))
 
     def target_features(self, image):
         """The 16-bit NHWC taps of the target, in trunk order (``layer_names``), computed without a gradient."""
         with torch.no_grad():
             return self._run(self._input(image), None)
 
-    def forward(self, image1, image2, features2=None):
+    def target_grams(self, features2):
+        """The fp32 [N, C, C] Gram matrices of the target's taps (``target_features``), in trunk order, without a gradient."""
+        features2 = tuple(features2)
+        if len(features2) != len(self.taps):
+            raise ValueError(f"VggFeatureLoss: features2 holds {len(features2)} maps, the module has {len(self.taps)} taps")
+        convs = self._convs()
+        with torch.no_grad():
+            return tuple(F.gram16(t, convs[o].out_channels) for t, (o, _, _, _) in zip(features2, self.taps))
+
+    def _targets(self, image2, features2, grams2):
         if image2 is not None and image2.requires_grad:
             raise ValueError("VggFeatureLoss: image2 is the target and gets no gradient; detach it (only image1 is differentiated)")
         if features2 is None:
@@ -214,6 +254,33 @@ class VggFeatureLoss(nn.Module):
         features2 = tuple(features2)
         if len(features2) != len(self.taps):
             raise ValueError(f"VggFeatureLoss: features2 holds {len(features2)} maps, the module has {len(self.taps)} taps")
-        values = self._run(self._input(image1), features2)
-        self.last_terms = {name: v.detach() for name, v in zip(self.layer_names, values)}
-        return F.weighted_sum(values, [self.perceptual_weight * w for _, _, _, w in self.taps])
+        if self.style_weight > 0.0:
+            grams2 = self.target_grams(features2) if grams2 is None else tuple(grams2)
+            if len(grams2) != len(self.taps):
+                raise ValueError(f"VggFeatureLoss: grams2 holds {len(grams2)} matrices, the module has {len(self.taps)} taps")
+        else:
+            grams2 = None
+        return features2, grams2
+
+    def terms(self, image1, image2, features2=None, grams2=None):
+        """(percep, style): the two weighted halves of the loss, None for a zero weight."""
+        features2, grams2 = self._targets(image2, features2, grams2)
+        if grams2 is None:
+            values, svalues = self._run(self._input(image1), features2), None
+        else:
+            values, svalues = self._run(self._input(image1), features2, grams2)
+        percep = style = None
+        self.last_terms, self.last_style_terms = {}, {}
+        if self.perceptual_weight > 0.0:
+            self.last_terms = {name: v.detach() for name, v in zip(self.layer_names, values)}
+            percep = F.weighted_sum(values, [self.perceptual_weight * w for _, _, _, w in self.taps])
+        if svalues is not None:
+            self.last_style_terms = {name: v.detach() for name, v in zip(self.layer_names, svalues)}
+            style = F.weighted_sum(svalues, [self.style_weight * w for _, _, _, w in self.taps])
+        return percep, style
+
+    def forward(self, image1, image2, features2=None, grams2=None):
+        percep, style = self.terms(image1, image2, features2, grams2)
+        if percep is None or style is None:
+            return style if percep is None else percep
+        return F.add_losses(percep, style)

@@ -82,6 +82,8 @@ def gen_perceptual_step(gen, opt, vggfeat, lr_patches, hr_patches, l1_weight=1.0
 
     `vggfeat`: a perceptual.VggFeatureLoss; its layer weights and perceptual_weight are the content term's whole weighting.
     Build it with range_norm=True for a tanh generator and scale_images targets in [-1, 1].  Only `fake` requires a gradient.
+    A module built with style_weight > 0 is taken as it is: the content term returned here (and by realesrgan_step and
+    gan_step) then includes its style term.
     Returns the unweighted L1 term, the (weighted) content term and `fake` as device tensors (no host sync here); usable
     inside GraphedStep.  `scaler`: an optim.DynamicLossScaler around the summed loss (needed for compute_dtype=float16: the
     feature loss keeps no gradient scale of its own)."""

@@ -735,6 +735,40 @@ int dsr_featloss_relu(int dtype, const void* x, void* out, size_t P, int Cp, dsr
 int dsr_featloss_combine(int n, const float* const* values, const float* weights, float* out, dsr_stream_t s);
 int dsr_featloss_combine_bwd(int n, const float* weights, const float* g, float* gout, dsr_stream_t s);
 
+/* ------------------------------------------------------------------ style (Gram-matrix) term of the feature loss (featstyle.hip)
+ * The texture half of the perceptual loss (perceptual.VggFeatureLoss(style_weight=), functional.FeatureStyleTap).  f is a
+ * tapped map [N][HW][Cp] (NHWC, HW pixels per image, Cp = round_up(C, 8) with zero pad channels), DSR_BF16 or DSR_F16, 16-byte
+ * aligned.  Limits of every entry point: Cp % 8 == 0, 1 <= C <= Cp <= 512, HW >= 1, N >= 1, N HW < 2^31.
+ * dsr_gram_chunks(HW): the number of pixel chunks of one image, ceil(HW / 1024).  The chunk size is a constant of the kernel,
+ *   so the summation order depends on the shape alone.  dsr_gram_workspace(N, HW, Cp): the fp32 ELEMENTS of the workspace,
+ *   N * chunks * Cp * Cp (0 for a shape outside the limits).
+ * dsr_gram_fwd: gram[N][C][C] (fp32) = scale * sum_p f[n][p][i] f[n][p][j]: MFMA with fp32 accumulation over the tile pairs on or
+ *   above the diagonal, one fp32 slab per pixel chunk in the workspace, then the slabs are summed in chunk order and entry
+ *   (i, j) and its mirror are written from the same sum: gram[n] is bit-symmetric.  No atomics: two calls give equal bits.
+ * dsr_gram_loss: value[0] = (float)(sum crit(gram_f - gram_t) / (N C C)), crit = |.| (DSR_FEAT_L1) or (.)^2 (DSR_FEAT_MSE),
+ *   accumulated in double in a fixed order; partial: DSR_GRAM_LOSS_PARTIALS * N doubles of scratch (per-slice sums and maxima;
+ *   N <= 65535).  It also writes the operand of the
+ *   backward GEMM, s16[N][Cp][Cp] in the map's dtype (pad rows and columns zero): sign(G - Gt) with sign(0) = 0 for L1 and
+ *   s_scale[n] = 1; (G - Gt) / s_scale[n] with s_scale[n] = max |G - Gt| of image n for MSE (an all-zero difference gives
+ *   s16 = 0, s_scale[n] = 1).  The entries are of order one, so fp16 neither overflows nor underflows.
+ * dsr_featstyle_tap_bwd: one launch and one rounding per element,
+ *     df[n][p][c] = (dnext ? dnext * m : 0) + g_content[0] * coef_content * d
+ *                   + g_style[0] * coef_style * s_scale[n] * sum_i f[n][p][i] * s16[n][i][c],
+ *   m, d, mode, masked, dnext as in dsr_featloss_tap_bwd; t and g_content are both null for a style-only tap.  coef_style is a
+ *   host float that carries every scalar factor of the style gradient -- 2 scale / (N C C) for the symmetric D + D^T, times 2
+ *   for MSE, times any loss scale the caller folds in -- so none of them is ever rounded to 16 bits.
+ * A null required pointer, a shape outside the limits or an unknown mode returns DSR_E_ARG before anything is launched. */
+#define DSR_GRAM_LOSS_SLICES 32
+#define DSR_GRAM_LOSS_PARTIALS (2 * DSR_GRAM_LOSS_SLICES)
+int dsr_gram_chunks(int HW);
+size_t dsr_gram_workspace(int N, int HW, int Cp);
+int dsr_gram_fwd(int dtype, const void* f, int N, int HW, int C, int Cp, float scale, float* workspace, float* gram, dsr_stream_t s);
+int dsr_gram_loss(int dtype, const float* gram_f, const float* gram_t, int N, int C, int Cp, int mode, double* partial, float* value,
+                  void* s16, float* s_scale, dsr_stream_t s);
+int dsr_featstyle_tap_bwd(int dtype, const void* f, const void* t, const void* dnext, const float* g_content, float coef_content,
+                          int mode, int masked, const void* s16, const float* s_scale, const float* g_style, float coef_style,
+                          void* df, int N, int HW, int Cp, dsr_stream_t s);
+
 /* ------------------------------------------------------------------ MATLAB-style antialiased resampling (imresize.hip)
  * y = W_h . x . W_w^T per plane in ONE launch: the H pass runs from global memory into an LDS strip, the W pass out of it; the
  * intermediate stays fp32 and never reaches HBM.  Per axis the caller passes DEVICE tables built on the host (utils/imresize.py:

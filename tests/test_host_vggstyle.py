@@ -1,0 +1,200 @@
+"""CPU: the style (Gram-matrix) term of perceptual.VggFeatureLoss without a device -- the float64 yardstick
+tests/vggstyle_ref.py against hand values, the constructor's refusals, the new methods' presence, and the argument checks of
+the entry points of csrc/featstyle.hip through the built library (every refusal precedes any launch)."""
+import ctypes
+import importlib
+import math
+
+import pytest
+import torch
+
+import vggstyle_ref
+
+PKG = "deep-super-resolution_amd"
+E_ARG = -1
+
+
+def P(sub):
+    return importlib.import_module(PKG + "." + sub)
+
+
+@pytest.fixture(scope="module")
+def so():
+    return P("_build").build()
+
+
+# ----------------------------------------------------------------------------- 11. the yardstick against hand values
+def test_gram_of_a_1x2x1x2_map_by_hand_pre_and_post_activation():
+    """phi: channel 0 holds (1, -2) and channel 1 holds (3, 4) in its two pixels; C H W = 4.
+    before the activation   phi phi^T = [[1 + 4, 3 - 8], [3 - 8, 9 + 16]] = [[5, -5], [-5, 25]]
+    after it (1, 0 | 3, 4)  phi phi^T = [[1, 3], [3, 25]]"""
+    phi = torch.tensor([[[[1.0, -2.0]], [[3.0, 4.0]]]])
+    assert phi.shape == (1, 2, 1, 2)
+    g_pre = vggstyle_ref.gram(phi)
+    g_post = vggstyle_ref.gram(torch.relu(phi))
+    assert g_pre.dtype == torch.float64 and g_pre.shape == (1, 2, 2)
+    assert torch.equal(g_pre, torch.tensor([[[5.0, -5.0], [-5.0, 25.0]]], dtype=torch.float64) / 4)
+    assert torch.equal(g_post, torch.tensor([[[1.0, 3.0], [3.0, 25.0]]], dtype=torch.float64) / 4)
+    # the criterion over the N C C = 4 entries: |d| = (4, 8, 8, 0) / 4
+    assert float(vggstyle_ref.crit(g_pre, g_post, "l1")) == (1 + 2 + 2 + 0) / 4
+    assert float(vggstyle_ref.crit(g_pre, g_post, "mse")) == (1 + 4 + 4 + 0) / 4
+    assert float(vggstyle_ref.crit(g_pre, g_post, "l2")) == float(vggstyle_ref.crit(g_pre, g_post, "mse"))
+    with pytest.raises(ValueError):
+        vggstyle_ref.crit(g_pre, g_post, "fro")
+
+
+def _toy():
+    """test_host_vggfeat's trunk: conv1_1 channel 0 = x_r - 0.5, channel 1 = -x_r, every other channel 0.  Image 1 holds
+    (1, 0.25, 0, 2) in its red plane, image 2 is zero."""
+    sd = {"0.weight": torch.zeros(64, 3, 3, 3), "0.bias": torch.zeros(64)}
+    sd["0.weight"][0, 0, 1, 1] = 1.0
+    sd["0.bias"][0] = -0.5
+    sd["0.weight"][1, 0, 1, 1] = -1.0
+    a = torch.zeros(1, 3, 2, 2)
+    a[0, 0] = torch.tensor([[1.0, 0.25], [0.0, 2.0]])
+    return sd, a, torch.zeros(1, 3, 2, 2)
+
+
+def test_yardstick_through_the_trunk_by_hand():
+    """conv1_1 of image 1: channel 0 = (0.5, -0.25, -0.5, 1.5), channel 1 = (-1, -0.25, 0, -2); C H W = 256, N C C = 4096.
+        G00 = 2.8125, G11 = 5.0625, G01 = G10 = -3.4375;  image 2: channel 0 = -0.5 everywhere, G00 = 1, the rest 0
+        L1 sum = 1.8125 + 5.0625 + 2 * 3.4375 = 13.75;  squares: 1.8125^2 + 5.0625^2 + 2 * 3.4375^2 = 52.546875
+    relu1_1 of image 1: channel 0 = (0.5, 0, 0, 1.5), G00 = 2.5; image 2: all zero.  The activation changes the term."""
+    sd, a, b = _toy()
+    kw = dict(use_input_norm=False, range_norm=False)
+    lw = {"conv1_1": 1.0, "relu1_1": 0.5}
+    t = vggstyle_ref.ref_style_terms(sd, a, b, lw, "l1", **kw)
+    assert float(t["conv1_1"]) == pytest.approx(13.75 / 256 / 4096, rel=1e-12)
+    assert float(t["relu1_1"]) == pytest.approx(2.5 / 256 / 4096, rel=1e-12)
+    t2 = vggstyle_ref.ref_style_terms(sd, a, b, lw, "mse", **kw)
+    assert float(t2["conv1_1"]) == pytest.approx(52.546875 / 256 ** 2 / 4096, rel=1e-12)
+    assert float(t2["relu1_1"]) == pytest.approx(6.25 / 256 ** 2 / 4096, rel=1e-12)
+    content, style = vggstyle_ref.ref_terms(sd, a, b, lw, "l1", **kw)
+    assert float(content["conv1_1"]) == pytest.approx(6.5 / 256, rel=1e-12)            # test_host_vggfeat's hand value
+    assert float(style["conv1_1"]) == float(t["conv1_1"])
+    both = vggstyle_ref.ref_loss(sd, a, b, lw, "l1", perceptual_weight=2.0, style_weight=8.0, **kw)
+    want = 2.0 * (6.5 / 256 + 0.5 * 2.0 / 256) + 8.0 * (13.75 + 0.5 * 2.5) / 256 / 4096
+    assert float(both) == pytest.approx(want, rel=1e-12)
+    only = vggstyle_ref.ref_loss(sd, a, b, lw, "l1", perceptual_weight=0.0, style_weight=8.0, **kw)
+    assert float(only) == pytest.approx(8.0 * (13.75 + 0.5 * 2.5) / 256 / 4096, rel=1e-12)
+
+
+# ----------------------------------------------------------------------------- 12. the constructor's refusals
+def test_constructor_refusals():
+    V = P("perceptual").VggFeatureLoss
+    for w in (-0.5, math.nan, math.inf, -math.inf, "x", None, [1.0]):
+        with pytest.raises(ValueError, match="style_weight"):
+            V(style_weight=w)
+    with pytest.raises(ValueError, match="at least one"):
+        V(perceptual_weight=0.0, style_weight=0.0)
+    with pytest.raises(ValueError, match="at least one"):
+        V(perceptual_weight=0.0)
+    with pytest.raises(ValueError, match="criterion"):
+        V(criterion="fro", style_weight=1.0)
+    m = V(style_weight=2)
+    assert m.style_weight == 2.0 and m.perceptual_weight == 1.0
+    only = V({"conv1_2": 1.0}, "mse", perceptual_weight=0.0, style_weight=0.5)
+    assert only.perceptual_weight == 0.0 and only.style_weight == 0.5
+    assert V().style_weight == 0.0
+
+
+# ----------------------------------------------------------------------------- 13. the surface exists without a device
+def test_new_surface_imports_without_a_gpu():
+    pc, F = P("perceptual"), P("functional")
+    m = pc.VggFeatureLoss(style_weight=1.0)
+    assert callable(m.terms) and callable(m.target_grams) and callable(m.target_features)
+    assert m.last_terms == {} and m.last_style_terms == {}
+    assert callable(F.gram16) and hasattr(F.FeatureStyleTap, "apply") and hasattr(F.FeatureTap, "apply")
+    a = torch.zeros(1, 3, 32, 32)
+    with pytest.raises(ValueError, match="image2"):
+        m.terms(a, a.clone().requires_grad_(True))
+    with pytest.raises(ValueError, match="features2"):
+        m.target_grams(())
+    if not torch.cuda.is_available():
+        with pytest.raises(RuntimeError, match="MI355X"):
+            F.gram16(torch.zeros(1, 2, 2, 8, dtype=torch.bfloat16), 3)
+    assert "no style" not in pc.__doc__ and "Gram" in pc.__doc__
+
+
+# ----------------------------------------------------------------------------- 14. the C entries refuse bad arguments on the host
+def test_abi_version_is_still_8(so):
+    L = P("_lib")
+    assert L.ABI_VERSION == 8 and L.lib().dsr_abi_version() == 8
+    for name in ("dsr_gram_chunks", "dsr_gram_workspace", "dsr_gram_fwd", "dsr_gram_loss", "dsr_featstyle_tap_bwd"):
+        assert name in L.SIGNATURES
+    assert "dsr_gram_chunks" in L._NO_LAUNCH and "dsr_gram_workspace" in L._NO_LAUNCH
+
+
+def test_size_queries(so):
+    lib = P("_lib").lib()
+    assert [lib.dsr_gram_chunks(hw) for hw in (0, -3, 1, 1024, 1025, 2209, 65536)] == [0, 0, 1, 1, 2, 3, 64]
+    assert lib.dsr_gram_workspace(2, 2209, 64) == 2 * 3 * 64 * 64
+    assert lib.dsr_gram_workspace(3, 9, 8) == 3 * 64
+    assert lib.dsr_gram_workspace(12, 256, 512) == 12 * 512 * 512
+    for bad in ((0, 9, 8), (2, 0, 8), (2, 9, 12), (2, 9, 0), (2, 9, 520), (1 << 16, 1 << 15, 8)):
+        assert lib.dsr_gram_workspace(*bad) == 0, bad
+
+
+def test_bad_arguments_return_e_arg_without_a_launch(so):
+    L = P("_lib")
+    lib = L.lib()
+    N, st = None, None
+    one = ctypes.c_void_p(4096)          # a non-null, aligned "pointer" that is never dereferenced: validation fails first
+    odd = ctypes.c_void_p(4100)          # ... and one that is not 16-byte aligned
+    B = L.BF16
+
+    def bwd(dtype=B, f=one, t=one, dnext=N, gc=one, mode=0, s16=one, ss=one, gs=one, df=one, n=2, hw=9, cp=64):
+        return lib.dsr_featstyle_tap_bwd(dtype, f, t, dnext, gc, 1.0, mode, 0, s16, ss, gs, 1.0, df, n, hw, cp, st)
+
+    calls = [
+        lambda: lib.dsr_gram_fwd(B, N, 2, 9, 64, 64, 1.0, one, one, st),                 # f
+        lambda: lib.dsr_gram_fwd(B, one, 2, 9, 64, 64, 1.0, N, one, st),                 # workspace
+        lambda: lib.dsr_gram_fwd(B, one, 2, 9, 64, 64, 1.0, one, N, st),                 # gram
+        lambda: lib.dsr_gram_fwd(B, one, 2, 9, 12, 12, 1.0, one, one, st),               # Cp % 8
+        lambda: lib.dsr_gram_fwd(B, one, 2, 9, 3, 0, 1.0, one, one, st),                 # Cp == 0
+        lambda: lib.dsr_gram_fwd(B, one, 2, 9, 512, 520, 1.0, one, one, st),             # Cp > 512
+        lambda: lib.dsr_gram_fwd(B, one, 2, 9, 9, 8, 1.0, one, one, st),                 # C > Cp
+        lambda: lib.dsr_gram_fwd(B, one, 2, 9, 0, 8, 1.0, one, one, st),                 # C == 0
+        lambda: lib.dsr_gram_fwd(B, one, 2, 0, 64, 64, 1.0, one, one, st),               # HW == 0
+        lambda: lib.dsr_gram_fwd(B, one, 0, 9, 64, 64, 1.0, one, one, st),               # N == 0
+        lambda: lib.dsr_gram_fwd(B, one, 1 << 16, 1 << 15, 64, 64, 1.0, one, one, st),   # N HW = 2^31
+        lambda: lib.dsr_gram_fwd(2, one, 2, 9, 64, 64, 1.0, one, one, st),               # dtype
+        lambda: lib.dsr_gram_fwd(B, odd, 2, 9, 64, 64, 1.0, one, one, st),               # alignment
+        lambda: lib.dsr_gram_loss(B, N, one, 2, 64, 64, 0, one, one, one, one, st),      # gram_f
+        lambda: lib.dsr_gram_loss(B, one, N, 2, 64, 64, 0, one, one, one, one, st),      # gram_t
+        lambda: lib.dsr_gram_loss(B, one, one, 2, 64, 64, 0, N, one, one, one, st),      # partial
+        lambda: lib.dsr_gram_loss(B, one, one, 2, 64, 64, 0, one, N, one, one, st),      # value
+        lambda: lib.dsr_gram_loss(B, one, one, 2, 64, 64, 0, one, one, N, one, st),      # s16
+        lambda: lib.dsr_gram_loss(B, one, one, 2, 64, 64, 0, one, one, one, N, st),      # s_scale
+        lambda: lib.dsr_gram_loss(B, one, one, 2, 12, 12, 0, one, one, one, one, st),    # Cp % 8
+        lambda: lib.dsr_gram_loss(B, one, one, 2, 512, 520, 0, one, one, one, one, st),  # Cp > 512
+        lambda: lib.dsr_gram_loss(B, one, one, 2, 9, 8, 0, one, one, one, one, st),      # C > Cp
+        lambda: lib.dsr_gram_loss(B, one, one, 0, 64, 64, 0, one, one, one, one, st),    # N == 0
+        lambda: lib.dsr_gram_loss(B, one, one, 2, 64, 64, 2, one, one, one, one, st),    # mode
+        lambda: lib.dsr_gram_loss(B, one, one, 2, 64, 64, -1, one, one, one, one, st),
+        lambda: lib.dsr_gram_loss(5, one, one, 2, 64, 64, 0, one, one, one, one, st),    # dtype
+        lambda: lib.dsr_gram_loss(B, one, one, 2, 64, 64, 0, odd, one, one, one, st),    # partial holds doubles
+        lambda: bwd(f=N),
+        lambda: bwd(s16=N),
+        lambda: bwd(ss=N),
+        lambda: bwd(gs=N),
+        lambda: bwd(df=N),
+        lambda: bwd(t=N),                 # t without g_content's partner: they are null together or not at all
+        lambda: bwd(gc=N),
+        lambda: bwd(cp=12),               # Cp % 8
+        lambda: bwd(cp=0),
+        lambda: bwd(cp=520),              # Cp > 512
+        lambda: bwd(hw=0),                # HW == 0
+        lambda: bwd(n=0),
+        lambda: bwd(n=1 << 16, hw=1 << 15),
+        lambda: bwd(mode=2),
+        lambda: bwd(mode=-1),
+        lambda: bwd(dtype=2),
+        lambda: bwd(f=odd),
+        lambda: bwd(dnext=odd),
+        lambda: bwd(s16=odd),
+    ]
+    for i, call in enumerate(calls):
+        assert call() == E_ARG, i
+        msg = lib.dsr_last_error()
+        assert b"gram" in msg or b"featstyle" in msg, (i, msg)
