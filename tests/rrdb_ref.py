@@ -97,6 +97,24 @@ EXACT_SLOPE = EXACT_BETA = 0.25
 R2_OFF = 64        # the second residual is read at this channel offset of its own buffer (the first at 0 of the input buffer)
 
 
+# the launcher's work partition (csrc/conv_rdb.hip), restated: a work item of the forward is one 8 x 64 pixel tile of one image,
+# the grid is min(items, max_blocks or 256) blocks, and block b takes the items b, b + blocks, b + 2 blocks, ...
+RDB_GRID_CAP = 256
+CAP_SHAPE = (65, 9, 65)                # 65 images of 4 ragged tiles = 260 items: past the natural cap, no max_blocks
+FLOAT_PARTITIONS = (0, 1, 3)           # max_blocks of the partition-independence test on float data at (2, 9, 65), 8 items
+FLOAT_PARTITION_CASES = [(96, 32, 0), (128, 32, 0), (192, 64, 1), (192, 64, 2)]      # 3 | 4 | 6 K-blocks: both parities
+
+
+def rdb_tiles(n, h, w):
+    return n * -(-h // 8) * -(-w // 64)
+
+
+def fwd_plan(n, h, w, max_blocks=0):
+    """(work items, blocks) of one forward launch."""
+    items = rdb_tiles(n, h, w)
+    return items, min(items, max_blocks if max_blocks > 0 else RDB_GRID_CAP)
+
+
 def exact_launch(n, h, w, cin, cout, nres, amp=3):
     """One launch of the sweep as the GPU test issues it: (buf, wt, bias, res2 buffer or None, keyword arguments of
     prefix_conv).  Cout = 32: LeakyReLU(0.25), in place.  Cout = 64: no activation, res1 = channels [0, 64) of the input

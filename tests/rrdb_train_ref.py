@@ -88,6 +88,51 @@ def wgrad_tiles(n, h, w):
     return n * ((h + 1) // 2) * ((w + 31) // 32)
 
 
+# ----------------------------------------------------------------------------- the launchers' work partition, restated
+RDB_GRID_CAP = R.RDB_GRID_CAP   # csrc/conv_rdb.hip: blocks of a forward / input-gradient launch unless max_blocks overrides it
+WGRAD_WANT, COLSUM_ROWS, COLSUM_MIN_PPB = 64, 256, 64          # csrc/conv_rdb_bwd.hip, rdb_wgrad_plan
+
+
+def dgrad_slices(k):
+    """Output-channel slices per tile of dgrad_k: Cout / 64 where 64 divides Cout, else Cout / 32."""
+    cout = launch_geometry(k)[2]
+    return cout // 64 if cout % 64 == 0 else cout // 32
+
+
+def dgrad_plan(n, h, w, k, max_blocks=0):
+    """(work items, blocks) of dgrad_k: item t is slice t % nslices of tile t / nslices, block b walks b, b + blocks, ..."""
+    items = R.rdb_tiles(n, h, w) * dgrad_slices(k)
+    return items, min(items, max_blocks if max_blocks > 0 else RDB_GRID_CAP)
+
+
+def dgrad_walk(n, h, w, k, max_blocks=0):
+    """[[(image, tile of the image, slice), ...] per block]: the items of each block in the order it takes them."""
+    per_img, ns = R.rdb_tiles(1, h, w), dgrad_slices(k)
+    items, blocks = dgrad_plan(n, h, w, k, max_blocks)
+    return [[((t // ns) // per_img, (t // ns) % per_img, t % ns) for t in range(b, items, blocks)] for b in range(blocks)]
+
+
+# (N, H, W, k, max_blocks) of the forced partitions: 8 ragged tiles over two images with one block, three blocks and one
+# block per slice; 9 tiles with an interior column boundary on two blocks
+DGRAD_FORCED = [(2, 9, 65, k, mb) for k in (1, 2, 3, 4, 5) for mb in sorted({1, 3, dgrad_slices(k)})] + \
+               [(1, 17, 130, k, 2) for k in (1, 2, 3, 4, 5)]
+DGRAD_CAP_SHAPE = (65, 9, 65)          # 260 tiles: every k has more than RDB_GRID_CAP items without max_blocks
+DGRAD_FLOAT_PARTITIONS = (0, 1, 3, 5)  # max_blocks of the partition-independence test on float data, (2, 9, 65), k = 2, 4, 5
+WGRAD_SCALED_SHAPE = (2, 174, 65)      # 522 tiles, 22,620 pixels: tiles_per_block 9, 58 chunks, cs_ppb 89, 255 column-sum rows
+
+
+def wgrad_plan(n, h, w):
+    """rdb_wgrad_plan of csrc/conv_rdb_bwd.hip: tiles, tiles per chunk, chunks, column-sum pixels per block and rows, bytes."""
+    tiles = wgrad_tiles(n, h, w)
+    tpb = max(8, -(-tiles // WGRAD_WANT))
+    chunks = -(-tiles // tpb)
+    pix = n * h * w
+    ppb = max(COLSUM_MIN_PPB, -(-pix // COLSUM_ROWS))
+    rows = -(-pix // ppb)
+    nbytes = 4 * (chunks * 9 * (128 + 64) * LD + rows * LD)
+    return dict(tiles=tiles, tiles_per_block=tpb, chunks=chunks, cs_ppb=ppb, cs_rows=rows, bytes=nbytes)
+
+
 def network_grads(sd, x, probe, dtype, scale=4):
     """Gradients of sum(network(x) * probe) for every state_dict entry and the input ('input'): float64 (dtype=None) or
     the storage model with the fused rounding points (rrdb_ref.network(..., dtype, fused=True))."""

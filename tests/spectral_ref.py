@@ -34,6 +34,36 @@ def backward(g, w_sn, u, v, sigma):
     return ((G - d * torch.outer(u.double(), v.double())) / sigma).reshape(g.shape)
 
 
+# ----------------------------------------------------------------------------- the launch group's partition, restated
+MAX_LAYERS = 64              # layers of one call (csrc/multi_tensor.h, DSR_MT_MAX)
+V_THREADS = 1024             # sn_v_kernel: one block per layer; a thread takes 4 columns a turn on the 16-byte path, else 1
+ROWS, CHUNK = 32, 4096       # rows of W behind one W^T u partial; elements of W per block of the streaming kernels
+
+WIDE_VECTOR = (256, 4608)    # UNetDiscriminatorSN(num_feat=64).conv4: K > 4096, a second turn on the 16-byte path
+WIDE_SCALAR = (32, 1152)     # K > 1024: a second turn on the 4-byte path (reached with pointers off their 16-byte boundary)
+# 64 layers of one call: small mixed shapes, K % 4 != 0 ((8, 27), (7, 33), (12, 37)) and Cout % 32 != 0 (all but (32, 256) and (64, 64))
+FULL_TABLE = [(8, 27), (16, 128), (130, 52), (7, 33), (32, 256), (12, 37), (64, 64), (24, 100)] * 8
+
+
+def v_turns(k, vec):
+    """Turns of sn_v_kernel's column loops for a layer of K columns."""
+    return -(-k // (V_THREADS * (4 if vec else 1)))
+
+
+def _r4(x):
+    return (x + 3) & ~3
+
+
+def fwd_workspace_bytes(shapes):
+    """dsr_spectral_norm_workspace: per layer s [round_up(Cout, 4)], then ceil(Cout / 32) partial rows of K floats, rounded up to 4."""
+    return 4 * sum(_r4(c) + _r4(-(-c // ROWS) * k) for c, k in shapes)
+
+
+def bwd_workspace_bytes(shapes):
+    """dsr_spectral_norm_bwd_workspace: per layer one partial per 4096 elements, rounded up to 4."""
+    return 4 * sum(_r4(-(-(c * k) // CHUNK)) for c, k in shapes)
+
+
 def hadamard(n):
     """Sylvester's n x n Hadamard matrix (n a power of two), entries +-1, float64."""
     h = torch.ones(1, 1, dtype=torch.float64)

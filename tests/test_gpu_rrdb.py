@@ -1,7 +1,8 @@
 """GPU: RRDBNet on the HIP path (models/GAN/rrdbnet.py, csrc/conv_rdb.hip) against the float64 yardstick tests/rrdb_ref.py.
 
-1. one dsr_conv_rdb_fwd launch on exact-integer operands: bit for bit, every byte outside the output range untouched;
-2. one launch on float data: a derived per-element bound;
+1. one dsr_conv_rdb_fwd launch on exact-integer operands: bit for bit, every byte outside the output range untouched, also
+   with 260 work items on the launcher's cap of 256 blocks;
+2. one launch on float data: a derived per-element bound, and the same bits under every partition (max_blocks);
 3. whole networks, fused and composed, against the float64 network with the storage-model network as the floor;
 4. gradients of the composed path (tests/parity_util.compare_grads);
 5. the training recipe, HIP-graph replay and the refreshed weight images;
@@ -72,9 +73,10 @@ def _nchw64(t, c0, c):
     return t[..., c0:c0 + c].double().permute(0, 3, 1, 2).contiguous().cpu()
 
 
-def _launch(dev, dtype, n, h, w, cin, cout, nres, max_blocks, buf, wt, bias, res2, kw, y_off64=64, exact=True):
+def _launch(dev, dtype, n, h, w, cin, cout, nres, max_blocks, buf, wt, bias, res2, kw, y_off64=64, exact=True, bits=False):
     """Issue the launch as the model does (Cout = 32 in place; Cout = 64 into a second 192-channel tensor at channel offset
-    y_off64) and return (y [N, Cout, H, W] float64, the untouched-bytes verdict)."""
+    y_off64) and return (y [N, Cout, H, W] float64, the untouched-bytes verdict) -- with `bits` the stored 16-bit patterns
+    [N, H, W, Cout] (int16, on the host) instead of the float64 values."""
     F = P("functional")
     raw = Raw(dev)
     put = raw.put if exact else (lambda t, d: t.permute(0, 2, 3, 1).contiguous().to(R.DTYPES[d]).to(dev))
@@ -102,6 +104,8 @@ def _launch(dev, dtype, n, h, w, cin, cout, nres, max_blocks, buf, wt, bias, res
     untouched = torch.equal(i16(yb)[..., keep_mask], i16(ybefore)[..., keep_mask])
     if cout == 64:
         untouched = untouched and torch.equal(i16(xb), i16(before))
+    if bits:
+        return i16(yb)[..., y_off:y_off + cout].cpu(), untouched
     return _nchw64(yb, y_off, cout), untouched
 
 
@@ -121,6 +125,29 @@ def test_single_launch_exact(dev, dtype, n, h, w, mb, cin, cout, nres):
 
 
 @pytest.mark.parametrize("dtype", DT)
+@pytest.mark.parametrize("cin,cout,nres", [(64, 32, 0), (96, 32, 0), (128, 32, 0), (160, 32, 0), (192, 64, 2)])
+def test_single_launch_exact_natural_cap(dev, dtype, cin, cout, nres):
+    """No max_blocks: the launcher's own cap of 256 blocks.  (65, 9, 65) is 65 images x 2 x 2 ragged tiles = 260 work items on
+    256 blocks, so blocks 0..3 take a second item (tile 256 + b: the four tiles of the last image) after the hand-over under
+    their last K-block -- with 2, 3, 4, 5 and 6 K-blocks, both parities of the stage index at that point.  Operands and
+    assertions of test_single_launch_exact."""
+    n, h, w = R.CAP_SHAPE
+    items, blocks = R.fwd_plan(n, h, w)
+    assert (items, blocks) == (260, R.RDB_GRID_CAP)
+    if (cin, nres) not in _CAP_REF:                # operands and the float64 value: once for both types, never modified
+        case = R.exact_launch(n, h, w, cin, cout, nres)
+        _CAP_REF[(cin, nres)] = (case, R.prefix_conv(case[0][:, :cin], case[1], case[2], **case[4]))
+    (buf, wt, bias, res2, kw), y64 = _CAP_REF[(cin, nres)]
+    want = R.r16(y64, dtype)
+    got, untouched = _launch(dev, dtype, n, h, w, cin, cout, nres, 0, buf, wt, bias, res2, kw, y_off64=0)
+    assert torch.equal(got, want), float((got - want).abs().max())
+    assert untouched
+
+
+_CAP_REF = {}
+
+
+@pytest.mark.parametrize("dtype", DT)
 @pytest.mark.parametrize("cin,cout,nres", [(160, 32, 0), (192, 64, 2)])
 def test_single_launch_exact_rounded(dev, dtype, cin, cout, nres):
     """x in [-15, 15]: the sums leave bf16's 8 bits, the one rounding (to nearest even) is the yardstick's r16."""
@@ -135,14 +162,8 @@ def test_single_launch_exact_rounded(dev, dtype, cin, cout, nres):
         assert not torch.equal(want, exact)
 
 
-@pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("cin,cout,nres", [(64, 32, 0), (96, 32, 0), (128, 32, 0), (160, 32, 0), (192, 64, 1), (192, 64, 2)])
-def test_single_launch_float(dev, dtype, cin, cout, nres):
-    """N(0, 1) data, N(0, 0.05) weights, slope = beta = 0.2.  Per element, none excluded:
-        |y - y64| <= u |y64| + (9 Cin + 4) 2^-24 A,   u = one ulp of the type, A = conv(|x|, |w|) + |b| (+ |residuals|):
-    9 Cin + 4 fp32 operations of relative error 2^-24 each on magnitudes bounded by A, then one rounding to 16 bits.
-    Measured on the MI355X: the largest (error - bound) over all twelve cases is -1.2e-4 (192 -> 64 with both residuals)."""
-    n, h, w = 2, 9, 65
+def _float_case(dtype, cin, cout, nres, n=2, h=9, w=65):
+    """The float operands of one launch: (buf, wt, bias, res2 buffer or None, keyword arguments of prefix_conv)."""
     g = torch.Generator().manual_seed(cin + nres)
     t16 = lambda t: t.to(R.DTYPES[dtype]).double()
     buf = t16(torch.randn(n, 192, h, w, generator=g, dtype=torch.float64))
@@ -154,6 +175,40 @@ def test_single_launch_float(dev, dtype, cin, cout, nres):
         kw.update(res1=buf[:, :cout], beta1=R.F32(0.2))
     if nres == 2:
         kw.update(res2=res2[:, R.R2_OFF:R.R2_OFF + cout], beta2=R.F32(0.2))
+    return buf, wt, bias, res2, kw
+
+
+@pytest.mark.parametrize("dtype", DT)
+@pytest.mark.parametrize("cin,cout,nres", R.FLOAT_PARTITION_CASES)
+def test_single_launch_partition_independent_float(dev, dtype, cin, cout, nres):
+    """The operands of test_single_launch_float under max_blocks = 0, 1, 3: the partition assigns tiles to blocks and enters
+    no sum, so the stored output is the same bits for all three.  (2, 9, 65) is 8 tiles: 8 blocks of one item, one block of 8,
+    three blocks of 3, 3 and 2.  Cin = 96, 128, 192 are 3, 4 and 6 K-blocks: the hand-over to the next item happens on
+    either halo stage; Cout = 32 in place and Cout = 64 with one and two residuals.  The max_blocks = 0 result is the one
+    test_single_launch_float holds to its bound."""
+    n, h, w = 2, 9, 65
+    buf, wt, bias, res2, kw = _float_case(dtype, cin, cout, nres)
+    runs = {}
+    for mb in R.FLOAT_PARTITIONS:
+        items, blocks = R.fwd_plan(n, h, w, mb)
+        assert (items, blocks) == (8, mb or 8)
+        runs[mb], untouched = _launch(dev, dtype, n, h, w, cin, cout, nres, mb, buf, wt, bias, res2, kw, y_off64=0, exact=False,
+                                      bits=True)
+        assert untouched, mb
+    for mb in R.FLOAT_PARTITIONS[1:]:
+        diff = runs[mb] != runs[0]
+        assert not bool(diff.any()), (mb, int(diff.sum()))
+
+
+@pytest.mark.parametrize("dtype", DT)
+@pytest.mark.parametrize("cin,cout,nres", [(64, 32, 0), (96, 32, 0), (128, 32, 0), (160, 32, 0), (192, 64, 1), (192, 64, 2)])
+def test_single_launch_float(dev, dtype, cin, cout, nres):
+    """N(0, 1) data, N(0, 0.05) weights, slope = beta = 0.2.  Per element, none excluded:
+        |y - y64| <= u |y64| + (9 Cin + 4) 2^-24 A,   u = one ulp of the type, A = conv(|x|, |w|) + |b| (+ |residuals|):
+    9 Cin + 4 fp32 operations of relative error 2^-24 each on magnitudes bounded by A, then one rounding to 16 bits.
+    Measured on the MI355X: the largest (error - bound) over all twelve cases is -1.2e-4 (192 -> 64 with both residuals)."""
+    n, h, w = 2, 9, 65
+    buf, wt, bias, res2, kw = _float_case(dtype, cin, cout, nres)
     y64 = R.prefix_conv(buf[:, :cin], wt, bias, **kw)
     bkw = {k: v for k, v in kw.items() if k != "slope"}
     A = R.prefix_conv_bound(buf[:, :cin], wt, bias, cin, **bkw)

@@ -1,9 +1,11 @@
 """GPU: training RRDBNet on its growth buffers (RRDBNet.set_fused_training, functional.RRDBBody, dsr_conv_rdb_dgrad,
 dsr_conv_rdb_wgrad) against the float64 yardstick tests/rrdb_train_ref.py.
 
-1. one dsr_conv_rdb_dgrad launch per k = 1..5 on exact-integer operands: the float64 value rounded once, bytes outside untouched;
-2. the same launch on float data: a derived per-element bound;
-3. dsr_conv_rdb_wgrad: `==` on integer operands for all ten gradients, a derived bound on float data, two runs bit-equal;
+1. one dsr_conv_rdb_dgrad launch per k = 1..5 on exact-integer operands: the float64 value rounded once, bytes outside untouched
+   -- one work item per block, several per block under max_blocks, and past the launcher's own cap of 256 blocks;
+2. the same launch on float data: a derived per-element bound, and the same bits under every partition;
+3. dsr_conv_rdb_wgrad: `==` on integer operands for all ten gradients, a derived bound on float data, two runs bit-equal --
+   at 8 tiles per chunk and where the plan scales its chunks (58 chunks of 9 tiles, 255 column-sum rows);
 4. whole-network gradients (tests/parity_util.compare_grads), forward bits and the launch log;
 5. fallbacks and the default;
 6. the training steps, eager and replayed;
@@ -62,8 +64,9 @@ def _wd(weight64, n, h, w, dtype, dev):
     return wd, weight
 
 
-def _dgrad_launch(dev, dtype, n, h, w, k, B, G0, g, wt, kw, exact=True):
-    """Issue dgrad_k as RRDBBody.backward does; returns (G after [N, 192, H, W] float64, untouched verdict)."""
+def _dgrad_launch(dev, dtype, n, h, w, k, B, G0, g, wt, kw, exact=True, max_blocks=0, bits=False):
+    """Issue dgrad_k as RRDBBody.backward does; returns (G after [N, 192, H, W] float64, untouched verdict) -- with `bits`
+    the stored 16-bit patterns of G (int16, on the host) instead of the float64 values."""
     F = P("functional")
     can = Canaries(dev)
     K, dy_off, cout, mask_lo = T.launch_geometry(k)
@@ -74,14 +77,14 @@ def _dgrad_launch(dev, dtype, n, h, w, k, B, G0, g, wt, kw, exact=True):
     wd, keep = _wd(wt, n, h, w, dtype, dev)
     if k == 5:
         F.rdb_dgrad(gd, 0, 64, wd, Gd, 192, scale=kw["scale"], g=gd, g_limit=64, g_scale=kw["g_scale"], act_out=Bd,
-                    mask_lo=mask_lo, slope=kw["slope"])
+                    mask_lo=mask_lo, slope=kw["slope"], max_blocks=max_blocks)
     else:
         F.rdb_dgrad(Gd, dy_off, K, wd, Gd, cout, accumulate=True, g=gd, g_limit=64, g_scale=kw["g_scale"],
-                    act_out=Bd if mask_lo is not None else None, mask_lo=mask_lo, slope=kw["slope"])
+                    act_out=Bd if mask_lo is not None else None, mask_lo=mask_lo, slope=kw["slope"], max_blocks=max_blocks)
     can.check()
     i16 = lambda t: t.view(torch.int16)
     untouched = torch.equal(i16(Bd), i16(b_before)) and torch.equal(i16(Gd)[..., cout:], i16(g_before)[..., cout:])
-    return _nchw64(Gd, 0, 192), untouched
+    return (i16(Gd).cpu() if bits else _nchw64(Gd, 0, 192)), untouched
 
 
 def _dgrad_want(k, B, G0, g, wt, kw):
@@ -111,14 +114,62 @@ def test_dgrad_launch_exact(dev, dtype, n, h, w, k):
         assert bool(m.any()) and bool((~m).any())
 
 
-# ----------------------------------------------------------------------------- 2. float data
+_EXACT_REF = {}
+
+
+def _exact_dgrad_ref(n, h, w, k):
+    """(operands, float64 value) of one exact case: computed once, shared by both types and every partition, never modified."""
+    key = (n, h, w, k)
+    if key not in _EXACT_REF:
+        case = T.exact_dgrad_case(n, h, w, k)
+        _EXACT_REF[key] = (case, _dgrad_want(k, *case)[0])
+    return _EXACT_REF[key]
+
+
+def _assert_exact_dgrad(dev, dtype, n, h, w, k, max_blocks):
+    (B, G0, g, wt, kw), v64 = _exact_dgrad_ref(n, h, w, k)
+    cout = T.launch_geometry(k)[2]
+    want = R.r16(v64, dtype)
+    got, untouched = _dgrad_launch(dev, dtype, n, h, w, k, B, G0, g, wt, kw, max_blocks=max_blocks)
+    assert torch.equal(got[:, :cout], want), float((got[:, :cout] - want).abs().max())
+    assert untouched
+
+
 @pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("k", [2, 5])
-def test_dgrad_launch_float(dev, dtype, k):
-    """N(0, 1) data, N(0, 0.05) weights, slope = beta = 0.2.  Per element, none excluded:
-        |v - v64| <= u |v64| + (9 K + 4) 2^-24 A,   u = the unit roundoff of the type, A = the same sum with absolute values:
-    9 K + 4 fp32 operations of relative error 2^-24 on magnitudes bounded by A, then one rounding to 16 bits."""
-    n, h, w = 2, 9, 65
+@pytest.mark.parametrize("n,h,w,k,mb", T.DGRAD_FORCED, ids=lambda v: str(v))
+def test_dgrad_forced_partitions_exact(dev, dtype, n, h, w, k, mb):
+    """The operands and assertions of test_dgrad_launch_exact with max_blocks below the item count, so that a block takes
+    several (tile, slice) items: the fetch of the next item under the last K-block, the consumed halo stage reused as the C
+    staging area, the next slice's weight rows, the in-place read-then-store of a second item of one block.
+
+    (2, 9, 65) is 8 tiles (2 images x 2 x 2, ragged both ways) of 1, 3, 2, 5, 3 slices for k = 1..5 = 8, 24, 16, 40, 24 items:
+      max_blocks = 1         one block walks every slice of every tile of both images in order;
+      max_blocks = 3         for k = 4 (5 slices) and k = 3 (2) the stride is coprime to the slice count: consecutive items of
+                             a block always differ in slice, three times in five (k = 4) also in tile, once in image;
+      max_blocks = nslices   a block keeps its slice and its weight rows, only the tile changes.
+    (1, 17, 130) with max_blocks = 2 is 9 tiles = 9, 27, 18, 45, 27 items; tiles with an interior column boundary are
+    revisited by both blocks."""
+    items, blocks = T.dgrad_plan(n, h, w, k, mb)
+    assert blocks == mb and items >= 2 * blocks
+    _assert_exact_dgrad(dev, dtype, n, h, w, k, mb)
+
+
+@pytest.mark.parametrize("dtype", DT)
+@pytest.mark.parametrize("k", [1, 2, 3, 4, 5])
+def test_dgrad_natural_cap_exact(dev, dtype, k):
+    """No max_blocks: the launcher's own cap of 256 blocks.  (65, 9, 65) is 65 images x 4 tiles = 260 tiles, so k = 1..5 are
+    260, 780, 520, 1300, 780 items on 256 blocks -- for k = 1 four blocks take a second item, for k = 4 every block takes five
+    or six.  Same operands rule and assertions as test_dgrad_launch_exact (38,025 pixels; the largest tensor is 15 MB).  k = 1 has
+    one item per tile, so more than 256 tiles are needed whatever the shape; fewer pixels per tile than these 2 x 2 ragged
+    tiles of an image would leave no tile with a full row or column of neighbours."""
+    n, h, w = T.DGRAD_CAP_SHAPE
+    items, blocks = T.dgrad_plan(n, h, w, k)
+    assert blocks == T.RDB_GRID_CAP and items > blocks
+    _assert_exact_dgrad(dev, dtype, n, h, w, k, 0)
+
+
+# ----------------------------------------------------------------------------- 2. float data
+def _float_dgrad_case(dtype, k, n=2, h=9, w=65):
     gen = torch.Generator().manual_seed(50 + k)
     t16 = lambda t: t.to(R.DTYPES[dtype]).double()
     K, dy_off, cout, mask_lo = T.launch_geometry(k)
@@ -129,6 +180,17 @@ def test_dgrad_launch_float(dev, dtype, k):
     beta = R.F32(0.2)
     kw = dict(scale=R.F32(beta * beta) if k == 5 else 1.0, g=g, g_scale=beta if k == 5 else 1.0, mask_lo=mask_lo,
               slope=R.F32(0.2))
+    return B, G0, g, wt, kw
+
+
+@pytest.mark.parametrize("dtype", DT)
+@pytest.mark.parametrize("k", [2, 5])
+def test_dgrad_launch_float(dev, dtype, k):
+    """N(0, 1) data, N(0, 0.05) weights, slope = beta = 0.2.  Per element, none excluded:
+        |v - v64| <= u |v64| + (9 K + 4) 2^-24 A,   u = the unit roundoff of the type, A = the same sum with absolute values:
+    9 K + 4 fp32 operations of relative error 2^-24 on magnitudes bounded by A, then one rounding to 16 bits."""
+    n, h, w = 2, 9, 65
+    B, G0, g, wt, kw = _float_dgrad_case(dtype, k)
     v64, A, cout, K = _dgrad_want(k, B, G0, g, wt, kw)
     got, untouched = _dgrad_launch(dev, dtype, n, h, w, k, B, G0, g, wt, kw, exact=False)
     u = 2.0 ** -8 if dtype == R.BF16 else 2.0 ** -10
@@ -137,6 +199,35 @@ def test_dgrad_launch_float(dev, dtype, k):
     print(f"float dgrad k={k}: max err {float((got[:, :cout] - v64).abs().max()):.3e}, max (err - bound) {float(excess):.3e}")
     assert float(excess) <= 0.0
     assert untouched
+
+
+@pytest.mark.parametrize("dtype", DT)
+@pytest.mark.parametrize("k", [2, 4, 5])
+def test_dgrad_partition_independent_float(dev, dtype, k):
+    """The operands of test_dgrad_launch_float under max_blocks = 0, 1, 3, 5: the partition assigns (tile, slice) items to
+    blocks and enters no sum, so the stored G is the same bits for all four.  (2, 9, 65) is 8 tiles x 3, 5, 3 slices = 24, 40,
+    24 items for k = 2, 4, 5: one block per item with max_blocks = 0, then 24 | 40, 8 | 14 and 5 | 8 items per block.  The
+    max_blocks = 0 result is held to the bound of test_dgrad_launch_float (k = 4 is not among that test's cases).
+    Measured on the MI355X, max error / bound: 0.976, 0.980, 0.978 in bf16 and 0.470, 0.474, 0.461 in fp16 for k = 2, 4, 5 (the
+    rounding to 16 bits dominates: a bf16 value just above a power of two is half an ulp = 2^-8 of itself away)."""
+    n, h, w = 2, 9, 65
+    B, G0, g, wt, kw = _float_dgrad_case(dtype, k)
+    v64, A, cout, K = _dgrad_want(k, B, G0, g, wt, kw)
+    runs = {}
+    for mb in T.DGRAD_FLOAT_PARTITIONS:
+        items, blocks = T.dgrad_plan(n, h, w, k, mb)
+        assert blocks == (mb or items)
+        runs[mb], untouched = _dgrad_launch(dev, dtype, n, h, w, k, B, G0, g, wt, kw, exact=False, max_blocks=mb, bits=True)
+        assert untouched, mb
+    for mb in T.DGRAD_FLOAT_PARTITIONS[1:]:
+        diff = runs[mb] != runs[0]
+        assert not bool(diff.any()), (mb, int(diff.sum()))
+    got = runs[0].view(R.DTYPES[dtype])[..., :cout].double().permute(0, 3, 1, 2)
+    u = 2.0 ** -8 if dtype == R.BF16 else 2.0 ** -10
+    bound = u * v64.abs() + (9 * K + 4) * 2.0 ** -24 * A
+    err = (got - v64).abs()
+    print(f"float dgrad k={k}, four partitions: max err / bound {float((err / bound).max()):.3f}")
+    assert float((err - bound).max()) <= 0.0
 
 
 # ----------------------------------------------------------------------------- 3. weight and bias gradients
@@ -198,6 +289,64 @@ def test_wgrad_float_and_deterministic(dev, dtype):
         eb = float(((dbs[k].double().cpu() - want_b[k]).abs() - eps * abs_b[k]).max())
         print(f"float wgrad conv{k + 1}: max (err - bound) dW {ew:.3e} db {eb:.3e}")
         assert ew <= 0.0 and eb <= 0.0, (k, ew, eb)
+        assert torch.equal(dws[k], dws2[k]) and torch.equal(dbs[k], dbs2[k])
+
+
+_WGRAD_REF = {}
+
+
+def _scaled_wgrad_ref():
+    """Operands and float64 gradients of the exact case at T.WGRAD_SCALED_SHAPE: computed once for both types."""
+    if not _WGRAD_REF:
+        B, Gm, g = T.exact_wgrad_case(*T.WGRAD_SCALED_SHAPE)
+        _WGRAD_REF["exact"] = (B, Gm, g, T.block_param_grads(B, Gm, g, T.EXACT_BETA))
+    return _WGRAD_REF["exact"]
+
+
+def _assert_scaled_plan():
+    F = P("functional")
+    n, h, w = T.WGRAD_SCALED_SHAPE
+    plan = T.wgrad_plan(n, h, w)
+    assert (plan["tiles"], plan["tiles_per_block"], plan["chunks"], plan["cs_ppb"], plan["cs_rows"]) == (522, 9, 58, 89, 255)
+    assert F.rdb_wgrad_workspace(n, h, w, torch.bfloat16) == (plan["bytes"], 58)
+    return n, h, w
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_wgrad_scaled_chunks_exact(dev, dtype):
+    """(2, 174, 65): 522 tiles of 2 x 32 pixels, past 8 x 64, so the plan scales its chunks -- tiles_per_block = 9, 58 chunks (the
+    last one of 9 tiles too: 58 x 9 = 522) folded in chunk order; 22,620 pixels, so cs_ppb = 89 and 255 column-sum rows (the
+    last one of 14 pixels).  The operands of test_wgrad_exact: every product is an integer of magnitude <= 9 and every partial
+    sum one below 9 x 22,620 < 2^24, gscale = 0.25 is a power of two -- `==` on all ten gradients."""
+    n, h, w = _assert_scaled_plan()
+    B, Gm, g, (want_w, want_b) = _scaled_wgrad_ref()
+    (dws, dbs), = _wgrad_launch(dev, dtype, B, Gm, g, T.EXACT_BETA)
+    for k in range(5):
+        assert torch.equal(dws[k].double().cpu(), want_w[k]), (k, float((dws[k].double().cpu() - want_w[k]).abs().max()))
+        assert torch.equal(dbs[k].double().cpu(), want_b[k]), k
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_wgrad_scaled_chunks_float_and_deterministic(dev, dtype):
+    """test_wgrad_float_and_deterministic at (2, 174, 65) (58 chunks of 9 tiles, 255 column-sum rows of 89 pixels): the same
+    bound (P + 4) 2^-24 sum |x| |dy| with P = 22,620, two runs the same bits.  Measured on the MI355X, max error / bound over
+    the five convolutions: dW 1.2e-5, db 6.8e-6 (the bound is a worst case over 22,624 roundings of one sign; the `==` of
+    test_wgrad_scaled_chunks_exact is what a dropped or doubled tile cannot pass)."""
+    n, h, w = _assert_scaled_plan()
+    gen = torch.Generator().manual_seed(78)
+    t16 = lambda t: t.to(R.DTYPES[dtype]).double()
+    B, Gm = (t16(torch.randn(n, 192, h, w, generator=gen, dtype=torch.float64)) for _ in range(2))
+    g = t16(torch.randn(n, 64, h, w, generator=gen, dtype=torch.float64))
+    gscale = R.F32(R.F32(0.2) * R.F32(0.2))
+    want_w, want_b = T.block_param_grads(B, Gm, g, gscale)
+    abs_w, abs_b = T.block_param_grads(B.abs(), Gm.abs(), g.abs(), gscale)
+    (dws, dbs), (dws2, dbs2) = _wgrad_launch(dev, dtype, B, Gm, g, gscale, exact=False, runs=2)
+    eps = (n * h * w + 4) * 2.0 ** -24
+    for k in range(5):
+        rw = float(((dws[k].double().cpu() - want_w[k]).abs() / (eps * abs_w[k])).max())
+        rb = float(((dbs[k].double().cpu() - want_b[k]).abs() / (eps * abs_b[k])).max())
+        print(f"float wgrad at 58 chunks conv{k + 1}: max err / bound dW {rw:.2e} db {rb:.2e}")
+        assert rw <= 1.0 and rb <= 1.0, (k, rw, rb)
         assert torch.equal(dws[k], dws2[k]) and torch.equal(dbs[k], dbs2[k])
 
 

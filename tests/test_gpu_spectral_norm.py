@@ -2,7 +2,8 @@
 with every buffer inside sentinel margins.
 
 1. an exact case (Hadamard rows): bit for bit whatever the summation order, forward and backward;
-2. float data: derived bounds, per shape and for a group of eight layers in one call;
+2. float data: derived bounds, per shape (up to K = 4608: a second turn of sn_v_kernel's column loop, on either access path),
+   for a group of eight layers and for the full table of 64 in one call; 65 layers are refused and nothing is written;
 3. the sentinel margins (every launch here runs between them), also with every pointer 4 bytes off a 16-byte boundary;
 4. two runs from one state: the same bits;  5. eval mode leaves u and v alone;  6. graph replay = eager, bit for bit;
 7. W = 0: finishes, with torch's non-finite pattern."""
@@ -218,7 +219,7 @@ def _check_layer(tag, W, u, v, res, sigma, kind, dev_bwd=None):
     return ur, vr, sr, wr
 
 
-SHAPES = [(8, 27), (64, 576), (128, 1024), (512, 4096)]
+SHAPES = [(8, 27), (64, 576), (128, 1024), (512, 4096), SR.WIDE_VECTOR]      # the last: K = 4608, a second turn of sn_v_kernel
 GROUP = [(8, 27), (16, 128), (32, 256), (64, 512), (32, 576), (16, 288), (8, 144), (130, 52)]
 
 
@@ -251,7 +252,10 @@ def test_float_data(dev, cout, k, kind):
         [64, 576]    signed   0.002 (4.29)  0.004 (0.39)  0.001 (8.03)   0.002 (8.03)    positive 0.003  0.006  0.001  0.002
         [128, 1024]  signed   0.001 (4.88)  0.002 (0.30)  <5e-4 (9.00)   0.001 (9.00)    positive 0.001  0.003  <5e-4  0.001
         [512, 4096]  signed   <5e-4 (6.18)  0.001 (0.19)  <5e-4 (12.30)  0.001 (12.30)   positive 0.001  0.001  <5e-4  <5e-4
-    backward, max|dW - dW64| / max|dW64| (signed): 3.6e-8, 6.7e-8, 9.2e-8, 7.7e-8; the largest (error - bound) is -3.4e-10."""
+        [256, 4608]  signed   <5e-4 (2.91)  0.001 (0.11)  <5e-4 (5.32)   0.001 (5.32)    positive <5e-4  0.001  <5e-4  <5e-4
+    backward, max|dW - dW64| / max|dW64| (signed): 3.6e-8, 6.7e-8, 9.2e-8, 7.7e-8, 8.6e-8; the largest (error - bound) is
+    -1.0e-10 ([256, 4608]).  [256, 4608] is the one shape with K > 4096: threads 0..127 of sn_v_kernel take a second turn of the
+    16-byte column loops (SR.v_turns)."""
     W, u, v = _data(cout, k, kind, 100 * cout + k)
     (res,), sigma, _ = run_fwd(dev, [(W, u, v)], True)
     _check_layer("single", W, u, v, res, sigma[0], kind)
@@ -289,6 +293,88 @@ def test_group_of_eight(dev, shift):
         assert float(((dw.double().cpu() - want).abs() - b).max()) <= 0.0
         (alone,) = run_bwd(dev, [it], shift)
         assert torch.equal(alone, dw)
+
+
+def _check_backward(tag, it, dw):
+    want = SR.backward(*it)
+    b = backward_bound(*it) + EPS32 * want.abs()
+    err = (dw.double().cpu() - want).abs()
+    assert float((err - b).max()) <= 0.0, (tag, float((err - b).max()))
+    return float((err / b).max())
+
+
+def test_scalar_path_second_turn(dev):
+    """[32, 1152] with every pointer 4 bytes off a 16-byte boundary: the layer runs on 4-byte accesses, where a thread of
+    sn_v_kernel's one block of 1024 takes one column a turn -- K = 1152 > 1024 is a second turn for threads 0..127 (and five
+    column tiles of sn_wtu_kernel, the last of 128).  Held to _check_layer and backward_bound as in test_group_of_eight;
+    forward_bound's n_v = 4 ceil(K / 4096) + 21 = 25 covers this path's ceil(K / 1024) + 21 = 23."""
+    cout, k = SR.WIDE_SCALAR
+    assert SR.v_turns(k, vec=False) == 2 and SR.v_turns(k, vec=True) == 1
+    W, u, v = _data(cout, k, "signed", 100 * cout + k)
+    (res,), sigma, _ = run_fwd(dev, [(W, u, v)], True, shift=1)
+    assert all(t.data_ptr() % 16 == 4 for t in res)
+    _check_layer("scalar, second turn", W, u, v, res, sigma[0], "signed")
+    G = torch.randn(W.shape, generator=torch.Generator().manual_seed(11)).float()
+    it = (G, res[2].cpu(), res[0].cpu(), res[1].cpu(), float(sigma[0]))
+    (dw,) = run_bwd(dev, [it], shift=1)
+    print(f"spectral norm backward {SR.WIDE_SCALAR} scalar path: max error / bound {_check_backward('scalar', it, dw):.3f}")
+
+
+def test_full_table_of_64_layers(dev):
+    """One call with SR.MAX_LAYERS = 64 layers (SR.FULL_TABLE: eight small shapes eight times over, each with data of its own;
+    K % 4 != 0 in three of the eight, Cout % 32 != 0 in six): the last entries of every per-layer array and of the block tables
+    are used.  Each layer is held to _check_layer and is bit-equal to that layer alone, forward and backward."""
+    assert len(SR.FULL_TABLE) == SR.MAX_LAYERS
+    assert any(k % 4 for _, k in SR.FULL_TABLE) and any(c % 32 for c, _ in SR.FULL_TABLE)
+    layers = [_data(c, k, "signed", 1000 * i + 100 * c + k) for i, (c, k) in enumerate(SR.FULL_TABLE)]
+    res, sigma, _ = run_fwd(dev, layers, True)
+    items = []
+    g = torch.Generator().manual_seed(12)
+    for i, ((W, u, v), r) in enumerate(zip(layers, res)):
+        _check_layer(f"table[{i}]", W, u, v, r, sigma[i], "signed")
+        (alone,), sig1, _ = run_fwd(dev, [(W, u, v)], True)
+        assert all(torch.equal(a, b) for a, b in zip(alone, r)) and torch.equal(sig1[0], sigma[i]), i
+        G = torch.randn(W.shape, generator=g).float()
+        items.append((G, r[2].cpu(), r[0].cpu(), r[1].cpu(), float(sigma[i])))
+    dws = run_bwd(dev, items)
+    for i, (it, dw) in enumerate(zip(items, dws)):
+        _check_backward(f"table[{i}]", it, dw)
+        (alone,) = run_bwd(dev, [it])
+        assert torch.equal(alone, dw), i
+
+
+def test_65_layers_are_refused_and_nothing_is_written(dev):
+    """count = 65: the forward, the backward and both workspace queries refuse (argument error, 0 bytes) before any launch --
+    every output still holds what it was filled with, u and v are unchanged, the margins are intact."""
+    L, F = P("_lib"), P("functional")
+    lib = L.lib()
+    shapes = (SR.FULL_TABLE + [(8, 27)])
+    layers = [_data(c, k, "signed", 7 + i) for i, (c, k) in enumerate(shapes)]
+    n, ci, ki = _tables(layers)
+    assert n == SR.MAX_LAYERS + 1
+    assert lib.dsr_spectral_norm_workspace(n, ci, ki) == 0 and lib.dsr_spectral_norm_bwd_workspace(n, ci, ki) == 0
+    assert lib.dsr_spectral_norm_workspace(n - 1, ci, ki) == SR.fwd_workspace_bytes(SR.FULL_TABLE)
+    assert lib.dsr_spectral_norm_bwd_workspace(n - 1, ci, ki) == SR.bwd_workspace_bytes(SR.FULL_TABLE)
+    raw = Raw(dev)
+    ws = [raw.put(w) for w, _, _ in layers]
+    us = [raw.put(u) for _, u, _ in layers]
+    vs = [raw.put(v) for _, _, v in layers]
+    outs = [raw.empty(w.shape) for w, _, _ in layers]
+    sigma = raw.empty((n,))
+    nbytes = SR.fwd_workspace_bytes(shapes)
+    work = raw.put(torch.full((nbytes // 4,), float("nan")))
+    E_ARG = -1
+    rc = lib.dsr_spectral_norm_fwd(n, L.ptr_table(ws), L.ptr_table(us), L.ptr_table(vs), ci, ki, 1, SR.EPS,
+                                   C.c_void_p(sigma.data_ptr()), L.ptr_table(outs), C.c_void_p(work.data_ptr()), nbytes, F._stream())
+    assert rc == E_ARG and b"count" in lib.dsr_last_error()
+    # the backward, with the same buffers in the roles of G, W_sn, u, v and dW
+    rc = lib.dsr_spectral_norm_bwd(n, L.ptr_table(ws), L.ptr_table(ws), L.ptr_table(us), L.ptr_table(vs), ci, ki,
+                                   C.c_void_p(sigma.data_ptr()), L.ptr_table(outs), C.c_void_p(work.data_ptr()), nbytes, F._stream())
+    assert rc == E_ARG and b"count" in lib.dsr_last_error()
+    raw.check()
+    assert bool(torch.isnan(sigma).all()) and bool(torch.isnan(work).all()) and all(bool(torch.isnan(o).all()) for o in outs)
+    for (w, u, v), wd, ud, vd in zip(layers, ws, us, vs):
+        assert torch.equal(wd.cpu(), w) and torch.equal(ud.cpu(), u) and torch.equal(vd.cpu(), v)
 
 
 # ----------------------------------------------------------------------------- 4, 5. reproducibility, eval mode

@@ -105,6 +105,30 @@ def test_exact_sweep_stays_in_its_regime():
         R.r16(y, R.BF16)
 
 
+def test_forward_cases_take_several_items_per_block():
+    """The launcher's partition (R.fwd_plan, restated from csrc/conv_rdb.hip) of the multi-item forward cases of
+    tests/test_gpu_rrdb.py, and that the case at the natural cap stays exact."""
+    n, h, w = R.CAP_SHAPE
+    items, blocks = R.fwd_plan(n, h, w)
+    print(f"forward at {R.CAP_SHAPE} without max_blocks: {items} items on {blocks} blocks")
+    assert (items, blocks) == (260, 256) and items > blocks
+    assert R.fwd_plan(1, 16, 130, 2) == (6, 2)                     # the one multi-item case of R.EXACT_SHAPES: three a block
+    assert all(R.fwd_plan(n_, h_, w_, mb)[0] <= 256 for n_, h_, w_, mb in R.EXACT_SHAPES)
+    plans = [R.fwd_plan(2, 9, 65, mb) for mb in R.FLOAT_PARTITIONS]
+    print("float forward partitions at (2, 9, 65), (items, blocks):", plans)
+    assert plans == [(8, 8), (8, 1), (8, 3)]
+    assert sorted({cin // 32 % 2 for cin, _, _ in R.FLOAT_PARTITION_CASES}) == [0, 1]       # K-block counts of both parities
+    assert {cout for _, cout, _ in R.FLOAT_PARTITION_CASES} == {32, 64}
+    # exact at the cap: |acc| <= 27 Cin + 4, the residual steps make it a multiple of 1/16 -- far below 2^24 in any order;
+    # the stored value is r16 of it (the operands are checked where they are uploaded, the values here for one case)
+    assert (27 * 192 + 4 + 12 + 48) * 16 < 2 ** 24
+    buf, wt, b, res2, kw = R.exact_launch(n, h, w, 64, 32, 0)
+    assert all(R.representable(t, d) for t in (buf, wt, b) for d in (R.BF16, R.F16))
+    y = R.prefix_conv(buf[:, :64], wt, b, **kw)
+    assert torch.equal(y * 4, (y * 4).round())
+    R.r16(y, R.BF16)                                               # (asserts that the value is exact in fp32)
+
+
 def test_receptive_halo_and_scale_errors():
     M, I = P("models.GAN.rrdbnet"), P("infer")
     assert M.RRDBNet(num_block=1).receptive_halo() == 19

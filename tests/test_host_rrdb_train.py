@@ -81,6 +81,90 @@ def test_wgrad_arguments_sizes_and_chunks(lib):
         assert F.rdb_wgrad_workspace(n, h, w, torch.float16)[1] == -(-tiles // per), (n, h, w)
 
 
+def test_dgrad_cases_take_several_items_per_block():
+    """The launcher's partition (T.dgrad_plan / T.dgrad_walk, restated from csrc/conv_rdb.hip) of every multi-item case of
+    tests/test_gpu_rrdb_train.py: more items than blocks, and the block walks the docstrings there rely on."""
+    assert [T.dgrad_slices(k) for k in (1, 2, 3, 4, 5)] == [1, 3, 2, 5, 3]
+    for n, h, w, k, mb in T.DGRAD_FORCED:
+        items, blocks = T.dgrad_plan(n, h, w, k, mb)
+        print(f"dgrad_{k} at {(n, h, w)} max_blocks={mb}: {items} items on {blocks} blocks")
+        assert blocks == mb and items >= 2 * blocks, (n, h, w, k, mb)
+        walk = T.dgrad_walk(n, h, w, k, mb)
+        assert sorted(it for b in walk for it in b) == sorted(set(it for b in walk for it in b)) and sum(map(len, walk)) == items
+    assert len(T.DGRAD_FORCED) == 2 + 2 + 3 + 3 + 2 + 5            # {1, 3, nslices(k)} without repeats, and (1, 17, 130)
+    # one block: every slice of every tile of both images, in order
+    (walk,) = T.dgrad_walk(2, 9, 65, 4, 1)
+    assert walk == [(i, t, s) for i in range(2) for t in range(4) for s in range(5)]
+    # three blocks on five slices: consecutive items of a block always differ in slice, more often than not in tile too (the
+    # others are two slices of one tile), and once in image
+    for b in T.dgrad_walk(2, 9, 65, 4, 3):
+        steps = list(zip(b, b[1:]))
+        moved = sum(p[:2] != q[:2] for p, q in steps)
+        assert all(p[2] != q[2] for p, q in steps) and len(steps) / 2 < moved < len(steps)
+        assert sum(p[0] != q[0] for p, q in steps) == 1
+    # one block per slice: a block keeps its slice, the tile changes with every item
+    for k in (2, 3, 4, 5):
+        for b in T.dgrad_walk(2, 9, 65, k, T.dgrad_slices(k)):
+            assert len({it[2] for it in b}) == 1 and len({it[:2] for it in b}) == len(b) == 8
+    # (1, 17, 130): 3 x 3 tiles, the middle column has both column neighbours inside the image; both blocks visit it
+    for k in (1, 2, 3, 4, 5):
+        assert all(any(t % 3 == 1 for _, t, _ in b[1:]) for b in T.dgrad_walk(1, 17, 130, k, 2))
+    # the natural cap
+    n, h, w = T.DGRAD_CAP_SHAPE
+    counts = [T.dgrad_plan(n, h, w, k) for k in (1, 2, 3, 4, 5)]
+    print("dgrad_1..5 at", T.DGRAD_CAP_SHAPE, "without max_blocks, (items, blocks):", counts)
+    assert counts == [(260, 256), (780, 256), (520, 256), (1300, 256), (780, 256)]
+    assert n * h * w * 192 * 2 < 16 * 2 ** 20                       # the largest tensor of the sweep
+    # float data, (2, 9, 65): one block per item without max_blocks, several items per block with it
+    for k in (2, 4, 5):
+        plans = [T.dgrad_plan(2, 9, 65, k, mb) for mb in T.DGRAD_FLOAT_PARTITIONS]
+        print(f"float dgrad_{k} partitions (items, blocks):", plans)
+        assert plans[0][0] == plans[0][1] == 8 * T.dgrad_slices(k) and all(i > b == mb for (i, b), mb in zip(plans[1:], (1, 3, 5)))
+
+
+def test_exact_dgrad_cases_stay_exact():
+    """Integers in [-3, 3] against ternary weights: |acc| <= 27 K <= 1728, times scale = 0.25, plus the addend (<= 3), plus
+    0.25 g, times the mask 1 | 0.25: a multiple of 1/16 below 2^11, so every fp32 step is exact whatever the order (2^11 x 16
+    is far below 2^24) and the one rounding to 16 bits is r16's.  The operands themselves are representable in both types."""
+    for k in (1, 2, 3, 4, 5):
+        K = T.launch_geometry(k)[0]
+        assert (27 * K + 3 + 1) * 16 < 2 ** 24
+        B, G0, g, wt, kw = T.exact_dgrad_case(2, 9, 65, k)
+        for t in (B, G0, wt) + ((g,) if g is not None else ()):
+            assert float(t.abs().max()) <= 3 and torch.equal(t, t.round())
+            assert T.R.representable(t, T.R.BF16) and T.R.representable(t, T.R.F16)
+        assert kw["slope"] == 0.25 and kw["scale"] in (0.25, 1.0) and kw["g_scale"] in (0.25, 1.0)
+        v = T.dgrad_value(g if k == 5 else G0[:, 32 * (k + 1):32 * (k + 2)], wt, None if k == 5 else G0[:, :32 * (k + 1)],
+                          act=B[:, :T.launch_geometry(k)[2]], **kw)
+        assert torch.equal(v * 16, (v * 16).round()) and float(v.abs().max()) < 2 ** 11
+        T.R.r16(v, T.R.BF16)                                       # (asserts that the value is exact in fp32)
+
+
+def test_scaled_wgrad_case_reaches_its_regime(lib):
+    """T.WGRAD_SCALED_SHAPE against the plan restated in T.wgrad_plan and against the library's own answers."""
+    F = P("functional")
+    n, h, w = T.WGRAD_SCALED_SHAPE
+    plan = T.wgrad_plan(n, h, w)
+    print("wgrad plan at", T.WGRAD_SCALED_SHAPE, plan)
+    assert plan["tiles"] == 522 and plan["tiles_per_block"] == 9 > F.RDB_WGRAD_MIN_TILES and plan["chunks"] == 58
+    assert n * h * w == 22620 and plan["cs_ppb"] == 89 > T.COLSUM_MIN_PPB and plan["cs_rows"] == 255
+    assert F.rdb_wgrad_workspace(n, h, w, torch.bfloat16) == (plan["bytes"], 58) == F.rdb_wgrad_workspace(n, h, w, torch.float16)
+    # every shape the GPU tests use is in the first regime, and the restated plan agrees with the library there too
+    for shape in ((1, 5, 33), (2, 9, 65), (1, 4, 129), (2, 12, 20), (16, 32, 32), (16, 64, 64), (3, 100, 300)):
+        p = T.wgrad_plan(*shape)
+        assert F.rdb_wgrad_workspace(*shape, torch.bfloat16) == (p["bytes"], p["chunks"]), shape
+    assert all(T.wgrad_plan(*s)["tiles_per_block"] == 8 and T.wgrad_plan(*s)["cs_ppb"] == 64
+               for s in ((1, 5, 33), (2, 9, 65), (1, 4, 129), (2, 12, 20)))
+    big = T.wgrad_plan(16, 64, 64)                                  # the Real-ESRGAN batch: 1024 tiles, 65,536 pixels
+    assert (big["tiles"], big["tiles_per_block"], big["chunks"], big["cs_ppb"], big["cs_rows"]) == (1024, 16, 64, 256, 256)
+    # exact: products of integers in [-3, 3], P pixels -- every partial sum of any grouping is an integer <= 9 P < 2^24
+    assert 9 * n * h * w < 2 ** 24
+    for t in T.exact_wgrad_case(n, h, w):
+        assert float(t.abs().max()) <= 3 and torch.equal(t, t.round())
+        assert T.R.representable(t, T.R.BF16) and T.R.representable(t, T.R.F16)
+    assert T.EXACT_BETA == 0.25
+
+
 def test_module_switch_is_an_attribute_only():
     M = P("models.GAN.rrdbnet")
     net = M.RRDBNet(num_block=1)

@@ -231,3 +231,36 @@ def test_bad_arguments_return_codes():
     assert lib.dsr_gan_loss(p, 4, 0, 1, 0, p, None, p + 128, None) == E_ARG
     assert lib.dsr_gan_loss(p, 4, 0, 1, 0, p, p + 64, None, None) == E_ARG
     assert lib.dsr_abi_version() == L.ABI_VERSION == 8
+
+
+def test_spectral_norm_wide_and_full_table_cases():
+    """The cases of tests/test_gpu_spectral_norm.py past one turn of sn_v_kernel's column loops and at the table's limit:
+    the regime each is meant to reach (SR.v_turns, restated from csrc/spectral_norm.hip), the workspace formulas of
+    tests/spectral_ref.py against the library's, and the refusal of a 65th layer by all four entry points."""
+    L = P("_lib")
+    lib = L.lib()
+    ints = lambda v: (C.c_int * len(v))(*v)
+    cout, k = SR.WIDE_VECTOR
+    print(f"vector path {SR.WIDE_VECTOR}: {SR.v_turns(k, True)} turns; scalar path {SR.WIDE_SCALAR}: {SR.v_turns(SR.WIDE_SCALAR[1], False)}")
+    assert k > 4096 and k % 4 == 0 and SR.v_turns(k, True) == 2 and SR.v_turns(4096, True) == 1
+    assert SR.WIDE_SCALAR[1] > 1024 and SR.v_turns(SR.WIDE_SCALAR[1], False) == 2 and SR.v_turns(576, False) == 1
+    conv4 = {name: (co, ci * kk * kk) for name, co, ci, kk, _, _ in U.layer_table(num_feat=64)}["conv4"]
+    assert conv4 == SR.WIDE_VECTOR                                 # the widest normalised layer of the default discriminator
+    for shapes in ([SR.WIDE_VECTOR], [SR.WIDE_SCALAR], SR.FULL_TABLE, [(512, 4096)], [(8, 27), (130, 52)]):
+        c, kk = ints([s[0] for s in shapes]), ints([s[1] for s in shapes])
+        assert lib.dsr_spectral_norm_workspace(len(shapes), c, kk) == SR.fwd_workspace_bytes(shapes), shapes
+        assert lib.dsr_spectral_norm_bwd_workspace(len(shapes), c, kk) == SR.bwd_workspace_bytes(shapes), shapes
+    assert len(SR.FULL_TABLE) == SR.MAX_LAYERS == 64
+    assert any(kk % 4 for _, kk in SR.FULL_TABLE) and any(c % 32 for c, _ in SR.FULL_TABLE)
+    # 65 layers: refused by the size queries (0 bytes) and, before any pointer is looked at, by the forward and the backward
+    shapes = SR.FULL_TABLE + [(8, 27)]
+    c, kk = ints([s[0] for s in shapes]), ints([s[1] for s in shapes])
+    assert lib.dsr_spectral_norm_workspace(65, c, kk) == 0 and lib.dsr_spectral_norm_bwd_workspace(65, c, kk) == 0
+    buf = (C.c_float * 64)()
+    p = (C.cast(buf, C.c_void_p).value + 63) & ~63
+    tab = (C.c_void_p * 65)(*([p] * 65))
+    assert lib.dsr_spectral_norm_fwd(65, tab, tab, tab, c, kk, 1, 1e-12, p, tab, p, 1 << 30, None) == -1
+    assert b"count 65" in lib.dsr_last_error()
+    assert lib.dsr_spectral_norm_bwd(65, tab, tab, tab, tab, c, kk, p, tab, p, 1 << 30, None) == -1
+    assert b"count 65" in lib.dsr_last_error()
+    assert all(v == 0.0 for v in buf)
