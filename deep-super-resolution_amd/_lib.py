@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "csrc", "libdsr_hip.so")
 
-ABI_VERSION = 8          # bumped whenever a signature in include/dsr_hip.h changes; checked against the loaded library
+ABI_VERSION = 9          # bumped whenever a signature in include/dsr_hip.h changes; checked against the loaded library
 BF16, F16 = 0, 1
 F32 = 2                  # the luma entry points (csrc/luma.hip) also read fp32 images
 ACT_NONE, ACT_LEAKY, ACT_PRELU, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_ELU = range(7)
@@ -181,8 +181,6 @@ SIGNATURES = {
     "dsr_downsample_dense_dgrad": (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
     "dsr_downsample_dense_wgrad_workspace": (_Z, [_I] * 7),
     "dsr_downsample_dense_wgrad": (_I, [_P, _P, _P, _P, _P, _Z] + [_I] * 7 + [_P]),
-    "dsr_ssim_blocks": (_I, [_I, _I, _I]),
-    "dsr_ssim_f32": (_I, [_P, _P, _I, _I, _I, _F, _P, _P]),
     "dsr_lpips_tap_sizes": (_I, [_I, _I, C.POINTER(_I)]),
     "dsr_lpips_stem_prep": (_I, [_I, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "dsr_maxpool3s2_fwd": (_I, [_I, _P, _P, _I, _I, _I, _I, _P]),
@@ -274,7 +272,7 @@ LAUNCH_LOG = None
 _NO_LAUNCH = ("dsr_last_error", "dsr_abi_version", "dsr_conv_dgrad_ps_supported", "dsr_conv_dgrad_ps_rows", "dsr_conv_dgrad_bn_supported", "dsr_conv_dgrad_bn_rows", "dsr_conv_dgrad_first_bwd_supported", "dsr_conv_dgrad_first_bwd_workspace", "dsr_conv_kernel_name", "dsr_conv_wgrad_batchable", "dsr_conv_wgrad_batched_workspace", "dsr_conv_dgrad_add_supported", "dsr_conv_dgrad_masked_supported", "dsr_conv_fwd_affine_supported",
               "dsr_conv_first2_supported", "dsr_conv_first2_stats_rows", "dsr_conv_first_bwd_supported", "dsr_conv_first_bwd_workspace", "dsr_conv_out_size", "dsr_conv_stats_rows",
               "dsr_conv_packed_elems", "dsr_conv_dgrad_workspace", "dsr_conv_wgrad_workspace", "dsr_pw_scratch_rows",
-              "dsr_pw_reduce_blocks", "dsr_linear_fwd_workspace", "dsr_ssim_blocks", "dsr_lpips_tap_sizes", "dsr_lpips_distance_blocks",
+              "dsr_pw_reduce_blocks", "dsr_linear_fwd_workspace", "dsr_lpips_tap_sizes", "dsr_lpips_distance_blocks",
               "dsr_ssim_img_blocks", "dsr_psnr_blocks", "dsr_lbfgs_workspace", "dsr_lbfgs_vector_floats", "dsr_clip_sumsq_partials",
               "dsr_linear_factor_gram_workspace", "dsr_linear_factor_gram_dots", "dsr_downsample_dense_wgrad_workspace",
               "dsr_msssim_min_size", "dsr_msssim_pyramid_floats", "dsr_ssim_cs_img_blocks", "dsr_msssim_bwd_blocks", "dsr_luma_blocks",

@@ -136,6 +136,21 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;   // butterfly: every lane adds the same two operands at each level, so all lanes hold the same bits
+}
+
+// float -> unsigned key of the same order, and back: min / max of floats as unsigned min / max.  -0.0 orders below +0.0; a NaN
+// of either sign lands outside [-inf, +inf].
+__device__ __forceinline__ unsigned order_key(float f) {
+  const unsigned u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float order_unkey(unsigned k) {
+  return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
+}
 
 // MFMA 16x16x32, bf16 or f16 operands (8 elements / lane), fp32 accumulate
 template <int DT>

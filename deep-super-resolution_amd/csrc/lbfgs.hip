@@ -71,11 +71,6 @@ static T* lb_at(void* ws, size_t off) {
   return reinterpret_cast<T*>(static_cast<char*>(ws) + off);
 }
 
-__device__ __forceinline__ double lb_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;   // butterfly: every lane adds the same two operands at each level, so all lanes hold the same bits
-}
 __device__ __forceinline__ unsigned lb_wave_max(unsigned v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o, 64));
@@ -118,7 +113,7 @@ __global__ __launch_bounds__(256) void lbfgs_gather_kernel(const LbGroup a, Lbfg
     mx = max(mx, __float_as_uint(ag));
     sm += (double)ag;
   }
-  sm = lb_wave_sum(sm);
+  sm = wave_sum(sm);
   mx = lb_wave_max(mx);
   const int w = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
@@ -167,7 +162,7 @@ __global__ __launch_bounds__(256) void lbfgs_dot_kernel(const LbfgsHdr* __restri
   int par = 0;
   auto emit = [&](double* v, int row) {
 #pragma unroll
-    for (int c = 0; c < 6; ++c) v[c] = lb_wave_sum(v[c]);
+    for (int c = 0; c < 6; ++c) v[c] = wave_sum(v[c]);
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
       for (int c = 0; c < 6; ++c) red[par][w][c] = v[c];
@@ -233,7 +228,7 @@ __global__ __launch_bounds__(64) void lbfgs_dot_reduce_kernel(const LbfgsHdr* __
     const double* src = dpart + ((size_t)row * 6 + c) * bdot;
     double v = 0.0;
     for (unsigned b = threadIdx.x; b < bdot; b += 64) v += src[b];
-    v = lb_wave_sum(v);
+    v = wave_sum(v);
     if (threadIdx.x == 0) dots[row * 6 + c] = v;
   }
 }
@@ -271,7 +266,7 @@ __global__ __launch_bounds__(64) void lbfgs_scalar_kernel(const LbScalarArgs a) 
     gs += a.gsum[b];
     gm = max(gm, a.gmax[b]);
   }
-  gs = lb_wave_sum(gs);
+  gs = wave_sum(gs);
   gm = lb_wave_max(gm);
   const float loss = *a.loss;
   const bool opt_cond = (double)__uint_as_float(gm) <= a.tol_grad;
@@ -369,7 +364,7 @@ __global__ __launch_bounds__(64) void lbfgs_scalar_kernel(const LbScalarArgs a) 
     const double* row = a.gram + (size_t)lst[i] * nb;
     double acc = 0.0;
     for (int l = lane; l < L; l += 64) acc = fma(q[lst[l]], row[lst[l]], acc);
-    const double ali = lb_wave_sum(acc) * a.ro[lst[i]];
+    const double ali = wave_sum(acc) * a.ro[lst[i]];
     __syncthreads();
     if (lane == 0) {
       al[i] = ali;
@@ -384,7 +379,7 @@ __global__ __launch_bounds__(64) void lbfgs_scalar_kernel(const LbScalarArgs a) 
     const double* row = a.gram + (size_t)lst[k + i] * nb;
     double acc = 0.0;
     for (int l = lane; l < L; l += 64) acc = fma(q[lst[l]], row[lst[l]], acc);
-    const double be = lb_wave_sum(acc) * a.ro[lst[i]];
+    const double be = wave_sum(acc) * a.ro[lst[i]];
     __syncthreads();
     if (lane == 0) q[lst[i]] += al[i] - be;
     __syncthreads();
@@ -393,7 +388,7 @@ __global__ __launch_bounds__(64) void lbfgs_scalar_kernel(const LbScalarArgs a) 
   double acc = 0.0;
   const double* grow = a.gram + (size_t)G * nb;
   for (int l = lane; l < L; l += 64) acc = fma(q[lst[l]], grow[lst[l]], acc);
-  const double gtd = lb_wave_sum(acc);
+  const double gtd = wave_sum(acc);
   const int gvec = 2 * (m + 1) + 1 - h.gprev;    // vector index of the current gradient buffer
   for (int l = lane; l < L; l += 64) {
     const int c = lst[l];

@@ -51,12 +51,6 @@ static inline unsigned lp_grid(size_t n) {
   return (unsigned)(b < LPIPS_GRID_CAP ? (b > 0 ? b : 1) : LPIPS_GRID_CAP);
 }
 
-// float -> unsigned key of the same order (a NaN of either sign lands outside [-inf, +inf], so it fails the range test)
-__device__ __forceinline__ unsigned lp_key(float f) {
-  const unsigned b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 // ---------------------------------------------------------------------------------------------------- stem preparation
 template <int DT>
 __global__ __launch_bounds__(256) void lpips_stem_prep_kernel(const float* __restrict__ img1, const float* __restrict__ img2,
@@ -81,7 +75,7 @@ __global__ __launch_bounds__(256) void lpips_stem_prep_kernel(const float* __res
         const int y = 4 * by + (t >> 2) - 2, x = 4 * bx + (t & 3) - 2;      // padded coordinate - 2 = image coordinate
         if ((unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W) {
           const float raw = img[((size_t)c * H + y) * W + x];
-          const unsigned key = lp_key(raw);
+          const unsigned key = order_key(raw);           // a NaN lands outside [-inf, +inf], so it fails the range test
           kmin = key < kmin ? key : kmin;
           kmax = key > kmax ? key : kmax;
           // the scaling layer: (x - shift) / scale, shift (-.030, -.088, -.188), scale (.458, .448, .450)

@@ -92,12 +92,6 @@ __global__ __launch_bounds__(256) void luma_kernel(const void* __restrict__ p, c
   }
 }
 
-__device__ __forceinline__ double luma_wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // per_image[n] = 10 log10(count / SSE_n) (+inf when SSE_n == 0), SSE_n = the B partials of image n folded in a fixed order in
 // double; value = value_scale * sum_n per_image[n]; state[0] += sum_n per_image[n], state[1] += N (dsr_metric_accumulate's pair)
 __global__ __launch_bounds__(1024) void luma_psnr_finalize_kernel(const float* __restrict__ partial, int N, int B, double count,
@@ -109,7 +103,7 @@ __global__ __launch_bounds__(1024) void luma_psnr_finalize_kernel(const float* _
   for (int n = wave; n < N; n += 16) {
     double sse = 0.0;
     for (int k = lane; k < B; k += 64) sse += (double)partial[(size_t)n * B + k];
-    sse = luma_wave_sum_f64(sse);
+    sse = wave_sum(sse);
     const double v = sse > 0.0 ? 10.0 * log10(count / sse) : (double)INFINITY;
     if (lane == 0 && per_image) per_image[n] = (float)v;
     mine += v;

@@ -5,19 +5,19 @@
 // torchmetrics is not installed here and cannot be fetched: "parity unpinned"; the oracle (oracle/metrics.py) restates
 // the published formula with F.conv2d and is what the GPU test compares against.
 //
-// fp32 NCHW in, one partial sum per block out (deterministic two-stage reduction, no atomics).  A block computes a 32x8
-// patch of window centres from a (32+10)x(8+10) tile of both images staged in LDS; 121 taps x 5 moments per thread.
+// One forward kernel serves every caller (metrics.py's SSIM, MS-SSIM and SSIM_Y modules and evaluate.ssim): ssim_img_kernel,
+// fp32 NCHW in, one partial sum per block out, folded by a one-block launch (deterministic, no atomics).  With it in this file:
+// the SSIM and MS-SSIM input gradients, the 2x2 mean pool of the multi-scale pyramid, the PSNR statistics and the device-side
+// running state of the metric modules.
 // Every moment is accumulated the same way -- the product of the two pixels formed once, then one explicit fma per tap -- and
-// the position's value comes from ssim_of_moments: with `r += g * x * y` left to the compiler, hipcc packed some moments into
-// v_pk_fma_f32 and others into v_pk_mul_f32 + v_add_f32, so E[ab] and E[a^2] of IDENTICAL images differed in the last bit and
-// their SSIM was 1 - 1e-6 instead of 1 (the cancellation in the variances amplifies by 1 / (va + vb + c2)).
+// the position's value comes from ssim_of_moments: with `r += g * x * y` left to the compiler, hipcc packs some moments into
+// v_pk_fma_f32 and others into v_pk_mul_f32 + v_add_f32, so E[ab] and E[a^2] of IDENTICAL images differ in the last bit and
+// their SSIM is 1 - 1e-6 instead of 1 (the cancellation in the variances amplifies by 1 / (va + vb + c2)).
 #include "dsr_common.h"
 #include "dsr_kernels.h"
 #include "../../include/dsr_hip.h"
 
 #define SSIM_K 11
-#define SSIM_TW 32
-#define SSIM_TH 8
 
 struct SsimWindow {
   float g[SSIM_K];   // separable 1-D Gaussian, normalised to sum 1
@@ -32,95 +32,10 @@ __device__ __forceinline__ float ssim_of_moments(float ma, float mb, float saa, 
   return ((2.f * mab + c1) * (2.f * cab + c2)) / ((maa + mbb + c1) * (va + vb + c2));
 }
 
-__global__ __launch_bounds__(256) void ssim_kernel(const float* __restrict__ a, const float* __restrict__ b, int H, int W,
-                                                   int tiles_x, int tiles_y, float c1, float c2, SsimWindow win,
-                                                   float* __restrict__ partial) {
-  constexpr int LW = SSIM_TW + SSIM_K - 1, LH = SSIM_TH + SSIM_K - 1;
-  __shared__ float sa[LH][LW + 1], sb[LH][LW + 1];
-  __shared__ float red[4];
-  const int plane = blockIdx.x / (tiles_x * tiles_y);
-  const int t = blockIdx.x % (tiles_x * tiles_y);
-  const int ty0 = (t / tiles_x) * SSIM_TH, tx0 = (t % tiles_x) * SSIM_TW;
-  const float* pa = a + (size_t)plane * H * W;
-  const float* pb = b + (size_t)plane * H * W;
-  for (int i = threadIdx.x; i < LH * LW; i += 256) {
-    const int ly = i / LW, lx = i % LW;
-    const int y = ty0 + ly, x = tx0 + lx;
-    const bool ok = y < H && x < W;
-    sa[ly][lx] = ok ? pa[(size_t)y * W + x] : 0.f;
-    sb[ly][lx] = ok ? pb[(size_t)y * W + x] : 0.f;
-  }
-  __syncthreads();
-  const int lx = threadIdx.x % SSIM_TW, ly = threadIdx.x / SSIM_TW;
-  const int OH = H - SSIM_K + 1, OW = W - SSIM_K + 1;        // window centres fully inside the image
-  float v = 0.f;
-  if (ty0 + ly < OH && tx0 + lx < OW) {
-    float ma = 0.f, mb = 0.f, saa = 0.f, sbb = 0.f, sab = 0.f;
-#pragma unroll
-    for (int dy = 0; dy < SSIM_K; ++dy) {
-      float ra = 0.f, rb = 0.f, raa = 0.f, rbb = 0.f, rab = 0.f;
-#pragma unroll
-      for (int dx = 0; dx < SSIM_K; ++dx) {
-        const float xa = sa[ly + dy][lx + dx], xb = sb[ly + dy][lx + dx], g = win.g[dx];
-        const float paa = xa * xa, pbb = xb * xb, pab = xa * xb;
-        ra = fmaf(g, xa, ra);
-        rb = fmaf(g, xb, rb);
-        raa = fmaf(g, paa, raa);
-        rbb = fmaf(g, pbb, rbb);
-        rab = fmaf(g, pab, rab);
-      }
-      const float g = win.g[dy];
-      ma = fmaf(g, ra, ma);
-      mb = fmaf(g, rb, mb);
-      saa = fmaf(g, raa, saa);
-      sbb = fmaf(g, rbb, sbb);
-      sab = fmaf(g, rab, sab);
-    }
-    v = ssim_of_moments(ma, mb, saa, sbb, sab, c1, c2);
-  }
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-extern "C" int dsr_ssim_blocks(int planes, int H, int W) {
-  if (planes < 1 || H < SSIM_K || W < SSIM_K) return 0;
-  const int OH = H - SSIM_K + 1, OW = W - SSIM_K + 1;
-  return planes * ((OH + SSIM_TH - 1) / SSIM_TH) * ((OW + SSIM_TW - 1) / SSIM_TW);
-}
-
-extern "C" int dsr_ssim_f32(const float* img1, const float* img2, int planes, int H, int W, float data_range, float* partial,
-                            hipStream_t st) {
-  DSR_REQUIRE(img1 && img2 && partial && planes > 0, "ssim: null pointer or no planes");
-  DSR_REQUIRE(H >= SSIM_K && W >= SSIM_K, "ssim: image %dx%d smaller than the 11x11 window", H, W);
-  DSR_REQUIRE(data_range > 0.f, "ssim: data_range must be positive");
-  const int OH = H - SSIM_K + 1, OW = W - SSIM_K + 1;
-  const int tiles_y = (OH + SSIM_TH - 1) / SSIM_TH, tiles_x = (OW + SSIM_TW - 1) / SSIM_TW;
-  SsimWindow win;
-  double s = 0.0, g[SSIM_K];
-  for (int i = 0; i < SSIM_K; ++i) {
-    const double d = i - (SSIM_K - 1) / 2.0;
-    g[i] = exp(-d * d / (2.0 * 1.5 * 1.5));
-    s += g[i];
-  }
-  for (int i = 0; i < SSIM_K; ++i) win.g[i] = (float)(g[i] / s);
-  const float c1 = (0.01f * data_range) * (0.01f * data_range), c2 = (0.03f * data_range) * (0.03f * data_range);
-  hipLaunchKernelGGL(ssim_kernel, dim3(planes * tiles_x * tiles_y), dim3(256), 0, st, img1, img2, H, W, tiles_x, tiles_y, c1, c2,
-                     win, partial);
-  return dsr_launch_status("dsr_ssim_f32");
-}
-
 // ================================================================================ metrics.StructuralSimilarityIndexMeasure
 // Per-image SSIM, its input gradient, PSNR statistics and the device-side running state of the two metric modules
-// (metrics.py).  Same window and unclamped formula as ssim_kernel; c1 = (k1 range)^2, c2 = (k2 range)^2 are arguments.
+// (metrics.py).  The formula is unclamped; c1 = (k1 range)^2, c2 = (k2 range)^2 are arguments.
 // Reductions are deterministic: one partial per block (plain stores), folded in a fixed order by a one-block finalise launch.
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 static SsimWindow ssim_gauss_window() {
   SsimWindow win;
@@ -634,7 +549,7 @@ __global__ __launch_bounds__(256) void msssim_combine_kernel(const float* __rest
     }
     mine += (double)(float)out;
   }
-  mine = wave_sum_f64(mine);
+  mine = wave_sum(mine);
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = mine;
   __syncthreads();
   if (threadIdx.x == 0 && total) total[0] = (float)((double)total_scale * ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])));
@@ -686,17 +601,9 @@ extern "C" int dsr_msssim_bwd_blocks(int N, int C, int H, int W) {
 
 // ================================================================================ metrics.PeakSignalNoiseRatio
 // One pass over preds and target: per block (PSNR_CHUNK elements of one image, 64 per thread, then tree sums) the sum of
-// squared errors and the target's (min, max) as order-preserving keys.  The finalise folds them per image / per batch in
-// double, in a fixed order.
+// squared errors and the target's (min, max) as order-preserving keys (order_key).  The finalise folds them per image / per
+// batch in double, in a fixed order.
 #define PSNR_CHUNK 16384
-
-__device__ __forceinline__ unsigned metric_key(float f) {          // float -> unsigned key of the same order
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float metric_unkey(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
 
 template <bool V4>
 __global__ __launch_bounds__(256) void psnr_stats_kernel(const float* __restrict__ p, const float* __restrict__ t, int E, int B,
@@ -721,7 +628,7 @@ __global__ __launch_bounds__(256) void psnr_stats_kernel(const float* __restrict
         s = fmaf(d1, d1, s);
         s = fmaf(d2, d2, s);
         s = fmaf(d3, d3, s);
-        const unsigned k0 = metric_key(y.x), k1 = metric_key(y.y), k2 = metric_key(y.z), k3 = metric_key(y.w);
+        const unsigned k0 = order_key(y.x), k1 = order_key(y.y), k2 = order_key(y.z), k3 = order_key(y.w);
         kmin = min(kmin, min(min(k0, k1), min(k2, k3)));
         kmax = max(kmax, max(max(k0, k1), max(k2, k3)));
       }
@@ -734,7 +641,7 @@ __global__ __launch_bounds__(256) void psnr_stats_kernel(const float* __restrict
       if (e < E) {
         const float y = tn[e], d = pn[e] - y;
         s = fmaf(d, d, s);
-        const unsigned key = metric_key(y);
+        const unsigned key = order_key(y);
         kmin = min(kmin, key);
         kmax = max(kmax, key);
       }
@@ -781,7 +688,7 @@ __global__ __launch_bounds__(1024) void psnr_finalize_kernel(const float* __rest
       kmin = min(kmin, partial_keys[2 * j]);
       kmax = max(kmax, partial_keys[2 * j + 1]);
     }
-    s = wave_sum_f64(s);
+    s = wave_sum(s);
     if (per_image) {
       const double v = (double)log_scale * (2.0 * log((double)range) - log(s / (double)E));
       if (lane == 0) per_image[n] = (float)v;
@@ -817,7 +724,7 @@ __global__ __launch_bounds__(1024) void psnr_finalize_kernel(const float* __rest
     }
     return;
   }
-  const double lo = (double)metric_unkey(mn), hi = (double)metric_unkey(mx), cnt = (double)N * (double)E;
+  const double lo = (double)order_unkey(mn), hi = (double)order_unkey(mx), cnt = (double)N * (double)E;
   const double r = infer_range ? fmax(hi, 0.0) - fmin(lo, 0.0) : (double)range;
   if (value) value[0] = (float)((double)log_scale * (2.0 * log(r) - log(acc / cnt)));
   if (state) {
@@ -832,7 +739,7 @@ __global__ __launch_bounds__(1024) void psnr_finalize_kernel(const float* __rest
 __global__ __launch_bounds__(64) void metric_accumulate_kernel(const float* __restrict__ per, int N, double* __restrict__ state) {
   double s = 0.0;
   for (int n = threadIdx.x; n < N; n += 64) s += (double)per[n];
-  s = wave_sum_f64(s);
+  s = wave_sum(s);
   if (threadIdx.x == 0) {
     state[0] += s;
     state[1] += (double)N;

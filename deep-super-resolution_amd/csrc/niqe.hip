@@ -49,12 +49,6 @@ __global__ __launch_bounds__(256) void niqe_plane_kernel(const void* __restrict_
   plane[i] = (float)(16 + q);
 }
 
-__device__ __forceinline__ double niqe_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // One workgroup per block of B x B pixels.  LDS: v [B][B] fp64, the plane's tile with a 3-pixel halo [B + 6][B + 6] fp32, the
 // waves' partial sums and the window -- 118 KB at B = 96 (the opt-in), 31 KB at B = 48.
 template <int B, int T>
@@ -124,7 +118,7 @@ __global__ __launch_bounds__(T) void niqe_moments_kernel(const float* __restrict
   for (int k = 0; k < 5; ++k)
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
-      const double s = niqe_wave_sum(acc[k][j]);
+      const double s = wave_sum(acc[k][j]);
       if (lane == 0) red[wave * 25 + k * 5 + j] = s;
     }
   __syncthreads();

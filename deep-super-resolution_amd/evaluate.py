@@ -59,27 +59,18 @@ def psnr(pred, target, data_range=None):
 
 def ssim(pred, target, data_range=1.0):
     """Host float: mean SSIM (Gaussian 11x11, sigma 1.5, K1 0.01, K2 0.03 -- the torchmetrics defaults the reference's scripts
-    run with, ``SSIM(data_range=1.)`` at eval_GAN.py:31) of fp32 NCHW device tensors, on the HIP kernel dsr_ssim_f32."""
-    import ctypes as C
-    from . import _lib
+    run with, ``SSIM(data_range=1.)`` at eval_GAN.py:31) of fp32 NCHW device tensors, on the HIP kernel dsr_ssim_img_f32: the
+    value of ``metrics.SSIM(data_range=data_range)(pred, target)``, bit for bit."""
+    from . import metrics
     pred, target = pred.detach().contiguous().float(), target.detach().contiguous().float()
-    if pred.shape != target.shape or pred.dim() != 4:
+    if pred.shape != target.shape or pred.dim() != 4 or pred.numel() == 0:
         raise RuntimeError(f"ssim: operands must be two [N,C,H,W] tensors of one shape, got {tuple(pred.shape)} and {tuple(target.shape)}")
-    n, c, h, w = pred.shape
-    lib = _lib.lib()
-    blocks = lib.dsr_ssim_blocks(n * c, h, w)
-    if blocks <= 0:
+    n, _, h, w = pred.shape
+    if h < 11 or w < 11:
         raise RuntimeError(f"ssim: images of {h}x{w} are smaller than the 11x11 window")
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    rows = (blocks + 63) // 64                      # block sums as a [rows][64] table (zero padded): two-stage column sum
-    part = torch.zeros(rows * 64, dtype=torch.float32, device=pred.device)
-    _lib.check(lib.dsr_ssim_f32(C.c_void_p(pred.data_ptr()), C.c_void_p(target.data_ptr()), n * c, h, w, float(data_range),
-                                C.c_void_p(part.data_ptr()), st))
-    cols = torch.empty(64, dtype=torch.float32, device=pred.device)
-    total = torch.empty(1, dtype=torch.float32, device=pred.device)
-    _lib.check(lib.dsr_pw_sum_rows(C.c_void_p(part.data_ptr()), rows, 64, 0, 64, 1.0, C.c_void_p(cols.data_ptr()), 0, 1, st))
-    _lib.check(lib.dsr_pw_sum_rows(C.c_void_p(cols.data_ptr()), 64, 1, 0, 1, 1.0 / (n * c * (h - 10) * (w - 10)),
-                                   C.c_void_p(total.data_ptr()), 0, 0, st))
+    if not data_range > 0:
+        raise RuntimeError(f"ssim: data_range must be positive, got {data_range!r}")
+    _, total = metrics._ssim_img("ssim", pred, target, (0.01 * data_range) ** 2, (0.03 * data_range) ** 2, 1.0 / n)
     return float(total)
 
 

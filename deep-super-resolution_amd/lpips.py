@@ -137,7 +137,7 @@ def load_lin_state(obj):
 
 
 def _decode_key(k):
-    """Inverse of lp_key (csrc/lpips.hip): order-preserving unsigned key -> float."""
+    """Inverse of order_key (csrc/dsr_common.h): order-preserving unsigned key -> float."""
     k &= 0xFFFFFFFF
     bits = (k ^ 0x80000000) if k & 0x80000000 else (~k & 0xFFFFFFFF)
     return struct.unpack("<f", struct.pack("<I", bits))[0]

@@ -304,6 +304,22 @@ def _check_constants(name, data_range, k1, k2):
     return data_range, k1, k2, c1, c2
 
 
+def _ssim_img(name, a, b, c1, c2, scale, want_total=True):
+    """(per_image [N], total [1] = scale * their sum, or None): dsr_ssim_img_f32 on two fp32 [N,C,H,W] tensors of one shape,
+    each side at least the window's.  The one SSIM forward launch: the SSIM modules and ``evaluate.ssim`` all come here."""
+    n, c, h, w = a.shape
+    lib = _lib.lib()
+    blocks = lib.dsr_ssim_img_blocks(n, c, h, w)
+    if blocks <= 0:
+        raise RuntimeError(f"{name}: {tuple(a.shape)} needs too many window tiles")
+    dev = a.device
+    partial = torch.empty(blocks, dtype=torch.float32, device=dev)
+    per = torch.empty(n, dtype=torch.float32, device=dev)
+    tot = torch.empty(1, dtype=torch.float32, device=dev) if want_total else None
+    check(lib.dsr_ssim_img_f32(_ptr(a), _ptr(b), n, c, h, w, c1, c2, _ptr(partial), _ptr(per), _ptr(tot), scale, 0, _stream()))
+    return per, tot
+
+
 class StructuralSimilarityIndexMeasure(_PerImageMetric):
     """torchmetrics ``StructuralSimilarityIndexMeasure`` on the HIP path, for what the reference uses: the Gaussian 11x11 window
     with sigma 1.5 and a positive ``data_range`` (the reference passes 1.0).  ``reduction``: 'elementwise_mean' (0-dim),
@@ -341,20 +357,9 @@ class StructuralSimilarityIndexMeasure(_PerImageMetric):
     # ---- the device path
     def _run(self, preds, target, a=None, b=None):
         """(per_image [N], total [1] = the reduction's scale * sum) of fp32 copies a, b of the inputs."""
-        n, c, h, w = preds.shape
         a = _f32(preds) if a is None else a
         b = _f32(target) if b is None else b
-        lib = _lib.lib()
-        blocks = lib.dsr_ssim_img_blocks(n, c, h, w)
-        if blocks <= 0:
-            raise RuntimeError(f"StructuralSimilarityIndexMeasure: {tuple(preds.shape)} needs too many window tiles")
-        dev = a.device
-        partial = torch.empty(blocks, dtype=torch.float32, device=dev)
-        per = torch.empty(n, dtype=torch.float32, device=dev)
-        tot = torch.empty(1, dtype=torch.float32, device=dev)
-        check(lib.dsr_ssim_img_f32(_ptr(a), _ptr(b), n, c, h, w, self.c1, self.c2, _ptr(partial), _ptr(per), _ptr(tot),
-                                   self._total_scale(n), 0, _stream()))
-        return per, tot
+        return _ssim_img("StructuralSimilarityIndexMeasure", a, b, self.c1, self.c2, self._total_scale(a.shape[0]))
 
 
 class _SSIMFunction(torch.autograd.Function):
@@ -632,19 +637,8 @@ _SSIM_C1, _SSIM_C2 = 0.01 ** 2, 0.03 ** 2
 
 
 def _luma_ssim(yp, yt, scale, want_total=True):
-    """(per_image [N], total [1] or None): dsr_ssim_img_f32 on the two luma planes (C = 1, data_range 1)."""
-    n, _, h, w = yp.shape
-    lib = _lib.lib()
-    blocks = lib.dsr_ssim_img_blocks(n, 1, h, w)
-    if blocks <= 0:
-        raise RuntimeError(f"LumaStructuralSimilarityIndexMeasure: {tuple(yp.shape)} needs too many window tiles")
-    dev = yp.device
-    partial = torch.empty(blocks, dtype=torch.float32, device=dev)
-    per = torch.empty(n, dtype=torch.float32, device=dev)
-    tot = torch.empty(1, dtype=torch.float32, device=dev) if want_total else None
-    check(lib.dsr_ssim_img_f32(_ptr(yp), _ptr(yt), n, 1, h, w, _SSIM_C1, _SSIM_C2, _ptr(partial), _ptr(per), _ptr(tot), scale, 0,
-                               _stream()))
-    return per, tot
+    """(per_image [N], total [1] or None) of the two luma planes (C = 1, data_range 1)."""
+    return _ssim_img("LumaStructuralSimilarityIndexMeasure", yp, yt, _SSIM_C1, _SSIM_C2, scale, want_total)
 
 
 def luma_psnr_ssim(preds, target, shave=0, quantize=True, with_ssim=True):

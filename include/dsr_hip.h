@@ -397,14 +397,8 @@ int dsr_downsample_dense_wgrad(const float* x, const float* dy, float* dw, float
                                size_t workspace_bytes, int N, int C, int H, int W, int k, int f, int p, dsr_stream_t s);
 
 /* SSIM as the reference's scripts measure it (torchmetrics StructuralSimilarityIndexMeasure at train_GAN.py:31,111,
- * eval_GAN.py:31,48): Gaussian 11x11 sigma 1.5 window, K1 0.01, K2 0.03, per plane (planes = N*C fp32 H x W images),
- * window positions inside the image.  Writes dsr_ssim_blocks(planes, H, W) partial sums; their total divided by
- * planes * (H-10) * (W-10) is the mean SSIM. */
-int dsr_ssim_blocks(int planes, int H, int W);
-int dsr_ssim_f32(const float* img1, const float* img2, int planes, int H, int W, float data_range, float* partial,
-                 dsr_stream_t s);
-
-/* The metric modules of metrics.py (same window and formula; c1 = (k1 range)^2, c2 = (k2 range)^2, both > 0 and finite).
+ * eval_GAN.py:31,48): Gaussian 11x11 sigma 1.5 window, per plane, window positions inside the image; c1 = (k1 range)^2,
+ * c2 = (k2 range)^2 (K1 0.01, K2 0.03 there), both > 0 and finite.  The metric modules of metrics.py and evaluate.ssim.
  * dsr_ssim_img_f32: fp32 NCHW img1, img2 [N][C][H][W] -> per_image[N] = mean SSIM over the image's C x (H-10) x (W-10) window
  * positions (nullable), total[0] (+= if accumulate; nullable) = total_scale * sum_n per_image[n]; partial: scratch of
  * dsr_ssim_img_blocks(N, C, H, W) floats.  Two launches (tiles, then a one-block fold in a fixed order).

@@ -75,7 +75,8 @@ def pool_items(n, h, w, cp):
 
 
 def lp_key(f):
-    """lp_key of csrc/lpips.hip on the fp32 bits of f: an unsigned key of the same order; a NaN lands outside [-inf, +inf]."""
+    """order_key of csrc/dsr_common.h (lpips.hip's range words) on the fp32 bits of f: an unsigned key of the same order; a NaN
+    lands outside [-inf, +inf]."""
     (b,) = struct.unpack("<I", struct.pack("<f", f))
     return (~b & 0xFFFFFFFF) if b & 0x80000000 else (b | 0x80000000)
 

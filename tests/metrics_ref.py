@@ -25,7 +25,6 @@ import ssim_ref
 F64, F32 = torch.float64, torch.float32
 SSIM_K = 11
 SF_TH, SF_TW = 16, 64            # ssim_img_kernel<CS>: window positions per block
-SSIM_TH, SSIM_TW = 8, 32         # ssim_kernel (dsr_ssim_f32)
 SB_T = 32                        # ssim_bwd_kernel<MS>: gradient pixels per block (square)
 PSNR_CHUNK = 16384               # psnr_stats_kernel<V4>: elements per block
 FIN_WAVES, FIN_LANES = 16, 64    # the one-block finalisers: images stride the waves, blocks of an image stride the lanes
@@ -84,7 +83,6 @@ def blocks_per_image(shape, th, tw):
 
 AMPLITUDES = (0.05, 0.3, 1.0)
 FWD_SHAPES = [(1, 1, 11, 11), (2, 3, 27, 75), (2, 3, 43, 139), (1, 3, 91, 203), (17, 1, 12, 76), (64, 1, 11, 11)]
-OLD_SHAPES = [(1, 1, 11, 11), (2, 3, 19, 43), (2, 3, 27, 75)]          # dsr_ssim_f32, tile 8 x 32: the analogous edges
 
 
 @functools.lru_cache(maxsize=None)
@@ -122,13 +120,11 @@ def fwd_reference(shape, th, tw):
 @functools.lru_cache(maxsize=None)
 def fwd_floor(th, tw):
     """F(n): the largest |sum32 - sum64| over all tiles with n positions of the sweep of that tile size (every shape, the SSIM
-    and, for the 16 x 64 kernels, the contrast-structure sums), n -> F(n)."""
-    shapes = FWD_SHAPES if (th, tw) == (SF_TH, SF_TW) else OLD_SHAPES
+    and the contrast-structure sums), n -> F(n)."""
     out = {}
-    for shape in shapes:
+    for shape in FWD_SHAPES:
         r = fwd_reference(shape, th, tw)
-        kinds = ("sim", "cs") if (th, tw) == (SF_TH, SF_TW) else ("sim",)
-        for kind in kinds:
+        for kind in ("sim", "cs"):
             d = (r[kind + "32"] - r[kind]).abs()
             for n in r["cnt"].unique().tolist():
                 out[n] = max(out.get(n, 0.0), float(d[r["cnt"] == n].max()))

@@ -2,7 +2,7 @@
 generators, case tables and floors: metrics_ref.py; the references against the suite's restatements, the exactness of the
 regimes, the branches the tables reach and the floors on the CPU: test_host_metrics_sweep.py).
 
-A  forward tiles: every partial[block] of dsr_ssim_img_f32, dsr_ssim_cs_img_f32 and dsr_ssim_f32 against the float64 sum of that
+A  forward tiles: every partial[block] of dsr_ssim_img_f32 and dsr_ssim_cs_img_f32 against the float64 sum of that
    tile, bar 4 x max(F(n), 1e-6 n) for a tile of n positions (F(n): the float32 CPU restatement's largest deviation on tiles of
    that size); the finalisers against the read-back partials folded in float64, within the summation-chain bound.
 B  exact regime, no tolerance: identical images give partial == the tile's position count; an impulse changes exactly the tiles
@@ -31,7 +31,6 @@ PKG = "deep-super-resolution_amd"
 F64, F32 = torch.float64, torch.float32
 NAN = float("nan")
 IMG = (R.SF_TH, R.SF_TW)
-OLD = (R.SSIM_TH, R.SSIM_TW)
 SHAPE_ID = lambda s: "x".join(map(str, s))
 
 
@@ -110,14 +109,6 @@ class Calls:
         cs = self.out((n,), "ssim_cs_img cs") if cs else None
         self.call("ssim_cs_img_f32", ptr(a), ptr(b), n, c, h, w, R.C1, R.C2, ptr(partial), ptr(sim), ptr(cs))
         return partial, sim, cs
-
-    def ssim_old(self, a, b, shape):
-        n, c, h, w = shape
-        blocks = self.lib.dsr_ssim_blocks(n * c, h, w)
-        assert blocks == n * R.blocks_per_image(shape, *OLD)
-        partial = self.out((blocks,), "ssim partial")
-        self.call("ssim_f32", ptr(a), ptr(b), n * c, h, w, 1.0, ptr(partial))
-        return partial
 
 
 def cpu64(t):
@@ -201,22 +192,6 @@ def test_forward_tiles_vs_float64(dev, shape):
         assert abs(float(tot[0]) - (base + want)) <= tol, f"{shape} total (held {base}): got {float(tot[0])!r} want {base + want!r} tol {tol:.3e}"
 
 
-@pytest.mark.parametrize("shape", R.OLD_SHAPES, ids=SHAPE_ID)
-def test_old_forward_tiles_vs_float64(dev, shape):
-    """dsr_ssim_f32 (8 x 32 positions per block, evaluate.py's kernel): every partial against the float64 sum of its tile.
-    Measured on the MI355X: F(1) 7.6e-6, F(8) 4.7e-5, F(32) 9.4e-5, F(256) 2.9e-4; worst error over max(F(n), 1e-6 n) 0.24, 0.37,
-    0.37, 0.45."""
-    k = Calls(dev)
-    a, b = R.fwd_case(shape)
-    part = k.ssim_old(k.up(a), k.up(b), shape)
-    k.can.check()
-    no_nan(part, f"{shape} partial")
-    ref = R.fwd_reference(shape, *OLD)
-    rat = Ratios(OLD, f"forward (8 x 32 kernel) {shape}")
-    rat.add(cpu64(part), ref["sim"].numpy(), ref["cnt"].numpy(), f"ssim {shape}")
-    rat.report()
-
-
 # ============================================================================= B: the exact regime
 @pytest.mark.parametrize("shape", R.FWD_SHAPES, ids=SHAPE_ID)
 def test_identical_and_swapped_images_exact(dev, shape):
@@ -266,41 +241,6 @@ def test_impulse_changes_exactly_its_tiles(dev, shape):
             assert bool(same[~hit].all()), f"{shape} impulse {(y, x)} {what}: tiles {(~same & ~hit).nonzero().flatten().tolist()} changed, " \
                                            f"only {hit.nonzero().flatten().tolist()} may"
             rat.add(g.to(F64).numpy(), R.tile_sums(m, *IMG)[0].numpy(), cnt.numpy(), f"{what} {shape} impulse {(y, x)}", only=hit.numpy())
-    rat.report()
-
-
-@pytest.mark.parametrize("shape", R.OLD_SHAPES, ids=SHAPE_ID)
-def test_old_kernel_identical_and_impulse(dev, shape):
-    """dsr_ssim_f32: |partial - count| <= 16 x 2^-24 per position -- far below one position -- for identical images and for
-    every tile an impulse does not reach; the tiles it reaches meet the bar of A.  This sweep found the kernel outside the bound
-    (up to 21 x 2^-24 per position, on the one-column tiles of 2 x 3 x 19 x 43): its tap loop left `r += g * x * y` to the
-    compiler, which packed some of the five moments into v_pk_fma_f32 and others into v_pk_mul_f32 + v_add_f32, so E[ab] and
-    E[a^2] of identical windows differed in the last bit, amplified by 1 / (va + vb + c2).  The kernel now accumulates every
-    moment with an explicit fma and calls ssim_of_moments like the per-image kernels; measured on the MI355X since: deviation
-    exactly 0 on every tile.  The largest deviation is printed."""
-    cnt = R.tile_counts(shape, *OLD)
-    tol = 16 * R.EPS32 * cnt.to(F64)
-    rat = Ratios(OLD, f"impulse (8 x 32 kernel) {shape}")
-    k = Calls(dev)
-    a, b = R.fwd_case(shape)
-    for x in (a, b):
-        xd = k.up(x)
-        part = k.ssim_old(xd, xd, shape)
-        k.can.check()
-        dev_ = (part.cpu().to(F64) - cnt).abs()
-        print(f"\nssim (8 x 32 kernel) {shape} identical images: largest |partial - count| / count = {float((dev_ / cnt).max()):.3e} "
-              f"(bound {16 * R.EPS32:.3e})")
-        assert bool((dev_ <= tol).all()), f"{shape}: identical images: tiles {(dev_ > tol).nonzero().flatten().tolist()}"
-    for y, x in R.impulse_pixels(shape, *OLD):
-        k = Calls(dev)
-        a, b, _ = R.impulse_case(shape, y, x)
-        part = k.ssim_old(k.up(a), k.up(b), shape)
-        k.can.check()
-        hit = R.impulse_tiles(shape, y, x, *OLD)
-        got = part.cpu().to(F64)
-        near = (got - cnt).abs() <= tol
-        assert bool(near[~hit].all()), f"{shape} impulse {(y, x)}: tiles {(~near & ~hit).nonzero().flatten().tolist()}"
-        rat.add(got.numpy(), R.tile_sums(R.fwd_maps(a, b)[0], *OLD)[0].numpy(), cnt.numpy(), f"ssim {shape} impulse {(y, x)}", only=hit.numpy())
     rat.report()
 
 

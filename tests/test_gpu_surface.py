@@ -322,11 +322,12 @@ def test_evaluate_generator_loop(dev, tmp_path):
     assert g.training                                            # super_resolve restores the caller's mode
 
 
-@pytest.mark.parametrize("shape", [(2, 3, 40, 52), (1, 1, 11, 11), (1, 3, 97, 33)])
+@pytest.mark.parametrize("shape", [(2, 3, 40, 52), (1, 1, 11, 11), (1, 3, 97, 33), (2, 3, 27, 75)])
 def test_ssim_kernel_vs_oracle(dev, shape):
-    """dsr_ssim_f32 (Gaussian 11x11, sigma 1.5, K1 0.01, K2 0.03; SSIM(data_range=1.) of eval_GAN.py:31) against the float64
-    restatement in oracle/metrics.py, plus the metric's defining properties: identical images give exactly 1, and it is
-    symmetric in its arguments."""
+    """evaluate.ssim on dsr_ssim_img_f32 (Gaussian 11x11, sigma 1.5, K1 0.01, K2 0.03; SSIM(data_range=1.) of eval_GAN.py:31)
+    against the float64 restatement in oracle/metrics.py, plus the metric's defining properties: identical images give exactly
+    1, and it is symmetric in its arguments.  (2, 3, 27, 75) is 17 x 65 window positions: a ragged second tile in both
+    directions of the 16 x 64 tiling.  It is the metric module's launch, so its value equals ``metrics.SSIM``'s exactly."""
     ev = P("evaluate")
     a = filler.tensor("ssim:a" + str(shape), shape, 0.5, 0.5)
     b = (a + filler.tensor("ssim:n" + str(shape), shape, 0.15)).clamp(0, 1)
@@ -339,3 +340,6 @@ def test_ssim_kernel_vs_oracle(dev, shape):
         assert 0.0 < got < 1.0
     with pytest.raises(RuntimeError):
         ev.ssim(a.to(dev)[..., :10], b.to(dev)[..., :10])
+    assert got == float(P("metrics").SSIM(data_range=1.0)(a.to(dev), b.to(dev)))
+    with pytest.raises(RuntimeError):
+        ev.ssim(a.to(dev), b.to(dev), 0.0)

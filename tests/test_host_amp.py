@@ -33,7 +33,7 @@ def test_amp_symbols_declared_and_bound(so):
         assert len(L.SIGNATURES[name][1]) == decl[name], name
         assert hasattr(ctypes.CDLL(so), name)
         assert name not in L._NO_LAUNCH            # every one of them launches, so each is timed by LAUNCH_LOG
-    assert L.ABI_VERSION == 8 and L.lib().dsr_abi_version() == 8
+    assert L.ABI_VERSION == 9 and L.lib().dsr_abi_version() == 9
 
 
 def test_amp_entry_points_reject_bad_arguments(so):

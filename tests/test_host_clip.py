@@ -38,7 +38,7 @@ def test_clip_symbols_declared_and_bound(so):
         assert len(L.SIGNATURES[name][1]) == decl[name], name
         assert hasattr(ctypes.CDLL(so), name)
         assert (name in L._NO_LAUNCH) == (name in QUERIES), name
-    assert L.ABI_VERSION == 8 and L.lib().dsr_abi_version() == 8
+    assert L.ABI_VERSION == 9 and L.lib().dsr_abi_version() == 9
 
 
 def test_constructor_validation():

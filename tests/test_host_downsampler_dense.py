@@ -159,4 +159,4 @@ def test_bad_arguments_return_codes_not_crashes(lib):
     with pytest.raises(RuntimeError):
         L.check(lib.dsr_downsample_dense_wgrad(one, one, one, one, one, 0, *shape, st))
     assert "dsr_downsample_dense_wgrad_workspace" in L._NO_LAUNCH
-    assert L.lib().dsr_abi_version() == L.ABI_VERSION == 8
+    assert L.lib().dsr_abi_version() == L.ABI_VERSION == 9

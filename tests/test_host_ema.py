@@ -36,7 +36,7 @@ def test_ema_symbols_declared_and_bound(so):
         assert decl.get(name) == nargs and len(L.SIGNATURES[name][1]) == nargs, name
         assert hasattr(ctypes.CDLL(so), name)
         assert name not in L._NO_LAUNCH
-    assert L.ABI_VERSION == 8 and L.lib().dsr_abi_version() == 8
+    assert L.ABI_VERSION == 9 and L.lib().dsr_abi_version() == 9
 
 
 # ----------------------------------------------------------------------------- 1: the yardstick is torch's AveragedModel

@@ -226,7 +226,7 @@ def test_symbols_declared_bound_and_exported(so):
         assert decl.get(name) == nargs and len(L.SIGNATURES[name][1]) == nargs, name
         assert hasattr(ctypes.CDLL(so), name)
         assert (name in L._NO_LAUNCH) == (name == "dsr_jpeg_workspace"), name
-    assert L.ABI_VERSION == 8 and L.lib().dsr_abi_version() == 8
+    assert L.ABI_VERSION == 9 and L.lib().dsr_abi_version() == 9
     assert "jpeg.hip" in P("_build").SOURCES
     header = open(os.path.join(ROOT, "include", "dsr_hip.h")).read()
     for word in ("jfdctint", "jidctint", "25172", "F(.33126)", "F(1.772)", "ceil(H/2) - 1"):                # the definition is there

@@ -143,7 +143,7 @@ def test_lbfgs_symbols_declared_and_bound(so):
         assert len(L.SIGNATURES[name][1]) == decl[name], name
         assert hasattr(ctypes.CDLL(so), name)
     assert {"dsr_lbfgs_workspace", "dsr_lbfgs_vector_floats"} <= set(L._NO_LAUNCH)
-    assert L.ABI_VERSION == 8
+    assert L.ABI_VERSION == 9
 
 
 def test_lbfgs_entry_points_reject_bad_arguments(so):

@@ -32,21 +32,20 @@ def test_tile_sums_fold_back_to_the_per_image_means():
         a, b = R.fwd_case(shape)
         n, c, h, w = shape
         count = c * (h - 10) * (w - 10)
-        for th, tw in ((R.SF_TH, R.SF_TW), (R.SSIM_TH, R.SSIM_TW)):
-            ref = R.fwd_reference(shape, th, tw) if (th, tw) == (R.SF_TH, R.SF_TW) else None
-            sim, cs = R.fwd_maps(a, b)
-            s, cnt = R.tile_sums(sim, th, tw)
-            q, _ = R.tile_sums(cs, th, tw)
-            nblk = R.blocks_per_image(shape, th, tw)
-            assert s.numel() == n * nblk and int(cnt.view(n, nblk).sum(1)[0]) == count and int(cnt.min()) >= 1
-            assert float((s.view(n, nblk).sum(1) / count - ssim_ref.ssim_per_image(a, b)).abs().max()) <= 1e-12
-            if min(h, w) >= 22:                               # two scales fit: row 0 is the cs mean of scale 0
-                raw = msssim_ref.raw_scales(a, b, 2)
-                assert float((q.view(n, nblk).sum(1) / count - raw[0]).abs().max()) <= 1e-12
-            assert float((q.view(n, nblk).sum(1) / count - cs.mean(dim=(1, 2, 3))).abs().max()) <= 1e-12
-            assert float((s.view(n, nblk).sum(1) / count - msssim_ref.raw_scales(a, b, 1)[0]).abs().max()) <= 1e-12
-            if ref is not None:
-                assert torch.equal(ref["sim"], s) and torch.equal(ref["cnt"], cnt)
+        th, tw = R.SF_TH, R.SF_TW
+        ref = R.fwd_reference(shape, th, tw)
+        sim, cs = R.fwd_maps(a, b)
+        s, cnt = R.tile_sums(sim, th, tw)
+        q, _ = R.tile_sums(cs, th, tw)
+        nblk = R.blocks_per_image(shape, th, tw)
+        assert s.numel() == n * nblk and int(cnt.view(n, nblk).sum(1)[0]) == count and int(cnt.min()) >= 1
+        assert float((s.view(n, nblk).sum(1) / count - ssim_ref.ssim_per_image(a, b)).abs().max()) <= 1e-12
+        if min(h, w) >= 22:                               # two scales fit: row 0 is the cs mean of scale 0
+            raw = msssim_ref.raw_scales(a, b, 2)
+            assert float((q.view(n, nblk).sum(1) / count - raw[0]).abs().max()) <= 1e-12
+        assert float((q.view(n, nblk).sum(1) / count - cs.mean(dim=(1, 2, 3))).abs().max()) <= 1e-12
+        assert float((s.view(n, nblk).sum(1) / count - msssim_ref.raw_scales(a, b, 1)[0]).abs().max()) <= 1e-12
+        assert torch.equal(ref["sim"], s) and torch.equal(ref["cnt"], cnt)
     # the block order: plane-major, then tile row, then tile column
     m = torch.arange(2 * 17 * 65, dtype=F64).view(1, 2, 17, 65)
     s, cnt = R.tile_sums(m, 16, 64)
@@ -165,7 +164,7 @@ def test_identical_windows_give_exactly_one_in_float32():
     sab = (ma * mb + rng.uniform(-0.05, 0.05, 20000).astype(f)).astype(f)
     for u, v in zip(both(ma, mb, saa, sbb, sab), both(mb, ma, sbb, saa, sab)):
         assert np.array_equal(u.view(np.uint32), v.view(np.uint32))
-    assert R.SF_TH * R.SF_TW <= 2 ** 24 and R.SSIM_TH * R.SSIM_TW <= 2 ** 24
+    assert R.SF_TH * R.SF_TW <= 2 ** 24
 
 
 def test_psnr_cases_are_exact():
@@ -217,8 +216,8 @@ def test_pool_and_accumulate_cases_are_exact():
 # ----------------------------------------------------------------------------- the tables reach every branch
 def test_case_tables_reach_every_branch():
     src = _flat_src()
-    for line in (f"#defineSSIM_K{R.SSIM_K}", f"#defineSF_TW{R.SF_TW}", f"#defineSF_TH{R.SF_TH}", f"#defineSSIM_TW{R.SSIM_TW}",
-                 f"#defineSSIM_TH{R.SSIM_TH}", f"#defineSB_T{R.SB_T}", f"#definePSNR_CHUNK{R.PSNR_CHUNK}",
+    for line in (f"#defineSSIM_K{R.SSIM_K}", f"#defineSF_TW{R.SF_TW}", f"#defineSF_TH{R.SF_TH}",
+                 f"#defineSB_T{R.SB_T}", f"#definePSNR_CHUNK{R.PSNR_CHUNK}",
                  "constintnm=(want_a&&want_b)?4:3;",
                  "constboolv4=E%4==0&&((uintptr_t)preds&15)==0&&((uintptr_t)target&15)==0;",
                  "constboolv4=W%4==0&&(((uintptr_t)in1|(uintptr_t)in2)&15)==0&&(((uintptr_t)out1|(uintptr_t)out2)&7)==0;"):
@@ -228,16 +227,16 @@ def test_case_tables_reach_every_branch():
     assert src.count(f"for(intk=lane;k<nblk;k+={R.FIN_LANES})") == 2 and src.count(f"for(intk=lane;k<B;k+={R.FIN_LANES})") == 1
     assert f"for(intn=threadIdx.x;n<N;n+={R.COMBINE_THREADS})" in src and f"for(intn=threadIdx.x;n<N;n+={R.ACC_LANES})" in src
     # forward tiles: 1 position, 1 column, 1 row, full; blocks per image on both sides of the lane stride; N of the wave stride
-    for shapes, th, tw in ((R.FWD_SHAPES, R.SF_TH, R.SF_TW), (R.OLD_SHAPES, R.SSIM_TH, R.SSIM_TW)):
-        kinds = set()
-        for shape in shapes:
-            _, _, h, w = shape
-            oh, ow = h - 10, w - 10
-            ty, tx = R.tile_grid(oh, ow, th, tw)
-            for iy in range(ty):
-                for ix in range(tx):
-                    kinds.add((min(th, oh - iy * th), min(tw, ow - ix * tw)))
-        assert {(1, 1), (th, 1), (1, tw), (th, tw)} <= kinds, kinds
+    shapes, th, tw = R.FWD_SHAPES, R.SF_TH, R.SF_TW
+    kinds = set()
+    for shape in shapes:
+        _, _, h, w = shape
+        oh, ow = h - 10, w - 10
+        ty, tx = R.tile_grid(oh, ow, th, tw)
+        for iy in range(ty):
+            for ix in range(tx):
+                kinds.add((min(th, oh - iy * th), min(tw, ow - ix * tw)))
+    assert {(1, 1), (th, 1), (1, tw), (th, tw)} <= kinds, kinds
     nblk = {R.blocks_per_image(s, R.SF_TH, R.SF_TW) for s in R.FWD_SHAPES}
     assert min(nblk) == 1 and max(nblk) > R.FIN_LANES and any(1 < b <= R.FIN_LANES for b in nblk)
     ns = {s[0] for s in R.FWD_SHAPES}
@@ -288,17 +287,17 @@ def test_case_tables_reach_every_branch():
 
 # ----------------------------------------------------------------------------- the floors of the measured bars
 def test_forward_floors():
-    """F(n) of both tile sizes, printed; the bar is 4 x max(F(n), 1e-6 n).  A wrong mask (one position more or less in a tile)
+    """F(n) of the forward tile, printed; the bar is 4 x max(F(n), 1e-6 n).  A wrong mask (one position more or less in a tile)
     moves a sum by about one SSIM value, 0.1 .. 1: far above every bar of a tile that can hold such an error."""
-    for th, tw, shapes in ((R.SF_TH, R.SF_TW, R.FWD_SHAPES), (R.SSIM_TH, R.SSIM_TW, R.OLD_SHAPES)):
-        fl = R.fwd_floor(th, tw)
-        print(f"\nforward floors, tile {th} x {tw}: " + ", ".join(f"F({n}) = {f:.3e} ({f / n:.2e}/pos)" for n, f in sorted(fl.items())))
-        for n, f in fl.items():
-            assert 0.0 <= f <= 2e-5 * n, (n, f)
-            assert float(R.fwd_bar(np.array([n]), th, tw)[0]) <= 0.1
-        assert {1, th, tw, th * tw} <= set(fl)
-        for shape in shapes:
-            assert set(R.tile_counts(shape, th, tw).tolist()) <= set(fl)
+    th, tw, shapes = R.SF_TH, R.SF_TW, R.FWD_SHAPES
+    fl = R.fwd_floor(th, tw)
+    print(f"\nforward floors, tile {th} x {tw}: " + ", ".join(f"F({n}) = {f:.3e} ({f / n:.2e}/pos)" for n, f in sorted(fl.items())))
+    for n, f in fl.items():
+        assert 0.0 <= f <= 2e-5 * n, (n, f)
+        assert float(R.fwd_bar(np.array([n]), th, tw)[0]) <= 0.1
+    assert {1, th, tw, th * tw} <= set(fl)
+    for shape in shapes:
+        assert set(R.tile_counts(shape, th, tw).tolist()) <= set(fl)
 
 
 def test_backward_floors():

@@ -230,7 +230,7 @@ def test_bad_arguments_return_codes():
     assert lib.dsr_gan_loss(p, 4, 0, 1, 0, None, p + 64, p + 128, None) == E_ARG
     assert lib.dsr_gan_loss(p, 4, 0, 1, 0, p, None, p + 128, None) == E_ARG
     assert lib.dsr_gan_loss(p, 4, 0, 1, 0, p, p + 64, None, None) == E_ARG
-    assert lib.dsr_abi_version() == L.ABI_VERSION == 8
+    assert lib.dsr_abi_version() == L.ABI_VERSION == 9
 
 
 def test_spectral_norm_wide_and_full_table_cases():

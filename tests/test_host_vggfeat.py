@@ -171,7 +171,7 @@ def test_perceptual_loss_takes_a_supplied_content_module():
 # ----------------------------------------------------------------------------- the C entries refuse bad arguments on the host
 def test_abi_version_and_loss_codes(so):
     L = P("_lib")
-    assert L.ABI_VERSION == 8 and L.lib().dsr_abi_version() == 8
+    assert L.ABI_VERSION == 9 and L.lib().dsr_abi_version() == 9
     assert (L.FEAT_L1, L.FEAT_MSE) == (0, 1)
 
 

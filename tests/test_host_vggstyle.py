@@ -117,9 +117,9 @@ def test_new_surface_imports_without_a_gpu():
 
 
 # ----------------------------------------------------------------------------- 14. the C entries refuse bad arguments on the host
-def test_abi_version_is_still_8(so):
+def test_abi_version_and_gram_symbols(so):
     L = P("_lib")
-    assert L.ABI_VERSION == 8 and L.lib().dsr_abi_version() == 8
+    assert L.ABI_VERSION == 9 and L.lib().dsr_abi_version() == 9
     for name in ("dsr_gram_chunks", "dsr_gram_workspace", "dsr_gram_fwd", "dsr_gram_loss", "dsr_featstyle_tap_bwd"):
         assert name in L.SIGNATURES
     assert "dsr_gram_chunks" in L._NO_LAUNCH and "dsr_gram_workspace" in L._NO_LAUNCH

@@ -1,14 +1,13 @@
 """Device-event time per call of the metric kernels (csrc/metrics.hip) at [32,3,512,512] fp32 (the train_GAN.py:110-111 logging
 batch) and [1,3,2048,2048]:
-  ssim_old     the parent's SSIM path: dsr_ssim_f32 + its two dsr_pw_sum_rows (what evaluate.ssim launches)
-  ssim_img     dsr_ssim_img_f32: per-image SSIM (tile launch + one-block fold)
+  ssim_img     dsr_ssim_img_f32: per-image SSIM (tile launch + one-block fold; what the SSIM modules and evaluate.ssim launch)
   ssim_bwd1    dsr_ssim_bwd_f32 writing the gradient of img1 only
   ssim_bwd2    dsr_ssim_bwd_f32 writing both gradients
   psnr         dsr_psnr_stats_f32 + dsr_psnr_finalize (whole batch, inferred range, running state)
 
     python tools/microbench_metrics.py [--repeats 30] [--warmup 5]
 
-Every shape is warmed up first; the timed repeats then run the five calls in turn (old and new alternate within one run),
+Every shape is warmed up first; the timed repeats then run the four calls in turn,
 each between its own pair of HIP events with a synchronise after it.  Reported per call: median, min and max over the repeats;
 the FLOPs and bytes of the formulas below over the median time; and the share of the larger of the two lower bounds
 (FLOPs / FP32 vector peak, bytes / HBM peak: MI355X_MICROARCH.md, 157.3 TFLOP/s and 8.0 TB/s), which names what bounds the
@@ -34,12 +33,6 @@ K = 11
 TAP = 3 + 5 * 2               # per window tap of a moment pass: the products a^2, b^2, ab, then 5 FMAs
 SSIM_FORMULA = 20             # the SSIM of one position from its 5 moments
 COEF = 30                     # the four coefficient maps of one position
-
-
-def flops_ssim_old(n, c, h, w):
-    """121 taps x (products + 5 FMAs) per window position, 11 x 5 column FMAs, the formula."""
-    pos = n * c * (h - 10) * (w - 10)
-    return pos * (K * K * TAP + K * 5 * 2 + SSIM_FORMULA)
 
 
 def flops_ssim_img(n, c, h, w):
@@ -81,13 +74,6 @@ def main():
         a = torch.rand(shape, generator=g).to(dev)
         b = (a + 0.1 * torch.randn(shape, generator=g).to(dev)).clamp(0, 1)
         c1, c2 = 1e-4, 9e-4
-        # the parent's path (evaluate.ssim without its host read)
-        ob = lib.dsr_ssim_blocks(n * c, h, w)
-        rows = (ob + 63) // 64
-        opart = torch.zeros(rows * 64, dtype=torch.float32, device=dev)
-        ocols = torch.empty(64, dtype=torch.float32, device=dev)
-        otot = torch.empty(1, dtype=torch.float32, device=dev)
-        # the new entry points
         nb = lib.dsr_ssim_img_blocks(n, c, h, w)
         npart = torch.empty(nb, dtype=torch.float32, device=dev)
         per = torch.empty(n, dtype=torch.float32, device=dev)
@@ -100,11 +86,6 @@ def main():
         keys = torch.empty(2 * pb, dtype=torch.int32, device=dev)
         state = torch.zeros(4, dtype=torch.float64, device=dev)
         pval = torch.empty(1, dtype=torch.float32, device=dev)
-
-        def ssim_old():
-            L.check(lib.dsr_ssim_f32(P(a), P(b), n * c, h, w, 1.0, P(opart), st))
-            L.check(lib.dsr_pw_sum_rows(P(opart), rows, 64, 0, 64, 1.0, P(ocols), 0, 1, st))
-            L.check(lib.dsr_pw_sum_rows(P(ocols), 64, 1, 0, 1, 1.0 / (n * c * (h - 10) * (w - 10)), P(otot), 0, 0, st))
 
         def ssim_img():
             L.check(lib.dsr_ssim_img_f32(P(a), P(b), n, c, h, w, c1, c2, P(npart), P(per), P(tot), 1.0 / n, 0, st))
@@ -119,9 +100,8 @@ def main():
             L.check(lib.dsr_psnr_stats_f32(P(b), P(a), n, e, P(sse), P(keys), st))
             L.check(lib.dsr_psnr_finalize(P(sse), P(keys), n, e, 1, 1.0, 10 / math.log(10), None, P(pval), 1.0, P(state), st))
 
-        calls = {"ssim_old": ssim_old, "ssim_img": ssim_img, "ssim_bwd1": ssim_bwd1, "ssim_bwd2": ssim_bwd2, "psnr": psnr}
-        work = {"ssim_old": (flops_ssim_old(*shape), bytes_io(*shape, 2, 0)),
-                "ssim_img": (flops_ssim_img(*shape), bytes_io(*shape, 2, 0)),
+        calls = {"ssim_img": ssim_img, "ssim_bwd1": ssim_bwd1, "ssim_bwd2": ssim_bwd2, "psnr": psnr}
+        work = {"ssim_img": (flops_ssim_img(*shape), bytes_io(*shape, 2, 0)),
                 "ssim_bwd1": (flops_ssim_bwd(*shape, 3), bytes_io(*shape, 2, 1)),
                 "ssim_bwd2": (flops_ssim_bwd(*shape, 4), bytes_io(*shape, 2, 2)),
                 "psnr": (3 * n * e, bytes_io(*shape, 2, 0))}
@@ -138,7 +118,6 @@ def main():
                 e1.record()
                 torch.cuda.synchronize()
                 times[k].append(e0.elapsed_time(e1))
-        old_mean, new_mean = float(otot), float(tot)
         for k, ts in times.items():
             med = statistics.median(ts)
             fl, by = work[k]
@@ -148,13 +127,6 @@ def main():
                               "tflops": round(fl / med / 1e9, 2), "tbs": round(by / med / 1e9, 3),
                               "bound": "fp32" if t_f >= t_b else "hbm",
                               "share_of_bound": round(max(t_f, t_b) * 1e3 / med, 3)}), flush=True)
-        old = times["ssim_old"]
-        spread = max(old) - min(old)
-        print(json.dumps({"shape": list(shape), "ssim_old_mean": old_mean, "ssim_img_mean": new_mean,
-                          "ssim_img_median_ms": round(statistics.median(times["ssim_img"]), 4),
-                          "ssim_old_median_ms": round(statistics.median(old), 4), "ssim_old_spread_ms": round(spread, 4),
-                          "ssim_img_no_slower": statistics.median(times["ssim_img"]) <= statistics.median(old) + spread}),
-              flush=True)
 
 
 if __name__ == "__main__":
