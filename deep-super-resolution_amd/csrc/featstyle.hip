@@ -13,6 +13,10 @@
 //              (G - Gt) / max|G - Gt| for MSE with that divisor in s_scale[n] (1 for L1, 1 for an all-zero difference).  Its
 //              entries are of order one whatever the normalisation, so fp16 can neither overflow nor underflow; every scalar
 //              factor stays in fp32 and enters in the backward's epilogue.  A one-block launch folds the sums into the mean.
+//              A NaN or an Inf in G - Gt (an overflow upstream) is not hidden from a loss scaler that reads gradients: it makes
+//              the value non-finite, it leaves a non-finite entry in s16 in BOTH modes (L1 stores it as it is, never as the
+//              sign of an Inf), and for MSE it is the image's s_scale, so tap_bwd writes non-finite values into df of that
+//              image and of no other.
 //   tap_bwd  : df = (dnext ? dnext * m : 0) + g_content * coef_content * d + g_style * coef_style * s_scale[n] * (f[n] . s16[n])
 //              a per-image [HW x Cp] . [Cp x Cp] GEMM (f read row-wise, s16 through the transposing read) with the pointwise
 //              terms of featloss_tap_bwd in its epilogue: one launch, one rounding per element, and no 16-bit image of the
@@ -191,7 +195,8 @@ __global__ __launch_bounds__(256) void gram_loss_operand_kernel(const float* __r
     float v = 0.f;
     if (i < C && j < C) {
       const float d = (float)((double)x[i * C + j] - (double)y[i * C + j]);
-      v = mode == DSR_FEAT_L1 ? (d > 0.f ? 1.f : (d < 0.f ? -1.f : d)) : (zero ? 0.f : d / div);
+      // L1: the sign, but a non-finite d as it is -- sign(Inf) = 1 would hand a finite gradient on after an overflow upstream
+      v = mode == DSR_FEAT_L1 ? ((d > 0.f && d <= __FLT_MAX__) ? 1.f : ((d < 0.f && d >= -__FLT_MAX__) ? -1.f : d)) : (zero ? 0.f : d / div);
     }
     out[e] = f2h<DT>(v);
   }

@@ -744,7 +744,10 @@ int dsr_featloss_combine_bwd(int n, const float* weights, const float* g, float*
  *   N <= 65535).  It also writes the operand of the
  *   backward GEMM, s16[N][Cp][Cp] in the map's dtype (pad rows and columns zero): sign(G - Gt) with sign(0) = 0 for L1 and
  *   s_scale[n] = 1; (G - Gt) / s_scale[n] with s_scale[n] = max |G - Gt| of image n for MSE (an all-zero difference gives
- *   s16 = 0, s_scale[n] = 1).  The entries are of order one, so fp16 neither overflows nor underflows.
+ *   s16 = 0, s_scale[n] = 1).  The entries are of order one, so fp16 neither overflows nor underflows.  A NaN or an Inf in
+ *   G - Gt makes value[0] non-finite, leaves a non-finite entry in s16 in both modes (L1 stores it as it is and does not take
+ *   the sign of an Inf) and, for MSE, is s_scale[n]: dsr_featstyle_tap_bwd then writes non-finite values into df of image n,
+ *   and of image n alone.
  * dsr_featstyle_tap_bwd: one launch and one rounding per element,
  *     df[n][p][c] = (dnext ? dnext * m : 0) + g_content[0] * coef_content * d
  *                   + g_style[0] * coef_style * s_scale[n] * sum_i f[n][p][i] * s16[n][i][c],
