@@ -45,6 +45,29 @@ def load_model(model, model_path):
     return model
 
 
+def interpolate_state_dicts(sd_a, sd_b, alpha):
+    """ESRGAN's network interpolation (net_interp.py): a state dict between the PSNR-trained generator `sd_a` and the
+    GAN-trained one `sd_b`.  Every floating tensor becomes (1 - alpha) * a + alpha * b, computed in fp32 and cast back to a's
+    dtype; every other entry (an integer buffer such as a batch counter) is taken from `sd_b`.  The two dicts must hold the
+    same keys with the same shapes: anything else is a ValueError that names the key.  Plain torch on whatever device the
+    tensors live on; the result loads into a fresh RRDBNet / Generator."""
+    alpha = float(alpha)
+    only = [k for k in sd_a if k not in sd_b] + [k for k in sd_b if k not in sd_a]
+    if only:
+        raise ValueError(f"interpolate_state_dicts: key {only[0]!r} is in one state dict only ({len(only)} such keys)")
+    out = OrderedDict()
+    for k, a in sd_a.items():
+        b = sd_b[k]
+        if tuple(a.shape) != tuple(b.shape):
+            raise ValueError(f"interpolate_state_dicts: {k!r} has shape {tuple(a.shape)} in one state dict and {tuple(b.shape)} "
+                             "in the other")
+        if a.is_floating_point() and b.is_floating_point():
+            out[k] = (a.detach().float() * (1.0 - alpha) + b.detach().float() * alpha).to(a.dtype)
+        else:
+            out[k] = b.detach().clone()
+    return out
+
+
 def psnr(pred, target, data_range=None):
     """Host float: 10*log10(range^2 / MSE(pred, target)) for fp32 NCHW device tensors.
     ``data_range=None`` follows what torchmetrics' ``PeakSignalNoiseRatio()`` (eval_GAN.py:30,47: the metric is CALLED per

@@ -1088,6 +1088,46 @@ def gan_loss(logits, target_is_real, kind="vanilla", is_disc=False):
     return GanLoss.apply(logits, target_is_real, _GAN_KINDS[kind], is_disc)
 
 
+class RelGanLoss(torch.autograd.Function):
+    """The relativistic average GAN term of ESRGAN (dsr_rel_gan_loss): gan_loss(pred - mean(other)), with the mean, the loss and
+    both gradients formed by fixed-order sums on the device.  A gradient is written only for the operand that requires one:
+    grad_pred in the element pass, grad_other (one value for all its elements) by a broadcast store."""
+
+    @staticmethod
+    def forward(ctx, pred, other, target_is_real, kind, is_disc):
+        _need_gpu(pred)
+        _need_gpu(other)
+        x = pred.contiguous().float()
+        o = other.contiguous().float()
+        n, m = x.numel(), o.numel()
+        if n == 0 or m == 0:
+            raise ValueError("relativistic_gan_loss: empty logits")
+        lib = _lib.lib()
+        ws = torch.empty(lib.dsr_rel_gan_loss_workspace(n, m) // 8, dtype=torch.float64, device=x.device)
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        go = torch.empty_like(o) if ctx.needs_input_grad[1] else None
+        loss = torch.empty(1, dtype=torch.float32, device=x.device)
+        check(lib.dsr_rel_gan_loss(_ptr(x), n, _ptr(o), m, kind, int(bool(target_is_real)), int(bool(is_disc)), _ptr(gx),
+                                   _ptr(go), _ptr(ws), _ptr(loss), _stream()))
+        ctx.save_for_backward(gx, go)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        gx, go = ctx.saved_tensors
+        return (axpby(gx, None, 1.0, 0.0, g) if gx is not None else None,
+                axpby(go, None, 1.0, 0.0, g) if go is not None else None, None, None, None)
+
+
+def relativistic_gan_loss(pred, other, target_is_real, kind="vanilla", is_disc=False):
+    """BasicSR's GANLoss(gan_type=kind)(pred - mean(other), target_is_real, is_disc), unweighted: the relativistic average
+    form of ESRGAN.  `pred` and `other` are logits of any shapes (their sizes are independent); the gradient goes to whichever
+    of them requires one.  Returns an fp32 scalar on the device."""
+    if kind not in _GAN_KINDS:
+        raise ValueError(f"relativistic_gan_loss: kind must be one of {sorted(_GAN_KINDS)}, got {kind!r}")
+    return RelGanLoss.apply(pred, other, target_is_real, _GAN_KINDS[kind], is_disc)
+
+
 # ----------------------------------------------------------------------------- spectral normalisation
 SN_EPS = 1e-12           # torch.nn.utils.spectral_norm's default
 _sn_pending = {}         # id(weight_orig) -> results of a group launch that SpectralNormWeight.forward picks up

@@ -6,7 +6,8 @@ gen_msssim_step : the same step with the structural loss alpha * (1 - MS-SSIM(fa
 gen_perceptual_step : the same step with the content loss l1_weight * L1 + VggFeatureLoss(fake, hr) (ESRGAN / Real-ESRGAN).
 gan_step    : train_GAN.py:38-71 (do_epoch): D step, then G step with the detached adversarial term.
 realesrgan_step : the GAN stage of Real-ESRGAN (L1 + VGG features + a logits GAN loss whose gradient flows through D into G).
-dip_step    : DIP.py:47-95 closure + utils/DIP.py:33-40 Adam iteration.
+esrgan_step : the GAN stage of ESRGAN (the same terms under the relativistic average discriminator, five D forwards).
+dip_step   : DIP.py:47-95 closure + utils/DIP.py:33-40 Adam iteration.
 """
 import os
 
@@ -266,6 +267,79 @@ def realesrgan_step(gen, disc, vggfeat, opt_g, opt_d, lq, gt, *, l1_weight=1.0, 
         for p, r in zip(d_params, was):
             p.requires_grad_(r)
     return l_pix.detach(), l_percep.detach(), l_g_gan.detach(), l_d_real.detach(), l_d_fake.detach(), fake.detach()
+
+
+def esrgan_step(gen, disc, vggfeat, opt_g, opt_d, lq, gt, *, l1_weight=1e-2, gan_weight=5e-3, gan_type="vanilla", ema=None):
+    """One GAN-stage step of the ESRGAN recipe (BasicSR ESRGANModel.optimize_parameters): realesrgan_step with the relativistic
+    average discriminator.  Each logit is judged against the batch mean of the opposite class, rel(x, other, label) =
+    F.relativistic_gan_loss, so D's gradient depends on both of its passes and G's adversarial gradient on the ground truth.
+
+    Generator half, D frozen:
+        real_pred = disc(gt) (no gradient);  fake_pred = disc(fake)
+        l_g_gan = (rel(real_pred, fake_pred, fake) + rel(fake_pred, real_pred, real)) / 2
+        l_g = l1_weight * L1(fake, gt) + vggfeat(fake, gt) + gan_weight * l_g_gan          (vggfeat=None: no content term)
+    Discriminator half, in the published order:
+        fake_pred = disc(fake.detach()) (no gradient);  real_pred = disc(gt)
+        l_d_real = rel(real_pred, fake_pred, real, is_disc) / 2, backward
+        fake_pred = disc(fake.detach());  l_d_fake = rel(fake_pred, real_pred.detach(), fake, is_disc) / 2, backward
+    then opt_d.step().  These are five forwards of D: in train mode one step advances every u and v of a spectral-norm D by
+    five power iterations, as the published loop does.
+
+    `disc`: any module of fp32 NCHW in, logits (of any shape) out; it is left in the mode it came in.  Returns (l_pix,
+    l_percep, l_g_gan, l_d_real, l_d_fake, fake) as detached device tensors: the unweighted L1, the (weighted) content term
+    (a zero scalar without vggfeat), the generator's GAN term and D's two terms with their 1/2 inside, as BasicSR logs them.
+    One stream, no host read: usable inside GraphedStep with a FusedAdam for each optimiser."""
+    rel = F.relativistic_gan_loss
+    d_params = [p for p in disc.parameters()]
+    was = [p.requires_grad for p in d_params]
+    # --- generator
+    for p in d_params:
+        p.requires_grad_(False)
+    try:
+        opt_g.zero_grad()
+        fake = gen(lq)
+        l_pix = F.l1_loss(fake, gt)
+        l_g = F.scale_loss(l_pix, float(l1_weight))
+        if vggfeat is not None:
+            l_percep = vggfeat(fake, gt)
+            l_g = F.add_losses(l_g, l_percep)
+        else:
+            l_percep = torch.zeros((), dtype=torch.float32, device=fake.device)
+        with torch.no_grad():
+            real_pred = disc(gt)
+        fake_pred = disc(fake)
+        l_g_gan = F.scale_loss(F.add_losses(rel(real_pred, fake_pred, False, gan_type, is_disc=False),
+                                            rel(fake_pred, real_pred, True, gan_type, is_disc=False)), 0.5)
+        l_g = F.add_losses(l_g, F.scale_loss(l_g_gan, float(gan_weight)))
+        with F.batched_wgrad():
+            l_g.backward()
+        opt_g.step()
+        if ema is not None:
+            ema.update()
+    finally:
+        for p, r in zip(d_params, was):
+            p.requires_grad_(r)
+    # --- discriminator
+    for p in d_params:
+        p.requires_grad_(True)
+    try:
+        opt_d.zero_grad()
+        fake_det = fake.detach()
+        with torch.no_grad():
+            fake_pred = disc(fake_det)
+        real_pred = disc(gt)
+        l_d_real = F.scale_loss(rel(real_pred, fake_pred, True, gan_type, is_disc=True), 0.5)
+        with F.batched_wgrad():
+            l_d_real.backward()
+        fake_pred = disc(fake_det)
+        l_d_fake = F.scale_loss(rel(fake_pred, real_pred.detach(), False, gan_type, is_disc=True), 0.5)
+        with F.batched_wgrad():
+            l_d_fake.backward()
+        opt_d.step()
+    finally:
+        for p, r in zip(d_params, was):
+            p.requires_grad_(r)
+    return l_pix.detach(), l_percep.detach(), l_g_gan.detach(), l_d_real.detach(), l_d_fake.detach(), fake_det
 
 
 class GraphedStep:

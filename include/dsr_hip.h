@@ -926,6 +926,24 @@ int dsr_gan_loss_blocks(size_t n);
 int dsr_gan_loss(const float* x, size_t n, int kind, int target_is_real, int is_disc, float* grad, double* partial, float* loss,
                  dsr_stream_t s);
 
+/* ------------------------------------------------------------------ relativistic average GAN loss on logits (ragan.hip)
+ * ESRGAN's RaGAN term (BasicSR ESRGANModel.optimize_parameters): each of the n fp32 logits x is judged against the mean of
+ * the m fp32 logits of the opposite class.  n and m are independent.
+ *   rel(x[n], other[m], kind, target_is_real, is_disc)
+ *     mu    = (sum_j other[j]) / m        added in double in a fixed order, rounded to fp32 ONCE
+ *     z_i   = x_i - mu                    one fp32 subtraction
+ *     loss  = (sum_i l(z_i)) / n          l = the per-element term of dsr_gan_loss for (kind, target_is_real, is_disc),
+ *                                         evaluated in fp32 exactly as there, added in double, one rounding
+ *     grad_x[i]     = l'(z_i) / n                          (optional output: null = not written)
+ *     grad_other[j] = -(sum_i l'(z_i)) / (n m)   for all j (optional output; the sum in double, one rounding)
+ * Every sum is thread-strided, then folded over the wave, the block and the blocks in block order: no atomics, no host
+ * read, the same input gives the same bits.  Three launches, with or without the gradients, all on `s`.  ws: DEVICE scratch, 8-byte
+ * aligned, of dsr_rel_gan_loss_workspace(n, m) bytes (0 for n == 0 or m == 0).  A null x / other / ws / loss, n == 0 or
+ * m == 0, an unknown kind, a tensor off its 4-byte or ws off its 8-byte alignment return DSR_E_ARG before any launch. */
+size_t dsr_rel_gan_loss_workspace(size_t n, size_t m);
+int dsr_rel_gan_loss(const float* x, size_t n, const float* other, size_t m, int kind, int target_is_real, int is_disc,
+                     float* grad_x, float* grad_other, void* ws, float* loss, dsr_stream_t s);
+
 /* ------------------------------------------------------------------ second-order Real-ESRGAN degradation
  * fp32 [B][C][H][W] batches in [0, 1] scaling; every call only enqueues on `s` (no allocation, no sync, no host read).
  *
