@@ -68,6 +68,62 @@ def interpolate_state_dicts(sd_a, sd_b, alpha):
     return out
 
 
+def vgg_discriminator_layout(num_in_ch=3, num_feat=64, input_size=128):
+    """[(key, shape)] of the state dict of BasicSR's ``VGGStyleDiscriminator(num_in_ch, num_feat, input_size)``, in torch's
+    order: the ``net_d`` checkpoints that go with the ESRGAN generators.  conv0_0 (3x3, bias), then per stage conv{s}_1 / bn{s}_1
+    (4x4 stride 2) behind conv{s}_0 / bn{s}_0 (3x3), no conv bias, widths nf | 2nf | 4nf | 8nf | 8nf (| 8nf for input_size
+    256), linear1 (8nf * 4 * 4 -> 100), linear2 (100 -> 1).  The module itself is not in this package yet; this is its
+    checkpoint surface, written from the published definition (parity with BasicSR unpinned; tests/test_host_vggd.py holds
+    it to a copy built from torch.nn layers)."""
+    if input_size not in (128, 256):
+        raise ValueError(f"vgg_discriminator_layout: input_size must be 128 or 256, got {input_size}")
+    nf = int(num_feat)
+    if nf < 1 or int(num_in_ch) < 1:
+        raise ValueError(f"vgg_discriminator_layout: num_in_ch and num_feat must be positive, got {num_in_ch}, {num_feat}")
+    out = [("conv0_0.weight", (nf, int(num_in_ch), 3, 3)), ("conv0_0.bias", (nf,))]
+
+    def block(conv, bn, cout, cin, k):
+        return [(conv + ".weight", (cout, cin, k, k)), (bn + ".weight", (cout,)), (bn + ".bias", (cout,)),
+                (bn + ".running_mean", (cout,)), (bn + ".running_var", (cout,)), (bn + ".num_batches_tracked", ())]
+
+    out += block("conv0_1", "bn0_1", nf, nf, 4)
+    widths = [(nf, 2 * nf), (2 * nf, 4 * nf), (4 * nf, 8 * nf), (8 * nf, 8 * nf)] + ([(8 * nf, 8 * nf)] if input_size == 256 else [])
+    for s, (cin, cout) in enumerate(widths, start=1):
+        out += block(f"conv{s}_0", f"bn{s}_0", cout, cin, 3) + block(f"conv{s}_1", f"bn{s}_1", cout, cout, 4)
+    return out + [("linear1.weight", (100, 8 * nf * 16)), ("linear1.bias", (100,)), ("linear2.weight", (1, 100)),
+                  ("linear2.bias", (1,))]
+
+
+def inspect_vgg_discriminator(state):
+    """{'num_in_ch', 'num_feat', 'input_size', 'parameters'} of a ``VGGStyleDiscriminator`` state dict, read off conv0_0's
+    shape and the presence of stage 5, after checking every key and shape against vgg_discriminator_layout.  `state` may carry
+    BasicSR's ``{'params': ...}`` / ``{'params_ema': ...}`` wrapping and the ``module.`` prefix, as load_model accepts them.  A
+    missing, unexpected or misshapen entry is a ValueError that names the key.  Plain torch, offline."""
+    for key in ("params_ema", "params"):
+        if isinstance(state.get(key), dict):
+            state = state[key]
+            break
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state.items()}
+    w0 = sd.get("conv0_0.weight")
+    if w0 is None or w0.dim() != 4:
+        raise ValueError("inspect_vgg_discriminator: 'conv0_0.weight' is missing or not a 4-d tensor")
+    nf, cin = int(w0.shape[0]), int(w0.shape[1])
+    size = 256 if "conv5_0.weight" in sd else 128
+    layout = vgg_discriminator_layout(cin, nf, size)
+    want = dict(layout)
+    extra = [k for k in sd if k not in want]
+    if extra:
+        raise ValueError(f"inspect_vgg_discriminator: unexpected key {extra[0]!r} ({len(extra)} such keys)")
+    for k, shape in layout:
+        if k not in sd:
+            raise ValueError(f"inspect_vgg_discriminator: key {k!r} is missing")
+        if tuple(sd[k].shape) != shape:
+            raise ValueError(f"inspect_vgg_discriminator: {k!r} has shape {tuple(sd[k].shape)}, expected {shape} for "
+                             f"num_in_ch={cin}, num_feat={nf}, input_size={size}")
+    params = sum(math.prod(shape) for k, shape in layout if not k.endswith(("running_mean", "running_var", "num_batches_tracked")))
+    return {"num_in_ch": cin, "num_feat": nf, "input_size": size, "parameters": params}
+
+
 def psnr(pred, target, data_range=None):
     """Host float: 10*log10(range^2 / MSE(pred, target)) for fp32 NCHW device tensors.
     ``data_range=None`` follows what torchmetrics' ``PeakSignalNoiseRatio()`` (eval_GAN.py:30,47: the metric is CALLED per
