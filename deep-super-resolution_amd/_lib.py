@@ -256,6 +256,9 @@ SIGNATURES = {
     "dsr_gan_loss": (_I, [_P, _Z, _I, _I, _I, _P, _P, _P, _P]),
     "dsr_rel_gan_loss_workspace": (_Z, [_Z, _Z]),
     "dsr_rel_gan_loss": (_I, [_P, _Z, _P, _Z, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "dsr_ldl_workspace": (_Z, [_I, _I, _I, _I, _I]),
+    "dsr_ldl_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "dsr_ldl_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "dsr_filter2d_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dsr_noise_gaussian_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "dsr_noise_poisson_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
@@ -280,7 +283,8 @@ _NO_LAUNCH = ("dsr_last_error", "dsr_abi_version", "dsr_conv_dgrad_ps_supported"
               "dsr_msssim_min_size", "dsr_msssim_pyramid_floats", "dsr_ssim_cs_img_blocks", "dsr_msssim_bwd_blocks", "dsr_luma_blocks",
               "dsr_featloss_blocks", "dsr_jpeg_workspace", "dsr_conv_rdb_supported", "dsr_conv_rdb_dgrad_supported",
               "dsr_conv_rdb_wgrad_supported", "dsr_conv_rdb_wgrad_workspace", "dsr_conv_rdb_wgrad_chunks", "dsr_spectral_norm_workspace",
-              "dsr_spectral_norm_bwd_workspace", "dsr_gan_loss_blocks", "dsr_gram_chunks", "dsr_gram_workspace", "dsr_rel_gan_loss_workspace")
+              "dsr_spectral_norm_bwd_workspace", "dsr_gan_loss_blocks", "dsr_gram_chunks", "dsr_gram_workspace", "dsr_rel_gan_loss_workspace",
+              "dsr_ldl_workspace")
 
 
 class _Lib:

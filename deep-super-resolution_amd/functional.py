@@ -1128,6 +1128,73 @@ def relativistic_gan_loss(pred, other, target_is_real, kind="vanilla", is_disc=F
     return RelGanLoss.apply(pred, other, target_is_real, _GAN_KINDS[kind], is_disc)
 
 
+# ----------------------------------------------------------------------------- LDL artifact-map loss
+def _ldl_forward(pred, target, pred_ema, ksize, want_map):
+    """The two forward launches of csrc/ldl.hip: (x, gt, ws, loss, map or None)."""
+    for t in (pred, target, pred_ema):
+        _need_gpu(t)
+        if t.dtype != torch.float32:
+            raise TypeError(f"ldl_loss takes fp32 tensors, got {t.dtype}")
+    if pred.dim() != 4 or pred.shape != target.shape or pred.shape != pred_ema.shape:
+        raise RuntimeError(f"ldl_loss operands must be [N, C, H, W] of one shape: {tuple(pred.shape)}, {tuple(target.shape)}, "
+                           f"{tuple(pred_ema.shape)}")
+    if isinstance(ksize, bool) or not isinstance(ksize, int) or ksize < 3 or ksize > 11 or ksize % 2 == 0:
+        raise ValueError(f"ldl_loss: ksize must be an odd int in 3..11, got {ksize!r}")
+    n, c, h, w = pred.shape
+    if h <= ksize // 2 or w <= ksize // 2:
+        raise ValueError(f"ldl_loss: a {h}x{w} image cannot be reflect-padded by {ksize // 2}")
+    x, gt, e = pred.detach().contiguous(), target.detach().contiguous(), pred_ema.detach().contiguous()
+    lib = _lib.lib()
+    nbytes = lib.dsr_ldl_workspace(n, c, h, w, ksize)
+    if nbytes == 0:
+        raise ValueError(f"ldl_loss: shape {tuple(pred.shape)} is empty or has 2^31 elements or more")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+    loss = torch.empty(1, dtype=torch.float32, device=x.device)
+    amap = torch.empty((n, 1, h, w), dtype=torch.float32, device=x.device) if want_map else None
+    check(lib.dsr_ldl_fwd(_ptr(x), _ptr(gt), _ptr(e), n, c, h, w, ksize, _ptr(ws), _ptr(loss), _ptr(amap), _stream()))
+    return x, gt, ws, loss, amap
+
+
+class LdlLoss(torch.autograd.Function):
+    """The LDL artifact-map term (dsr_ldl_fwd / dsr_ldl_bwd, csrc/ldl.hip): mean |w pred - w target| with the refined artifact
+    map w of ldl_artifact_map.  Two launches forward, one backward; the backward reads the incoming gradient on the device.
+    Gradient for `pred` only.  Like DiffLoss it has nothing to do under an ambient loss scale: the scale enters the backward pass
+    at the net's output, after this op."""
+
+    @staticmethod
+    def forward(ctx, pred, target, pred_ema, ksize, detach_weight):
+        x, gt, ws, loss, _ = _ldl_forward(pred, target, pred_ema, ksize, False)
+        ctx.save_for_backward(x, gt, ws)
+        ctx.ksize, ctx.detach_weight = ksize, bool(detach_weight)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        x, gt, ws = ctx.saved_tensors
+        n, c, h, w = x.shape
+        g = g.reshape(1).float().contiguous()
+        dx = torch.empty_like(x)
+        check(_lib.lib().dsr_ldl_bwd(_ptr(x), _ptr(gt), _ptr(ws), _ptr(g), n, c, h, w, ctx.ksize, int(ctx.detach_weight), _ptr(dx),
+                                     _stream()))
+        return dx, None, None, None, None
+
+
+def ldl_loss(pred, target, pred_ema, ksize=7, detach_weight=False):
+    """BasicSR's LDL term (ldl_opt; "Details or Artifacts", CVPR 2022), unweighted: L1(w * pred, w * target) with
+    w = get_refined_artifact_map(target, pred, pred_ema, ksize).  fp32 [N, C, H, W] operands on the device; returns an fp32
+    scalar.  ``detach_weight=False`` (BasicSR's behaviour) lets the gradient flow through the map as well; ``True`` treats the
+    map as a constant.  Where an image's residual is constant (its map is all zero) the image adds 0 to the loss and its
+    gradient is 0, where torch's own autograd gives 0 * inf = NaN.  Parity with BasicSR is unpinned (tests/ldl_ref.py)."""
+    return LdlLoss.apply(pred, target, pred_ema, ksize, detach_weight)
+
+
+def ldl_artifact_map(pred, target, pred_ema, ksize=7):
+    """BasicSR's get_refined_artifact_map(target, pred, pred_ema, ksize), without a gradient: [N, 1, H, W] fp32,
+    var(r[n])^(1/5) * (the k x k local variance of r = sum_c |target - pred|), zero where r < sum_c |target - pred_ema|."""
+    with torch.no_grad():
+        return _ldl_forward(pred, target, pred_ema, ksize, True)[4]
+
+
 # ----------------------------------------------------------------------------- spectral normalisation
 SN_EPS = 1e-12           # torch.nn.utils.spectral_norm's default
 _sn_pending = {}         # id(weight_orig) -> results of a group launch that SpectralNormWeight.forward picks up

@@ -211,7 +211,8 @@ def gan_step(gen, disc, perceptual, opt_g, opt_d, lr_patches, hr_patches, sync_g
 
 
 def realesrgan_step(gen, disc, vggfeat, opt_g, opt_d, lq, gt, *, l1_weight=1.0, gan_weight=0.1, gan_type="vanilla", ema=None,
-                    gt_usm=None, l1_gt_usm=True, percep_gt_usm=True, gan_gt_usm=False):
+                    gt_usm=None, l1_gt_usm=True, percep_gt_usm=True, gan_gt_usm=False, ldl_weight=0.0, gen_ema=None,
+                    ldl_detach=False):
     """One GAN-stage step of the Real-ESRGAN recipe (BasicSR RealESRGANModel.optimize_parameters).  Unlike gan_step, the
     adversarial gradient flows through D into G.  With ``gt_usm=None`` `gt` is the target of all three terms.  With a tensor
     (``utils.degradation.usm_sharp(gt)``, the unsharp-masked ground truth) the L1 term, the content term and the
@@ -227,10 +228,27 @@ def realesrgan_step(gen, disc, vggfeat, opt_g, opt_d, lq, gt, *, l1_weight=1.0, 
     in train mode one step advances every u and v by three power iterations, as the published loop does.  Returns (l_pix,
     l_percep, l_g_gan, l_d_real, l_d_fake, fake): the unweighted L1, the (weighted) content term, the unweighted three GAN
     terms and the generator's output, as detached device tensors.  One stream, no host read: usable inside GraphedStep with a
-    FusedAdam for each optimiser."""
+    FusedAdam for each optimiser.
+
+    ``ldl_weight > 0`` adds the LDL artifact term (BasicSR's ldl_opt, functional.ldl_loss) and needs ``gen_ema``, a second
+    generator module that holds the averaged weights:
+        fake_ema = gen_ema(lq)  (no gradient; the average as it stood BEFORE this step's update, the published order)
+        l_g += ldl_weight * ldl_loss(fake, l1_gt, fake_ema, detach_weight=ldl_detach)
+    The term takes the L1 term's target (gt_usm or gt by `l1_gt_usm`), as BasicSR's does.  After ``ema.update()`` the step writes
+    the new average into `gen_ema` (``ema.copy_to(gen_ema)``) when both are given, and it returns a seven-tuple with the unweighted
+    term appended: (l_pix, l_percep, l_g_gan, l_d_real, l_d_fake, fake, l_g_ldl).
+    With ``ldl_weight == 0`` (the default) neither keyword is looked at: the launches, the bits and the six-tuple are as before."""
+    ldl = float(ldl_weight)
+    if ldl < 0.0 or ldl != ldl:
+        raise ValueError(f"realesrgan_step: ldl_weight must be >= 0, got {ldl_weight!r}")
+    if ldl > 0.0 and gen_ema is None:
+        raise ValueError("realesrgan_step: ldl_weight > 0 needs gen_ema, a generator module holding the averaged weights")
     l1_gt = gt_usm if (gt_usm is not None and l1_gt_usm) else gt
     percep_gt = gt_usm if (gt_usm is not None and percep_gt_usm) else gt
     gan_gt = gt_usm if (gt_usm is not None and gan_gt_usm) else gt
+    if ldl > 0.0:
+        with torch.no_grad():
+            fake_ema = gen_ema(lq)
     d_params = [p for p in disc.parameters()]
     was = [p.requires_grad for p in d_params]
     # --- generator
@@ -243,11 +261,16 @@ def realesrgan_step(gen, disc, vggfeat, opt_g, opt_d, lq, gt, *, l1_weight=1.0, 
         l_percep = vggfeat(fake, percep_gt)
         l_g_gan = F.gan_loss(disc(fake), True, gan_type, is_disc=False)
         l_g = F.add_losses(F.add_losses(F.scale_loss(l_pix, float(l1_weight)), l_percep), F.scale_loss(l_g_gan, float(gan_weight)))
+        if ldl > 0.0:
+            l_g_ldl = F.ldl_loss(fake, l1_gt, fake_ema, detach_weight=ldl_detach)
+            l_g = F.add_losses(l_g, F.scale_loss(l_g_ldl, ldl))
         with F.batched_wgrad():
             l_g.backward()
         opt_g.step()
         if ema is not None:
             ema.update()
+            if ldl > 0.0:
+                ema.copy_to(gen_ema)
     finally:
         for p, r in zip(d_params, was):
             p.requires_grad_(r)
@@ -266,7 +289,8 @@ def realesrgan_step(gen, disc, vggfeat, opt_g, opt_d, lq, gt, *, l1_weight=1.0, 
     finally:
         for p, r in zip(d_params, was):
             p.requires_grad_(r)
-    return l_pix.detach(), l_percep.detach(), l_g_gan.detach(), l_d_real.detach(), l_d_fake.detach(), fake.detach()
+    out = (l_pix.detach(), l_percep.detach(), l_g_gan.detach(), l_d_real.detach(), l_d_fake.detach(), fake.detach())
+    return out + (l_g_ldl.detach(),) if ldl > 0.0 else out
 
 
 def esrgan_step(gen, disc, vggfeat, opt_g, opt_d, lq, gt, *, l1_weight=1e-2, gan_weight=5e-3, gan_type="vanilla", ema=None):

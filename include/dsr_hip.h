@@ -944,6 +944,36 @@ size_t dsr_rel_gan_loss_workspace(size_t n, size_t m);
 int dsr_rel_gan_loss(const float* x, size_t n, const float* other, size_t m, int kind, int target_is_real, int is_disc,
                      float* grad_x, float* grad_other, void* ws, float* loss, dsr_stream_t s);
 
+/* ------------------------------------------------------------------ LDL artifact-map loss (ldl.hip)
+ * "Details or Artifacts: A Locally Discriminative Learning Approach" (CVPR 2022) as BasicSR's ldl_opt computes it (PARITY
+ * UNPINNED: restated, the float64 statement is tests/ldl_ref.py).  x (the generator's output, which carries the gradient), gt
+ * and e (the EMA generator's output): fp32 [N][C][H][W], contiguous.  k: the odd window, p = (k - 1) / 2, K = k k, M = N C H W.
+ *   r[n,y,x]  = sum_c |gt - x|,  re = sum_c |gt - e|         fp32, in channel order
+ *   mu, v     = mean and unbiased variance (/ (K - 1)) of r over the k x k window of the reflect-padded plane (the edge is not
+ *               repeated), in two passes:  mu = r_q + (sum (r - r_q)) / K,  v = (sum (r - mu)^2) / (K - 1)
+ *   V_n       = unbiased variance of r[n] over its H W values, from double sums shifted by r[n,0,0];  g_n = V_n^(1/5), formed in
+ *               double and rounded to fp32 once
+ *   m         = 0 where r < re, otherwise 1 (a tie keeps the weight; a NaN compares false and stays in the loss)
+ *   w         = g_n v m                                        the artifact map [N][1][H][W] (optional output `map`)
+ *   loss[0]   = (sum_n g_n S_n) / M,  S_n = sum m r v          in double, one rounding  (= mean |w x - w gt|, as w >= 0)
+ *   dx[n,c,q] = sign(x - gt) dr[n,q] upstream[0],  sign(0) = 0:
+ *     detach_weight:  dr = w / M
+ *     otherwise:      dr = [ w + (2 / (K - 1)) g_n sum_{u in pre(q)} sum_{q' in window(u)} (m r)[q'] (r[q] - mu[q'])
+ *                            + S_n (1/5) V_n^(-4/5) 2 (r - rbar_n) / (H W - 1) ] / M
+ *     pre(q): q and its mirror images in the pad, window(u): the part of u's window inside the image (the adjoint of
+ *     reflect-pad + box sum); the mask is a constant of the gradient.
+ *   V_n == 0 (r constant): that image adds 0 to the loss, and its map and gradient are 0 (torch: 0 * inf = NaN).
+ * dsr_ldl_fwd: two launches (tile pass, finalize); it leaves what dsr_ldl_bwd (one launch) needs in ws.  No atomics, no host
+ * read (upstream is a DEVICE scalar), per-image sums are double block partials folded in a fixed order: the same input gives
+ * the same bits.  ws: DEVICE scratch, 8-byte aligned, of dsr_ldl_workspace(N, C, H, W, k) bytes (0 for a shape the entry points
+ * refuse).  A null pointer, k not odd in 3..11, H or W <= p, N C H W >= 2^31 or a misaligned pointer return DSR_E_ARG before
+ * anything is launched. */
+size_t dsr_ldl_workspace(int N, int C, int H, int W, int k);
+int dsr_ldl_fwd(const float* x, const float* gt, const float* e, int N, int C, int H, int W, int k, void* ws, float* loss,
+                float* map, dsr_stream_t s);
+int dsr_ldl_bwd(const float* x, const float* gt, const void* ws, const float* upstream, int N, int C, int H, int W, int k,
+                int detach_weight, float* dx, dsr_stream_t s);
+
 /* ------------------------------------------------------------------ second-order Real-ESRGAN degradation
  * fp32 [B][C][H][W] batches in [0, 1] scaling; every call only enqueues on `s` (no allocation, no sync, no host read).
  *
