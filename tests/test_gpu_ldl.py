@@ -53,7 +53,13 @@ def dev():
 
 
 CASES = [((1, 3, 4, 4), 7), ((2, 3, 7, 5), 7), ((2, 3, 33, 40), 7), ((2, 1, 16, 16), 7), ((3, 3, 64, 96), 7), ((1, 3, 256, 256), 7),
-         ((2, 3, 33, 40), 3), ((2, 3, 33, 40), 11), ((1, 3, 12, 12), 3), ((1, 3, 12, 12), 11)]
+         ((2, 3, 33, 40), 3), ((2, 3, 33, 40), 11), ((1, 3, 12, 12), 3), ((1, 3, 12, 12), 11),
+         # past the first turn of every loop over images and tiles (csrc/ldl.hip): N = 5, the four waves of ldl_finalize_kernel take
+         # a second image (n += 4); 2 x 2 ragged tiles with N = 6; N = 65, the second lane turn of the loss fold (n += 64);
+         # 9 x 9 = 81 tiles, ragged on both axes, the second lane turn of ldl_image_stats (t += 64); then the k = 5 and k = 9
+         # instantiations of ldl_tile_kernel and ldl_bwd_kernel
+         ((5, 1, 16, 16), 7), ((6, 3, 17, 70), 7), ((65, 1, 8, 8), 3), ((2, 3, 130, 513), 7),
+         ((2, 3, 33, 40), 5), ((2, 3, 33, 40), 9), ((1, 3, 12, 12), 5), ((1, 3, 12, 12), 9)]
 CASE_IDS = ["x".join(map(str, s)) + f"-k{k}" for s, k in CASES]
 
 
@@ -178,7 +184,8 @@ def test_planted_ties_keep_the_weight_and_equal_elements_get_no_gradient(dev):
         assert float(grad.cpu()[x == gt].abs().max()) == 0.0 and float(grad.abs().max()) > 0.0
 
 
-@pytest.mark.parametrize("case", [((2, 3, 33, 40), 7), ((1, 3, 256, 256), 7), ((3, 3, 64, 96), 11)], ids=["33x40", "256x256", "64x96-k11"])
+@pytest.mark.parametrize("case", [((2, 3, 33, 40), 7), ((1, 3, 256, 256), 7), ((3, 3, 64, 96), 11), ((65, 1, 8, 8), 3),
+                                  ((2, 3, 130, 513), 7)], ids=["33x40", "256x256", "64x96-k11", "65x8x8-k3", "130x513"])
 def test_two_runs_give_equal_bits(dev, case):
     F = P("functional")
     shape, k = case
