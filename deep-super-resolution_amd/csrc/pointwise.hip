@@ -1590,8 +1590,11 @@ extern "C" int dsr_pw_adam(float* p, const float* g, float* m, float* v, size_t 
                            const dsr_adam_args* args, hipStream_t st) {
   DSR_REQUIRE(p && g && m && v && n > 0, "adam: null pointer or empty tensor");
   DSR_REQUIRE(adam_args_ok(args), "adam: null or misaligned argument block, step counter or device word");
-  DSR_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 3) == 0 && ((uintptr_t)shadow_bf16 & 1) == 0,
-              "adam: misaligned pointer");
+  // adam_stream moves p, g, m, v as 16-byte vectors and the shadow as 8-byte ones (a view off such a boundary belongs to
+  // dsr_pw_adam_multi, whose accesses are scalar)
+  DSR_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0,
+              "adam: p, g, m and v must be 16-byte aligned");
+  DSR_REQUIRE(((uintptr_t)shadow_bf16 & 7) == 0, "adam: the bf16 shadow must be 8-byte aligned");
   size_t want = (n / 4 + 511) / 512;
   unsigned blocks = (unsigned)(want < 1 ? 1 : (want > 65536 ? 65536 : want));
   adam_dispatch(*args, [&](auto dev, const auto& a) {

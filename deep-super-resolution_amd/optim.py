@@ -190,9 +190,22 @@ class FusedAdam:
             if g.dtype != torch.float32 or not g.is_contiguous():
                 g = g.float().contiguous()
                 keep.append(g)
-            grads.append(g)
             sh = shadow_for_update(p)        # bf16 image kept by DenseHead for this matrix (or None)
-            if sh is None and p.numel() <= self.MULTI_MAX and p.is_contiguous():
+            # the per-tensor launch moves 16-byte vectors (dsr_pw_adam refuses anything else): a parameter that is a view
+            # off such a boundary takes the multi-tensor launch, whose accesses are scalar, whatever its size
+            skew = p.data_ptr() % 16 != 0 and p.numel() > 0
+            if skew and (sh is not None or not p.is_contiguous()):
+                idx = next(i for i, q in enumerate(self.params) if q is p)
+                raise ValueError(f"FusedAdam: parameter {idx} of shape {tuple(p.shape)} starts "
+                                 f"{p.data_ptr() % 16} bytes off a 16-byte boundary and "
+                                 + ("has a bf16 shadow" if sh is not None else "is not contiguous")
+                                 + ": the per-tensor Adam launch that would serve it needs 16-byte aligned tensors")
+            multi = sh is None and p.is_contiguous() and (skew or p.numel() <= self.MULTI_MAX)
+            if not multi and g.data_ptr() % 16 != 0:
+                g = g.clone()                # a gradient view bound for the per-tensor launch: copied, like a strided one
+                keep.append(g)
+            grads.append(g)
+            if multi:
                 if p.numel():                # (a zero-element parameter has nothing to update, in any mode)
                     small.append((p, g, m, v))
                 bump(p)                      # (rewritten by the multi-tensor launch below, before anything reads it)

@@ -240,8 +240,11 @@ int dsr_pw_bce_const(const float* p, int n, float target, float* loss, float* gr
  *                        (dsr_clip_finalize writes both): hyper[1] == 1 gives the bits of the same call without hyper.
  * With all three NULL the kernels that run hold no trace of the pointers; any other combination is resolved on the device.
  * Every entry point checks the same things before its first launch (DSR_E_ARG): args and args->step non-NULL and 4-byte
- * aligned, hyper / loss_scale / found_inf 4-byte aligned when set, every tensor non-NULL, aligned (4 bytes; the shadow 2)
- * and of n > 0 elements, count > 0.  An empty tensor is refused in every mode, on purpose: one rule instead of one per mode.
+ * aligned, hyper / loss_scale / found_inf 4-byte aligned when set, every tensor non-NULL, aligned and of n > 0 elements,
+ * count > 0.  Tensor alignment follows the accesses of each launch: dsr_pw_adam moves p, g, m and v as 16-byte vectors and
+ * the shadow as 8-byte ones, so it wants them 16- and 8-byte aligned (as dsr_linear_wgrad_adam does) and refuses a view 4,
+ * 8 or 12 bytes off such a boundary; dsr_pw_adam_multi's accesses are scalar and its tensors need 4 bytes only, which is
+ * where optim.FusedAdam sends such a view.  An empty tensor is refused in every mode, on purpose: one rule instead of one per mode.
  * optim.FusedAdam leaves zero-element parameters out of its tables, so such a parameter is a no-op in every mode. */
 typedef struct dsr_adam_args {
   const int*   step;        /* device step counter, already advanced for this step; required            */

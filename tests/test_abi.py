@@ -221,6 +221,37 @@ def test_adam_argument_block_is_checked_alike_by_every_launcher(so):
     assert lib.dsr_pw_adam_multi(2, ptrs, ptrs, ptrs, ptrs, big, good, st) == -4                    # 32-bit element indices
 
 
+def test_per_tensor_adam_wants_16_byte_operands(so):
+    """dsr_pw_adam moves p, g, m, v as 16-byte vectors and the shadow as 8-byte ones: each of the four 4, 8 or 12 bytes off a
+    16-byte boundary, and a shadow 2, 4 or 6 bytes off an 8-byte one, is DSR_E_ARG with a message that names the alignment, in
+    every mode, before any launch (there is no GPU here).  dsr_pw_adam_multi's accesses are scalar: its table check accepts
+    the same addresses (the call then stops at a tensor too large for it, DSR_E_UNSUPPORTED, which comes after that check)."""
+    L = importlib.import_module(PKG + "._lib")
+    lib = L.lib()
+    N, st = None, None
+    base = 4096
+    a, sh = ctypes.c_void_p(base), ctypes.c_void_p(base + 8)          # accepted: 16- and 8-byte aligned
+    modes = ({}, {"loss_scale": 64, "found_inf": 64}, {"hyper": 64}, {"hyper": 64, "loss_scale": 64, "found_inf": 64})
+    big = (ctypes.c_size_t * 2)(400, 1 << 32)
+    for mode in modes:
+        blk = adam_args(64, **mode)
+        for off in (4, 8, 12):
+            skew = ctypes.c_void_p(base + off)
+            for slot in range(4):
+                ops = [a, a, a, a]
+                ops[slot] = skew
+                for shadow in (N, sh):
+                    assert lib.dsr_pw_adam(*ops, 16, shadow, blk, st) == -1, (mode, off, slot)
+                    assert b"16-byte aligned" in lib.dsr_last_error()
+                tabs = [(ctypes.c_void_p * 2)(base, 2 * base) for _ in range(4)]
+                tabs[slot] = (ctypes.c_void_p * 2)(base + off, 2 * base + off)
+                assert lib.dsr_pw_adam_multi(2, *tabs, big, blk, st) == -4, (mode, off, slot)
+                assert b"too large" in lib.dsr_last_error()
+        for off in (2, 4, 6):
+            assert lib.dsr_pw_adam(a, a, a, a, 16, ctypes.c_void_p(base + off), blk, st) == -1, (mode, off)
+            assert b"8-byte aligned" in lib.dsr_last_error()
+
+
 def test_entry_point_without_return_does_not_compile(tmp_path):
     """The 06:58 round-1 segfault (functional.py:286, inside dsr_pw_bn_eval_affine): that entry point had lost its
     `return` statement -- undefined behaviour, hipcc -O3 emits no `ret` and the host runs off the function's end.  The
