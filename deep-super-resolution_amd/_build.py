@@ -12,7 +12,7 @@ OBJ = os.path.join(CSRC, "build")
 SOURCES = ["conv_gemm.hip", "conv_gemm_persist.hip", "conv_wgrad.hip", "conv_wgrad_tile.hip", "conv_smalln.hip",
            "conv_c64.hip", "conv_halo64.hip", "conv_rdb.hip", "conv_rdb_bwd.hip", "conv_cin8.hip", "conv_rgb9.hip", "conv_dgrad_s2.hip", "conv_first_bwd.hip", "conv_first2.hip", "conv_api.hip", "pointwise.hip", "linear.hip",
            "resample.hip", "downsample_dense.hip", "metrics.hip", "lpips.hip", "data.hip", "d4.hip", "degrade.hip", "jpeg.hip", "lbfgs.hip", "ema.hip", "luma.hip", "featloss.hip", "featstyle.hip", "imresize.hip", "spectral_norm.hip",
-           "filter2d.hip", "degrade_noise.hip", "niqe.hip", "ragan.hip", "ldl.hip"]
+           "filter2d.hip", "degrade_noise.hip", "niqe.hip", "ragan.hip", "ldl.hip", "conv_compact.hip", "pw_compact.hip"]
 SO = os.path.join(CSRC, "libdsr_hip.so")
 # -Werror=return-type: a C-ABI entry point that flows off its end without `return` is undefined behaviour (hipcc -O3
 # emits no `ret`, the call runs into the next function) -- that was the round-1 host segfault in dsr_pw_bn_eval_affine.

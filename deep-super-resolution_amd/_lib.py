@@ -56,6 +56,19 @@ class RdbWgrad(C.Structure):
                 ("dw", C.c_void_p * 5), ("db", C.c_void_p * 5)]
 
 
+class CompactConv(C.Structure):
+    """dsr_compact_conv: one body layer of SRVGGNetCompact, conv + per-channel PReLU (csrc/conv_compact.hip)."""
+    _fields_ = [("dtype", C.c_int), ("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("x", C.c_void_p), ("w", C.c_void_p),
+                ("bias", C.c_void_p), ("slope", C.c_void_p), ("y", C.c_void_p), ("max_blocks", C.c_int)]
+
+
+class CompactTail(C.Structure):
+    """dsr_compact_tail: SRVGGNetCompact's tail, conv + PixelShuffle(s) + the input image (csrc/conv_compact.hip)."""
+    _fields_ = [("dtype", C.c_int), ("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("s", C.c_int),
+                ("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("base", C.c_void_p), ("out", C.c_void_p),
+                ("max_blocks", C.c_int)]
+
+
 class AdamArgs(C.Structure):
     """dsr_adam_args: where an Adam launch takes its coefficients from (hyper, loss_scale, found_inf: device words, each
     nullable); one block for dsr_pw_adam, dsr_pw_adam_multi and dsr_linear_wgrad_adam."""
@@ -267,6 +280,16 @@ SIGNATURES = {
     "dsr_niqe_plane": (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _P]),
     "dsr_niqe_moments": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "dsr_niqe_features": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "dsr_conv_prelu_c_supported": (_I, [C.POINTER(CompactConv)]),
+    "dsr_conv_prelu_c_fwd": (_I, [C.POINTER(CompactConv), _P]),
+    "dsr_conv_shuffle_add_supported": (_I, [C.POINTER(CompactTail)]),
+    "dsr_conv_shuffle_add_fwd": (_I, [C.POINTER(CompactTail), _P]),
+    "dsr_pw_prelu_c_fwd": (_I, [_I, _P, _P, _P, _Z, _I, _I, _P]),
+    "dsr_pw_prelu_c_rows": (_I, [_Z]),
+    "dsr_pw_prelu_c_fold_width": (_I, []),
+    "dsr_pw_prelu_c_bwd": (_I, [_I, _P, _P, _P, _P, _Z, _I, _I, _P, _P, _P]),
+    "dsr_shuffle_add_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "dsr_shuffle_add_bwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
 }
 
 _lib = None
@@ -284,7 +307,8 @@ _NO_LAUNCH = ("dsr_last_error", "dsr_abi_version", "dsr_conv_dgrad_ps_supported"
               "dsr_featloss_blocks", "dsr_jpeg_workspace", "dsr_conv_rdb_supported", "dsr_conv_rdb_dgrad_supported",
               "dsr_conv_rdb_wgrad_supported", "dsr_conv_rdb_wgrad_workspace", "dsr_conv_rdb_wgrad_chunks", "dsr_spectral_norm_workspace",
               "dsr_spectral_norm_bwd_workspace", "dsr_gan_loss_blocks", "dsr_gram_chunks", "dsr_gram_workspace", "dsr_rel_gan_loss_workspace",
-              "dsr_ldl_workspace")
+              "dsr_ldl_workspace", "dsr_conv_prelu_c_supported", "dsr_conv_shuffle_add_supported", "dsr_pw_prelu_c_rows",
+              "dsr_pw_prelu_c_fold_width")
 
 
 class _Lib:

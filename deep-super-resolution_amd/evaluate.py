@@ -124,6 +124,58 @@ def inspect_vgg_discriminator(state):
     return {"num_in_ch": cin, "num_feat": nf, "input_size": size, "parameters": params}
 
 
+def inspect_srvgg(state):
+    """dict(num_in_ch, num_out_ch, num_feat, num_conv, upscale, act_type): the constructor arguments of the
+    ``models.GAN.srvgg.SRVGGNetCompact`` that a checkpoint loads into, read off its keys and shapes.  `state` may be plain,
+    carry BasicSR's ``{'params_ema': ...}`` / ``{'params': ...}`` wrapping, and the ``module.`` prefix, as load_model accepts
+    them.  num_out_ch is num_in_ch (the network adds its input to its output) and upscale = sqrt(Cout_last / num_in_ch) must
+    be an integer.  act_type is 'prelu' when the odd-index keys ``body.{odd}.weight`` exist, else None: ReLU and LeakyReLU
+    have no parameters, so a file cannot tell them apart.  A missing, unexpected or misshapen key is a ValueError that names
+    the key.  Plain torch, offline."""
+    for key in ("params_ema", "params"):
+        if isinstance(state.get(key), dict):
+            state = state[key]
+            break
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state.items()}
+    idx = {}
+    for k in sd:
+        parts = k.split(".")
+        if len(parts) != 3 or parts[0] != "body" or not parts[1].isdigit() or parts[2] not in ("weight", "bias"):
+            raise ValueError(f"inspect_srvgg: unexpected key {k!r}")
+        idx.setdefault(int(parts[1]), set()).add(parts[2])
+    w0 = sd.get("body.0.weight")
+    if w0 is None or w0.dim() != 4:
+        raise ValueError("inspect_srvgg: 'body.0.weight' is missing or not a 4-d tensor")
+    nf, cin = int(w0.shape[0]), int(w0.shape[1])
+    last = max(i for i in idx if i % 2 == 0)
+    if last < 2:
+        raise ValueError("inspect_srvgg: key 'body.2.weight' is missing (the network has a head and a tail at least)")
+    num_conv = (last - 2) // 2
+    prelu = any(i % 2 for i in idx)
+    want = OrderedDict()
+    for i in range(0, last + 1, 2):
+        want[f"body.{i}.weight"] = (nf if i < last else None, cin if i == 0 else nf, 3, 3)
+        want[f"body.{i}.bias"] = (nf if i < last else None,)
+        if prelu and i < last:
+            want[f"body.{i + 1}.weight"] = (nf,)
+    for k in sd:
+        if k not in want:
+            raise ValueError(f"inspect_srvgg: unexpected key {k!r}")
+    for k, shape in want.items():
+        if k not in sd:
+            raise ValueError(f"inspect_srvgg: key {k!r} is missing")
+        got = tuple(sd[k].shape)
+        if len(got) != len(shape) or any(s is not None and s != g for s, g in zip(shape, got)):
+            raise ValueError(f"inspect_srvgg: {k!r} has shape {got}, expected {shape} for num_in_ch={cin}, num_feat={nf}")
+    q = int(sd[f"body.{last}.weight"].shape[0])
+    s = math.isqrt(q // cin) if q % cin == 0 else 0
+    if s < 1 or s * s * cin != q:
+        raise ValueError(f"inspect_srvgg: 'body.{last}.weight' has {q} outputs, which is not num_in_ch ({cin}) times a square")
+    if tuple(sd[f"body.{last}.bias"].shape) != (q,):
+        raise ValueError(f"inspect_srvgg: 'body.{last}.bias' has shape {tuple(sd[f'body.{last}.bias'].shape)}, expected {(q,)}")
+    return dict(num_in_ch=cin, num_out_ch=cin, num_feat=nf, num_conv=num_conv, upscale=s, act_type="prelu" if prelu else None)
+
+
 def psnr(pred, target, data_range=None):
     """Host float: 10*log10(range^2 / MSE(pred, target)) for fp32 NCHW device tensors.
     ``data_range=None`` follows what torchmetrics' ``PeakSignalNoiseRatio()`` (eval_GAN.py:30,47: the metric is CALLED per

@@ -2450,3 +2450,146 @@ class Imresize(torch.autograd.Function):
         dx = torch.empty((n, c, h, w), dtype=torch.float32, device=dy.device)
         _imresize_launch(dy, dx, n * c, th.n_out, tw.n_out, h, w, th.t_idx, th.t_w, th.q, tw.t_idx, tw.t_w, tw.q)
         return dx, None, None
+
+
+# ----------------------------------------------------------------------------- SRVGGNetCompact (csrc/conv_compact.hip, pw_compact.hip)
+def compact_fused_enabled():
+    """DSR_COMPACT_FUSED (read per call): 0 = the no-grad forward of SRVGGNetCompact also takes the composed launches."""
+    return os.environ.get("DSR_COMPACT_FUSED", "1") != "0"
+
+
+def compact_supported(x_shape, dtype, num_feat, num_ch, upscale):
+    """Do dsr_conv_prelu_c_fwd and dsr_conv_shuffle_add_fwd take the body and the tail of an SRVGGNetCompact on an
+    [N,H,W,*] input (and is the switch on)?  The kernels are 64-channel ones: any other width is the composed form's."""
+    if not compact_fused_enabled() or dtype not in (torch.bfloat16, torch.float16) or num_feat != 64:
+        return False
+    n, h, w = (int(v) for v in x_shape[:3])
+    dt = BF16 if dtype == torch.bfloat16 else F16
+    lib = _lib.lib()
+    body = _lib.CompactConv(dt, n, h, w, None, None, None, None, None, 0)
+    tail = _lib.CompactTail(dt, n, h, w, int(num_ch), int(upscale), None, None, None, None, None, 0)
+    return bool(lib.dsr_conv_prelu_c_supported(C.byref(body))) and bool(lib.dsr_conv_shuffle_add_supported(C.byref(tail)))
+
+
+def _compact_check(x):
+    _need_gpu(x)
+    if not (x.dim() == 4 and x.shape[3] == 64 and x.is_contiguous()):
+        raise ValueError(f"compact conv: a contiguous 16-bit NHWC tensor with 64 channels is expected, got {tuple(x.shape)}")
+    return _dt(x)
+
+
+def compact_conv(x, weight, bias, slope, max_blocks=0):
+    """One dsr_conv_prelu_c_fwd launch, no autograd: r16(prelu_c(conv3x3(x, weight) + bias, slope)) on [N,H,W,64].
+
+    weight: fp32 OIHW [64,64,3,3]; bias, slope: fp32 [64] device tensors or None (slope None: no activation).  The slope is
+    read from the tensor's own storage by the launch."""
+    dt = _compact_check(x)
+    if tuple(weight.shape) != (64, 64, 3, 3):
+        raise ValueError(f"compact_conv: weight of shape {tuple(weight.shape)}, expected (64, 64, 3, 3)")
+    for name, t in (("bias", bias), ("slope", slope)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.numel() == 64 and t.is_contiguous()):
+            raise ValueError(f"compact_conv: {name} must be a contiguous fp32 device tensor of 64 elements")
+    n, h, w, _ = x.shape
+    wf, _ = packed_weights(weight, ConvDesc(dt, n, h, w, 64, 64, 3, 3, 1, 1, PAD_ZERO), x.dtype)
+    y = torch.empty_like(x)
+    d = _lib.CompactConv(dt, n, h, w, x.data_ptr(), wf.data_ptr(), None if bias is None else bias.data_ptr(),
+                         None if slope is None else slope.data_ptr(), y.data_ptr(), int(max_blocks))
+    check(_lib.lib().dsr_conv_prelu_c_fwd(C.byref(d), _stream()))
+    return y
+
+
+def compact_tail(x, weight, bias, base, upscale, max_blocks=0):
+    """One dsr_conv_shuffle_add_fwd launch, no autograd: pixel_shuffle(conv3x3(x, weight) + bias, s) + nearest_s(base) as
+    fp32 NCHW [N,C,sH,sW].  weight: fp32 OIHW [C s^2,64,3,3]; bias [C s^2] or None; base fp32 [N,C,H,W] or None."""
+    dt = _compact_check(x)
+    s = int(upscale)
+    q = weight.shape[0]
+    if tuple(weight.shape[1:]) != (64, 3, 3) or s < 1 or q % (s * s):
+        raise ValueError(f"compact_tail: weight of shape {tuple(weight.shape)} for upscale {s}")
+    c = q // (s * s)
+    n, h, w, _ = x.shape
+    if bias is not None and not (bias.is_cuda and bias.dtype == torch.float32 and bias.numel() == q and bias.is_contiguous()):
+        raise ValueError(f"compact_tail: bias must be a contiguous fp32 device tensor of {q} elements")
+    if base is not None:
+        if not (base.is_cuda and base.dtype == torch.float32 and tuple(base.shape) == (n, c, h, w)):
+            raise ValueError(f"compact_tail: base of shape {tuple(base.shape)} {base.dtype}, expected fp32 {(n, c, h, w)}")
+        base = base.contiguous()
+    wf, _ = packed_weights(weight, ConvDesc(dt, n, h, w, 64, q, 3, 3, 1, 1, PAD_ZERO), x.dtype)
+    out = torch.empty((n, c, s * h, s * w), dtype=torch.float32, device=x.device)
+    d = _lib.CompactTail(dt, n, h, w, c, s, x.data_ptr(), wf.data_ptr(), None if bias is None else bias.data_ptr(),
+                         None if base is None else base.data_ptr(), out.data_ptr(), int(max_blocks))
+    check(_lib.lib().dsr_conv_shuffle_add_fwd(C.byref(d), _stream()))
+    return out
+
+
+def prelu_channel(z, slope):
+    """r16(z > 0 ? z : z * slope[c]) on a 16-bit NHWC tensor, no autograd: dsr_pw_prelu_c_fwd."""
+    _need_gpu(z)
+    z = z.contiguous()
+    cp = z.shape[-1]
+    y = torch.empty_like(z)
+    check(_lib.lib().dsr_pw_prelu_c_fwd(_dt(z), _ptr(z), _ptr(slope), _ptr(y), z.numel() // cp, slope.numel(), cp, _stream()))
+    return y
+
+
+class PReLUChannel(torch.autograd.Function):
+    """nn.PReLU(num_parameters=C) on a 16-bit NHWC tensor [N,H,W,r8(C)]; slope: fp32 [C] on the device, any sign.
+
+    Saves the PRE-ACTIVATION z: the backward takes its branch from z (torch's rules at 0: dz = dy * slope and the slope
+    gradient gets dy * 0 there), so -- unlike the output-masked conv + PReLU launches of ConvAct -- a negative or zero slope
+    is exact and check_prelu_slopes has nothing to check.  The slope gradient is a fixed-order fold of fp32 partial rows
+    (no atomics; scratch from torch's allocator)."""
+
+    @staticmethod
+    def forward(ctx, z, slope):
+        if not (slope.dtype == torch.float32 and slope.dim() == 1 and slope.is_contiguous() and slope.numel() <= z.shape[-1]):
+            raise ValueError(f"PReLUChannel: slope of shape {tuple(slope.shape)} {slope.dtype} for {z.shape[-1]} stored channels")
+        z = z.contiguous()
+        ctx.save_for_backward(z, slope)
+        return prelu_channel(z, slope.detach())
+
+    @staticmethod
+    def backward(ctx, dy):
+        z, slope = ctx.saved_tensors
+        dy = dy.contiguous()
+        lib = _lib.lib()
+        cp = z.shape[-1]
+        p = z.numel() // cp
+        c = slope.numel()
+        dz = torch.empty_like(z)
+        part = dslope = None
+        if ctx.needs_input_grad[1]:
+            part = torch.empty(lib.dsr_pw_prelu_c_rows(p) * cp, dtype=torch.float32, device=z.device)
+            dslope = torch.empty(c, dtype=torch.float32, device=z.device)
+        check(lib.dsr_pw_prelu_c_bwd(_dt(z), _ptr(dy), _ptr(z), _ptr(slope.detach()), _ptr(dz), p, c, cp, _ptr(part), _ptr(dslope),
+                                     _stream()))
+        return dz, dslope
+
+
+class ShuffleAdd(torch.autograd.Function):
+    """pixel_shuffle(t, s) + nearest_upsample(base, s) on fp32 NCHW: t [N,C s^2,H,W], base [N,C,H,W] -> [N,C,sH,sW]
+    (dsr_shuffle_add_f32).  Backward: the un-shuffle of the gradient and, where the image wants one, its s^2-pixel sums."""
+
+    @staticmethod
+    def forward(ctx, t, base, s):
+        _need_gpu(t)
+        t = t.contiguous().float()
+        base = base.contiguous().float()
+        n, q, h, w = t.shape
+        s = int(s)
+        c = q // (s * s)
+        if q != c * s * s or tuple(base.shape) != (n, c, h, w):
+            raise ValueError(f"ShuffleAdd: t {tuple(t.shape)} and base {tuple(base.shape)} for upscale {s}")
+        out = torch.empty((n, c, s * h, s * w), dtype=torch.float32, device=t.device)
+        check(_lib.lib().dsr_shuffle_add_f32(_ptr(t), _ptr(base), _ptr(out), n, c, s, h, w, _stream()))
+        ctx.dims = (n, c, s, h, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        n, c, s, h, w = ctx.dims
+        dout = dout.contiguous().float()
+        dt = torch.empty((n, c * s * s, h, w), dtype=torch.float32, device=dout.device)
+        dbase = torch.empty((n, c, h, w), dtype=torch.float32, device=dout.device) if ctx.needs_input_grad[1] else None
+        check(_lib.lib().dsr_shuffle_add_bwd_f32(_ptr(dout), _ptr(dt), _ptr(dbase), n, c, s, h, w, _stream()))
+        return dt, dbase, None

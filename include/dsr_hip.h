@@ -1029,6 +1029,69 @@ int dsr_niqe_plane(int dtype, const void* x, int N, int C, int H, int W, int sha
 int dsr_niqe_moments(const float* plane, int N, int hc, int wc, int block, const double* window, double* out, dsr_stream_t s);
 int dsr_niqe_features(const double* m1, const double* m2, int N, int nb, const double* tables, double* feat, dsr_stream_t s);
 
+/* ------------------------------------------------------------------ SRVGGNetCompact (conv_compact.hip, pw_compact.hip)
+ * BasicSR's compact generator (models/GAN/srvgg.py; PARITY UNPINNED, the float64 statement is tests/compact_ref.py).
+ *
+ * dsr_conv_prelu_c_fwd, a body layer: 3x3 / stride 1 / zero-pad 1 from x [N][H][W][64] (16-bit) to y [N][H][W][64] with a
+ * per-channel PReLU, nn.PReLU(num_parameters=64).  w: the packed forward image [9][64][64] of dsr_conv_pack_weight; bias: fp32
+ * [64] or NULL; slope: fp32 [64] ON THE DEVICE, read by every launch (a HIP-graph replay after an optimiser step uses the new
+ * slopes), or NULL for no activation:
+ *     v = sum_taps sum_ci x[n, y+dy, x+dx, ci] * w[c, ci, dy, dx] + bias[c]       fp32 accumulation
+ *     v = v > 0 ? v : v * slope[c]                                                 any sign of slope
+ *     y[n, y, x, c] = r16(v)                                                       one rounding, to nearest even
+ * dsr_conv_shuffle_add_fwd, the tail: the same convolution to Q = C s^2 outputs (s, C in 1..4), stored through PixelShuffle(s)
+ * with the fp32 image `base` [N][C][H][W] (or NULL) added per LR pixel; w: [9][r8(Q)][64], whose pad rows are never stored;
+ * bias: fp32 [Q] or NULL; out: fp32 [N][C][s H][s W]:
+ *     v = sum_taps sum_ci x * w[q] + bias[q];  v = v + base[n, c, y, x];  out[n, c, s y + i, s x + j] = v,  q = c s^2 + i s + j
+ * in fp32 with no 16-bit rounding.
+ * Both: DSR_E_ARG before anything is launched for a NULL x / w / y (out), a bad dtype, N, H or W < 1, an output range that
+ * overlaps x (or base), a tensor of 2^31 bytes or more per image or 2^32 or more in total; s or C outside 1..4 is
+ * DSR_E_UNSUPPORTED.  max_blocks <= 0: one persistent block per CU; > 0 caps the grid (same bits for every value).  The
+ * _supported queries look at the shape fields only; 0 for a NULL argument. */
+typedef struct {
+  int dtype;               /* DSR_BF16 | DSR_F16 */
+  int N, H, W;
+  const void* x;           /* [N][H][W][64] */
+  const void* w;           /* [9][64][64] */
+  const float* bias;       /* [64] or NULL */
+  const float* slope;      /* [64] or NULL */
+  void* y;                 /* [N][H][W][64] */
+  int max_blocks;
+} dsr_compact_conv;
+int dsr_conv_prelu_c_supported(const dsr_compact_conv* c);
+int dsr_conv_prelu_c_fwd(const dsr_compact_conv* c, dsr_stream_t s);
+typedef struct {
+  int dtype;
+  int N, H, W;
+  int C, s;
+  const void* x;           /* [N][H][W][64] */
+  const void* w;           /* [9][r8(C s^2)][64] */
+  const float* bias;       /* [C s^2] or NULL */
+  const float* base;       /* [N][C][H][W] or NULL */
+  float* out;              /* [N][C][s H][s W] */
+  int max_blocks;
+} dsr_compact_tail;
+int dsr_conv_shuffle_add_supported(const dsr_compact_tail* c);
+int dsr_conv_shuffle_add_fwd(const dsr_compact_tail* c, dsr_stream_t s);
+
+/* Pointwise pieces of the composed (training) form.  z, y, dy, dz: 16-bit NHWC [P][Cp], Cp a multiple of 8; slope: fp32 [C],
+ * C <= Cp (pad channels take slope 0).
+ *     dsr_pw_prelu_c_fwd:  y = r16(z > 0 ? z : z * slope[c])
+ *     dsr_pw_prelu_c_bwd:  dz = r16(dy * (z > 0 ? 1 : slope[c]));  dslope[c] = sum_p dy * z * [z <= 0]     (torch's rules at 0)
+ * The mask comes from the stored pre-activation z, so every slope is exact.  partial: fp32 [dsr_pw_prelu_c_rows(P)][Cp]
+ * scratch, row r the sum over one pixel range; dslope [C] adds the rows in a fixed order (dsr_pw_prelu_c_fold_width() rows
+ * side by side): no atomics, two runs give equal bits.  partial and dslope are both NULL (no slope gradient) or both given.
+ * dsr_shuffle_add_f32: out[n][c][s y + i][s x + j] = t[n][c s^2 + i s + j][y][x] + base[n][c][y][x] (base may be NULL), fp32.
+ * dsr_shuffle_add_bwd_f32: dt = the un-shuffle of dout; dbase (or NULL) [n][c][y][x] = sum_{i, j} dout[...], i then j.
+ * A NULL required pointer or a size out of range (s outside 1..4, 2^31 elements or more) is DSR_E_ARG before any launch. */
+int dsr_pw_prelu_c_fwd(int dtype, const void* z, const float* slope, void* y, size_t P, int C, int Cp, dsr_stream_t s);
+int dsr_pw_prelu_c_rows(size_t P);
+int dsr_pw_prelu_c_fold_width(void);
+int dsr_pw_prelu_c_bwd(int dtype, const void* dy, const void* z, const float* slope, void* dz, size_t P, int C, int Cp,
+                       float* partial, float* dslope, dsr_stream_t s);
+int dsr_shuffle_add_f32(const float* t, const float* base, float* out, int N, int C, int s, int H, int W, dsr_stream_t st);
+int dsr_shuffle_add_bwd_f32(const float* dout, float* dt, float* dbase, int N, int C, int s, int H, int W, dsr_stream_t st);
+
 #ifdef __cplusplus
 }
 #endif
