@@ -20,7 +20,8 @@ pytestmark = pytest.mark.gpu
 PKG = "deep-super-resolution_amd"
 SENTINEL = -12345.0
 GUARD = 67
-SHAPES = [(3, 37, 70), (2, 64, 64), (1, 1, 5), (1, 5, 1), (1, 1, 1)]      # (planes, h, w)
+SHAPES = [(3, 37, 70), (2, 64, 64), (1, 1, 5), (1, 5, 1), (1, 1, 1),      # (planes, h, w)
+          (2, 130, 67), (1, 65, 129)]      # 3 x 2 and 2 x 3 tiles of 64 x 64, ragged on both axes: tile rows with a0 > 0
 
 
 def P(sub):

@@ -38,7 +38,7 @@ def test_transforms_invert_and_are_distinct():
                 assert not torch.equal(images[a], images[b]), (a, b)
 
 
-@pytest.mark.parametrize("shape", [(5, 7), (1, 4), (3, 1), (1, 1), (2, 6, 6)])
+@pytest.mark.parametrize("shape", [(5, 7), (1, 4), (3, 1), (1, 1), (2, 6, 6), (2, 130, 67), (1, 65, 129)])
 def test_yardstick_agrees_with_the_gather_table(shape):
     x = torch.arange(int(np.prod(shape)), dtype=torch.float32).reshape(shape)
     for k in range(8):
