@@ -364,6 +364,17 @@ def check(rc):
     return rc
 
 
+def _ptr(t):
+    """One tensor's device pointer as a C argument; None stays None (a NULL argument)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _stream():
+    """torch's current stream on the current device, as the C argument every launching entry point takes."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
 def ptr_table(tensors):
     """HOST table of device pointers for the multi-tensor entry points, one per tensor; None becomes a NULL entry."""
     return (C.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])

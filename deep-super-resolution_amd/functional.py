@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import (ACT_ELU, ACT_LEAKY, ACT_NONE, ACT_PRELU, ACT_RELU, ACT_SIGMOID, ACT_TANH, BF16, F16,  # noqa: F401
-                   FEAT_L1, FEAT_MSE, PAD_REFLECT, PAD_REPLICATE, PAD_ZERO, ConvDesc, Epilogue, check)
+                   FEAT_L1, FEAT_MSE, PAD_REFLECT, PAD_REPLICATE, PAD_ZERO, ConvDesc, Epilogue, _ptr, _stream, check)
 
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
@@ -32,14 +32,6 @@ def _dt(t):
     if t.dtype == torch.float16:
         return F16
     raise TypeError(f"activation dtype must be bfloat16 or float16, got {t.dtype}")
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _need_gpu(t):
@@ -177,8 +169,25 @@ def _out_hw(desc):
     return oh.value, ow.value
 
 
+def _conv_prologue(x, weight, cfg):
+    """What every conv node's forward starts from: (contiguous x, desc, oh, ow, forward image, dgrad image)."""
+    _need_gpu(x)
+    x = x.contiguous()
+    cout, cin, kh, kw = weight.shape
+    desc = make_desc(x, cout, kh, kw, cfg["stride"], cfg["pad"], cfg.get("pad_mode", PAD_ZERO), cin)
+    oh, ow = _out_hw(desc)
+    wf, wd = packed_weights(weight, desc, x.dtype)
+    return x, desc, oh, ow, wf, wd
+
+
 def _scr():
     return _lib.lib().dsr_pw_scratch_rows()
+
+
+def _partials(rows, width, device):
+    """fp32 scratch for `rows` partial rows of `width` floats, with the tail rows that compact_rows (csrc/pointwise.hip)
+    writes behind them when it folds the table."""
+    return torch.empty((rows + _scr()) * width, dtype=torch.float32, device=device)
 
 
 def _reduce_blocks(p):
@@ -465,7 +474,7 @@ def _conv_backward(desc, x, dy, wd, need_dx, need_dw, weight_shape, weight=None,
             y0, scale0, shift0, act0, slope0 = in_link.payload
             rows = lib.dsr_conv_dgrad_bn_rows(C.byref(desc))
             cp = x.shape[-1]
-            part = torch.empty((rows + _scr()) * 3 * cp, dtype=torch.float32, device=x.device)
+            part = _partials(rows, 3 * cp, x.device)
             check(_timed("dgrad", desc, lambda: lib.dsr_conv_dgrad_bn(
                 C.byref(desc), _ptr(dy), _ptr(wd), _ptr(dx), _ptr(y0), _ptr(scale0), _ptr(shift0), act0, slope0, _ptr(part),
                 _stream()), name="conv_dgrad_s2_kernel<bn>"))
@@ -510,11 +519,27 @@ def _colsum(dy, c):
     p = dy.numel() // dy.shape[-1]
     cp = dy.shape[-1]
     blocks, rpb = _reduce_blocks(p)
-    part = torch.empty((blocks + _scr()) * cp, dtype=torch.float32, device=dy.device)
+    part = _partials(blocks, cp, dy.device)
     check(lib.dsr_pw_colsum(_dt(dy), _ptr(dy), p, cp, blocks, rpb, _ptr(part), _stream()))
     out = torch.empty(c, dtype=torch.float32, device=dy.device)
     check(lib.dsr_pw_sum_rows(_ptr(part), blocks, cp, 0, c, 1.0, _ptr(out), 0, 1, _stream()))
     return out
+
+
+def _fold_bias_prelu(part, blocks, cout, cyp, has_bias, has_prelu):
+    """(db, dprelu) of a conv + activation backward from its `blocks` partial rows [bias sums (cyp) | slope sums (cyp)]:
+    fp32 [cout] and [1], each None unless asked for."""
+    lib = _lib.lib()
+    db = dprelu = None
+    if has_bias:
+        db = torch.empty(cout, dtype=torch.float32, device=part.device)
+        check(lib.dsr_pw_sum_rows(_ptr(part), blocks, 2 * cyp, 0, cout, 1.0, _ptr(db), 0, 1, _stream()))
+    if has_prelu:
+        chan = torch.empty(cyp, dtype=torch.float32, device=part.device)
+        check(lib.dsr_pw_sum_rows(_ptr(part), blocks, 2 * cyp, cyp, cyp, 1.0, _ptr(chan), 0, 1, _stream()))
+        dprelu = torch.empty(1, dtype=torch.float32, device=part.device)
+        check(lib.dsr_pw_sum_rows(_ptr(chan), cyp, 1, 0, 1, 1.0, _ptr(dprelu), 0, 0, _stream()))
+    return db, dprelu
 
 
 # ----------------------------------------------------------------------------- layout edges
@@ -584,11 +609,8 @@ class ConvAct(torch.autograd.Function):
         if cfg.get("act", ACT_NONE) == ACT_LEAKY and not float(cfg.get("slope", 0.0)) > 0.0:
             raise ValueError(f"ConvAct: LeakyReLU slope {cfg.get('slope', 0.0)} must be > 0 (the activation gradient is "
                              "derived from the stored output)")
-        x = x.contiguous()
-        cout, cin, kh, kw = weight.shape
-        desc = make_desc(x, cout, kh, kw, cfg["stride"], cfg["pad"], cfg.get("pad_mode", PAD_ZERO), cin)
-        oh, ow = _out_hw(desc)
-        wf, wd = packed_weights(weight, desc, x.dtype)
+        x, desc, oh, ow, wf, wd = _conv_prologue(x, weight, cfg)
+        cout = desc.Cout
         ps = bool(cfg.get("pixel_shuffle", False))
         n = x.shape[0]
         if ps:
@@ -674,14 +696,7 @@ class ConvAct(torch.autograd.Function):
             # the tail's input-gradient launch (dsr_conv_dgrad_ps) already produced the masked, un-shuffled gradient of this
             # layer's conv output and the partial sums; `dout` is a placeholder
             dy, part, blocks = got
-            db = dprelu = None
-            if ctx.has_bias:
-                db = torch.empty(cout, dtype=torch.float32, device=x.device)
-                check(lib.dsr_pw_sum_rows(_ptr(part), blocks, 2 * cyp, 0, cout, 1.0, _ptr(db), 0, 1, _stream()))
-            chan = torch.empty(cyp, dtype=torch.float32, device=x.device)
-            check(lib.dsr_pw_sum_rows(_ptr(part), blocks, 2 * cyp, cyp, cyp, 1.0, _ptr(chan), 0, 1, _stream()))
-            dprelu = torch.empty(1, dtype=torch.float32, device=x.device)
-            check(lib.dsr_pw_sum_rows(_ptr(chan), cyp, 1, 0, 1, 1.0, _ptr(dprelu), 0, 0, _stream()))
+            db, dprelu = _fold_bias_prelu(part, blocks, cout, cyp, ctx.has_bias, True)
         elif kind == "act" and got is not None:
             # the consumer of this layer's output already multiplied dout by act'(y): nothing left to do here
             dy = dout
@@ -694,19 +709,11 @@ class ConvAct(torch.autograd.Function):
             dy = torch.empty((n, oh, ow, cyp), dtype=x.dtype, device=x.device)
             p = n * oh * ow
             blocks, rpb = _reduce_blocks(p)
-            part = torch.empty((blocks + _scr()) * 2 * cyp, dtype=torch.float32, device=x.device) if need_partial else None
+            part = _partials(blocks, 2 * cyp, x.device) if need_partial else None
             check(lib.dsr_pw_act_bwd(_dt(x), _ptr(dout), _ptr(y), _ptr(dy), n, oh, ow, cyp, y.shape[-1], int(ctx.ps),
                                      ctx.act, float(ctx.cfg.get("slope", 0.0)), _ptr(prelu), blocks, rpb, _ptr(part),
                                      _stream()))
-            db = dprelu = None
-            if ctx.has_bias:
-                db = torch.empty(cout, dtype=torch.float32, device=x.device)
-                check(lib.dsr_pw_sum_rows(_ptr(part), blocks, 2 * cyp, 0, cout, 1.0, _ptr(db), 0, 1, _stream()))
-            if prelu is not None:
-                chan = torch.empty(cyp, dtype=torch.float32, device=x.device)
-                check(lib.dsr_pw_sum_rows(_ptr(part), blocks, 2 * cyp, cyp, cyp, 1.0, _ptr(chan), 0, 1, _stream()))
-                dprelu = torch.empty(1, dtype=torch.float32, device=x.device)
-                check(lib.dsr_pw_sum_rows(_ptr(chan), cyp, 1, 0, 1, 1.0, _ptr(dprelu), 0, 0, _stream()))
+            db, dprelu = _fold_bias_prelu(part, blocks, cout, cyp, ctx.has_bias, prelu is not None)
         dx, dw = _conv_backward(desc, x, dy, wd, ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.wshape,
                                  getattr(ctx, "weight_ref", None), in_link=ctx.cfg.get("in_link"))
         return dx, dw, db, dprelu, None
@@ -742,6 +749,56 @@ def _first2_backward(ctx, desc, x, dy, wd):
     return dx
 
 
+# ----------------------------------------------------------------------------- the BatchNorm recipe of ConvBNAct and BNAct
+def _bn_vectors(cp, dev):
+    """Uninitialised (scale, shift, mean, rstd), fp32 [cp] each."""
+    return tuple(torch.empty(cp, dtype=torch.float32, device=dev) for _ in range(4))
+
+
+def _bn_finalize(part, rows, cout, cp, count, gamma, beta, running_mean, running_var, nbt, cfg, vectors):
+    """Train mode: `rows` partial rows of per-channel sum / sum of squares over `count` pixels -> the affine map and the batch
+    statistics in `vectors` (scale, shift, mean, rstd), and the running statistics advanced like nn.BatchNorm2d's."""
+    scale, shift, mean, rstd = vectors
+    check(_lib.lib().dsr_pw_bn_finalize(_ptr(part), rows, cp, cout, cp, float(count), _ptr(gamma), _ptr(beta),
+                                        _ptr(running_mean), _ptr(running_var), _ptr(nbt), BN_MOMENTUM, BN_EPS,
+                                        int(cfg.get("bn_updates", 1)),
+                                        _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd), _stream()))
+    bump(running_mean)       # rewritten through their raw pointers: whatever is keyed on them (the inference
+    bump(running_var)        # affine map ConvBNAct keeps with running_mean) must see a new version
+
+
+def _bn_eval_affine(gamma, beta, running_mean, running_var, cout, cp, vectors):
+    """Eval mode: the fixed affine map of the running statistics into `vectors` (scale, shift, mean, rstd)."""
+    scale, shift, mean, rstd = vectors
+    check(_lib.lib().dsr_pw_bn_eval_affine(_ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), BN_EPS,
+                                           cout, cp, _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd), _stream()))
+
+
+def _bn_act_backward(dout, y, scale, shift, mean, rstd, p, c, cp, act, slope, prelu, train, part_rows=None):
+    """Backward of act(BN(y)) over p pixels: (dy, dgamma, dbeta, dprelu).  `part_rows` = (part, rows): the partial sums that
+    another launch already formed (Handover "bn"); without it they come from this recipe's own reduce pass."""
+    lib = _lib.lib()
+    dev, dt = y.device, _dt(y)
+    c1 = torch.empty(cp, dtype=torch.float32, device=dev)
+    c2 = torch.empty(cp, dtype=torch.float32, device=dev)
+    dgamma = torch.empty(c, dtype=torch.float32, device=dev)
+    dbeta = torch.empty(c, dtype=torch.float32, device=dev)
+    dprelu = torch.empty(1, dtype=torch.float32, device=dev) if prelu is not None else None
+    if part_rows is not None:
+        part, blocks = part_rows
+    else:
+        blocks, rpb = _bn_bwd_blocks(p, act)
+        part = _partials(blocks, 3 * cp, dev)
+        check(lib.dsr_pw_bn_act_bwd_reduce(dt, _ptr(dout), _ptr(y), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd), p, cp,
+                                           blocks, rpb, act, slope, _ptr(prelu), _ptr(part), _stream()))
+    check(lib.dsr_pw_bn_bwd_finalize(_ptr(part), blocks, c, cp, float(p), _ptr(mean), _ptr(rstd), _ptr(dgamma), _ptr(dbeta),
+                                     _ptr(dprelu), _ptr(c1), _ptr(c2), _stream()))
+    dy = torch.empty_like(y)
+    check(lib.dsr_pw_bn_act_bwd_apply(dt, _ptr(dout), _ptr(y), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd), _ptr(c1),
+                                      _ptr(c2), _ptr(dy), p, cp, act, slope, _ptr(prelu), int(train), _stream()))
+    return dy, dgamma, dbeta, dprelu
+
+
 # ----------------------------------------------------------------------------- conv + BatchNorm + activation (+ residual)
 class ConvBNAct(torch.autograd.Function):
     """out = act(BN(conv(x, W) + b)) [+ residual]   (train or eval mode BatchNorm2d).
@@ -761,22 +818,15 @@ class ConvBNAct(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, nbt, prelu, residual, cfg):
-        _need_gpu(x)
+        x, desc, oh, ow, wf, wd = _conv_prologue(x, weight, cfg)
         lib = _lib.lib()
-        x = x.contiguous()
-        cout, cin, kh, kw = weight.shape
-        desc = make_desc(x, cout, kh, kw, cfg["stride"], cfg["pad"], cfg.get("pad_mode", PAD_ZERO), cin)
-        oh, ow = _out_hw(desc)
-        wf, wd = packed_weights(weight, desc, x.dtype)
+        cout = desc.Cout
         n = x.shape[0]
         cp = r8(cout)
         train = bool(cfg["train"])
         dev = x.device
         y = torch.empty((n, oh, ow, cp), dtype=x.dtype, device=dev)
-        scale = torch.empty(cp, dtype=torch.float32, device=dev)
-        shift = torch.empty(cp, dtype=torch.float32, device=dev)
-        mean = torch.empty(cp, dtype=torch.float32, device=dev)
-        rstd = torch.empty(cp, dtype=torch.float32, device=dev)
+        scale, shift, mean, rstd = vectors = _bn_vectors(cp, dev)
         count = n * oh * ow
         in_link = cfg.get("in_link")
         if train and in_link is not None and in_link.kind == "first2":
@@ -787,30 +837,25 @@ class ConvBNAct(torch.autograd.Function):
             d0 = make_desc(img, w0.shape[0], 3, 3, 1, 1, PAD_ZERO, w0.shape[1])
             wf0, _ = packed_weights(w0, d0, x.dtype)
             rows = lib.dsr_conv_first2_stats_rows(C.byref(d0))
-            part = torch.empty((rows + _scr()) * 2 * cp, dtype=torch.float32, device=dev)
+            part = _partials(rows, 2 * cp, dev)
             keep = not cfg.get("infer", False)
             check(_timed("fwd", desc, lambda: lib.dsr_conv_first2_fwd(
                 C.byref(d0), C.byref(desc), _ptr(img), _ptr(wf0), _ptr(b0.detach() if b0 is not None else None), float(slope0),
                 _ptr(wf), _ptr(bias), _ptr(x) if keep else None, _ptr(y), _ptr(part), _stream()), name="conv_first2_kernel"))
         elif train:
             rows = lib.dsr_conv_stats_rows(C.byref(desc))
-            part = torch.empty((rows + _scr()) * 2 * cp, dtype=torch.float32, device=dev)
+            part = _partials(rows, 2 * cp, dev)
             ep = Epilogue(ACT_NONE, 0.0, None, _ptr(bias), _ptr(part), 0, None)
             check(_timed("fwd", desc, lambda: lib.dsr_conv_fwd(C.byref(desc), _ptr(x), _ptr(wf), C.byref(ep), _ptr(y),
                                                                  _stream()), ep))
         if train:
-            check(lib.dsr_pw_bn_finalize(_ptr(part), rows, cp, cout, cp, float(count), _ptr(gamma), _ptr(beta),
-                                         _ptr(running_mean), _ptr(running_var), _ptr(nbt), BN_MOMENTUM, BN_EPS,
-                                         int(cfg.get("bn_updates", 1)),
-                                         _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd), _stream()))
-            bump(running_mean)       # rewritten through their raw pointers: whatever is keyed on them (the inference
-            bump(running_var)        # affine map kept with running_mean, below) must see a new version
+            _bn_finalize(part, rows, cout, cp, count, gamma, beta, running_mean, running_var, nbt, cfg, vectors)
         else:
             infer = cfg.get("infer", False) and lib.dsr_conv_fwd_affine_supported(C.byref(desc))
             # inference: the affine map of an eval-mode BatchNorm changes only when its four tensors do -- keep it with the
             # running mean, keyed by their version counters (33 launches of ~3 us per x8 forward otherwise)
             # (_version(p) = torch's counter + the counter bump() advances when a HIP launch rewrites p through its raw
-            #  pointer -- FusedAdam for gamma / beta, the train-mode finalize below for the running statistics -- + the address)
+            #  pointer -- FusedAdam for gamma / beta, the train-mode _bn_finalize for the running statistics -- + the address)
             key = (_version(gamma), _version(beta), _version(running_mean), _version(running_var), str(dev))
             capturing = torch.cuda.is_current_stream_capturing()
             # a capture never takes the kept map: the graph would replay yesterday's scale / shift whatever the statistics
@@ -821,8 +866,7 @@ class ConvBNAct(torch.autograd.Function):
                 if hit[4] != torch.cuda.current_stream(dev).cuda_stream:
                     torch.cuda.current_stream(dev).wait_event(hit[3])      # computed on another stream
             else:
-                check(lib.dsr_pw_bn_eval_affine(_ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), BN_EPS,
-                                                cout, cp, _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd), _stream()))
+                _bn_eval_affine(gamma, beta, running_mean, running_var, cout, cp, vectors)
                 if infer and not capturing:
                     ev = torch.cuda.Event()
                     ev.record()
@@ -867,36 +911,15 @@ class ConvBNAct(torch.autograd.Function):
     def backward(ctx, dout, dcarry=None):
         x, y, wd, scale, shift, mean, rstd, prelu = ctx.saved_tensors
         prelu = prelu if prelu.numel() else None
-        lib = _lib.lib()
         desc = ctx.desc
         dout = dout.contiguous()
         cout = desc.Cout
-        cp = y.shape[-1]
-        dev = x.device
-        p = ctx.count
-        slope = float(ctx.cfg.get("slope", 0.0))
-        c1 = torch.empty(cp, dtype=torch.float32, device=dev)
-        c2 = torch.empty(cp, dtype=torch.float32, device=dev)
-        dgamma = torch.empty(cout, dtype=torch.float32, device=dev)
-        dbeta = torch.empty(cout, dtype=torch.float32, device=dev)
-        dprelu = torch.empty(1, dtype=torch.float32, device=dev) if prelu is not None else None
         out_link = ctx.cfg.get("out_link")
+        # (a deposit: the launch that produced `dout` -- the next layer's input gradient, dsr_conv_dgrad_bn -- formed the
+        #  BatchNorm-backward sums already, and the reduce pass is skipped)
         got = out_link.collect(dout) if out_link is not None else None
-        if got is not None:
-            # the launch that produced `dout` (the next layer's input gradient, dsr_conv_dgrad_bn) formed the two sums already
-            part, blocks = got
-        else:
-            blocks, rpb = _bn_bwd_blocks(p, ctx.act)
-            part = torch.empty((blocks + _scr()) * 3 * cp, dtype=torch.float32, device=dev)
-            check(lib.dsr_pw_bn_act_bwd_reduce(_dt(x), _ptr(dout), _ptr(y), _ptr(scale), _ptr(shift), _ptr(mean),
-                                               _ptr(rstd), p, cp, blocks, rpb, ctx.act, slope, _ptr(prelu), _ptr(part),
-                                               _stream()))
-        check(lib.dsr_pw_bn_bwd_finalize(_ptr(part), blocks, cout, cp, float(p), _ptr(mean), _ptr(rstd), _ptr(dgamma),
-                                         _ptr(dbeta), _ptr(dprelu), _ptr(c1), _ptr(c2), _stream()))
-        dy = torch.empty_like(y)
-        check(lib.dsr_pw_bn_act_bwd_apply(_dt(x), _ptr(dout), _ptr(y), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd),
-                                          _ptr(c1), _ptr(c2), _ptr(dy), p, cp, ctx.act, slope, _ptr(prelu),
-                                          int(ctx.train), _stream()))
+        dy, dgamma, dbeta, dprelu = _bn_act_backward(dout, y, scale, shift, mean, rstd, ctx.count, cout, y.shape[-1], ctx.act,
+                                                     float(ctx.cfg.get("slope", 0.0)), prelu, ctx.train, got)
         fused = _first2_backward(ctx, desc, x, dy, wd) if dcarry is None else None
         if fused is not None:
             # the input gradient (of the image layer's activation) was consumed where it was formed: autograd gets a
@@ -923,13 +946,8 @@ class ConvOutNCHW(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, cfg):
-        _need_gpu(x)
-        x = x.contiguous()
-        cout, cin, kh, kw = weight.shape
-        desc = make_desc(x, cout, kh, kw, cfg["stride"], cfg["pad"], cfg.get("pad_mode", PAD_ZERO), cin)
-        oh, ow = _out_hw(desc)
-        wf, wd = packed_weights(weight, desc, x.dtype)
-        out = torch.empty((x.shape[0], cout, oh, ow), dtype=torch.float32, device=x.device)
+        x, desc, oh, ow, wf, wd = _conv_prologue(x, weight, cfg)
+        out = torch.empty((x.shape[0], desc.Cout, oh, ow), dtype=torch.float32, device=x.device)
         act = cfg.get("act", ACT_NONE)
         ep = Epilogue(act, 0.0, None, _ptr(bias), None, 0, _ptr(out))
         check(_timed("fwd", desc, lambda: _lib.lib().dsr_conv_fwd(C.byref(desc), _ptr(x), _ptr(wf), C.byref(ep), None,
@@ -961,7 +979,7 @@ class ConvOutNCHW(torch.autograd.Function):
             n_, h_, w_, _ = x.shape
             rows = lib.dsr_conv_dgrad_ps_rows(C.byref(desc))
             dyu = torch.empty((n_, h_ // 2, w_ // 2, 256), dtype=x.dtype, device=x.device)
-            part = torch.empty((rows + _scr()) * 2 * 256, dtype=torch.float32, device=x.device)
+            part = _partials(rows, 2 * 256, x.device)
             check(_timed("dgrad", desc, lambda: lib.dsr_conv_dgrad_ps(C.byref(desc), _ptr(dy), _ptr(wd), _ptr(x), _ptr(link.payload[0]),
                                                                        _ptr(dyu), _ptr(part), _stream()),
                          name="conv_dgrad_toeplitz9_kernel<ps>"))
@@ -1361,6 +1379,24 @@ class ScaleLossDevice(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------- feature-space loss taps
+def _content_forward(f, t, p, cp, mode, want_relu, count):
+    """The content term of a tap: (x_next, value) with value = sum |f - t| or (f - t)^2 over the p x cp map, divided by
+    `count`; x_next = max(f, 0), a new tensor written by the same pass, when want_relu and None otherwise."""
+    lib = _lib.lib()
+    blocks = lib.dsr_featloss_blocks(p)
+    part = torch.empty(max(blocks, 1), dtype=torch.float32, device=f.device)
+    x_next = torch.empty_like(f) if want_relu else None
+    check(lib.dsr_featloss_tap_fwd(_dt(f), _ptr(f), _ptr(t), _ptr(x_next), p, cp, mode, _ptr(part), _stream()))
+    value = torch.empty(1, dtype=torch.float32, device=f.device)
+    check(lib.dsr_featloss_fold(_ptr(part), blocks, float(count), _ptr(value), _stream()))
+    return x_next, value
+
+
+def _scalar_grad(g, device):
+    """The gradient of a one-element value as the contiguous fp32 [1] tensor the backward launches read; zeros for None."""
+    return torch.zeros(1, dtype=torch.float32, device=device) if g is None else g.reshape(1).contiguous().float()
+
+
 class FeatureTap(torch.autograd.Function):
     """One tap of a feature-space loss on the 16-bit NHWC map where it lives (csrc/featloss.hip).
 
@@ -1383,13 +1419,7 @@ class FeatureTap(torch.autograd.Function):
         n, h, w, cp = f.shape
         p = n * h * w
         count = p * (cp if c is None else int(c))
-        lib = _lib.lib()
-        blocks = lib.dsr_featloss_blocks(p)
-        part = torch.empty(max(blocks, 1), dtype=torch.float32, device=f.device)
-        x_next = torch.empty_like(f) if want_relu else None
-        check(lib.dsr_featloss_tap_fwd(_dt(f), _ptr(f), _ptr(t), _ptr(x_next), p, cp, mode, _ptr(part), _stream()))
-        value = torch.empty(1, dtype=torch.float32, device=f.device)
-        check(lib.dsr_featloss_fold(_ptr(part), blocks, float(count), _ptr(value), _stream()))
+        x_next, value = _content_forward(f, t, p, cp, mode, want_relu, count)
         ctx.mode, ctx.masked, ctx.coef, ctx.pc = mode, bool(want_relu), 1.0 / count, (p, cp)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(f, t)
@@ -1400,11 +1430,9 @@ class FeatureTap(torch.autograd.Function):
         f, t = ctx.saved_tensors
         if not ctx.needs_input_grad[0] or (d_next is None and g_value is None):
             return None, None, None, None, None
-        if g_value is None:
-            if not ctx.masked:
-                return d_next, None, None, None, None
-            g_value = torch.zeros(1, dtype=torch.float32, device=f.device)     # only the mask is left to apply
-        g = g_value.reshape(1).contiguous().float()
+        if g_value is None and not ctx.masked:
+            return d_next, None, None, None, None
+        g = _scalar_grad(g_value, f.device)      # (None: only the mask is left to apply)
         if d_next is not None:
             d_next = d_next.contiguous()
         p, cp = ctx.pc
@@ -1463,12 +1491,7 @@ class FeatureStyleTap(torch.autograd.Function):
             if t is None or f.shape != t.shape or f.dtype != t.dtype:
                 raise RuntimeError("FeatureStyleTap: with_content needs a target map of f's shape and dtype")
             t = t.contiguous()
-            blocks = lib.dsr_featloss_blocks(p)
-            part = torch.empty(max(blocks, 1), dtype=torch.float32, device=f.device)
-            x_next = torch.empty_like(f) if want_relu else None
-            check(lib.dsr_featloss_tap_fwd(_dt(f), _ptr(f), _ptr(t), _ptr(x_next), p, cp, mode, _ptr(part), _stream()))
-            content = torch.empty(1, dtype=torch.float32, device=f.device)
-            check(lib.dsr_featloss_fold(_ptr(part), blocks, float(p * c), _ptr(content), _stream()))
+            x_next, content = _content_forward(f, t, p, cp, mode, want_relu, p * c)
         else:
             t = None
             if want_relu:
@@ -1496,12 +1519,8 @@ class FeatureStyleTap(torch.autograd.Function):
             return none
         if g_content is None and g_style is None and not ctx.masked:
             return (d_next,) + none[1:]
-
-        def scalar(g):
-            return torch.zeros(1, dtype=torch.float32, device=f.device) if g is None else g.reshape(1).contiguous().float()
-
-        gs = scalar(g_style)
-        gc = None if t is None else scalar(g_content)
+        gs = _scalar_grad(g_style, f.device)
+        gc = None if t is None else _scalar_grad(g_content, f.device)
         if d_next is not None:
             d_next = d_next.contiguous()
         n, hw, cp = ctx.dims
@@ -1788,67 +1807,36 @@ class MaxPool2(torch.autograd.Function):
         return (dx, None) if ctx.nin == 2 else dx
 
 
-class AvgPool2(torch.autograd.Function):
-    """nn.AvgPool2d(2, 2) on NHWC: conv(..., downsample_mode='avg') of models/DIP/utils.py:86-94."""
+def _resample2x(name, fwd, bwd, up, doc):
+    """The autograd Function `name` of a 2x resampler on NHWC that needs nothing but the input's shape for its backward.
+    `fwd`, `bwd`: its entry points, both (dt, src, dst, n, h, w, cp, stream) with the INPUT's h and w; `up`: the output is
+    2h x 2w, otherwise h/2 x w/2."""
 
-    @staticmethod
     def forward(ctx, x):
         x = x.contiguous()
         n, h, w, cp = x.shape
-        y = torch.empty((n, h // 2, w // 2, cp), dtype=x.dtype, device=x.device)
-        check(_lib.lib().dsr_avgpool2_fwd(_dt(x), _ptr(x), _ptr(y), n, h, w, cp, _stream()))
+        y = torch.empty((n, 2 * h, 2 * w, cp) if up else (n, h // 2, w // 2, cp), dtype=x.dtype, device=x.device)
+        check(getattr(_lib.lib(), fwd)(_dt(x), _ptr(x), _ptr(y), n, h, w, cp, _stream()))
         ctx.shape = (n, h, w, cp)
         return y
 
-    @staticmethod
     def backward(ctx, dy):
         n, h, w, cp = ctx.shape
         dy = dy.contiguous()
         dx = torch.empty((n, h, w, cp), dtype=dy.dtype, device=dy.device)
-        check(_lib.lib().dsr_avgpool2_bwd(_dt(dy), _ptr(dy), _ptr(dx), n, h, w, cp, _stream()))
+        check(getattr(_lib.lib(), bwd)(_dt(dy), _ptr(dy), _ptr(dx), n, h, w, cp, _stream()))
         return dx
 
-
-class Nearest2x(torch.autograd.Function):
-    """nn.Upsample(scale_factor=2, mode='nearest') on NHWC (models/DIP/skip.py:77, skip()'s default mode)."""
-
-    @staticmethod
-    def forward(ctx, x):
-        x = x.contiguous()
-        n, h, w, cp = x.shape
-        y = torch.empty((n, 2 * h, 2 * w, cp), dtype=x.dtype, device=x.device)
-        check(_lib.lib().dsr_nearest2x_fwd(_dt(x), _ptr(x), _ptr(y), n, h, w, cp, _stream()))
-        ctx.shape = (n, h, w, cp)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        n, h, w, cp = ctx.shape
-        dy = dy.contiguous()
-        dx = torch.empty((n, h, w, cp), dtype=dy.dtype, device=dy.device)
-        check(_lib.lib().dsr_nearest2x_bwd(_dt(dy), _ptr(dy), _ptr(dx), n, h, w, cp, _stream()))
-        return dx
+    return type(name, (torch.autograd.Function,),
+                {"__doc__": doc, "forward": staticmethod(forward), "backward": staticmethod(backward)})
 
 
-class Bilinear2x(torch.autograd.Function):
-    """nn.Upsample(scale_factor=2, mode='bilinear') (align_corners=False) on NHWC (models/DIP/skip.py:77)."""
-
-    @staticmethod
-    def forward(ctx, x):
-        x = x.contiguous()
-        n, h, w, cp = x.shape
-        y = torch.empty((n, 2 * h, 2 * w, cp), dtype=x.dtype, device=x.device)
-        check(_lib.lib().dsr_bilinear2x_fwd(_dt(x), _ptr(x), _ptr(y), n, h, w, cp, _stream()))
-        ctx.shape = (n, h, w, cp)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        n, h, w, cp = ctx.shape
-        dy = dy.contiguous()
-        dx = torch.empty((n, h, w, cp), dtype=dy.dtype, device=dy.device)
-        check(_lib.lib().dsr_bilinear2x_bwd(_dt(dy), _ptr(dy), _ptr(dx), n, h, w, cp, _stream()))
-        return dx
+AvgPool2 = _resample2x("AvgPool2", "dsr_avgpool2_fwd", "dsr_avgpool2_bwd", False,
+                       """nn.AvgPool2d(2, 2) on NHWC: conv(..., downsample_mode='avg') of models/DIP/utils.py:86-94.""")
+Nearest2x = _resample2x("Nearest2x", "dsr_nearest2x_fwd", "dsr_nearest2x_bwd", True,
+                        """nn.Upsample(scale_factor=2, mode='nearest') on NHWC (models/DIP/skip.py:77, skip()'s default mode).""")
+Bilinear2x = _resample2x("Bilinear2x", "dsr_bilinear2x_fwd", "dsr_bilinear2x_bwd", True,
+                         """nn.Upsample(scale_factor=2, mode='bilinear') (align_corners=False) on NHWC (models/DIP/skip.py:77).""")
 
 
 class ResizeNorm(torch.autograd.Function):
@@ -2281,23 +2269,14 @@ class BNAct(torch.autograd.Function):
         p = x.numel() // cp
         dev = x.device
         train = bool(cfg["train"])
-        scale = torch.empty(cp, dtype=torch.float32, device=dev)
-        shift = torch.empty(cp, dtype=torch.float32, device=dev)
-        mean = torch.empty(cp, dtype=torch.float32, device=dev)
-        rstd = torch.empty(cp, dtype=torch.float32, device=dev)
+        scale, shift, mean, rstd = vectors = _bn_vectors(cp, dev)
         if train:
             blocks, rpb = _reduce_blocks(p)
-            part = torch.empty((blocks + _scr()) * 2 * cp, dtype=torch.float32, device=dev)
+            part = _partials(blocks, 2 * cp, dev)
             check(lib.dsr_pw_channel_stats(_dt(x), _ptr(x), p, cp, blocks, rpb, _ptr(part), _stream()))
-            check(lib.dsr_pw_bn_finalize(_ptr(part), blocks, cp, c, cp, float(p), _ptr(gamma), _ptr(beta),
-                                         _ptr(running_mean), _ptr(running_var), _ptr(nbt), BN_MOMENTUM, BN_EPS,
-                                         int(cfg.get("bn_updates", 1)),
-                                         _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd), _stream()))
-            bump(running_mean)
-            bump(running_var)
+            _bn_finalize(part, blocks, c, cp, p, gamma, beta, running_mean, running_var, nbt, cfg, vectors)
         else:
-            check(lib.dsr_pw_bn_eval_affine(_ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), BN_EPS, c,
-                                            cp, _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd), _stream()))
+            _bn_eval_affine(gamma, beta, running_mean, running_var, c, cp, vectors)
         act = cfg.get("act", ACT_NONE)
         out = torch.empty_like(x)
         check(lib.dsr_pw_bn_act_fwd(_dt(x), _ptr(x), _ptr(scale), _ptr(shift), None, _ptr(out), p, cp, act,
@@ -2309,26 +2288,8 @@ class BNAct(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         x, scale, shift, mean, rstd = ctx.saved_tensors
-        lib = _lib.lib()
-        dout = dout.contiguous()
-        cp = x.shape[-1]
-        dev = x.device
-        p, c = ctx.p, ctx.c
-        slope = float(ctx.cfg.get("slope", 0.0))
-        c1 = torch.empty(cp, dtype=torch.float32, device=dev)
-        c2 = torch.empty(cp, dtype=torch.float32, device=dev)
-        dgamma = torch.empty(c, dtype=torch.float32, device=dev)
-        dbeta = torch.empty(c, dtype=torch.float32, device=dev)
-        blocks, rpb = _bn_bwd_blocks(p, ctx.act)
-        part = torch.empty((blocks + _scr()) * 3 * cp, dtype=torch.float32, device=dev)
-        check(lib.dsr_pw_bn_act_bwd_reduce(_dt(x), _ptr(dout), _ptr(x), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd),
-                                           p, cp, blocks, rpb, ctx.act, slope, None, _ptr(part), _stream()))
-        check(lib.dsr_pw_bn_bwd_finalize(_ptr(part), blocks, c, cp, float(p), _ptr(mean), _ptr(rstd), _ptr(dgamma),
-                                         _ptr(dbeta), None, _ptr(c1), _ptr(c2), _stream()))
-        dx = torch.empty_like(x)
-        check(lib.dsr_pw_bn_act_bwd_apply(_dt(x), _ptr(dout), _ptr(x), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd),
-                                          _ptr(c1), _ptr(c2), _ptr(dx), p, cp, ctx.act, slope, None, int(ctx.train),
-                                          _stream()))
+        dx, dgamma, dbeta, _ = _bn_act_backward(dout.contiguous(), x, scale, shift, mean, rstd, ctx.p, ctx.c, x.shape[-1], ctx.act,
+                                                float(ctx.cfg.get("slope", 0.0)), None, ctx.train)
         return dx, dgamma, dbeta, None, None, None, None, None
 
 

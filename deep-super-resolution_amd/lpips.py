@@ -49,7 +49,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import ACT_RELU, BF16, F16, PAD_ZERO, ConvDesc, Epilogue, check
+from ._lib import ACT_RELU, BF16, F16, PAD_ZERO, ConvDesc, Epilogue, _ptr, _stream, check
 
 SHIFT = (-.030, -.088, -.188)
 SCALE = (.458, .448, .450)
@@ -141,14 +141,6 @@ def _decode_key(k):
     k &= 0xFFFFFFFF
     bits = (k ^ 0x80000000) if k & 0x80000000 else (~k & 0xFFFFFFFF)
     return struct.unpack("<f", struct.pack("<I", bits))[0]
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 # ----------------------------------------------------------------------------- the module

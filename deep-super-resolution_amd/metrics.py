@@ -66,18 +66,10 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import check
+from ._lib import _ptr, _stream, check
 
 _WIN = 11
 _REDUCTIONS = ("elementwise_mean", "sum", "none", None)
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _check_pair(name, preds, target):

@@ -9,6 +9,7 @@ realesrgan_step : the GAN stage of Real-ESRGAN (L1 + VGG features + a logits GAN
 esrgan_step : the GAN stage of ESRGAN (the same terms under the relativistic average discriminator, five D forwards).
 dip_step   : DIP.py:47-95 closure + utils/DIP.py:33-40 Adam iteration.
 """
+import contextlib
 import os
 
 import torch
@@ -31,6 +32,19 @@ def _backward_and_step(loss, opt, scaler, ema=None):
         if ema is not None:
             ema.update(scaler)
         scaler.update()
+
+
+@contextlib.contextmanager
+def _requires_grad(params, flag):
+    """Every parameter's requires_grad set to `flag` inside the block; the flags found on entry are put back on exit."""
+    was = [p.requires_grad for p in params]
+    for p in params:
+        p.requires_grad_(flag)
+    try:
+        yield
+    finally:
+        for p, r in zip(params, was):
+            p.requires_grad_(r)
 
 
 def gen_l1_step(gen, opt, lr_patches, hr_patches, *, scaler=None, ema=None):
@@ -250,11 +264,8 @@ def realesrgan_step(gen, disc, vggfeat, opt_g, opt_d, lq, gt, *, l1_weight=1.0, 
         with torch.no_grad():
             fake_ema = gen_ema(lq)
     d_params = [p for p in disc.parameters()]
-    was = [p.requires_grad for p in d_params]
     # --- generator
-    for p in d_params:
-        p.requires_grad_(False)
-    try:
+    with _requires_grad(d_params, False):
         opt_g.zero_grad()
         fake = gen(lq)
         l_pix = F.l1_loss(fake, l1_gt)
@@ -271,13 +282,8 @@ def realesrgan_step(gen, disc, vggfeat, opt_g, opt_d, lq, gt, *, l1_weight=1.0, 
             ema.update()
             if ldl > 0.0:
                 ema.copy_to(gen_ema)
-    finally:
-        for p, r in zip(d_params, was):
-            p.requires_grad_(r)
     # --- discriminator
-    for p in d_params:
-        p.requires_grad_(True)
-    try:
+    with _requires_grad(d_params, True):
         opt_d.zero_grad()
         l_d_real = F.gan_loss(disc(gan_gt), True, gan_type, is_disc=True)
         with F.batched_wgrad():
@@ -286,9 +292,6 @@ def realesrgan_step(gen, disc, vggfeat, opt_g, opt_d, lq, gt, *, l1_weight=1.0, 
         with F.batched_wgrad():
             l_d_fake.backward()
         opt_d.step()
-    finally:
-        for p, r in zip(d_params, was):
-            p.requires_grad_(r)
     out = (l_pix.detach(), l_percep.detach(), l_g_gan.detach(), l_d_real.detach(), l_d_fake.detach(), fake.detach())
     return out + (l_g_ldl.detach(),) if ldl > 0.0 else out
 
@@ -315,11 +318,8 @@ def esrgan_step(gen, disc, vggfeat, opt_g, opt_d, lq, gt, *, l1_weight=1e-2, gan
     One stream, no host read: usable inside GraphedStep with a FusedAdam for each optimiser."""
     rel = F.relativistic_gan_loss
     d_params = [p for p in disc.parameters()]
-    was = [p.requires_grad for p in d_params]
     # --- generator
-    for p in d_params:
-        p.requires_grad_(False)
-    try:
+    with _requires_grad(d_params, False):
         opt_g.zero_grad()
         fake = gen(lq)
         l_pix = F.l1_loss(fake, gt)
@@ -340,13 +340,8 @@ def esrgan_step(gen, disc, vggfeat, opt_g, opt_d, lq, gt, *, l1_weight=1e-2, gan
         opt_g.step()
         if ema is not None:
             ema.update()
-    finally:
-        for p, r in zip(d_params, was):
-            p.requires_grad_(r)
     # --- discriminator
-    for p in d_params:
-        p.requires_grad_(True)
-    try:
+    with _requires_grad(d_params, True):
         opt_d.zero_grad()
         fake_det = fake.detach()
         with torch.no_grad():
@@ -360,9 +355,6 @@ def esrgan_step(gen, disc, vggfeat, opt_g, opt_d, lq, gt, *, l1_weight=1e-2, gan
         with F.batched_wgrad():
             l_d_fake.backward()
         opt_d.step()
-    finally:
-        for p, r in zip(d_params, was):
-            p.requires_grad_(r)
     return l_pix.detach(), l_percep.detach(), l_g_gan.detach(), l_d_real.detach(), l_d_fake.detach(), fake_det
 
 
