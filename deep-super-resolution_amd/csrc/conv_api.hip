@@ -184,7 +184,8 @@ static ConvPlan plan_fwd(const dsr_conv_desc* d, const dsr_epilogue* e) {
       (e->act == DSR_ACT_NONE || e->act == DSR_ACT_RELU || e->act == DSR_ACT_LEAKY) &&
       dsr_halo64_supported(d->KH, d->KW, d->stride, d->pad, d->pad_mode, d->H, d->W, r8(d->Cin), d->Cout))
     return {ConvKernel::Halo64};
-  if (((is_c64(d) && !e->pixel_shuffle) || is_c64_wide(d)) && !e->out_nchw_f32)
+  // (PixelShuffle on conv_c64 is one 64-channel slice per sub-pixel: 64 -> 256 only, the shape every model here has)
+  if (((is_c64(d) && !e->pixel_shuffle) || (is_c64_wide(d) && (!e->pixel_shuffle || d->Cout == 256))) && !e->out_nchw_f32)
     return {ConvKernel::C64, dsr_c64_mode(fwd_flags(e), e->act, d->Cout)};
   if (is_rgb9(d, e)) return {ConvKernel::Rgb9};
   if (is_cin8(d, e)) return {ConvKernel::Cin8};

@@ -68,16 +68,21 @@ __global__ __launch_bounds__(256, 2) void conv_c64_kernel(const C64Args a) {
   // Two accumulator layouts (uniform per launch).  Launches that emit BatchNorm statistics keep pixels on the MFMA's M
   // axis: a lane then holds 4 PIXELS of one channel and the per-channel sums need two cross-row shuffles.  All other
   // launches swap the operands (weights on M): a lane holds 4 consecutive CHANNELS of one pixel, which leave as one
-  // 8-byte LDS write after two packed conversions instead of four 2-byte writes.  For PixelShuffle(2) launches the
-  // weight rows of each 16-channel tile are taken in the order m -> 4 (m & 3) + (m >> 2), so that those 4 values are
-  // the 4 consecutive output channels of ONE sub-pixel (conv channel 4c + s -> sub-pixel s, channel c).
+  // 8-byte LDS write after two packed conversions instead of four 2-byte writes.
+  // PixelShuffle(2) launches (64 -> 256 only: plan_fwd sends no other here) give slice s = blockIdx.y the conv channels
+  // {4c + s : c = 0..63}, i.e. all 64 output channels of sub-pixel s = (sy, sx): the slice gathers its weight rows and
+  // bias with stride 4 from the unchanged packed image, keeps the plain C-tile layout and stores whole 128-byte output
+  // pixels at (2y + sy, 2x + sx).  (A slice of 64 CONSECUTIVE conv channels is 16 channels x 4 sub-pixels: 32-byte pieces
+  // of four different output pixels, every 128-byte line assembled from four blocks.)  Conv channel of this slice's
+  // local channel c: cbase + cmul * c.
   constexpr bool FOLD = MODE == 2;
   constexpr bool RES_EARLY = MODE == 3 || MODE == 2;   // residual tile requested at the top of the tile (see above)
   constexpr bool swp = MODE != 0;
   const bool do_stats = MODE == 0 && (a.flags & DSR_F_STATS) != 0;
-  const bool pixshuf = (a.flags & DSR_F_PIXSHUF) != 0;
-  const int wrow = (swp && pixshuf) ? 4 * (r16 & 3) + (r16 >> 2) : r16;
-  // ---- weights: registers, once (rows = output channels wc*32 + nt*16 + wrow).  Requested FIRST: they are the long pole of
+  // (mode 1 only: dsr_conv_fwd refuses PixelShuffle together with statistics, folded BatchNorm or a residual)
+  const bool pixshuf = MODE == 1 && (a.flags & DSR_F_PIXSHUF) != 0;
+  const int cbase = pixshuf ? (int)blockIdx.y : c0, cmul = pixshuf ? 4 : 1;
+  // ---- weights: registers, once (rows = conv channels of the slice's wc*32 + nt*16 + r16).  Requested FIRST: they are the long pole of
   // the prologue (36 x 16 B per lane, 2 us through the L1), and the integer set-up below runs under their latency (requested
   // behind the first tile's DMA instead, every launch of a few tiles per block measured 2 us slower)
   U4 fw[9][2][2];
@@ -87,7 +92,7 @@ __global__ __launch_bounds__(256, 2) void conv_c64_kernel(const C64Args a) {
     for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt)
-        fw[t][kk][nt] = *reinterpret_cast<const U4*>(W + ((size_t)(t * a.CoutP + c0 + wc * 32 + nt * 16 + wrow)) * 64 + kk * 32 + g * 8);
+        fw[t][kk][nt] = *reinterpret_cast<const U4*>(W + ((size_t)(t * a.CoutP + cbase + cmul * (wc * 32 + nt * 16 + r16))) * 64 + kk * 32 + g * 8);
 
   // A-fragment LDS offsets: halo column (16 wq + tx + r16) -> *128 + swizzled chunk (key = column & 7); + halo row * HC * 128
   int lds_off[3][2];
@@ -184,10 +189,10 @@ __global__ __launch_bounds__(256, 2) void conv_c64_kernel(const C64Args a) {
   };
 
   const float slope = (a.flags & DSR_F_PRELU_PTR) ? a.prelu[0] : a.slope;
-  // channel of accumulator register r of n-tile nt: pixel-major layout: wc*32 + nt*16 + r16 (all r);
-  // swapped: wc*32 + nt*16 + (4g + r), through the PixelShuffle row order: wc*32 + nt*16 + 4r + g
+  // local channel of accumulator register r of n-tile nt: pixel-major layout: wc*32 + nt*16 + r16 (all r);
+  // swapped: wc*32 + nt*16 + (4g + r)
   auto chan = [&](int nt, int r) {
-    return wc * 32 + nt * 16 + (!swp ? r16 : (pixshuf ? 4 * r + g : 4 * g + r));
+    return wc * 32 + nt * 16 + (!swp ? r16 : 4 * g + r);
   };
   constexpr int NB = swp ? 4 : 1;              // distinct channels among a lane's 4 accumulator registers
   // (FOLD launches keep no bias registers: the bias is folded into the shift of the affine map, see below)
@@ -195,7 +200,7 @@ __global__ __launch_bounds__(256, 2) void conv_c64_kernel(const C64Args a) {
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-    for (int r = 0; r < NB; ++r) bias_v[nt][r] = (!FOLD && (a.flags & DSR_F_BIAS)) ? a.bias[c0 + chan(nt, r)] : 0.f;
+    for (int r = 0; r < NB; ++r) bias_v[nt][r] = (!FOLD && (a.flags & DSR_F_BIAS)) ? a.bias[cbase + cmul * chan(nt, r)] : 0.f;
   if constexpr (FOLD) {
     // inference: eval-mode BatchNorm folded in, y = act((conv + bias) * scale + shift) = act(conv * scale + shift') with
     // shift' = shift + bias * scale.  The per-channel pair lives in the (otherwise unused) statistics area of LDS: a load
@@ -210,30 +215,22 @@ __global__ __launch_bounds__(256, 2) void conv_c64_kernel(const C64Args a) {
     }
   }
 
-  // C tile in LDS: pixel rows of 64 channels.  PixelShuffle(2) launches store channel 4c + s at byte s*32 + c*2, i.e.
-  // already grouped by sub-pixel, so that the store loop reads whole 16-byte vectors in both layouts.
+  // C tile in LDS: pixel rows of the slice's 64 channels
   int cw_base[2];                              // this lane's write address in the C tile for n-tile nt (tile pixel = 32 row + column):
 #pragma unroll                                 //   pixel-major: pixel (16 wq + 4g [+ 32 i + r]), one channel;
   for (int nt = 0; nt < 2; ++nt) {             //   swapped: pixel (16 wq + r16 [+ 32 i]), 4 channels (8 bytes)
-    const int col = wc * 32 + nt * 16 + r16;
     if constexpr (!swp)
-      cw_base[nt] = (wq * 16 + 4 * g) * C_STRIDE + (pixshuf ? (col & 3) * 32 + (col >> 2) * 2 : col * 2);
+      cw_base[nt] = (wq * 16 + 4 * g) * C_STRIDE + (wc * 32 + nt * 16 + r16) * 2;
     else
-      cw_base[nt] = (wq * 16 + r16) * C_STRIDE + (pixshuf ? g * 32 + (wc * 8 + nt * 4) * 2 : (wc * 32 + nt * 16 + 4 * g) * 2);
+      cw_base[nt] = (wq * 16 + r16) * C_STRIDE + (wc * 32 + nt * 16 + 4 * g) * 2;
   }
   // store loop: thread tid moves the 16-byte vectors idx = tid + 256 it of the tile (pixel idx >> 3, vector idx & 7): row `it`
   const int cr_base = (tid >> 3) * C_STRIDE + (tid & 7) * 16;          // + it * 32 * C_STRIDE
-  int st_part;                                                          // byte offset of vector `tid` relative to the tile origin
-  int st_step;                                                          // ... and of vector tid + 256 relative to vector tid
-  if (!pixshuf) {
-    st_part = ((tid >> 3) & 31) * a.CoutP * 2 + (tid & 7) * 16;       // prow = tid >> 3 (0..31): row 0 of the tile
-    st_step = a.W * a.CoutP * 2;                                       // prow + 32: row 1
-  } else {
-    const int OCp = a.CoutP / 4;
-    const int sub = (tid >> 1) & 3, cq = tid & 1, pxc = (tid >> 3) & 31;
-    st_part = ((sub >> 1) * 2 * a.W + 2 * pxc + (sub & 1)) * OCp * 2 + cq * 16;
-    st_step = 2 * (2 * a.W) * OCp * 2;                                 // conv row + 1 = output rows + 2
-  }
+  // byte offset of vector `tid` relative to the tile origin (prow = tid >> 3 (0..31): row 0 of the tile), and of vector
+  // tid + 256 (prow + 32: the next conv row) relative to vector tid.  PixelShuffle: conv pixel (y, x) is output pixel
+  // (2y + sy, 2x + sx) of 128 bytes, so columns step by two pixels and rows by two output rows.
+  const int st_part = ((tid >> 3) & 31) * (pixshuf ? 2 * 128 : a.CoutP * 2) + (tid & 7) * 16;
+  const int st_step = pixshuf ? 2 * (2 * a.W) * 128 : a.W * a.CoutP * 2;
 
   int t = xcd_remap(blockIdx.x, gridDim.x);
   const int tstep = gridDim.x;
@@ -462,7 +459,8 @@ __global__ __launch_bounds__(256, 2) void conv_c64_kernel(const C64Args a) {
     }
     {
       // exactly TR stores per thread (see the wait above).  Scalar part: byte offset of the tile origin in y.
-      const unsigned sorg = pixshuf ? (unsigned)(((n * 2 * a.H + 2 * oy0) * (2 * a.W) + 2 * ox0) * (a.CoutP / 4) * 2 + (c0 / 4) * 2)
+      // (PixelShuffle: slice s = blockIdx.y owns sub-pixel (s >> 1, s & 1) of every conv pixel)
+      const unsigned sorg = pixshuf ? (unsigned)(((n * 2 * a.H + 2 * oy0 + ((int)blockIdx.y >> 1)) * (2 * a.W) + 2 * ox0 + ((int)blockIdx.y & 1)) * 128)
                                     : (unsigned)(((n * a.H + oy0) * a.W + ox0) * a.CoutP * 2 + c0 * 2);
 #pragma unroll
       for (int it = 0; it < TR; ++it) {
@@ -560,7 +558,7 @@ void dsr_launch_conv_c64(C64Args& a, int N, int dtype, hipStream_t st) {
   a.tiles_x = (a.W + 31) / 32;
   a.ntiles = N * a.tiles_y * a.tiles_x;
   a.x_bytes = (unsigned)((size_t)N * a.H * a.W * 128);
-  a.y_bytes = (unsigned)((size_t)N * a.H * a.W * a.CoutP * 2);   // (PixelShuffle: [N][2H][2W][CoutP/4] is the same size)
+  a.y_bytes = (unsigned)((size_t)N * a.H * a.W * a.CoutP * 2);   // (PixelShuffle, CoutP == 256 by plan_fwd: [N][2H][2W][64] is the same size)
   int per_slice = 512 / slices;                               // 2 resident blocks per CU over all slices
 #ifdef DSR_C64_STAMPS
   if (const char* e = getenv("DSR_C64_BLOCKS")) per_slice = atoi(e) / slices;

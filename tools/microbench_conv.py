@@ -40,6 +40,13 @@ SHAPES = [  # name, N, H, W, Cin, Cout, k, stride, pad
     ("V.512->512 @28", 32, 28, 28, 512, 512, 3, 1, 1),
     ("V.512->512 @14", 32, 14, 14, 512, 512, 3, 1, 1),
 ]
+# forward only, with the epilogue the step runs (no statistics): the generator's PixelShuffle(2) + PReLU convs ("ps": one
+# 64-channel slice per sub-pixel, whole 128-byte output pixels) beside the plain 64 -> 128 launch of the same instantiation
+FWD_FORMS = [  # name, N, H, W, Cout, form
+    ("G.ps0 64->256 @128 fwd shuffle", 32, 128, 128, 256, "ps"),
+    ("G.ps1 64->256 @256 fwd shuffle", 32, 256, 256, 256, "ps"),
+    ("D.b1 64->128 @256 fwd plain", 32, 256, 256, 128, "plain"),
+]
 
 
 def r8(c):
@@ -94,6 +101,23 @@ def main():
                  for op in (0, 1, 2)]
         print(f"{name:28s} {fl/1e9:8.1f} | {tf*1e3:8.3f} {fl/tf/1e12:6.0f} | {td*1e3:8.3f} {fl/td/1e12:6.0f} | {tw*1e3:8.3f} {fl/tw/1e12:6.0f}"
               f" | {' / '.join(names)}", flush=True)
+    for name, n, h, w, cout, form in FWD_FORMS:
+        if flt and flt not in name:
+            continue
+        d = L.ConvDesc(L.BF16, n, h, w, 64, cout, 3, 3, 1, 1, 0)
+        fl = 2.0 * n * h * w * cout * 9 * 64
+        x = (torch.rand(n, h, w, 64, device=dev) - 0.5).to(torch.bfloat16)
+        wt = (torch.rand(cout, 64, 3, 3, device=dev) - 0.5) * 0.1
+        bias, slope = torch.zeros(cout, device=dev), torch.full((1,), 0.25, device=dev)
+        wf = torch.empty(lib.dsr_conv_packed_elems(C.byref(d), 0), dtype=torch.bfloat16, device=dev)
+        wd = torch.empty(lib.dsr_conv_packed_elems(C.byref(d), 1), dtype=torch.bfloat16, device=dev)
+        L.check(lib.dsr_conv_pack_weight(C.byref(d), wt.data_ptr(), wf.data_ptr(), wd.data_ptr(), st))
+        y = torch.empty(n * h * w * cout, dtype=torch.bfloat16, device=dev)     # (shuffled: [N][2H][2W][Cout/4], the same size)
+        ep = (L.Epilogue(L.ACT_PRELU, 0.25, slope.data_ptr(), bias.data_ptr(), None, 1, None) if form == "ps" else
+              L.Epilogue(0, 0.0, None, bias.data_ptr(), None, 0, None))
+        tf = timeit(lambda: L.check(lib.dsr_conv_fwd(C.byref(d), x.data_ptr(), wf.data_ptr(), C.byref(ep), y.data_ptr(), st)), reps=20)
+        kname = lib.dsr_conv_kernel_name(C.byref(d), 0, C.byref(ep)).decode().replace("conv_", "").replace("_kernel", "")
+        print(f"{name:28s} {fl/1e9:8.1f} | {tf*1e3:8.3f} {fl/tf/1e12:6.0f} | {tf*1e6/(fl/1e9):8.4f} us/GFLOP | {kname}", flush=True)
 
 
 if __name__ == "__main__":
